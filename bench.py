@@ -24,8 +24,16 @@ code path.  The only collective of the path -- the halo all-gather before marchi
 through RCCL (backend "nccl"); if RCCL cannot initialise the run FAILS unless --allow-gloo is given,
 and the JSON line records which backend and how many ranks the collective saw ("collective").
 
-Prints ONE JSON line (rank 0).  value = whole-job Mvoxel*views/s.  The marching-cubes rate
-(Mcells/s) is measured after the timed region and reported in the same line under "mc".
+Prints ONE JSON line (rank 0).  value = whole-job Mvoxel*views/s.
+
+A plain run does only what that figure needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and
+the line.  Everything else needs --full: after the timed region the marching-cubes rate (Mcells/s, under "mc"), the
+live shader clock, the measured HBM bandwidth, the pair count, the variants, BASELINE.json's other configurations and
+the CPU baseline; before it, with N > 1, the small-grid preflight of the sharded path.
+
+--dump-outputs DIR writes what the last timed step computed -- the carved grid state a caller reads back -- as
+DIR/sdf.npy and DIR/update_num.npy (float32) for a fixed, seeded sample of voxels (DIR/voxel_ids.npy, float64); the
+inputs are synthetic and the same for the same arguments, so two builds can be compared output for output.
 """
 import argparse
 import datetime
@@ -105,7 +113,15 @@ def parse(argv=None):
     ap.add_argument("--plumbing-check", action="store_true",
                     help="no GPU work: launch, rendezvous and the halo all-gather of this configuration with "
                          "rank-stamped host buffers (CPU test of the multi-rank launch path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, measure and check everything beyond the headline figure (marching cubes, "
+                         "clock probe, bandwidth, pair count, variants, configs, CPU baseline, N > 1 preflight); the --no-* "
+                         "options above select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: write the state of a fixed sample of voxels after the last timed step to DIR/*.npy")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.config == 1:
         a.grid, a.views, a.width, a.height, a.mode = 512, 16, 640, 480, "tsdf"
     elif a.config in (2, 3):
@@ -413,7 +429,7 @@ def contract_roofline(roofline, *, mode, cull, n, nv, bpv, launches_per_step, pa
     elif cull:
         # (neither a dropping-off run nor a pair count: nothing that is a fraction can be stated)
         roofline["achieved"] = None
-        src = "unavailable: run without --no-variants (dropping-off launch) or on one GPU (pair count)"
+        src = "unavailable: needs --full (the dropping-off launch of the variants, or the pair count)"
     else:
         src = "the timed launch itself (view dropping is off: every voxel*view evaluated)"
     roofline["frac"] = round(roofline["achieved"] / HBM_PEAK_GBS, 4) if roofline.get("achieved") else None
@@ -687,6 +703,37 @@ def bunny_sequence(device, resolution=2.5, reps=2):
         c.close()
 
 
+DUMP_VOXELS = 1 << 21  # sampled voxels of --dump-outputs: 16 B each over the three files (32 MiB)
+
+
+def dump_outputs(out_dir, carvers):
+    """--dump-outputs: the state a caller of the timed path reads back after its last step (vcy_download_voxels) for a
+    fixed sample of voxels -- every voxel of a grid of at most DUMP_VOXELS, else DUMP_VOXELS drawn uniformly with seed 0
+    (duplicates dropped, ascending) -- as float32 sdf / update_num and the float64 global voxel ids (x fastest).
+    `carvers` are this process's slab contexts; together they must hold the whole grid."""
+    import numpy as np
+    nx, ny, nz = carvers[0].dims
+    plane = nx * ny
+    total = plane * nz
+    if sum(c.slab_voxels for c in carvers) != total:
+        raise SystemExit("bench: --dump-outputs needs the whole grid in this process")
+    if total <= DUMP_VOXELS:
+        ids = np.arange(total, dtype=np.int64)
+    else:
+        ids = np.unique(np.random.RandomState(0).randint(0, total, DUMP_VOXELS, dtype=np.int64))
+    sdf = np.empty(len(ids), np.float32)
+    cnt = np.empty(len(ids), np.float32)
+    for c in carvers:
+        z0, z1 = c.z_range
+        sel = (ids >= z0 * plane) & (ids < z1 * plane)
+        s, u = c.download_voxels(ids[sel])
+        sdf[sel], cnt[sel] = s, u
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sdf.npy"), sdf)
+    np.save(os.path.join(out_dir, "update_num.npy"), cnt)
+    np.save(os.path.join(out_dir, "voxel_ids.npy"), ids.astype(np.float64))
+
+
 def run_inprocess(args, why=None):
     """N GPUs from ONE process (vacancy_amd.sharded.ShardedVoxelCarver): a host thread per device over the
     C-ABI, no torch, no rendezvous; the halo exchange is the library's own RCCL all-gather.  Same workload,
@@ -721,7 +768,7 @@ def run_inprocess(args, why=None):
     # before anything is timed: the whole sharded path once on a small grid, merged mesh against a single context
     # (the one-process-per-GPU form does the same; config.preflight_mesh_check)
     preflight = None
-    if G * k > 1 and not args.no_preflight and args.batch:
+    if G * k > 1 and args.full and not args.no_preflight and args.batch:
         try:
             from vacancy_amd import dist as vdist_
             pn, pnv = 256, 8
@@ -776,18 +823,19 @@ def run_inprocess(args, why=None):
     if args.batch and args.cull:
         # the timed launches drop (brick, view) pairs that provably change nothing: `frac` counts the pairs really
         # evaluated (the one-GPU line measures the dropping-off launch itself; see contract_roofline)
-        pairs = None
-        try:
-            sh.set_param("paircount", 1)
-            sh.carve_batch(batches, steps=1)
-            proc = tot = 0
-            for c in sh.slabs:
-                a, b, _ = c.last_carve_pairs()
-                proc, tot = proc + a, tot + b
-            sh.set_param("paircount", 0)
-            pairs = round(proc / float(tot), 4) if tot else None
-        except Exception as e:
-            pairs = "%s: %s" % (type(e).__name__, e)
+        pairs = "not counted: run with --full"
+        if args.full:
+            try:
+                sh.set_param("paircount", 1)
+                sh.carve_batch(batches, steps=1)
+                proc = tot = 0
+                for c in sh.slabs:
+                    a, b, _ = c.last_carve_pairs()
+                    proc, tot = proc + a, tot + b
+                sh.set_param("paircount", 0)
+                pairs = round(proc / float(tot), 4) if tot else None
+            except Exception as e:
+                pairs = "%s: %s" % (type(e).__name__, e)
         roofline["headline_kernel"] = {"avg_launch_ms": roofline["avg_launch_ms"], "pairs_processed_frac": pairs,
                                        "per_view_api_equivalent": {"gbs": roofline["achieved"], "frac": roofline["frac"]}}
         if isinstance(pairs, float):
@@ -797,10 +845,10 @@ def run_inprocess(args, why=None):
                                        "evaluates that share of the voxel*views; the rest is dropped as provably unchanged)")
         else:
             roofline["achieved"] = roofline["frac"] = None
-            roofline["frac_source"] = "unavailable (pair count failed)"
+            roofline["frac_source"] = "unavailable (no pair count: %s)" % pairs
     mc = None
     collective = None
-    if not args.no_mc:
+    if args.full and not args.no_mc:
         try:
             sh.set_param("meshkeys", 1)
             sh.extract_slabs(0.0, True)  # first run allocates
@@ -824,7 +872,7 @@ def run_inprocess(args, why=None):
     # the streamed entry point with the producer shared by the devices (vcy_carve_batch_silhouettes_sharded) next to
     # round 4's form (every slab builds every SDF); wall time, PCIe inclusive: never `value`
     variants = None
-    want = set() if args.no_variants else set(x.strip() for x in args.variants.split(","))
+    want = set() if args.no_variants or not args.full else set(x.strip() for x in args.variants.split(","))
     if ("all" in want or "streamed" in want) and args.batch and G * k > 1:
         variants = {}
         try:
@@ -912,6 +960,8 @@ def emit(obj):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("bench: --dump-outputs is for --gpus 1")
     if "WORLD_SIZE" in os.environ or args.gpus == 1 or args.launch == "inprocess":
         quiet_stdout()  # (the self-launching parent only relays its children's output)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1108,7 +1158,7 @@ def main():
     # grid: a record from a node nobody has run on before says by itself whether its exchange worked
     # (config.preflight_mesh_check, config.collective).
     preflight = None
-    if world > 1 and not args.no_preflight and args.batch:
+    if world > 1 and args.full and not args.no_preflight and args.batch:
         try:
             pn, pnv, pw, ph = 256, 8, 320, 240
             popt = synth.sphere_option(pn, uo)
@@ -1154,13 +1204,15 @@ def main():
     my_elapsed_ms = elapsed * 1e3
     avg_prepass_ms, avg_kernel_ms = read_logs(devs, args.steps) if args.batch else (0.0, my_elapsed_ms / args.steps)
     main_kernel_launches = kernel_launches[0] if args.batch else float(nv * len(devs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, devs)
     # The shader clock of THIS run, for the VALU issue fraction below: one wave on a stream of its own samples the clock
     # counter (vcy_clock_probe_*) during six more steps of the same workload queued right behind the timed region --
     # not inside it: beside the timed steps the probe's second hardware queue costs the carve kernel 1.7 %
     # (profiles/r05/clock_probe_ab.txt); an idle device would have dropped its clock, six more steps keep it where it was
     # (the clock over the second half of the probe's span is the one used: setting the probe up idles the device for a millisecond).
     live_clock = None
-    if world == 1 and args.batch and "VCY_BENCH_NO_CLOCK_PROBE" not in os.environ:
+    if args.full and world == 1 and args.batch and "VCY_BENCH_NO_CLOCK_PROBE" not in os.environ:
         try:
             probe = vc.ClockProbe(local_rank)
             try:
@@ -1301,8 +1353,9 @@ def main():
             roofline["frac_binding_note"] = "measured: this kernel's rate / the rate of its own instruction stream without tile loads and stores"
     # marching cubes (second half of the metric), outside the timed region
     mc = None
-    collective = {"backend": "none", "ranks": world, "bytes_per_rank": 0, "note": "one slab: nothing to exchange"}
-    if not args.no_mc:
+    collective = {"backend": "none", "ranks": world, "bytes_per_rank": 0,
+                  "note": "one slab: nothing to exchange" if world * k_slabs == 1 else "the halo exchange runs with --full"}
+    if args.full and not args.no_mc:
         try:
             info = vdist.exchange_halo(devs, rank, world)
             if info:
@@ -1374,14 +1427,15 @@ def main():
 
     # measured streaming bandwidth of this box next to the vendor figure (after the timed region and after the extractions:
     # freeing the probe's 4 GiB slows the next few device-to-host copies down by 2 ms)
-    try:
-        rd, cp = vc.measure_bandwidth(local_rank, 1 << 31, 3)
-        roofline["measured_read_gbs"] = round(rd, 1)
-        roofline["measured_copy_gbs"] = round(cp, 1)
-        roofline["frac_of_measured_read"] = round(achieved / rd, 4) if rd > 0 else None
-    except Exception as e:
-        roofline["measured_read_gbs"] = None
-        roofline["measured_error"] = "%s: %s" % (type(e).__name__, e)
+    if args.full:
+        try:
+            rd, cp = vc.measure_bandwidth(local_rank, 1 << 31, 3)
+            roofline["measured_read_gbs"] = round(rd, 1)
+            roofline["measured_copy_gbs"] = round(cp, 1)
+            roofline["frac_of_measured_read"] = round(achieved / rd, 4) if rd > 0 else None
+        except Exception as e:
+            roofline["measured_read_gbs"] = None
+            roofline["measured_error"] = "%s: %s" % (type(e).__name__, e)
 
     # the same kernel without view dropping and in TSDF mode (weighted average + truncation), measured in
     # the same run so that the headline's dependence on the scene is visible in the driver's record
@@ -1399,7 +1453,7 @@ def main():
         return round(proc / float(tot), 4) if tot else None
 
     pairs_main = None
-    if args.batch:
+    if args.full and args.batch:
         # (every rank counts the pairs of its slabs; the fraction is over the whole grid)
         proc = tot = 0
         err = None
@@ -1427,7 +1481,7 @@ def main():
     # (warm device, steps queued back to back) so that the headline's dependence on scene and call pattern is in the
     # driver's record.
     variants = None
-    want = set() if args.no_variants else set(x.strip() for x in args.variants.split(","))
+    want = set() if args.no_variants or not args.full else set(x.strip() for x in args.variants.split(","))
     if "all" in want:
         want = {"modes", "scenes", "per_view", "streamed"}
     if world == 1 and want and args.batch:
@@ -1697,7 +1751,7 @@ def main():
     # configs[0] the bunny sequence of examples.cc, configs[1] 512^3 x 16 TSDF, and the configs[4] shape 2048^3 x 64 on
     # this one GPU.  After the timed region and the variants, each on contexts of its own; < 60 s together.
     headline = (n, nv, args.width, args.height, args.mode, args.cull) == (1024, 32, 1280, 720, "default", 1)
-    if rank == 0 and world == 1 and args.batch and headline and not (args.no_configs or args.no_variants):
+    if args.full and rank == 0 and world == 1 and args.batch and headline and not (args.no_configs or args.no_variants):
         t_cfg = time.perf_counter()
         out["configs"] = {
             "note": "BASELINE.json configs other than the headline (configs[2]; configs[3] is the same grid with --gpus N), "
@@ -1708,7 +1762,7 @@ def main():
                                                         2048, 64, 1920, 1080, "default", steps=3, warmup=1, settle_ms=0.0),
         }
         out["configs"]["wall_s_spent"] = round(time.perf_counter() - t_cfg, 2)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, views, sdfs, args.cpu_seconds)
     if args.batch:
         out["roofline"] = contract_roofline(roofline, mode=args.mode, cull=args.cull, n=n, nv=nv, bpv=bytes_per_vv(args.mode, uo),

@@ -6,7 +6,7 @@ OUT=$R/$1
 LIB=${2:-$R/vacancy_amd/csrc/libvacancy_hip.so}
 mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
-VCY_HIP_LIB=$LIB rocprofv3 --kernel-trace --stats -d "$OUT" -o t --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-variants > "$OUT/bench.log" 2>&1
+VCY_HIP_LIB=$LIB rocprofv3 --kernel-trace --stats -d "$OUT" -o t --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-variants > "$OUT/bench.log" 2>&1
 python - "$OUT" <<'PY'
 import csv, re, sys
 rows = list(csv.DictReader(open(sys.argv[1] + "/t_kernel_trace.csv")))

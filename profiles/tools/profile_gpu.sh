@@ -9,7 +9,7 @@ REPO=$(pwd)
 mkdir -p "$OUT"
 OUT=$(cd "$OUT" && pwd)
 export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-variants $*"
+ARGS="--full --no-cpu-baseline --no-variants $*"
 run() {  # name, rocprofv3 options...
   local name=$1; shift
   ( cd /tmp && rocprofv3 "$@" -d "$OUT" -o "$name" --output-format csv -- python "$REPO/bench.py" $ARGS ) > "$OUT/$name.log" 2>&1
@@ -17,10 +17,10 @@ run() {  # name, rocprofv3 options...
 # PASSES (default: all) selects the runs; STEPS_TRACE overrides bench.py's default steps for the traced run
 PASSES=${PASSES:-"trace fetch write sq1 sq2 sq3 grbm"}
 want() { case " $PASSES " in *" $1 "*) return 0;; esac; return 1; }
-ARGS="--no-cpu-baseline --no-variants $* ${STEPS_TRACE:-}"
+ARGS="--full --no-cpu-baseline --no-variants $* ${STEPS_TRACE:-}"
 want trace && run trace --kernel-trace --stats
 STEPS="--steps 2 --warmup 1"
-ARGS="--no-cpu-baseline --no-variants $* $STEPS"
+ARGS="--full --no-cpu-baseline --no-variants $* $STEPS"
 want fetch && run fetch --pmc FETCH_SIZE
 want write && run write --pmc WRITE_SIZE
 want sq1 && run sq1 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY

@@ -28,9 +28,9 @@ python profiles/tools/summarize_pmc.py "$O/config1" "$O/pmc_512x16_tsdf_config1.
 PASSES="trace fetch write sq1 grbm" STEPS_TRACE="--steps 3 --warmup 1" bash profiles/tools/profile_gpu.sh gpurun_out/$RND/config4 --no-mc --config 4
 python profiles/tools/summarize_pmc.py "$O/config4" "$O/pmc_2048x64_config4.json" --key default_2048_64_b1_c1 --counters "$CTR"
 # marching cubes: trace with the extraction inside, HBM bytes of its kernels
-( cd /tmp && rocprofv3 --kernel-trace --stats -d "$O/mc" -o trace --output-format csv -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-variants ) > "$O/mc_trace.log" 2>&1
-( cd /tmp && rocprofv3 --pmc FETCH_SIZE -d "$O/mc" -o fetch --output-format csv -- python "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-variants ) > "$O/mc_fetch.log" 2>&1
-( cd /tmp && rocprofv3 --pmc WRITE_SIZE -d "$O/mc" -o write --output-format csv -- python "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-variants ) > "$O/mc_write.log" 2>&1
+( cd /tmp && rocprofv3 --kernel-trace --stats -d "$O/mc" -o trace --output-format csv -- python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-variants ) > "$O/mc_trace.log" 2>&1
+( cd /tmp && rocprofv3 --pmc FETCH_SIZE -d "$O/mc" -o fetch --output-format csv -- python "$R/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline --no-variants ) > "$O/mc_fetch.log" 2>&1
+( cd /tmp && rocprofv3 --pmc WRITE_SIZE -d "$O/mc" -o write --output-format csv -- python "$R/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline --no-variants ) > "$O/mc_write.log" 2>&1
 python profiles/tools/summarize_pmc.py "$O/mc" "$O/pmc_1024_marching_cubes.json" --mc-key mc_1024 --counters "$CTR"
 profiles/tools/ab_mc.sh prod > "$O/mc_unprofiled.txt" 2>&1
 # the one-sweep cell search against the bit planes in memory ("mcsweep" 1 / 0), alternating in one process
@@ -47,11 +47,11 @@ if [ -f build/variants/floorTS/libvacancy_hip.so ]; then
   python profiles/tools/summarize_floor.py "$O/issue_floor.txt" "$CTR"
 fi
 # N GPUs from one process (threads + vcy_halo_allgather): two "GPUs" on this one device
-VCY_BENCH_FORCE_DEVICE=0 python bench.py --gpus 2 --launch inprocess --slabs-per-gpu 2 --steps 5 --warmup 1 > "$O/bench_inprocess_2x_one_device.json" 2> "$O/bench_inprocess_2x_one_device.err"
+VCY_BENCH_FORCE_DEVICE=0 python bench.py --full --gpus 2 --launch inprocess --slabs-per-gpu 2 --steps 5 --warmup 1 > "$O/bench_inprocess_2x_one_device.json" 2> "$O/bench_inprocess_2x_one_device.err"
 echo "in-process 2 x one device rc=$?" >> "$O/status.txt"
 # --launch auto (the default): torch.distributed.run first; RCCL refuses two ranks on one device, so the parent falls
 # back to the in-process form and says so in config.launch_note
-VCY_BENCH_FORCE_DEVICE=0 python bench.py --gpus 2 --slabs-per-gpu 2 --steps 5 --warmup 1 --no-mc > "$O/bench_auto_fallback_2x_one_device.json" 2> "$O/bench_auto_fallback_2x_one_device.err"
+VCY_BENCH_FORCE_DEVICE=0 python bench.py --full --gpus 2 --slabs-per-gpu 2 --steps 5 --warmup 1 --no-mc > "$O/bench_auto_fallback_2x_one_device.json" 2> "$O/bench_auto_fallback_2x_one_device.err"
 echo "launch auto -> in-process fallback rc=$?" >> "$O/status.txt"
 # phase breakdown of the fused kernel (development build with s_memtime marks)
 if [ -f build/variants/phase/libvacancy_hip.so ]; then
@@ -60,14 +60,14 @@ if [ -f build/variants/phase/libvacancy_hip.so ]; then
 fi
 # the multi-rank path of bench.py on this one device: 2 ranks, 2 slabs each, halo exchange over gloo (RCCL refuses
 # two ranks on one device; --allow-gloo is the documented escape for exactly this check)
-VCY_BENCH_FORCE_DEVICE=0 python bench.py --gpus 2 --launch torchrun --slabs-per-gpu 2 --steps 3 --warmup 1 --no-cpu-baseline --no-variants --allow-gloo > "$O/bench_2ranks_one_device_gloo.json" 2> "$O/bench_2ranks_one_device_gloo.err"
+VCY_BENCH_FORCE_DEVICE=0 python bench.py --full --gpus 2 --launch torchrun --slabs-per-gpu 2 --steps 3 --warmup 1 --no-cpu-baseline --no-variants --allow-gloo > "$O/bench_2ranks_one_device_gloo.json" 2> "$O/bench_2ranks_one_device_gloo.err"
 echo "2 ranks (gloo) rc=$?" >> "$O/status.txt"
-VCY_BENCH_FORCE_DEVICE=0 python bench.py --gpus 2 --launch torchrun --steps 3 --warmup 1 --no-cpu-baseline --no-variants > "$O/bench_2ranks_one_device_rccl.json" 2> "$O/bench_2ranks_one_device_rccl.err"
+VCY_BENCH_FORCE_DEVICE=0 python bench.py --full --gpus 2 --launch torchrun --steps 3 --warmup 1 --no-cpu-baseline --no-variants > "$O/bench_2ranks_one_device_rccl.json" 2> "$O/bench_2ranks_one_device_rccl.err"
 echo "2 ranks (rccl on one device, expected to be refused) rc=$?" >> "$O/status.txt"
 # round 5: the 8-rank launches rehearsed on this one device (gloo for the exchange: RCCL refuses two ranks per device), the
 # in-process form with eight "GPUs", the streamed emulation (sharded against replicated SDF producer), ExtractVoxel phases
-VCY_BENCH_FORCE_DEVICE=0 VCY_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 8 --launch torchrun --allow-gloo --verify-mesh --variants streamed --steps 10 > "$O/bench_8ranks_one_device_gloo.json" 2> "$O/bench_8ranks_one_device_gloo.err"; echo "8 ranks torchrun gloo rc=$?" >> "$O/status.txt"
-VCY_BENCH_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 8 --launch inprocess --verify-mesh --variants streamed --steps 10 > "$O/bench_inprocess_8x_one_device.json" 2> "$O/bench_inprocess_8x_one_device.err"; echo "8x inprocess rc=$?" >> "$O/status.txt"
+VCY_BENCH_FORCE_DEVICE=0 VCY_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 8 --launch torchrun --allow-gloo --verify-mesh --variants streamed --steps 10 > "$O/bench_8ranks_one_device_gloo.json" 2> "$O/bench_8ranks_one_device_gloo.err"; echo "8 ranks torchrun gloo rc=$?" >> "$O/status.txt"
+VCY_BENCH_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 8 --launch inprocess --verify-mesh --variants streamed --steps 10 > "$O/bench_inprocess_8x_one_device.json" 2> "$O/bench_inprocess_8x_one_device.err"; echo "8x inprocess rc=$?" >> "$O/status.txt"
 timeout 1200 python profiles/tools/streamed_emulation.py > "$O/streamed_emulation.txt" 2>&1; echo "streamed emulation rc=$?" >> "$O/status.txt"
 timeout 1200 python profiles/tools/slab_emulation.py > "$O/slab_emulation.txt" 2>&1; echo "slab emulation rc=$?" >> "$O/status.txt"
 VCY_XV_TIMING=1 timeout 300 python profiles/tools/xv_timing.py > "$O/extract_voxel_phases.txt" 2>&1
@@ -88,8 +88,8 @@ cp "$O/config1/trace_kernel_stats.csv" "$O/kernel_stats_512x16_tsdf_config1.csv"
 cp "$O/mc/trace_kernel_stats.csv" "$O/kernel_stats_1024x32_default_with_mc.csv"
 # the bench lines: with the counters of this session next to them
 mkdir -p profiles && cp "$CTR" profiles/counters.json
-python bench.py > "$O/bench_1024x32_default.json" 2> "$O/bench_default.err"; echo "bench default rc=$?" >> "$O/status.txt"
-python bench.py --config 1 --no-variants > "$O/bench_512x16_tsdf_config1.json" 2> "$O/bench_config1.err"; echo "bench config1 rc=$?" >> "$O/status.txt"
-python bench.py --config 4 --steps 5 --warmup 1 --variants streamed --no-cpu-baseline > "$O/bench_2048x64_config4.json" 2> "$O/bench_config4.err"; echo "bench config4 rc=$?" >> "$O/status.txt"
+python bench.py --full > "$O/bench_1024x32_default.json" 2> "$O/bench_default.err"; echo "bench default rc=$?" >> "$O/status.txt"
+python bench.py --full --config 1 --no-variants > "$O/bench_512x16_tsdf_config1.json" 2> "$O/bench_config1.err"; echo "bench config1 rc=$?" >> "$O/status.txt"
+python bench.py --full --config 4 --steps 5 --warmup 1 --variants streamed --no-cpu-baseline > "$O/bench_2048x64_config4.json" 2> "$O/bench_config4.err"; echo "bench config4 rc=$?" >> "$O/status.txt"
 cat "$O/status.txt"
 ls "$O"
