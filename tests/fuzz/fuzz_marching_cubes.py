@@ -29,7 +29,8 @@ for seed in range(lo, hi):
     if nx >= 256:
         ny, nz = min(ny, 50), min(nz, 40)
     dims = (nx, ny, nz)
-    uo = UpdateOption(voxel_max_update_num=int(rng.choice([200, 255, 70000])))  # u8 / u16 / u32 counters
+    max_update = int(rng.choice([200, 255, 70000]))
+    uo = UpdateOption(voxel_max_update_num=max_update)  # u8 / u16 / u32 counters
     opt = CarverOption(bb_min=[0.0, 0.0, 0.0], bb_max=[float(d) for d in dims], resolution=1.0, update_option=uo)
     orc = O.OracleGrid(opt)
     assert orc.dims == dims, (orc.dims, dims)
@@ -51,6 +52,13 @@ for seed in range(lo, hi):
     snap = rng.rand(n) < 0.02
     sdf[snap] = rng.uniform(-2e-5, 2e-5, int(snap.sum())).astype(np.float32)
     cnt = (rng.rand(n) < rng.choice([1.0, 0.98, 0.7])).astype(np.int32)
+    # counts up to max + 1, so that the array really is u8 / u16 / u32 (0 / 1 alone would keep it at one byte);
+    # 256 and 65536 are what a narrower counter would wrap to 0
+    edges = np.array([v for v in (2, 255, 256, 65535, 65536, max_update + 1) if v <= max_update + 1], np.int32)
+    wide = (cnt > 0) & (rng.rand(n) < 0.3)
+    cnt[wide] = edges[rng.randint(0, len(edges), int(wide.sum()))]
+    cnt[rng.randint(0, n)] = max_update + 1
+    width = 1 if max_update + 1 <= 255 else (2 if max_update + 1 <= 65535 else 4)
     orc.upload(sdf, cnt)
     iso = float(rng.choice([0.0, 0.0, 0.25, 0.3, -0.1]))
     interp = bool(rng.randint(0, 2))
@@ -58,6 +66,7 @@ for seed in range(lo, hi):
     whole = vc.VoxelCarver(opt)
     assert whole.Init(), vc.last_error()
     whole.upload(sdf, cnt)
+    assert (whole.get_param("count_bytes"), whole.get_param("count_bytes_final")) == (width, width), (seed, max_update)
     for sweep in (1, 0):
         whole.set_param("mcsweep", sweep)
         if not same(whole.ExtractIsoSurface(iso, interp), ref):

@@ -12,6 +12,7 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 LIB = os.path.join(ORACLE_DIR, "libvacancy_oracle.so")
 
 _lib = None
+_threads = None
 
 
 def build():
@@ -66,9 +67,22 @@ def load():
             usable = max(1, min(usable, int(round(int(quota) / float(period)))))
     except Exception:
         pass
-    lib.orc_set_num_threads(int(os.environ.get("VCY_ORACLE_THREADS", usable)))
+    global _threads
+    _threads = int(os.environ.get("VCY_ORACLE_THREADS", usable))
+    lib.orc_set_num_threads(_threads)
     _lib = lib
     return lib
+
+
+def set_num_threads(n):
+    """OpenMP threads of the oracle's carve from now on; returns the previous count.  (A carve of a few thousand
+    voxels is fastest on one thread: tests that apply tens of thousands of views to a small grid ask for that.)"""
+    global _threads
+    lib = load()
+    prev = _threads
+    _threads = int(n)
+    lib.orc_set_num_threads(_threads)
+    return prev
 
 
 def _p(a):

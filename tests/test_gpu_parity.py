@@ -442,7 +442,7 @@ def test_extract_voxel_predicates_on_adversarial_state():
     special = np.array([0.0, -0.0, 1e-45, -1e-45, 1e-39, -1e-39, 1.1754944e-38, -1.1754944e-38, 1e-23, -1e-23,
                         2.0**-75, -(2.0**-75), 2.0**-74, -(2.0**-74), 2.0**-76, -(2.0**-76), 1.5 * 2.0**-75,
                         np.inf, -np.inf, np.nan, 1.0, -1.0, np.finfo(np.float32).min], dtype=np.float32)
-    for max_update in (200, 255, 70000):  # u8, u16, u32 counters
+    for max_update, width in ((200, 1), (255, 2), (70000, 4)):  # u8, u16, u32 counters
         opt = vc.CarverOption(bb_min=(0, 0, 0), bb_max=(67, 9, 13), resolution=1.0,
                               update_option=UpdateOption(voxel_max_update_num=max_update))
         dev = vc.VoxelCarver(opt)
@@ -456,8 +456,16 @@ def test_extract_voxel_predicates_on_adversarial_state():
         pick = rng.rand(nvox) < 0.5
         sdf[pick] = special[rng.randint(0, len(special), int(pick.sum()))]
         cnt = rng.randint(0, 3, nvox).astype(np.int32)
+        # counts up to max + 1 that need the claimed width (a one-byte count would keep the array at one byte);
+        # 256 and 65536 are what a narrower counter would wrap to 0
+        edges = np.array([v for v in (3, 255, 256, 65535, 65536, max_update, max_update + 1) if v <= max_update + 1],
+                         np.int32)
+        wide = rng.rand(nvox) < 0.25
+        cnt[wide] = edges[rng.randint(0, len(edges), int(wide.sum()))]
+        cnt[rng.randint(0, nvox)] = max_update + 1
         dev.upload(sdf, cnt)
         orc.upload(sdf, cnt)
+        assert (dev.get_param("count_bytes"), dev.get_param("count_bytes_final")) == (width, width), max_update
         for inside_empty in (False, True):
             dv, ov = dev.ExtractVoxel(inside_empty), orc.extract_voxel(inside_empty)
             assert len(ov["faces"]) > 0
@@ -467,6 +475,7 @@ def test_extract_voxel_predicates_on_adversarial_state():
             iv = dev.ExtractVoxelInto(inside_empty)
             assert np.array_equal(iv["faces"], ov["faces"]), (max_update, inside_empty)
             assert np.array_equal(iv["vertices"].view(np.uint32), ov["vertices"].view(np.uint32)), (max_update, inside_empty)
+        assert dev.get_param("count_bytes") == width, max_update
     fresh = vc.VoxelCarver(opt)
     assert fresh.Init()
     assert len(fresh.ExtractVoxelInto(False)["vertices"]) == 0  # (nothing kept: the callback is never called)
@@ -1376,10 +1385,11 @@ def test_counters_widen_lazily_across_the_256th_view(mode):
     assert old.Init()
     old.set_param("lazycount", 0)
     assert old.get_param("count_bytes") == final
-    if final <= 2:
-        d2 = [old.upload_sdf(s_) for s_ in sdfs]
-        assert old.CarveBatchDevice(views, [d2[img(i)] for i in range(nv)]), vc.last_error()
-        assert_state_equal(old, orc, "lazycount 0")
+    # (max_update_70000: u32 from the start, so the per-view kernel with 32-bit counters, view by view)
+    d2 = [old.upload_sdf(s_) for s_ in sdfs]
+    assert old.CarveBatchDevice(views, [d2[img(i)] for i in range(nv)]), vc.last_error()
+    assert old.get_param("count_bytes") == final
+    assert_state_equal(old, orc, "lazycount 0")
 
 
 def test_halo_exchange_between_slabs_of_different_counter_width():
