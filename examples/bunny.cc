@@ -143,6 +143,16 @@ int main(int argc, char* argv[]) {
                 i, nv, nf, mesh.vertices().size(), mesh.vertex_indices().size(), sum[0], sum[1], sum[2], voxel_verts);
   }
 
+  // the last view once more with normals (computed on the device), as a binary PLY a viewer lights correctly
+  if (!poses.empty()) {
+    vacancy::Mesh lit;
+    carver.ExtractIsoSurface(&lit, 0.0, true, true);
+    const size_t last = std::min<size_t>(6, poses.size()) - 1;
+    lit.WritePlyBinary(out_dir + "/surface_normals_" + vacancy::zfill(last) + ".ply");
+    std::printf("NORMALS view %zu verts %zu normals %zu face_normals %zu\n", last, lit.vertices().size(), lit.normals().size(),
+                lit.face_normals().size());
+  }
+
   // The same six views through the batch overload (cameras held by shared_ptr, as examples.cc does) on a
   // second carver, read back as the reference's VoxelGrid: touched voxels, negative voxels, sum of update_num.
   {

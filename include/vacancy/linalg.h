@@ -46,6 +46,8 @@ struct Vec {
   }
   T norm() const { return std::sqrt(squaredNorm()); }
   Vec normalized() const { T n2 = squaredNorm(); return n2 > T(0) ? (*this) / std::sqrt(n2) : *this; }
+  Vec& operator/=(T s) { for (int i = 0; i < N; ++i) v[i] = v[i] / s; return *this; }
+  void normalize() { T n2 = squaredNorm(); if (n2 > T(0)) *this /= std::sqrt(n2); }
   Vec cross(const Vec& b) const {
     static_assert(N == 3, "");
     return Vec(v[1] * b.v[2] - v[2] * b.v[1], v[2] * b.v[0] - v[0] * b.v[2], v[0] * b.v[1] - v[1] * b.v[0]);

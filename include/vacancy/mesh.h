@@ -12,7 +12,24 @@ namespace vacancy {
 
 class Mesh {
  public:
-  void Clear() { vertices_.clear(); vertex_colors_.clear(); vertex_indices_.clear(); }
+  void Clear() {
+    vertices_.clear(); vertex_colors_.clear(); vertex_indices_.clear();
+    normals_.clear(); face_normals_.clear(); normal_indices_.clear();
+  }
+  // Reference mesh.cc:197-240, serial on the host (vcy_mesh_normals_host): face normal = ((p1 - p0).normalized() x
+  // (p2 - p0).normalized()).normalized(); vertex normal = its faces' normals summed in ascending face index, divided by
+  // their number, normalised; normal_indices = vertex_indices.  VoxelCarver::ExtractIsoSurface(..., with_normals = true)
+  // fills the same three vectors from the device, bit for bit.
+  void CalcNormal();
+  void CalcFaceNormal();
+  const std::vector<Eigen::Vector3f>& normals() const { return normals_; }
+  const std::vector<Eigen::Vector3f>& face_normals() const { return face_normals_; }
+  const std::vector<Eigen::Vector3i>& normal_indices() const { return normal_indices_; }
+  bool set_normals(const std::vector<Eigen::Vector3f>& n) { normals_ = n; return true; }
+  bool set_face_normals(const std::vector<Eigen::Vector3f>& n) { face_normals_ = n; return true; }
+  bool set_normal_indices(const std::vector<Eigen::Vector3i>& f) { normal_indices_ = f; return true; }
+  std::vector<Eigen::Vector3f>* mutable_normals() { return &normals_; }
+  std::vector<Eigen::Vector3f>* mutable_face_normals() { return &face_normals_; }
   const std::vector<Eigen::Vector3f>& vertices() const { return vertices_; }
   const std::vector<Eigen::Vector3f>& vertex_colors() const { return vertex_colors_; }
   const std::vector<Eigen::Vector3i>& vertex_indices() const { return vertex_indices_; }
@@ -23,12 +40,16 @@ class Mesh {
   std::vector<Eigen::Vector3f>* mutable_vertices() { return &vertices_; }
   std::vector<Eigen::Vector3i>* mutable_vertex_indices() { return &vertex_indices_; }
   bool WritePly(const std::string& ply_path) const;        // ASCII, reference format
-  bool WritePlyBinary(const std::string& ply_path) const;  // binary_little_endian, for large meshes
+  // binary_little_endian, for large meshes; with nx ny nz after z when normals().size() == vertices().size()
+  bool WritePlyBinary(const std::string& ply_path) const;
 
  private:
   std::vector<Eigen::Vector3f> vertices_;
   std::vector<Eigen::Vector3f> vertex_colors_;
   std::vector<Eigen::Vector3i> vertex_indices_;
+  std::vector<Eigen::Vector3f> normals_;
+  std::vector<Eigen::Vector3f> face_normals_;
+  std::vector<Eigen::Vector3i> normal_indices_;
 };
 
 }  // namespace vacancy

@@ -103,6 +103,9 @@ class VoxelCarver {
   bool Carve(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes);
   void ExtractVoxel(Mesh* mesh, bool inside_empty = false);
   void ExtractIsoSurface(Mesh* mesh, double iso_level = 0.0, bool linear_interp = true);
+  // with_normals: the mesh's normals(), face_normals() and normal_indices() as well -- Mesh::CalcNormal() of the result,
+  // computed on the device behind the extraction (vcy_extract_iso_normals), bit-equal to calling CalcNormal() afterwards
+  void ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals);
 
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;

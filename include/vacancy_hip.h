@@ -244,6 +244,38 @@ int vcy_last_extract_ms(const vcy_ctx* ctx, float* device_ms);
  * 226-227).  The arrays of a vcy_mesh are page-locked host memory from a pool owned by the library. */
 int vcy_last_extract_wall_ms(const vcy_ctx* ctx, float* wall_ms);
 
+/* ---- normals of the iso surface ------------------------------------------ */
+
+#define VCY_NORMALS_VERTEX 1
+#define VCY_NORMALS_FACE   2
+typedef struct vcy_mesh_normals {
+  float* vertex_normals;  /* 3 * n_vertices or NULL */
+  float* face_normals;    /* 3 * n_faces or NULL    */
+} vcy_mesh_normals;
+/* vcy_extract_iso plus Mesh::CalcNormal (mesh.cc:197-240) of its result, computed on the device.
+ * `which` = bit set of VCY_NORMALS_*.  The mesh (positions, faces, keys, n_foreign_vertices) is bit for bit what
+ * vcy_extract_iso returns; the normals' bits equal vcy_mesh_normals_host on that mesh: face normal =
+ * ((p1 - p0).normalized() x (p2 - p0).normalized()).normalized(), vertex normal = the face normals of the faces that
+ * name the vertex summed in ASCENDING FACE INDEX (once per corner), divided by their number, normalised -- float, with
+ * the evaluation order of include/vacancy/linalg.h.  Two launches behind the extraction's last kernel: one thread per
+ * face over the emitted arrays, and one thread per surface cell that sums, for every edge the cell owns, over the
+ * cells around that edge in raster order (no atomics, no sorting).  The mesh is staged in device memory whatever
+ * "mcdirect" says (the face kernel reads it there), so the call waits twice, like an extraction above that threshold.
+ * The arrays are page-locked host memory of the library's pool: vcy_mesh_normals_free.  An empty mesh has none.
+ * VCY_ERR_UNSUPPORTED for a context that does not own the whole grid (z_begin > 0 or z_end < nz): a vertex on a slab's
+ * top or bottom plane has faces in the neighbouring slab -- merge the slabs' meshes and use vcy_mesh_normals_host. */
+int vcy_extract_iso_normals(vcy_ctx* ctx, double iso_level, int linear_interp, int which,
+                            vcy_mesh* out, vcy_mesh_normals* normals_out);
+void vcy_mesh_normals_free(vcy_mesh_normals* n);
+/* Device milliseconds of the normals launches of the last vcy_extract_iso_normals (0 after vcy_extract_iso);
+ * vcy_last_extract_ms stays the mesh kernels alone. */
+int vcy_last_normals_ms(const vcy_ctx* ctx, float* device_ms);
+/* Mesh::CalcFaceNormal + Mesh::CalcNormal (mesh.cc:197-240) on raw arrays, serial, on the host (no GPU needed).
+ * face_normals (3*n_faces) and/or vertex_normals (3*n_vertices) may be NULL.  A vertex no face names gets 0 / 0 = NaN,
+ * as in the reference.  VCY_ERR_INVALID_ARG when a face names a vertex outside [0, n_vertices). */
+int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vertices,
+                          const int32_t* faces, float* vertex_normals, float* face_normals);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and

@@ -80,6 +80,17 @@ class Mesh(C.Structure):
     ]
 
 
+class MeshNormals(C.Structure):
+    """vcy_mesh_normals: what vcy_extract_iso_normals returns next to the Mesh."""
+    _fields_ = [
+        ("vertex_normals", C.POINTER(C.c_float)),
+        ("face_normals", C.POINTER(C.c_float)),
+    ]
+
+
+VCY_NORMALS_VERTEX, VCY_NORMALS_FACE = 1, 2
+
+
 # vcy_mesh_arrays_fn: int (*)(void* user, int64 n_vertices, int64 n_faces, float** vertices, int32** faces)
 MeshArraysFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.POINTER(C.c_float)),
                            C.POINTER(C.POINTER(C.c_int32)))
@@ -136,6 +147,10 @@ def load():
         "vcy_make_sdf_device": (C.c_int, [vp, vp, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32),
                                           C.c_int, C.c_int, C.c_float, P(vp)]),
         "vcy_extract_iso": (C.c_int, [vp, C.c_double, C.c_int, P(Mesh)]),
+        "vcy_extract_iso_normals": (C.c_int, [vp, C.c_double, C.c_int, C.c_int, P(Mesh), P(MeshNormals)]),
+        "vcy_mesh_normals_free": (None, [P(MeshNormals)]),
+        "vcy_last_normals_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_extract_voxel": (C.c_int, [vp, C.c_int, P(Mesh)]),
         "vcy_extract_voxel_ids": (C.c_int, [vp, C.c_int, P(P(C.c_int64)), P(C.c_int64)]),
         "vcy_ids_free": (None, [P(C.c_int64)]),

@@ -28,6 +28,19 @@ def last_error():
     return capi.load().vcy_last_error().decode()
 
 
+def mesh_normals_host(vertices, faces):
+    """vcy_mesh_normals_host: Mesh::CalcFaceNormal + Mesh::CalcNormal (reference mesh.cc:197-240) of a mesh in host
+    arrays, serial, no GPU needed.  Returns (vertex normals [n_vertices, 3], face normals [n_faces, 3]), float32."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    vn = np.zeros((len(v), 3), np.float32)
+    fn = np.zeros((len(f), 3), np.float32)
+    rc = capi.load().vcy_mesh_normals_host(len(v), len(f), _p(v), _p(f), _p(vn), _p(fn))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return vn, fn
+
+
 class VoxelCarver:
     def __init__(self, option=None, device_id=0, z_range=None):
         self._lib = capi.load()
@@ -176,11 +189,20 @@ class VoxelCarver:
         return self._lib.vcy_carve_batch_device(self._ctx, n, arr, ptrs) == 0
 
     # -- ExtractIsoSurface(mesh, iso_level, linear_interp)  (voxel_carver.cc:540-543)
-    def ExtractIsoSurface(self, iso_level=0.0, linear_interp=True):
+    def ExtractIsoSurface(self, iso_level=0.0, linear_interp=True, normals=False):
+        """normals=True: vcy_extract_iso_normals -- the dict gains "normals" (per vertex), "face_normals" and
+        "normals_device_ms": Mesh::CalcNormal of the mesh, computed on the device (bit-equal to mesh_normals_host)."""
         m = Mesh()
-        rc = self._lib.vcy_extract_iso(self._ctx, iso_level, int(linear_interp), C.byref(m))
+        mn = capi.MeshNormals()
+        if normals:
+            rc = self._lib.vcy_extract_iso_normals(self._ctx, iso_level, int(linear_interp),
+                                                   capi.VCY_NORMALS_VERTEX | capi.VCY_NORMALS_FACE, C.byref(m),
+                                                   C.byref(mn))
+        else:
+            rc = self._lib.vcy_extract_iso(self._ctx, iso_level, int(linear_interp), C.byref(m))
         if rc != 0:
             self._lib.vcy_mesh_free(C.byref(m))
+            self._lib.vcy_mesh_normals_free(C.byref(mn))
             raise RuntimeError(last_error())
         nv, nf = m.n_vertices, m.n_faces
         out = {
@@ -189,8 +211,14 @@ class VoxelCarver:
             "keys": _mesh_array(m.edge_keys, nv, 2, np.int64),
             "n_foreign": int(m.n_foreign_vertices),
         }
-        self._lib.vcy_mesh_free(C.byref(m))
         ms = C.c_float()
+        if normals:
+            out["normals"] = _mesh_array(mn.vertex_normals, nv, 3, np.float32)
+            out["face_normals"] = _mesh_array(mn.face_normals, nf, 3, np.float32)
+            self._lib.vcy_mesh_normals_free(C.byref(mn))
+            self._lib.vcy_last_normals_ms(self._ctx, C.byref(ms))
+            out["normals_device_ms"] = ms.value
+        self._lib.vcy_mesh_free(C.byref(m))
         self._lib.vcy_last_extract_ms(self._ctx, C.byref(ms))
         out["device_ms"] = ms.value
         self._lib.vcy_last_extract_wall_ms(self._ctx, C.byref(ms))

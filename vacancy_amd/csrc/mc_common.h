@@ -1,0 +1,185 @@
+// What the marching-cubes translation units share (mc_kernels.hip: the extraction chain; mc_normals.hip: the
+// normals behind it): the cell-word layout, the case tables' shape, VertexInterp and the block scan.  Everything
+// here has internal linkage or is inline, so each translation unit gets its own copy and no relocatable device
+// code is needed.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace vcy {
+namespace mc {
+
+typedef unsigned long long u64;
+
+struct McTables {
+  int8_t tri[256][16];     // edge numbers, -1 terminated (reference kTriTable)
+  uint8_t ntri[256];
+  uint16_t prec[256][12];  // prec[c][e] = edges whose vertex the serial scan creates before e's
+};
+
+// corner offsets relative to the cell's max corner (x,y,z), marching_cubes.cc:93-101
+static __device__ const int8_t kCornerOff[8][3] = {{-1, -1, -1}, {0, -1, -1}, {0, 0, -1}, {-1, 0, -1},
+                                            {-1, -1, 0},  {0, -1, 0},  {0, 0, 0},  {-1, 0, 0}};
+// interpolation argument order per edge (:138-197) and key order (always lower id first)
+static __device__ const int8_t kEdgeA[12] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3};
+static __device__ const int8_t kEdgeB[12] = {1, 2, 3, 0, 5, 6, 7, 4, 4, 5, 6, 7};
+
+// Cell (x, y, z) is named by its max corner; bit b of word w of a row is x = 64*w + b.
+// Cell rows: layer li = 0 is the ghost layer (z = zc0-1), li = l+1 the slab's own layer l;
+// word index of (li, cy = y-1, w):  li == 0 ? cy*Wr + w : G + ((li-1)*Yc + cy)*Wr + w,
+// Yc >= Y = rows a layer takes in the cell-word arrays (the sweep pads a layer to whole row groups, so that
+// a group is a whole number of 256-word blocks; padding rows hold no active cell),
+// G = ghost words rounded up to a whole block so that own cells start on a block boundary.
+// Exact n / d for 32-bit unsigned n (Granlund-Montgomery): three integer instructions instead of the
+// long 64-bit division sequence.
+struct FastDiv {
+  uint32_t d, m, s1, s2;
+};
+
+struct McParams {
+  const float* sdf;   // slab incl. halo slices
+  const void* cnt;
+  const float* px;
+  const float* py;
+  const float* pz;
+  const u64* in;      // bit planes [slice][y][Wr]
+  const u64* ok;
+  const u64* tc;
+  int nx, ny;
+  int nslices;        // stored voxel slices
+  int Wr;             // 64-bit words per row
+  int Y;              // cell rows per layer = ny-1
+  int Yc;             // rows per layer in the cell-word arrays (>= Y)
+  int L;              // own cell layers
+  int zc0;            // global z of own layer 0
+  int zs0;            // global z of stored slice 0
+  int has_ghost;
+  int64_t G;          // words reserved for the ghost layer
+  int64_t nwords;     // G + L*Yc*Wr
+  double iso;
+  int linear;
+  FastDiv div_row, div_layer;  // by Wr and by Yc * Wr; used when small32 (every word index < 2^32)
+  int small32;
+};
+
+constexpr int kWordsPerBlock = 256;
+
+__device__ __forceinline__ uint32_t fast_div(uint32_t n, const FastDiv& f) {
+  const uint32_t t = __umulhi(n, f.m);
+  return (t + ((n - t) >> f.s1)) >> f.s2;
+}
+
+__device__ __forceinline__ bool decode_word(const McParams& p, int64_t cw, int* li, int* cy, int* w) {
+  if (p.small32) {
+    uint32_t r;
+    if (cw < p.G) {
+      if (cw >= (int64_t)p.Yc * p.Wr) return false;  // padding
+      *li = 0;
+      r = (uint32_t)cw;
+    } else {
+      const uint32_t q = (uint32_t)(cw - p.G);
+      const uint32_t layer = fast_div(q, p.div_layer);
+      *li = (int)layer + 1;
+      r = q - layer * p.div_layer.d;
+    }
+    const uint32_t row = fast_div(r, p.div_row);
+    *cy = (int)row;
+    *w = (int)(r - row * p.div_row.d);
+    return *cy < p.Y;  // (rows Y .. Yc-1 are padding)
+  }
+  int64_t r;
+  if (cw < p.G) {
+    if (cw >= (int64_t)p.Yc * p.Wr) return false;  // padding
+    *li = 0;
+    r = cw;
+  } else {
+    const int64_t q = cw - p.G;
+    const int64_t layer = q / ((int64_t)p.Yc * p.Wr);
+    *li = (int)layer + 1;
+    r = q - layer * ((int64_t)p.Yc * p.Wr);
+  }
+  *cy = (int)(r / p.Wr);
+  *w = (int)(r - (int64_t)(*cy) * p.Wr);
+  return *cy < p.Y;
+}
+
+__device__ __forceinline__ int64_t word_index(const McParams& p, int li, int cy, int w) {
+  return (li == 0 ? 0 : p.G + (int64_t)(li - 1) * p.Yc * p.Wr) + (int64_t)cy * p.Wr + w;
+}
+
+__device__ __forceinline__ bool neighbour_active(const McParams& p, const u64* __restrict__ act, int li,
+                                                 int cy, int x, int dx, int dy, int dl) {
+  const int nl = li + dl, ncy = cy + dy, nxx = x + dx;
+  if (nl < 0 || ncy < 0 || ncy >= p.Y || nxx < 1 || nxx >= p.nx) return false;
+  return (act[word_index(p, nl, ncy, nxx >> 6)] >> (nxx & 63)) & 1ull;
+}
+
+// ---- block-level exclusive scan (256 threads = 4 waves) ---------------------------------------
+__device__ __forceinline__ int wave_inclusive_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+__device__ __forceinline__ int block_exclusive_scan(int v, int* total, int* sm /*[4]*/) {
+  const int incl = wave_inclusive_scan(v);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 63) sm[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int s = sm[w];
+    if (w < wave) base += s;
+    tot += s;
+  }
+  *total = tot;
+  return base + incl - v;
+}
+
+// VertexInterp, marching_cubes.cc:25-57 (fp64, then cast)
+__device__ __forceinline__ void vertex_interp(double iso, const float pa[3], const float pb[3], float va,
+                                              float vb, bool linear, float out[3]) {
+  if (!linear) {
+    out[0] = pa[0]; out[1] = pa[1]; out[2] = pa[2];
+    return;
+  }
+  const double v1 = va, v2 = vb;
+  if (fabs(iso - v1) < 0.00001) { out[0] = pa[0]; out[1] = pa[1]; out[2] = pa[2]; return; }
+  if (fabs(iso - v2) < 0.00001) { out[0] = pb[0]; out[1] = pb[1]; out[2] = pb[2]; return; }
+  if (fabs(v1 - v2) < 0.00001) { out[0] = pa[0]; out[1] = pa[1]; out[2] = pa[2]; return; }
+  const double mu = (iso - v1) / (v2 - v1);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = (float)((double)pa[k] + mu * ((double)pb[k] - (double)pa[k]));
+}
+
+// mc_normals.hip: Mesh::CalcFaceNormal + Mesh::CalcNormal (reference mesh.cc:197-240) of the mesh mc_emit has just
+// been enqueued for, behind it on the same stream.  Every pointer is device memory; `verts` / `faces` are the DEVICE
+// staging of the mesh.  vertex_normals / face_normals may be null.  The kernels read the counts where the chain left
+// them and return without a store when a capacity is exceeded, exactly as mc_emit does.
+struct NormalsLaunch {
+  const McTables* T;
+  const u64* act;
+  const u64* cell_list;
+  const u64* ncells_dev;
+  int64_t cap_cells;
+  const uint32_t* info;
+  const u64* block_offs;
+  const u64* grand_total_dev;
+  int64_t cap_verts, cap_faces;
+  const float* verts;
+  const int* faces;
+  float* vertex_normals;
+  float* face_normals;
+};
+hipError_t launch_normals(hipStream_t stream, const McParams& p, const NormalsLaunch& a);
+
+}  // namespace mc
+}  // namespace vcy

@@ -37,24 +37,21 @@
 #include <utility>
 #include <vector>
 
+#include "mc_common.h"
 #include "vcy_internal.h"
 
 namespace vcy {
 
+using namespace mc;
+
 namespace {
 
-typedef unsigned long long u64;
 
 // ---- tables ------------------------------------------------------------------------------
 const char* const kCaseStrings[256] = {
 #include "vacancy_mc_cases.inc"
 };
 
-struct McTables {
-  int8_t tri[256][16];     // edge numbers, -1 terminated (reference kTriTable)
-  uint8_t ntri[256];
-  uint16_t prec[256][12];  // prec[c][e] = edges whose vertex the serial scan creates before e's
-};
 
 void build_tables(McTables* t) {
   std::memset(t, 0, sizeof(*t));
@@ -78,12 +75,6 @@ void build_tables(McTables* t) {
   }
 }
 
-// corner offsets relative to the cell's max corner (x,y,z), marching_cubes.cc:93-101
-__device__ const int8_t kCornerOff[8][3] = {{-1, -1, -1}, {0, -1, -1}, {0, 0, -1}, {-1, 0, -1},
-                                            {-1, -1, 0},  {0, -1, 0},  {0, 0, 0},  {-1, 0, 0}};
-// interpolation argument order per edge (:138-197) and key order (always lower id first)
-__device__ const int8_t kEdgeA[12] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3};
-__device__ const int8_t kEdgeB[12] = {1, 2, 3, 0, 5, 6, 7, 4, 4, 5, 6, 7};
 __device__ const int8_t kKeyA[12] = {0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3};
 __device__ const int8_t kKeyB[12] = {1, 2, 2, 3, 5, 6, 6, 7, 4, 5, 6, 7};
 
@@ -112,45 +103,6 @@ __device__ const int8_t kNbr[kNbrCount][3] = {{0, -1, -1}, {0, 0, -1}, {0, -1, 0
 __device__ const int8_t kShareNbr[12][3] = {{0, 1, 2}, {1, 3, 0}, {1, 4, 0}, {5, 1, 6}, {2, 0, 0}, {0, 0, 0},
                                             {0, 0, 0}, {6, 0, 0}, {7, 2, 6}, {2, 8, 0}, {0, 0, 0}, {6, 0, 0}};
 
-// Cell (x, y, z) is named by its max corner; bit b of word w of a row is x = 64*w + b.
-// Cell rows: layer li = 0 is the ghost layer (z = zc0-1), li = l+1 the slab's own layer l;
-// word index of (li, cy = y-1, w):  li == 0 ? cy*Wr + w : G + ((li-1)*Yc + cy)*Wr + w,
-// Yc >= Y = rows a layer takes in the cell-word arrays (the sweep pads a layer to whole row groups, so that
-// a group is a whole number of 256-word blocks; padding rows hold no active cell),
-// G = ghost words rounded up to a whole block so that own cells start on a block boundary.
-// Exact n / d for 32-bit unsigned n (Granlund-Montgomery): three integer instructions instead of the
-// long 64-bit division sequence.
-struct FastDiv {
-  uint32_t d, m, s1, s2;
-};
-
-struct McParams {
-  const float* sdf;   // slab incl. halo slices
-  const void* cnt;
-  const float* px;
-  const float* py;
-  const float* pz;
-  const u64* in;      // bit planes [slice][y][Wr]
-  const u64* ok;
-  const u64* tc;
-  int nx, ny;
-  int nslices;        // stored voxel slices
-  int Wr;             // 64-bit words per row
-  int Y;              // cell rows per layer = ny-1
-  int Yc;             // rows per layer in the cell-word arrays (>= Y)
-  int L;              // own cell layers
-  int zc0;            // global z of own layer 0
-  int zs0;            // global z of stored slice 0
-  int has_ghost;
-  int64_t G;          // words reserved for the ghost layer
-  int64_t nwords;     // G + L*Yc*Wr
-  double iso;
-  int linear;
-  FastDiv div_row, div_layer;  // by Wr and by Yc * Wr; used when small32 (every word index < 2^32)
-  int small32;
-};
-
-constexpr int kWordsPerBlock = 256;
 
 // ---- pass 0: bit planes ----------------------------------------------------------------------
 // One wave turns kBitsWordsPerWave consecutive 64-voxel words into plane words; all loads of a
@@ -348,48 +300,6 @@ __global__ __launch_bounds__(256) void mc_bits_bricks_kernel(const float* __rest
 }
 
 // ---- shared cell-word helpers -----------------------------------------------------------------
-__device__ __forceinline__ uint32_t fast_div(uint32_t n, const FastDiv& f) {
-  const uint32_t t = __umulhi(n, f.m);
-  return (t + ((n - t) >> f.s1)) >> f.s2;
-}
-
-__device__ __forceinline__ bool decode_word(const McParams& p, int64_t cw, int* li, int* cy, int* w) {
-  if (p.small32) {
-    uint32_t r;
-    if (cw < p.G) {
-      if (cw >= (int64_t)p.Yc * p.Wr) return false;  // padding
-      *li = 0;
-      r = (uint32_t)cw;
-    } else {
-      const uint32_t q = (uint32_t)(cw - p.G);
-      const uint32_t layer = fast_div(q, p.div_layer);
-      *li = (int)layer + 1;
-      r = q - layer * p.div_layer.d;
-    }
-    const uint32_t row = fast_div(r, p.div_row);
-    *cy = (int)row;
-    *w = (int)(r - row * p.div_row.d);
-    return *cy < p.Y;  // (rows Y .. Yc-1 are padding)
-  }
-  int64_t r;
-  if (cw < p.G) {
-    if (cw >= (int64_t)p.Yc * p.Wr) return false;  // padding
-    *li = 0;
-    r = cw;
-  } else {
-    const int64_t q = cw - p.G;
-    const int64_t layer = q / ((int64_t)p.Yc * p.Wr);
-    *li = (int)layer + 1;
-    r = q - layer * ((int64_t)p.Yc * p.Wr);
-  }
-  *cy = (int)(r / p.Wr);
-  *w = (int)(r - (int64_t)(*cy) * p.Wr);
-  return *cy < p.Y;
-}
-
-__device__ __forceinline__ int64_t word_index(const McParams& p, int li, int cy, int w) {
-  return (li == 0 ? 0 : p.G + (int64_t)(li - 1) * p.Yc * p.Wr) + (int64_t)cy * p.Wr + w;
-}
 
 // padded per-cell index (info array)
 __device__ __forceinline__ int64_t cell_slot(int64_t cw, int b) { return cw * 64 + b; }
@@ -474,12 +384,6 @@ __device__ __forceinline__ int cut_edges(int c) {
   return m;
 }
 
-__device__ __forceinline__ bool neighbour_active(const McParams& p, const u64* __restrict__ act, int li,
-                                                 int cy, int x, int dx, int dy, int dl) {
-  const int nl = li + dl, ncy = cy + dy, nxx = x + dx;
-  if (nl < 0 || ncy < 0 || ncy >= p.Y || nxx < 1 || nxx >= p.nx) return false;
-  return (act[word_index(p, nl, ncy, nxx >> 6)] >> (nxx & 63)) & 1ull;
-}
 
 __device__ __forceinline__ int owned_edges(const McParams& p, const u64* __restrict__ act, int code, int li,
                                            int cy, int x, int* nactive_out = nullptr) {
@@ -512,33 +416,6 @@ __device__ __forceinline__ int owned_edges(const McParams& p, const u64* __restr
   return owned;
 }
 
-// ---- block-level exclusive scan (256 threads = 4 waves) ---------------------------------------
-__device__ __forceinline__ int wave_inclusive_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int* total, int* sm /*[4]*/) {
-  const int incl = wave_inclusive_scan(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 63) sm[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const int s = sm[w];
-    if (w < wave) base += s;
-    tot += s;
-  }
-  *total = tot;
-  return base + incl - v;
-}
 
 // ---- pass 1: active cells, counted per word --------------------------------------------------
 // A workgroup handles kActiveBlocks consecutive blocks of 256 words, and every thread requests the corner
@@ -1125,21 +1002,6 @@ __device__ __forceinline__ int64_t vertex_id_of(const McTables* T, const uint32_
   return (int64_t)(block_offs[i >> 8] >> 32) + in_block + __popc(owned & T->prec[code][edge]);
 }
 
-// VertexInterp, marching_cubes.cc:25-57 (fp64, then cast)
-__device__ __forceinline__ void vertex_interp(double iso, const float pa[3], const float pb[3], float va,
-                                              float vb, bool linear, float out[3]) {
-  if (!linear) {
-    out[0] = pa[0]; out[1] = pa[1]; out[2] = pa[2];
-    return;
-  }
-  const double v1 = va, v2 = vb;
-  if (fabs(iso - v1) < 0.00001) { out[0] = pa[0]; out[1] = pa[1]; out[2] = pa[2]; return; }
-  if (fabs(iso - v2) < 0.00001) { out[0] = pb[0]; out[1] = pb[1]; out[2] = pb[2]; return; }
-  if (fabs(v1 - v2) < 0.00001) { out[0] = pa[0]; out[1] = pa[1]; out[2] = pa[2]; return; }
-  const double mu = (iso - v1) / (v2 - v1);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) out[k] = (float)((double)pa[k] + mu * ((double)pb[k] - (double)pa[k]));
-}
 
 // Output staging of one block of 256 active cells.  A block's vertices and triangles are contiguous
 // ranges of the output arrays (cells are numbered in list order), so they are assembled in LDS and
@@ -1409,7 +1271,7 @@ int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long lo
 
 // ---- host driver ----------------------------------------------------------------------------
 
-int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
+int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int which, vcy_mesh_normals* normals_out) {
   out->n_vertices = out->n_faces = out->n_foreign_vertices = 0;
   out->vertices = nullptr;  // an empty mesh has no arrays
   out->faces = nullptr;
@@ -1436,6 +1298,8 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
   p.iso = iso;
   p.linear = linear_interp;
   c->last_extract_device_ms = 0.0f;
+  c->last_normals_device_ms = 0.0f;
+  if (normals_out == nullptr) which = 0;
   if (c->nx < 2 || p.Y <= 0 || p.L <= 0) return VCY_OK;  // no cells (reference loops do not run)
   // One sweep (mc_sweep_kernel) needs a voxel row that is a power-of-two number of whole words.  It moves 2 % fewer
   // bytes than the bit planes in memory (mc_bits + mc_active) but is not faster anywhere (sweep / planes, one box:
@@ -1741,7 +1605,9 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
     const size_t sz_k = align(sizeof(long long) * 2 * (size_t)std::max<int64_t>(cap_v, 1));
     const size_t sz_f = align(sizeof(int) * 3 * (size_t)std::max<int64_t>(cap_f, 1));
     direct = false;
-    if ((int64_t)(sz_v + sz_f + (c->mesh_keys ? sz_k : 0)) <= c->mc_direct_bytes) {
+    // (with normals the mesh is staged on the device: mc_face_normals reads the emitted arrays, and must not read them
+    // back over PCIe)
+    if (which == 0 && (int64_t)(sz_v + sz_f + (c->mesh_keys ? sz_k : 0)) <= c->mc_direct_bytes) {
       bool pinned = true, pk = true, pf = true;
       out->vertices = (float*)mesh_host_alloc(sz_v, &pinned);
       out->faces = (int32_t*)mesh_host_alloc(sz_f, &pf);
@@ -1772,6 +1638,50 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
     MC_TRY(hipGetLastError());
     return VCY_OK;
   };
+  // Normals (vcy_extract_iso_normals): two more launches behind mc_emit, behind the same capacity checks (they read
+  // the counts themselves), enqueued again with the chain when a guess was too small.  Their own event pair:
+  // last_extract_device_ms stays "the mesh kernels".
+  float* d_vn = nullptr;
+  float* d_fn = nullptr;
+  bool normals_timed = false;
+  auto enqueue_normals = [&](const CellBuffers& b, int64_t cap_cells, int64_t cap_v, int64_t cap_f) -> int {
+    const size_t sz_vn = (which & VCY_NORMALS_VERTEX) ? align(sizeof(float) * 3 * (size_t)std::max<int64_t>(cap_v, 1)) : 0;
+    const size_t sz_fn = (which & VCY_NORMALS_FACE) ? align(sizeof(float) * 3 * (size_t)std::max<int64_t>(cap_f, 1)) : 0;
+    if (c->mc_normals_bytes < sz_vn + sz_fn) {
+      MC_TRY(hipStreamSynchronize(s));
+      if (c->d_mc_normals) MC_TRY(hipFree(c->d_mc_normals));
+      c->d_mc_normals = nullptr;
+      c->mc_normals_bytes = 0;
+      MC_TRY(hipMalloc(&c->d_mc_normals, sz_vn + sz_fn));
+      c->mc_normals_bytes = sz_vn + sz_fn;
+    }
+    d_vn = sz_vn ? (float*)c->d_mc_normals : nullptr;
+    d_fn = sz_fn ? (float*)((char*)c->d_mc_normals + sz_vn) : nullptr;
+    if (!c->ev_nrm_begin) {
+      MC_TRY(hipEventCreate(&c->ev_nrm_begin));
+      MC_TRY(hipEventCreate(&c->ev_nrm_end));
+    }
+    NormalsLaunch a;
+    a.T = T;
+    a.act = d_act;
+    a.cell_list = b.list;
+    a.ncells_dev = d_total;
+    a.cap_cells = cap_cells;
+    a.info = b.info;
+    a.block_offs = b.counts;
+    a.grand_total_dev = b.total;
+    a.cap_verts = cap_v;
+    a.cap_faces = cap_f;
+    a.verts = d_verts;
+    a.faces = d_faces;
+    a.vertex_normals = d_vn;
+    a.face_normals = d_fn;
+    MC_TRY(hipEventRecord(c->ev_nrm_begin, s));
+    MC_TRY(launch_normals(s, p, a));
+    MC_TRY(hipEventRecord(c->ev_nrm_end, s));
+    normals_timed = true;
+    return VCY_OK;
+  };
   // number of active cells, and how many of them are ghost cells (words below G)
   int64_t ncells = 0, nghost = 0, nv = 0, nf = 0, nforeign = 0;
   CellBuffers cb{};
@@ -1798,6 +1708,10 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
     // (the end of the kernels: last_extract_device_ms is "kernels only")
     MC_TRY(hipEventRecord(c->ev_mc_end, s));
     end_recorded = true;
+    if (which != 0) {
+      rc = enqueue_normals(cb, cap_cells, cap_v, cap_f);
+      if (rc != VCY_OK) return rc;
+    }
     if (timing) t_ph[1] = now_us();
     MC_TRY(hipStreamSynchronize(s));  // the ONE wait of an extraction whose mesh went straight to host memory
     if (timing) t_ph[2] = now_us();
@@ -1835,6 +1749,10 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
       }
       MC_TRY(hipEventRecord(c->ev_mc_end, s));
       end_recorded = true;
+      if (which != 0) {
+        rc = enqueue_normals(cb, cap_cells, with_headroom(nv), with_headroom(nf));
+        if (rc != VCY_OK) return rc;
+      }
       MC_TRY(hipStreamSynchronize(s));
       read_report();
     } else {
@@ -1879,7 +1797,28 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
         MC_TRY(hipMemcpyAsync(out->edge_keys, d_keys, sizeof(long long) * 2 * (size_t)nv, hipMemcpyDeviceToHost, s));
     }
     if (nf > 0) MC_TRY(hipMemcpyAsync(out->faces, d_faces, sizeof(int) * 3 * (size_t)nf, hipMemcpyDeviceToHost, s));
+    if (which != 0 && ncells > 0) {
+      // (the caller -- vcy_extract_iso_normals -- releases both structs when this function fails)
+      if ((which & VCY_NORMALS_VERTEX) && nv > 0) {
+        normals_out->vertex_normals = (float*)mesh_host_alloc(sizeof(float) * 3 * (size_t)nv);
+        if (!normals_out->vertex_normals) {
+          set_error("out of host memory for the normals");
+          return VCY_ERR_INTERNAL;
+        }
+        MC_TRY(hipMemcpyAsync(normals_out->vertex_normals, d_vn, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, s));
+      }
+      if ((which & VCY_NORMALS_FACE) && nf > 0) {
+        normals_out->face_normals = (float*)mesh_host_alloc(sizeof(float) * 3 * (size_t)nf);
+        if (!normals_out->face_normals) {
+          set_error("out of host memory for the normals");
+          return VCY_ERR_INTERNAL;
+        }
+        MC_TRY(hipMemcpyAsync(normals_out->face_normals, d_fn, sizeof(float) * 3 * (size_t)nf, hipMemcpyDeviceToHost, s));
+      }
+    }
     if (nv > 0 || nf > 0) MC_TRY(hipStreamSynchronize(s));
+    if (normals_timed && ncells > 0) MC_TRY(hipEventSynchronize(c->ev_nrm_end));
+    if (normals_timed && ncells > 0) MC_TRY(hipEventElapsedTime(&c->last_normals_device_ms, c->ev_nrm_begin, c->ev_nrm_end));
   }
   out->n_vertices = nv;
   out->n_faces = nf;

@@ -507,6 +507,9 @@ void vcy_destroy(vcy_ctx* c) {
     if (c->ev_uploaded[k]) (void)hipEventDestroy(c->ev_uploaded[k]);
   }
   (void)hipFree(c->d_mc_out);
+  (void)hipFree(c->d_mc_normals);
+  if (c->ev_nrm_begin) (void)hipEventDestroy(c->ev_nrm_begin);
+  if (c->ev_nrm_end) (void)hipEventDestroy(c->ev_nrm_end);
   (void)hipFree(c->d_mc_flags);
   if (c->h_mc_report) (void)hipHostFree(c->h_mc_report);
   (void)hipFree(c->d_mc_cells);
@@ -1724,6 +1727,110 @@ int vcy_extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
   if (rc != VCY_OK) vcy_mesh_free(out);  // (whatever host arrays a failed extraction had already taken from the pool)
   c->last_extract_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
+}
+
+int vcy_extract_iso_normals(vcy_ctx* c, double iso, int linear_interp, int which, vcy_mesh* out,
+                            vcy_mesh_normals* normals_out) {
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  if (!out || !normals_out || (which & ~(VCY_NORMALS_VERTEX | VCY_NORMALS_FACE)) != 0) {
+    set_error("vcy_extract_iso_normals: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  std::memset(out, 0, sizeof(*out));
+  std::memset(normals_out, 0, sizeof(*normals_out));
+  if (c->z0 != 0 || c->z1 != c->nz || c->halo_lo != 0) {
+    // a vertex on a slab's top or bottom plane has faces in the neighbouring slab
+    set_error("vcy_extract_iso_normals: the context owns z [%d, %d) of %d slices; normals need the whole grid "
+              "(merge the slabs' meshes and call vcy_mesh_normals_host)", c->z0, c->z1, c->nz);
+    return VCY_ERR_UNSUPPORTED;
+  }
+  if (which == 0) return vcy_extract_iso(c, iso, linear_interp, out);
+  VCY_HIP_CHECK(hipSetDevice(c->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
+  const int rc = extract_iso(c, iso, linear_interp, out, which, normals_out);
+  if (rc != VCY_OK) {
+    vcy_mesh_free(out);
+    vcy_mesh_normals_free(normals_out);
+  }
+  c->last_extract_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+void vcy_mesh_normals_free(vcy_mesh_normals* n) {
+  if (!n) return;
+  mesh_host_free(n->vertex_normals);
+  mesh_host_free(n->face_normals);
+  std::memset(n, 0, sizeof(*n));
+}
+
+int vcy_last_normals_ms(const vcy_ctx* c, float* device_ms) {
+  if (!c || !device_ms) return VCY_ERR_INVALID_ARG;
+  *device_ms = c->last_normals_device_ms;
+  return VCY_OK;
+}
+
+namespace {
+// Eigen::Vector3f::normalize() as include/vacancy/linalg.h evaluates it
+inline void host_normalize3(float v[3]) {
+  const float n2 = v[0] * v[0] + (v[1] * v[1] + v[2] * v[2]);
+  if (n2 > 0.0f) {
+    const float n = std::sqrt(n2);
+    v[0] = v[0] / n;
+    v[1] = v[1] / n;
+    v[2] = v[2] / n;
+  }
+}
+}  // namespace
+
+int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                          float* vertex_normals, float* face_normals) {
+  if (n_vertices < 0 || n_faces < 0 || (n_vertices > 0 && !vertices) || (n_faces > 0 && !faces)) {
+    set_error("vcy_mesh_normals_host: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  for (int64_t i = 0; i < 3 * n_faces; ++i)
+    if (faces[i] < 0 || faces[i] >= n_vertices) {
+      set_error("vcy_mesh_normals_host: face %lld names vertex %d of %lld", (long long)(i / 3), faces[i], (long long)n_vertices);
+      return VCY_ERR_INVALID_ARG;
+    }
+  std::vector<int> count;
+  if (vertex_normals) {
+    count.assign((size_t)n_vertices, 0);
+    for (int64_t i = 0; i < 3 * n_vertices; ++i) vertex_normals[i] = 0.0f;
+  }
+  for (int64_t i = 0; i < n_faces; ++i) {  // Mesh::CalcFaceNormal (mesh.cc:231-240), then the sum of mesh.cc:213-221
+    const int32_t* f = faces + 3 * i;
+    const float *p0 = vertices + 3 * (int64_t)f[0], *p1 = vertices + 3 * (int64_t)f[1], *p2 = vertices + 3 * (int64_t)f[2];
+    float v1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+    float v2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+    host_normalize3(v1);
+    host_normalize3(v2);
+    float fn[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+    host_normalize3(fn);
+    if (face_normals) face_normals[3 * i + 0] = fn[0], face_normals[3 * i + 1] = fn[1], face_normals[3 * i + 2] = fn[2];
+    if (vertex_normals)
+      for (int j = 0; j < 3; ++j) {
+        float* n = vertex_normals + 3 * (int64_t)f[j];
+        n[0] += fn[0];
+        n[1] += fn[1];
+        n[2] += fn[2];
+        ++count[(size_t)f[j]];
+      }
+  }
+  if (vertex_normals)
+    for (int64_t k = 0; k < n_vertices; ++k) {  // (a vertex no face names: 0 / 0, as in the reference)
+      float* n = vertex_normals + 3 * k;
+      const float d = static_cast<float>(count[(size_t)k]);
+      n[0] = n[0] / d;
+      n[1] = n[1] / d;
+      n[2] = n[2] / d;
+      host_normalize3(n);
+    }
+  return VCY_OK;
 }
 
 int vcy_last_extract_wall_ms(const vcy_ctx* c, float* wall_ms) {

@@ -188,6 +188,10 @@ struct vcy_ctx {
   float last_extract_device_ms = 0.0f;
   float last_extract_wall_ms = 0.0f;  // call entry -> mesh arrays in host memory
   hipEvent_t ev_mc_begin = nullptr, ev_mc_end = nullptr;  // the extraction's own timer
+  void* d_mc_normals = nullptr;       // device staging of the normals of vcy_extract_iso_normals (grow-only)
+  size_t mc_normals_bytes = 0;
+  hipEvent_t ev_nrm_begin = nullptr, ev_nrm_end = nullptr;  // around the normals launches (vcy_last_normals_ms)
+  float last_normals_device_ms = 0.0f;
 
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
@@ -218,7 +222,9 @@ int flush_pending(vcy_ctx* ctx, bool from_carve = false);   // applies vcy_ctx::
 int check_carve_views(vcy_ctx* ctx, int n_views, const vcy_view* views);  // argument checks of the carve entry points (vcy_api.hip)
 int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy_ctx::carve_log, or -1 (vcy_api.hip)
 // mc_kernels.hip
-int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out);
+// `which` (VCY_NORMALS_*) != 0: the normals of the mesh as well, into `normals_out` (mc_normals.hip)
+int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int which = 0,
+                vcy_mesh_normals* normals_out = nullptr);
 // sdf2d.hip
 void host_distance_transform_l1(const uint8_t* mask, int w, int h, const int32_t* rmin,
                                 const int32_t* rmax, float* out);

@@ -4,6 +4,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -109,6 +110,24 @@ int main(int argc, char* argv[]) {
         vacancy::Mesh surface;
         c2.ExtractIsoSurface(&surface, 0.0);
         const double t_mc = now() - t0;
+        {
+          // normals: the device overload (call -> Mesh with normals) next to ExtractIsoSurface + CalcNormal() on the host
+          t0 = now();
+          vacancy::Mesh dn;
+          c2.ExtractIsoSurface(&dn, 0.0, true, true);
+          const double t_dev = now() - t0;
+          t0 = now();
+          vacancy::Mesh hn;
+          c2.ExtractIsoSurface(&hn, 0.0, true);
+          hn.CalcNormal();
+          const double t_host = now() - t0;
+          const bool same = dn.normals().size() == hn.normals().size() &&
+                            (dn.normals().empty() || !std::memcmp(dn.normals().data(), hn.normals().data(), 12 * hn.normals().size())) &&
+                            dn.face_normals().size() == hn.face_normals().size() &&
+                            (dn.face_normals().empty() || !std::memcmp(dn.face_normals().data(), hn.face_normals().data(), 12 * hn.face_normals().size()));
+          std::printf("XVTIME rep %d view %zu: ExtractIsoSurface(with_normals) %.3f ms, ExtractIsoSurface + CalcNormal() on the host %.3f ms (%zu vertices, identical %d)\n",
+                      rep, i, t_dev, t_host, dn.normals().size(), same ? 1 : 0);
+        }
         if (sh) {
           if (!sh->Carve(cam, sil)) return 7;
           t0 = now();
@@ -127,6 +146,46 @@ int main(int argc, char* argv[]) {
                     t_carve, t_xv, voxels.vertices().size(), t_mc, surface.vertices().size());
       }
     }
+    return 0;
+  }
+  if (argc > 3 && std::string(argv[2]) == "normals") {
+    // CPU only: Mesh::CalcNormal through the facade.   host_selftest <data dir> normals <dir>
+    //   reads <dir>/vertices.f32 and <dir>/faces.i32, writes <dir>/normals.f32, face_normals.f32, normal_indices.i32,
+    //   with_normals.ply and without_normals.ply (WritePlyBinary), prints NORMALS <ok> <sizes> <sizes after Clear()>
+    const std::string d = argv[3];
+    auto slurp = [](const std::string& path, std::vector<char>* out) {
+      std::FILE* fp = std::fopen(path.c_str(), "rb");
+      if (!fp) return false;
+      char buf[65536];
+      size_t n;
+      while ((n = std::fread(buf, 1, sizeof(buf), fp)) > 0) out->insert(out->end(), buf, buf + n);
+      std::fclose(fp);
+      return true;
+    };
+    auto dump = [](const std::string& path, const void* p, size_t bytes) {
+      std::FILE* fp = std::fopen(path.c_str(), "wb");
+      if (!fp) return false;
+      if (bytes) std::fwrite(p, 1, bytes, fp);
+      std::fclose(fp);
+      return true;
+    };
+    std::vector<char> vb, fb;
+    if (!slurp(d + "/vertices.f32", &vb) || !slurp(d + "/faces.i32", &fb)) return 4;
+    vacancy::Mesh mesh;
+    mesh.mutable_vertices()->resize(vb.size() / 12);
+    mesh.mutable_vertex_indices()->resize(fb.size() / 12);
+    if (!vb.empty()) std::memcpy(mesh.mutable_vertices()->data(), vb.data(), vb.size());
+    if (!fb.empty()) std::memcpy(mesh.mutable_vertex_indices()->data(), fb.data(), fb.size());
+    bool ok = mesh.WritePlyBinary(d + "/without_normals.ply");
+    mesh.CalcNormal();
+    ok = ok && dump(d + "/normals.f32", mesh.normals().data(), 12 * mesh.normals().size());
+    ok = ok && dump(d + "/face_normals.f32", mesh.face_normals().data(), 12 * mesh.face_normals().size());
+    ok = ok && dump(d + "/normal_indices.i32", mesh.normal_indices().data(), 12 * mesh.normal_indices().size());
+    ok = ok && mesh.WritePlyBinary(d + "/with_normals.ply");
+    const size_t a = mesh.normals().size(), b = mesh.face_normals().size(), c = mesh.normal_indices().size();
+    mesh.Clear();
+    std::printf("NORMALS %d %zu %zu %zu %zu %zu %zu\n", ok ? 1 : 0, a, b, c, mesh.normals().size(), mesh.face_normals().size(),
+                mesh.normal_indices().size());
     return 0;
   }
   if (argc > 3 && std::string(argv[2]) == "io") {

@@ -278,6 +278,11 @@ void ShardedVoxelCarver::ExtractVoxel(Mesh* mesh, bool inside_empty) {
   for (int64_t* p : ids) vcy_ids_free(p);
 }
 
+void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals) {
+  ExtractIsoSurface(mesh, iso_level, linear_interp);
+  if (with_normals) mesh->CalcNormal();
+}
+
 void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp) {
   mesh->Clear();
   const size_t ns = impl_->slabs.size();

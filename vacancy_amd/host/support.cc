@@ -11,6 +11,7 @@
 #include "vacancy/image.h"
 #include "vacancy/log.h"
 #include "vacancy/mesh.h"
+#include "vacancy_hip.h"
 
 namespace vacancy {
 
@@ -36,6 +37,38 @@ VACANCY_LOG_FN(LOGD, kDebug, "[D] ")
 VACANCY_LOG_FN(LOGI, kInfo, "[I] ")
 VACANCY_LOG_FN(LOGW, kWarning, "[W] ")
 VACANCY_LOG_FN(LOGE, kError, "[E] ")
+
+// ---- normals (reference mesh.cc:197-240) --------------------------------------------------------
+void Mesh::CalcFaceNormal() {
+  static_assert(sizeof(Eigen::Vector3f) == 3 * sizeof(float) && sizeof(Eigen::Vector3i) == 3 * sizeof(int32_t), "packed vector layout");
+  face_normals_.clear();
+  face_normals_.resize(vertex_indices_.size());
+  if (vcy_mesh_normals_host((int64_t)vertices_.size(), (int64_t)vertex_indices_.size(),
+                            reinterpret_cast<const float*>(vertices_.data()),
+                            reinterpret_cast<const int32_t*>(vertex_indices_.data()), nullptr,
+                            reinterpret_cast<float*>(face_normals_.data())) != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    face_normals_.clear();
+  }
+}
+
+void Mesh::CalcNormal() {
+  face_normals_.clear();
+  face_normals_.resize(vertex_indices_.size());
+  normals_.clear();
+  normals_.resize(vertices_.size());
+  normal_indices_ = vertex_indices_;
+  if (vcy_mesh_normals_host((int64_t)vertices_.size(), (int64_t)vertex_indices_.size(),
+                            reinterpret_cast<const float*>(vertices_.data()),
+                            reinterpret_cast<const int32_t*>(vertex_indices_.data()),
+                            reinterpret_cast<float*>(normals_.data()),
+                            reinterpret_cast<float*>(face_normals_.data())) != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    normals_.clear();
+    face_normals_.clear();
+    normal_indices_.clear();
+  }
+}
 
 // ---- PLY --------------------------------------------------------------------------------------
 // ASCII layout of the reference writer (mesh.cc:583-631): "x y z \n" with ostream default
@@ -70,11 +103,26 @@ bool Mesh::WritePlyBinary(const std::string& path) const {
     LOGE("couldn't open ply: %s\n", path.c_str());
     return false;
   }
+  const bool with_normals = !vertices_.empty() && normals_.size() == vertices_.size();
   std::fprintf(f,
                "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\n"
-               "property float z\nelement face %zu\nproperty list uchar int vertex_indices\nend_header\n",
-               vertices_.size(), vertex_indices_.size());
-  if (!vertices_.empty()) std::fwrite(vertices_.data(), sizeof(float) * 3, vertices_.size(), f);
+               "property float z\n%selement face %zu\nproperty list uchar int vertex_indices\nend_header\n",
+               vertices_.size(), with_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "",
+               vertex_indices_.size());
+  if (with_normals) {
+    std::vector<float> row(6 * 4096);
+    for (size_t i = 0; i < vertices_.size();) {
+      const size_t n = std::min<size_t>(4096, vertices_.size() - i);
+      for (size_t k = 0; k < n; ++k) {
+        std::memcpy(&row[6 * k], &vertices_[i + k], 12);
+        std::memcpy(&row[6 * k + 3], &normals_[i + k], 12);
+      }
+      std::fwrite(row.data(), 24, n, f);
+      i += n;
+    }
+  } else if (!vertices_.empty()) {
+    std::fwrite(vertices_.data(), sizeof(float) * 3, vertices_.size(), f);
+  }
   std::vector<unsigned char> rec(13 * 4096);
   for (size_t i = 0; i < vertex_indices_.size();) {
     size_t n = std::min<size_t>(4096, vertex_indices_.size() - i);

@@ -292,6 +292,35 @@ void VoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_in
   LOGI("MarchingCubes %02f\n", NowMs() - t0);
 }
 
+void VoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals) {
+  if (!with_normals) {
+    ExtractIsoSurface(mesh, iso_level, linear_interp);
+    return;
+  }
+  mesh->Clear();
+  if (!impl_->ctx) return;
+  const double t0 = NowMs();
+  vcy_mesh m;
+  vcy_mesh_normals n;
+  if (vcy_extract_iso_normals(impl_->ctx, iso_level, linear_interp ? 1 : 0, VCY_NORMALS_VERTEX | VCY_NORMALS_FACE, &m, &n) !=
+      VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    vcy_mesh_free(&m);
+    vcy_mesh_normals_free(&n);
+    LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+    return;
+  }
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  detail::CopyTriples(mesh->mutable_vertices(), m.vertices, static_cast<size_t>(m.n_vertices));
+  detail::CopyTriples(mesh->mutable_vertex_indices(), m.faces, static_cast<size_t>(m.n_faces));
+  detail::CopyTriples(mesh->mutable_normals(), n.vertex_normals, static_cast<size_t>(m.n_vertices));
+  detail::CopyTriples(mesh->mutable_face_normals(), n.face_normals, static_cast<size_t>(m.n_faces));
+  mesh->set_normal_indices(mesh->vertex_indices());
+  vcy_mesh_free(&m);
+  vcy_mesh_normals_free(&n);
+  LOGI("MarchingCubes with normals %02f\n", NowMs() - t0);
+}
+
 void VoxelCarver::ExtractVoxel(Mesh* mesh, bool inside_empty) {
   mesh->Clear();
   if (!impl_->ctx) return;

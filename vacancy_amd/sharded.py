@@ -238,8 +238,15 @@ class ShardedVoxelCarver:
         self._per_device(run)
         return meshes
 
-    def ExtractIsoSurface(self, iso_level=0.0, linear_interp=True):
-        return vdist.merge_meshes(self.extract_slabs(iso_level, linear_interp))
+    def ExtractIsoSurface(self, iso_level=0.0, linear_interp=True, normals=False):
+        """normals=True: "normals" and "face_normals" of the MERGED mesh, by the serial host walk (mesh_normals_host,
+        = Mesh::CalcNormal): a vertex on a slab's boundary plane has faces in two slabs, so the slabs' devices cannot
+        finish the sum on their own.  The bits equal the single-context device result."""
+        mesh = vdist.merge_meshes(self.extract_slabs(iso_level, linear_interp))
+        if normals:
+            from . import carver as _vc
+            mesh["normals"], mesh["face_normals"] = _vc.mesh_normals_host(mesh["vertices"], mesh["faces"])
+        return mesh
 
     # -- ExtractVoxel (voxel_carver.cc:530-538, extract_voxel.cc:258-317): the keep predicate and the compaction run on
     # every slab's device (the on-surface test reads the slice below a slab from its halo), the kept ids are walked in z
