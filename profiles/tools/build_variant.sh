@@ -15,8 +15,9 @@ mkdir -p "$OUT"
 make -C "$SRC" -s $(cd "$SRC" && ls *.hip | grep -v -e "^$VSRC\$" $([ "$VSRC" = carve_fused.hip ] && echo "-e ^carve_fused_u8.hip\$ -e ^carve_fused_u16.hip\$") | sed 's/\.hip$/.o/')
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
  -fno-gpu-flush-denormals-to-zero -Wall -Wno-unused-function -I$ROOT/include -I$SRC -fno-slp-vectorize"
-# (carve_fused.hip is compiled three times: by itself -- host side and small kernels -- and included by the two units that
-# hold the halves of the carve kernel's instances; a variant of it is a variant of all three)
+# (the fused carve step is three units -- carve_fused.hip: host side and pre-pass kernels; carve_fused_u8.hip and
+# carve_fused_u16.hip: the halves of the carve kernel's instances, carve_fused_kernel.h -- that share the tuning defaults
+# of carve_fused.h and the helpers of carve_fused_device.h; a variant of the carve kernel is a variant of all three)
 VSRCS="$VSRC"
 [ "$VSRC" = carve_fused.hip ] && VSRCS="carve_fused.hip carve_fused_u8.hip carve_fused_u16.hip"
 VOBJS=""; EXCL=""

@@ -4,7 +4,7 @@ costs measured on MI355X (profiles/r02/valu_ubench.txt).
 
   profiles/tools/isa_histogram.py [update-mode]     (0 = kMax default kernel, 2 = unit-weight average + truncation)
 
-Compiles vacancy_amd/csrc/carve_fused.hip to assembly (device only, the instantiations bench.py launches),
+Compiles vacancy_amd/csrc/carve_fused_u8.hip to assembly (device only, the instantiations bench.py launches),
 takes carve_fused_kernel<unsigned short, MODE, TRUNC, true, false, 16, false, 2> and prints
   * every opcode with its static count and issue class,
   * the same for every flavour of the select-free run: the straight-line code over a lane's eight voxels in

@@ -2,7 +2,7 @@
 
 The carve kernels skip a (wave brick, view) pair when an upper bound of every sample the brick can take is not above
 the brick's minimum (kMax) or lies below the truncation limit, and compile the `dist < -1` test out where a lower bound
-allows it (footprint_of, carve_fused.hip); marching cubes does not read a brick whose kept minimum lies above the iso
+allows it (footprint_of, carve_fused_device.h); marching cubes does not read a brick whose kept minimum lies above the iso
 level (mc_bits_bricks_kernel).  The smooth and noisy scenes of the other modules cannot tell a tight bound from one
 that is a pixel short: here the images are needle scenes (needle_scenes.py), on which a pair must not be dropped only
 because of one pixel on the outer ring of its footprint, and the states hold one low voxel per brick.  The CPU test at

@@ -1,6 +1,7 @@
 // The other half of the instances of carve_fused_kernel: update_num in TWO bytes (voxel_max_update_num > 254 once more
-// than 255 views have been applied).  See carve_fused_u8.hip; this unit exports launch_fused_counts16.
-#define VCY_FUSED_PART 16
-#define VCY_FUSED_PART_FN launch_fused_counts16
-#define VCY_FUSED_PART_TYPE uint16_t
-#include "carve_fused.hip"
+// than 255 views have been applied), behind launch_fused_counts16.  See carve_fused_u8.hip.
+#include "carve_fused_kernel.h"
+
+namespace vcy {
+void launch_fused_counts16(const CarveLaunch& launch) { launch_fused<uint16_t>(launch); }
+}  // namespace vcy

@@ -89,7 +89,7 @@ struct vcy_ctx {
   int eager_state = -1;               // "eagerstate": few-view launches request a brick's state next to its footprint record instead of behind the early-return test (-1: when most workgroups were live last time, 0 never, 1 always)
   int one_view = 1;                   // "oneview": single-view launches take the kernel instance compiled for one view (carve_fused_kernel NB == 0)
   int nt_store = -1;                  // "ntstore": streaming stores in the cooperative write-back (-1 / 1: whenever it runs -- 0.5 - 1.5 % on single-view launches; 0 never)
-  int row_kernel = 0;                 // "rowkernel": launches of up to this many views take the few-view flavour of the fused kernel (a wave walks the bricks of a row segment); -1 = up to 8, 0 = never (the default: measured slower, carve_fused.hip kRowBricks)
+  int row_kernel = 0;                 // "rowkernel": launches of up to this many views take the few-view flavour of the fused kernel (a wave walks the bricks of a row segment); -1 = up to 8, 0 = never (the default: measured slower, carve_fused.h kRowBricks)
   int mc_skip = 1;                    // marching cubes: bricks whose kept minimum is above the iso level are not read (vcy_set_param "mcskip": 0 never, 1 where it pays -- rows of 1024 voxels and more --, 2 wherever possible)
   bool mc_sweep = false;              // marching cubes: cell search in one sweep with the bit planes in LDS where the row shape allows (vcy_set_param "mcsweep")
   int tile_mode = 0;                  // 0 auto, 1 the 16 x 16 pixel tile, 2 the 2048-pixel tile filled in place (vcy_set_param "tile")
@@ -206,7 +206,7 @@ namespace vcy {
 
 // carve_kernels.hip
 int launch_carve(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* sdf_dev);
-// carve_fused.hip
+// carve_fused.hip (host side and pre-pass of the fused carve step; the kernel: carve_fused_kernel.h)
 struct GridParams;
 struct ViewParams;
 bool fused_eligible(const vcy_ctx* ctx, int n_views, const vcy_view* views);
