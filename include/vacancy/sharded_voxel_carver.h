@@ -44,8 +44,9 @@ class ShardedVoxelCarver {
   bool Carve(const Camera& camera, const Image1b& silhouette);
   bool Carve(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes);
   void ExtractIsoSurface(Mesh* mesh, double iso_level = 0.0, bool linear_interp = true);
-  // with_normals: Mesh::CalcNormal() on the MERGED mesh -- serial, on the host (a vertex on a slab's boundary plane has
-  // faces in two slabs); the bits equal VoxelCarver's device result
+  // with_normals: Mesh::CalcNormal() of the merged mesh.  Every slab's normals come from its own device
+  // (vcy_extract_iso_normals_slab); a vertex on a slab's boundary plane has faces in two slabs, so those -- a plane's
+  // worth per seam -- are finished on the host (vcy_mesh_normals_host_seam).  The bits equal VoxelCarver's device result
   void ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals);
   // VoxelCarver::ExtractVoxel over the slabs: the keep predicate and the compaction run on every slab's device, the
   // kept voxels of all slabs are walked in z order by ONE drifting cube on the host -- the reference's arithmetic

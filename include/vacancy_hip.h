@@ -18,6 +18,9 @@
  *   - outputs that the library allocates are released with the matching *_free;
  *   - one context = one GPU = one caller thread.  A context owns a z-slab
  *     [z_begin, z_end) of the global grid (the whole grid when world size is 1).
+ *     Every stage runs per slab -- carve, SDF producer, marching cubes, ExtractVoxel,
+ *     mesh normals; what spans two slabs (shared-plane vertices, the normals of the
+ *     vertices on a seam plane) is stitched on the host that merges the slabs' results.
  *   - there is NO CPU fallback: if no HIP device is usable, vcy_create fails.
  */
 #ifndef VACANCY_HIP_H_
@@ -263,9 +266,27 @@ typedef struct vcy_mesh_normals {
  * "mcdirect" says (the face kernel reads it there), so the call waits twice, like an extraction above that threshold.
  * The arrays are page-locked host memory of the library's pool: vcy_mesh_normals_free.  An empty mesh has none.
  * VCY_ERR_UNSUPPORTED for a context that does not own the whole grid (z_begin > 0 or z_end < nz): a vertex on a slab's
- * top or bottom plane has faces in the neighbouring slab -- merge the slabs' meshes and use vcy_mesh_normals_host. */
+ * top or bottom plane has faces in the neighbouring slab -- vcy_extract_iso_normals_slab and the seam finish below, or
+ * merge the slabs' meshes and use vcy_mesh_normals_host. */
 int vcy_extract_iso_normals(vcy_ctx* ctx, double iso_level, int linear_interp, int which,
                             vcy_mesh* out, vcy_mesh_normals* normals_out);
+/* The same for a context that owns a z-slab [z_begin, z_end) (any context: for a whole grid the mesh and the normals
+ * are exactly vcy_extract_iso_normals').  The mesh is bit for bit vcy_extract_iso's on that context.  The face normals
+ * are final.  The vertex normals are final for every vertex all of whose faces lie in this slab, i.e. all but the SEAM
+ * vertices: those on x- or y-axis edges in the plane of slice z_begin - 1 that cells of the slab below own (this slab's
+ * first n_foreign_vertices) and, when z_end < nz, those on such edges in the plane of slice z_end - 1 (the foreign
+ * vertices of the slab above).  Their faces lie in two slabs and a float sum cannot be continued as a lump, so their
+ * entries are zero here and the host that merges the slabs finishes them:
+ *   1. concatenate the slabs' normals with the merged numbering (a slab's foreign entries dropped, like its vertices);
+ *   2. per seam, vcy_mesh_normals_host_seam on the MERGED arrays with the face range
+ *      [first face of the upper slab - layer_faces[1] of the lower slab, first face of the upper slab + layer_faces[0]
+ *      of the upper slab) and the merged ids the upper slab's foreign vertices were mapped to by edge key.
+ * layer_faces[0] / [1] = the numbers of faces of the slab's first / last own cell layer (both n_faces for a slab of one
+ * cell layer): the last layer's faces are the end of the slab's face array, the next slab's first layer's the start of
+ * its own, and together they hold every face that names a vertex of the seam between them.
+ * A slab needs "meshkeys" 1 (VCY_ERR_INVALID_ARG otherwise) and its halo installed, as for vcy_extract_iso. */
+int vcy_extract_iso_normals_slab(vcy_ctx* ctx, double iso_level, int linear_interp, int which, vcy_mesh* out,
+                                 vcy_mesh_normals* normals_out, int64_t layer_faces[2]);
 void vcy_mesh_normals_free(vcy_mesh_normals* n);
 /* Device milliseconds of the normals launches of the last vcy_extract_iso_normals (0 after vcy_extract_iso);
  * vcy_last_extract_ms stays the mesh kernels alone. */
@@ -275,6 +296,13 @@ int vcy_last_normals_ms(const vcy_ctx* ctx, float* device_ms);
  * as in the reference.  VCY_ERR_INVALID_ARG when a face names a vertex outside [0, n_vertices). */
 int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vertices,
                           const int32_t* faces, float* vertex_normals, float* face_normals);
+/* The seam finish (host only, no GPU needed): Mesh::CalcFaceNormal of the faces [face_begin, face_end) and Mesh::CalcNormal's
+ * sum in ascending face index, division and normalisation for the n_seam listed vertices ONLY, with the arithmetic of
+ * vcy_mesh_normals_host; vertex_normals (3 * n_vertices, in-out) changes at the listed vertices and nowhere else.  The
+ * range must hold every face that names a listed vertex.  n_seam = 0 is a no-op.  VCY_ERR_INVALID_ARG for a listed id or
+ * a vertex named by a face of the range outside [0, n_vertices), or a range that is not 0 <= face_begin <= face_end. */
+int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const int32_t* faces, int64_t face_begin,
+                               int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals);
 
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 

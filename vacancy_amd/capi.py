@@ -148,9 +148,12 @@ def load():
                                           C.c_int, C.c_int, C.c_float, P(vp)]),
         "vcy_extract_iso": (C.c_int, [vp, C.c_double, C.c_int, P(Mesh)]),
         "vcy_extract_iso_normals": (C.c_int, [vp, C.c_double, C.c_int, C.c_int, P(Mesh), P(MeshNormals)]),
+        "vcy_extract_iso_normals_slab": (C.c_int, [vp, C.c_double, C.c_int, C.c_int, P(Mesh), P(MeshNormals),
+                                                   P(C.c_int64)]),
         "vcy_mesh_normals_free": (None, [P(MeshNormals)]),
         "vcy_last_normals_ms": (C.c_int, [vp, P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
+        "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_extract_voxel": (C.c_int, [vp, C.c_int, P(Mesh)]),
         "vcy_extract_voxel_ids": (C.c_int, [vp, C.c_int, P(P(C.c_int64)), P(C.c_int64)]),
         "vcy_ids_free": (None, [P(C.c_int64)]),

@@ -41,6 +41,25 @@ def mesh_normals_host(vertices, faces):
     return vn, fn
 
 
+def mesh_normals_host_seam(vertices, faces, face_begin, face_end, seam_vertex_ids, vertex_normals):
+    """vcy_mesh_normals_host_seam: finishes, IN PLACE in `vertex_normals` (C-contiguous float32 [n_vertices, 3]), the
+    normals of the listed vertices of a merged mesh from the faces [face_begin, face_end) -- the reference's sum in
+    ascending face index, division, normalisation; every other row stays as it is.  Serial, no GPU needed."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    ids = np.ascontiguousarray(seam_vertex_ids, np.int64).reshape(-1)
+    vn = vertex_normals
+    if not (isinstance(vn, np.ndarray) and vn.dtype == np.float32 and vn.flags.c_contiguous and vn.flags.writeable
+            and vn.shape == v.shape):
+        raise ValueError("vertex_normals must be a writeable C-contiguous float32 array of the vertices' shape")
+    if face_end > len(f):
+        raise ValueError("faces [%d, %d) of %d" % (face_begin, face_end, len(f)))
+    rc = capi.load().vcy_mesh_normals_host_seam(len(v), _p(v), _p(f), int(face_begin), int(face_end), len(ids), _p(ids), _p(vn))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return vn
+
+
 class VoxelCarver:
     def __init__(self, option=None, device_id=0, z_range=None):
         self._lib = capi.load()
@@ -223,6 +242,44 @@ class VoxelCarver:
         out["device_ms"] = ms.value
         self._lib.vcy_last_extract_wall_ms(self._ctx, C.byref(ms))
         out["wall_ms"] = ms.value  # vcy_extract_iso entry -> mesh arrays in host memory
+        return out
+
+    def ExtractIsoSurfaceSlab(self, iso_level=0.0, linear_interp=True, normals=True):
+        """vcy_extract_iso_normals_slab: the extraction of a context that owns a z-slab (or the whole grid) as one part
+        of a merge.  The dict of ExtractIsoSurface plus "normals", "face_normals", "normals_device_ms" and "layer_faces"
+        = (faces of the first, of the last own cell layer): the normals of the seam vertices are zero until
+        vacancy_amd.dist.merge_meshes has finished them on the host.  normals=False is ExtractIsoSurface."""
+        if not normals:
+            return self.ExtractIsoSurface(iso_level, linear_interp)
+        m = Mesh()
+        mn = capi.MeshNormals()
+        lf = (C.c_int64 * 2)()
+        rc = self._lib.vcy_extract_iso_normals_slab(self._ctx, iso_level, int(linear_interp),
+                                                    capi.VCY_NORMALS_VERTEX | capi.VCY_NORMALS_FACE, C.byref(m),
+                                                    C.byref(mn), lf)
+        if rc != 0:
+            self._lib.vcy_mesh_free(C.byref(m))
+            self._lib.vcy_mesh_normals_free(C.byref(mn))
+            raise RuntimeError(last_error())
+        nv, nf = m.n_vertices, m.n_faces
+        out = {
+            "vertices": _mesh_array(m.vertices, nv, 3, np.float32),
+            "faces": _mesh_array(m.faces, nf, 3, np.int32),
+            "keys": _mesh_array(m.edge_keys, nv, 2, np.int64),
+            "n_foreign": int(m.n_foreign_vertices),
+            "normals": _mesh_array(mn.vertex_normals, nv, 3, np.float32),
+            "face_normals": _mesh_array(mn.face_normals, nf, 3, np.float32),
+            "layer_faces": (int(lf[0]), int(lf[1])),
+        }
+        self._lib.vcy_mesh_normals_free(C.byref(mn))
+        self._lib.vcy_mesh_free(C.byref(m))
+        ms = C.c_float()
+        self._lib.vcy_last_normals_ms(self._ctx, C.byref(ms))
+        out["normals_device_ms"] = ms.value
+        self._lib.vcy_last_extract_ms(self._ctx, C.byref(ms))
+        out["device_ms"] = ms.value
+        self._lib.vcy_last_extract_wall_ms(self._ctx, C.byref(ms))
+        out["wall_ms"] = ms.value
         return out
 
     # -- ExtractVoxel(mesh, inside_empty)  (voxel_carver.cc:530-538)

@@ -164,6 +164,10 @@ __device__ __forceinline__ void vertex_interp(double iso, const float pa[3], con
 // been enqueued for, behind it on the same stream.  Every pointer is device memory; `verts` / `faces` are the DEVICE
 // staging of the mesh.  vertex_normals / face_normals may be null.  The kernels read the counts where the chain left
 // them and return without a store when a capacity is exceeded, exactly as mc_emit does.
+// `slab` != 0 (a context that owns a z-slab, vcy_extract_iso_normals_slab): the vertex kernel's slab instance, which
+// reads the ghost layer's ACT bits and leaves the seam vertices -- those of ghost cells, and with `open_top` those on
+// the slab's top plane -- at zero for the host's seam finish.  `report` != null: one more small launch writes the
+// numbers of faces of the slab's first and last own cell layer to report[0], report[1] (page-locked host memory).
 struct NormalsLaunch {
   const McTables* T;
   const u64* act;
@@ -178,6 +182,11 @@ struct NormalsLaunch {
   const int* faces;
   float* vertex_normals;
   float* face_normals;
+  int slab, open_top;
+  const uint32_t* word_cell_off;  // the three below: read by the layer count only (`report` != null)
+  const u64* block_cell_offs;
+  const u64* ghost_cells_dev;
+  u64* report;
 };
 hipError_t launch_normals(hipStream_t stream, const McParams& p, const NormalsLaunch& a);
 

@@ -1271,7 +1271,8 @@ int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long lo
 
 // ---- host driver ----------------------------------------------------------------------------
 
-int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int which, vcy_mesh_normals* normals_out) {
+int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int which, vcy_mesh_normals* normals_out,
+                int64_t* layer_faces) {
   out->n_vertices = out->n_faces = out->n_foreign_vertices = 0;
   out->vertices = nullptr;  // an empty mesh has no arrays
   out->faces = nullptr;
@@ -1300,6 +1301,7 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
   c->last_extract_device_ms = 0.0f;
   c->last_normals_device_ms = 0.0f;
   if (normals_out == nullptr) which = 0;
+  if (layer_faces) layer_faces[0] = layer_faces[1] = 0;
   if (c->nx < 2 || p.Y <= 0 || p.L <= 0) return VCY_OK;  // no cells (reference loops do not run)
   // One sweep (mc_sweep_kernel) needs a voxel row that is a power-of-two number of whole words.  It moves 2 % fewer
   // bytes than the bit planes in memory (mc_bits + mc_active) but is not faster anywhere (sweep / planes, one box:
@@ -1607,7 +1609,7 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
     direct = false;
     // (with normals the mesh is staged on the device: mc_face_normals reads the emitted arrays, and must not read them
     // back over PCIe)
-    if (which == 0 && (int64_t)(sz_v + sz_f + (c->mesh_keys ? sz_k : 0)) <= c->mc_direct_bytes) {
+    if (which == 0 && layer_faces == nullptr && (int64_t)(sz_v + sz_f + (c->mesh_keys ? sz_k : 0)) <= c->mc_direct_bytes) {
       bool pinned = true, pk = true, pf = true;
       out->vertices = (float*)mesh_host_alloc(sz_v, &pinned);
       out->faces = (int32_t*)mesh_host_alloc(sz_f, &pf);
@@ -1676,6 +1678,14 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
     a.faces = d_faces;
     a.vertex_normals = d_vn;
     a.face_normals = d_fn;
+    // a z-slab (vcy_extract_iso_normals_slab): the seam vertices are left to the host, the layer counts it needs come
+    // back in the report block, behind the four words of mc_emit
+    a.slab = (c->z0 != 0 || c->z1 != c->nz || c->halo_lo != 0) ? 1 : 0;
+    a.open_top = c->z1 < c->nz ? 1 : 0;
+    a.word_cell_off = d_woff;
+    a.block_cell_offs = d_wcounts;
+    a.ghost_cells_dev = d_wcounts + p.G / kWordsPerBlock;
+    a.report = layer_faces ? (u64*)c->h_mc_report + 4 : nullptr;
     MC_TRY(hipEventRecord(c->ev_nrm_begin, s));
     MC_TRY(launch_normals(s, p, a));
     MC_TRY(hipEventRecord(c->ev_nrm_end, s));
@@ -1683,7 +1693,7 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
     return VCY_OK;
   };
   // number of active cells, and how many of them are ghost cells (words below G)
-  int64_t ncells = 0, nghost = 0, nv = 0, nf = 0, nforeign = 0;
+  int64_t ncells = 0, nghost = 0, nv = 0, nf = 0, nforeign = 0, first_layer_faces = 0, last_layer_faces = 0;
   CellBuffers cb{};
   bool done = false, end_recorded = false;
   auto with_headroom = [](int64_t v) { return v + v / 4 + 4096; };  // the next view's mesh is a little different
@@ -1693,6 +1703,8 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
     nv = (int64_t)(report[2] >> 32);
     nf = (int64_t)(report[2] & 0xFFFFFFFFull);
     nforeign = (int64_t)report[3];
+    first_layer_faces = (int64_t)report[4];  // (written by the normals' layer count, when asked for)
+    last_layer_faces = (int64_t)report[5];
   };
   if (timing) t_ph[0] = now_us();
   if (c->mc_hint_cells > 0) {
@@ -1708,7 +1720,7 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
     // (the end of the kernels: last_extract_device_ms is "kernels only")
     MC_TRY(hipEventRecord(c->ev_mc_end, s));
     end_recorded = true;
-    if (which != 0) {
+    if (which != 0 || layer_faces) {
       rc = enqueue_normals(cb, cap_cells, cap_v, cap_f);
       if (rc != VCY_OK) return rc;
     }
@@ -1749,7 +1761,7 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
       }
       MC_TRY(hipEventRecord(c->ev_mc_end, s));
       end_recorded = true;
-      if (which != 0) {
+      if (which != 0 || layer_faces) {
         rc = enqueue_normals(cb, cap_cells, with_headroom(nv), with_headroom(nf));
         if (rc != VCY_OK) return rc;
       }
@@ -1822,6 +1834,7 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
   }
   out->n_vertices = nv;
   out->n_faces = nf;
+  if (layer_faces && ncells > 0 && nf > 0) layer_faces[0] = first_layer_faces, layer_faces[1] = last_layer_faces;
   if (timing) {
     t_ph[4] = now_us();
     fprintf(stderr, "[vcy mc timing] setup %.1f us | enqueue %.1f | wait %.1f | events %.1f | mesh to host %.1f | total %.1f "

@@ -45,8 +45,11 @@ struct Cell {
   int li, cy, x;
 };
 
+// SLAB: the ghost layer (li = 0, the last cell layer of the slab below) counts as well -- its cells own corners on the
+// lower seam plane, and with them the argument order of VertexInterp there.
+template <bool SLAB>
 __device__ __forceinline__ bool cell_active(const McParams& p, const u64* __restrict__ act, const Cell& s) {
-  if (s.li < 1 || s.li > p.L || s.cy < 0 || s.cy >= p.Y || s.x < 1 || s.x >= p.nx) return false;
+  if (s.li < ((SLAB && p.has_ghost) ? 0 : 1) || s.li > p.L || s.cy < 0 || s.cy >= p.Y || s.x < 1 || s.x >= p.nx) return false;
   return (act[word_index(p, s.li, s.cy, s.x >> 6)] >> (s.x & 63)) & 1ull;
 }
 
@@ -76,12 +79,13 @@ __device__ __forceinline__ int cell_case(const McParams& p, const Cell& s) {
 
 // The emitted position of the vertex on edge e of the ACTIVE cell s: VertexInterp with the arguments in the order of
 // the first active cell around the edge (the owner, where the reference's map insert happens).
+template <bool SLAB>
 __device__ __forceinline__ void edge_position(const McParams& p, const u64* __restrict__ act, const Cell& s, int e,
                                               float out[3]) {
   const int axis = kGrp[e][0], me = kGrp[e][1];
   int oe = e;
   for (int k = me - 1; k >= 0; --k)
-    if (cell_active(p, act, group_cell(s, axis, me, k))) oe = kGrpEdge[axis][k];
+    if (cell_active<SLAB>(p, act, group_cell(s, axis, me, k))) oe = kGrpEdge[axis][k];
   const bool flip = (((kEdgeReversed >> oe) ^ (kEdgeReversed >> e)) & 1) != 0;
   const int ca = flip ? kEdgeB[e] : kEdgeA[e], cb = flip ? kEdgeA[e] : kEdgeB[e];
   const int y = s.cy + 1, z = p.zc0 + s.li - 1;
@@ -147,6 +151,12 @@ __global__ __launch_bounds__(256) void mc_face_normals_kernel(NormalsLaunch a) {
 }
 
 // ---- vertex normals: one thread per active cell, the edges it owns ---------------------------------------------
+// SLAB (a context that owns z [z_begin, z_end) of the grid): a vertex on an x- or y-axis edge in the plane below the
+// slab's first cell layer or -- when z_end < nz -- in its top plane has faces in two slabs; the host finishes those
+// (vcy_mesh_normals_host_seam), here their slots get zeros.  The former are the vertices of the ghost cells, the latter
+// those of e4..e7 of the last own layer.  Every other vertex has all its faces in this slab and is final: the corners of
+// first-layer triangles that lie on the lower seam plane take their owners from the ghost layer's ACT bits.
+template <bool SLAB>
 __global__ __launch_bounds__(256) void mc_vertex_normals_kernel(McParams p, NormalsLaunch a) {
   int64_t ncells, nv, nf;
   if (!chain_fits(a, &ncells, &nv, &nf)) return;
@@ -159,17 +169,18 @@ __global__ __launch_bounds__(256) void mc_vertex_normals_kernel(McParams p, Norm
   c.x = w * 64 + (int)(slot & 63);
   const uint32_t inf = a.info[i];
   const int owned = inf & 0xFFF, code = (inf >> 12) & 0xFF;
-  if (owned == 0 || c.li < 1) return;
+  if (owned == 0 || (!SLAB && c.li < 1)) return;
   const int64_t v0 = (int64_t)(a.block_offs[i >> 8] >> 32) + (int64_t)(inf >> 20);  // first vertex of this cell
   for (int e = 0; e < 12; ++e) {
     if (!((owned >> e) & 1)) continue;
     const int axis = kGrp[e][0], me = kGrp[e][1];
     float n[3] = {0.0f, 0.0f, 0.0f};
     int count = 0;
+    const bool seam = SLAB && (c.li < 1 || (a.open_top != 0 && c.li == p.L && e >= 4 && e < 8));
     // this cell owns the edge: the cells before it around the edge are not active
-    for (int k = me; k < 4; ++k) {
+    for (int k = seam ? 4 : me; k < 4; ++k) {
       const Cell s = group_cell(c, axis, me, k);
-      if (k > me && !cell_active(p, a.act, s)) continue;
+      if (k > me && !cell_active<SLAB>(p, a.act, s)) continue;
       const int se = kGrpEdge[axis][k];
       const int scode = k == me ? code : cell_case(p, s);
       const uint4 trow = *reinterpret_cast<const uint4*>(&a.T->tri[scode][0]);
@@ -184,9 +195,9 @@ __global__ __launch_bounds__(256) void mc_vertex_normals_kernel(McParams p, Norm
         const int hits = (e0 == se ? 1 : 0) + (e1 == se ? 1 : 0) + (e2 == se ? 1 : 0);
         if (hits == 0) continue;
         float q0[3], q1[3], q2[3], fn[3];
-        edge_position(p, a.act, s, e0, q0);
-        edge_position(p, a.act, s, e1, q1);
-        edge_position(p, a.act, s, e2, q2);
+        edge_position<SLAB>(p, a.act, s, e0, q0);
+        edge_position<SLAB>(p, a.act, s, e1, q1);
+        edge_position<SLAB>(p, a.act, s, e2, q2);
         face_normal(q0, q1, q2, fn);
         for (int h = 0; h < hits; ++h) {  // (mesh.cc:215-219: once per corner that names the vertex)
           n[0] += fn[0];
@@ -196,11 +207,13 @@ __global__ __launch_bounds__(256) void mc_vertex_normals_kernel(McParams p, Norm
         }
       }
     }
-    const float d = (float)count;  // (>= 1: the owner's own triangle row names every edge it cuts)
-    n[0] = n[0] / d;
-    n[1] = n[1] / d;
-    n[2] = n[2] / d;
-    normalize3(n);
+    if (!seam) {
+      const float d = (float)count;  // (>= 1: the owner's own triangle row names every edge it cuts)
+      n[0] = n[0] / d;
+      n[1] = n[1] / d;
+      n[2] = n[2] / d;
+      normalize3(n);
+    }
     const int64_t vid = v0 + __popc(owned & (int)a.T->prec[code][e]);
     if (vid < nv) {
       a.vertex_normals[3 * vid + 0] = n[0];
@@ -210,13 +223,48 @@ __global__ __launch_bounds__(256) void mc_vertex_normals_kernel(McParams p, Norm
   }
 }
 
+// ---- how many faces the first and the last own cell layer have: one workgroup -----------------------------------
+// In the merged face array of a grid cut into slabs, the faces of a slab's last layer and of the next slab's first
+// layer are one contiguous range that holds every face of the seam vertices between them.  Faces are numbered in list
+// order, so a layer's faces start at the face offset of its first cell: the block's offset (block_offs) plus the
+// triangles of the cells before it in its block of 256 (the case of each is in info).  The list index of the first
+// cell of a cell word comes from the offsets mc_compact used.
+__global__ __launch_bounds__(256) void mc_layer_faces_kernel(McParams p, NormalsLaunch a) {
+  __shared__ int sm[4];
+  int64_t ncells, nv, nf;
+  if (!chain_fits(a, &ncells, &nv, &nf)) return;
+  const int64_t nghost = (int64_t)*a.ghost_cells_dev;
+  const int64_t layer_words = (int64_t)p.Yc * p.Wr;
+  u64 before[2];
+  for (int q = 0; q < 2; ++q) {  // (uniform) faces before layer 2, faces before layer L
+    const int64_t cw = p.G + (q == 0 ? 1 : (int64_t)p.L - 1) * layer_words;
+    const int64_t i = cw < p.nwords ? (int64_t)a.block_cell_offs[cw >> 8] + a.word_cell_off[cw] : ncells;
+    int tot = 0;
+    int ntri = 0;
+    if (i < ncells) {
+      const int64_t j = (i >> 8 << 8) + threadIdx.x;
+      if (j < i && j >= nghost) ntri = a.T->ntri[(a.info[j] >> 12) & 0xFF];  // (ghost cells have no faces)
+    }
+    (void)block_exclusive_scan(ntri, &tot, sm);
+    before[q] = i < ncells ? (a.block_offs[i >> 8] & 0xFFFFFFFFull) + (u64)tot : (u64)nf;
+  }
+  if (threadIdx.x == 0) {
+    a.report[0] = before[0];
+    a.report[1] = (u64)nf - before[1];
+  }
+}
+
 }  // namespace
 
 hipError_t launch_normals(hipStream_t stream, const McParams& p, const NormalsLaunch& a) {
   if (a.face_normals != nullptr && a.cap_faces > 0)
     hipLaunchKernelGGL(mc_face_normals_kernel, dim3((unsigned)((a.cap_faces + 255) / 256)), dim3(256), 0, stream, a);
-  if (a.vertex_normals != nullptr && a.cap_cells > 0)
-    hipLaunchKernelGGL(mc_vertex_normals_kernel, dim3((unsigned)((a.cap_cells + 255) / 256)), dim3(256), 0, stream, p, a);
+  if (a.vertex_normals != nullptr && a.cap_cells > 0) {
+    const dim3 grid((unsigned)((a.cap_cells + 255) / 256));
+    if (a.slab) hipLaunchKernelGGL(mc_vertex_normals_kernel<true>, grid, dim3(256), 0, stream, p, a);
+    else hipLaunchKernelGGL(mc_vertex_normals_kernel<false>, grid, dim3(256), 0, stream, p, a);
+  }
+  if (a.report != nullptr) hipLaunchKernelGGL(mc_layer_faces_kernel, dim3(1), dim3(256), 0, stream, p, a);
   return hipGetLastError();
 }
 

@@ -1760,6 +1760,39 @@ int vcy_extract_iso_normals(vcy_ctx* c, double iso, int linear_interp, int which
   return rc;
 }
 
+int vcy_extract_iso_normals_slab(vcy_ctx* c, double iso, int linear_interp, int which, vcy_mesh* out,
+                                 vcy_mesh_normals* normals_out, int64_t layer_faces[2]) {
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  if (!out || !normals_out || !layer_faces || (which & ~(VCY_NORMALS_VERTEX | VCY_NORMALS_FACE)) != 0) {
+    set_error("vcy_extract_iso_normals_slab: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  std::memset(out, 0, sizeof(*out));
+  std::memset(normals_out, 0, sizeof(*normals_out));
+  layer_faces[0] = layer_faces[1] = 0;
+  const bool whole = c->z0 == 0 && c->z1 == c->nz && c->halo_lo == 0;
+  if (!whole && !c->mesh_keys) {
+    // the seam vertices are found by the edge keys of the slab's foreign vertices
+    set_error("vcy_extract_iso_normals_slab: the context owns z [%d, %d) of %d slices; the merge of its normals needs "
+              "the edge keys (vcy_set_param \"meshkeys\" 1)", c->z0, c->z1, c->nz);
+    return VCY_ERR_INVALID_ARG;
+  }
+  VCY_HIP_CHECK(hipSetDevice(c->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
+  const int rc = extract_iso(c, iso, linear_interp, out, which, normals_out, layer_faces);
+  if (rc != VCY_OK) {
+    vcy_mesh_free(out);
+    vcy_mesh_normals_free(normals_out);
+    layer_faces[0] = layer_faces[1] = 0;
+  }
+  c->last_extract_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
 void vcy_mesh_normals_free(vcy_mesh_normals* n) {
   if (!n) return;
   mesh_host_free(n->vertex_normals);
@@ -1784,6 +1817,32 @@ inline void host_normalize3(float v[3]) {
     v[2] = v[2] / n;
   }
 }
+// Mesh::CalcFaceNormal for one face (mesh.cc:231-240)
+inline void host_face_normal(const float* vertices, const int32_t* f, float fn[3]) {
+  const float *p0 = vertices + 3 * (int64_t)f[0], *p1 = vertices + 3 * (int64_t)f[1], *p2 = vertices + 3 * (int64_t)f[2];
+  float v1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+  float v2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+  host_normalize3(v1);
+  host_normalize3(v2);
+  fn[0] = v1[1] * v2[2] - v1[2] * v2[1];
+  fn[1] = v1[2] * v2[0] - v1[0] * v2[2];
+  fn[2] = v1[0] * v2[1] - v1[1] * v2[0];
+  host_normalize3(fn);
+}
+// Mesh::CalcNormal: one term of a vertex's sum (mesh.cc:213-221), and the division and normalisation behind it
+inline void host_add_normal(float* n, int* count, const float fn[3]) {
+  n[0] += fn[0];
+  n[1] += fn[1];
+  n[2] += fn[2];
+  ++*count;
+}
+inline void host_finish_normal(float* n, int count) {
+  const float d = static_cast<float>(count);
+  n[0] = n[0] / d;
+  n[1] = n[1] / d;
+  n[2] = n[2] / d;
+  host_normalize3(n);
+}
 }  // namespace
 
 int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
@@ -1804,32 +1863,66 @@ int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vert
   }
   for (int64_t i = 0; i < n_faces; ++i) {  // Mesh::CalcFaceNormal (mesh.cc:231-240), then the sum of mesh.cc:213-221
     const int32_t* f = faces + 3 * i;
-    const float *p0 = vertices + 3 * (int64_t)f[0], *p1 = vertices + 3 * (int64_t)f[1], *p2 = vertices + 3 * (int64_t)f[2];
-    float v1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-    float v2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-    host_normalize3(v1);
-    host_normalize3(v2);
-    float fn[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
-    host_normalize3(fn);
+    float fn[3];
+    host_face_normal(vertices, f, fn);
     if (face_normals) face_normals[3 * i + 0] = fn[0], face_normals[3 * i + 1] = fn[1], face_normals[3 * i + 2] = fn[2];
     if (vertex_normals)
-      for (int j = 0; j < 3; ++j) {
-        float* n = vertex_normals + 3 * (int64_t)f[j];
-        n[0] += fn[0];
-        n[1] += fn[1];
-        n[2] += fn[2];
-        ++count[(size_t)f[j]];
-      }
+      for (int j = 0; j < 3; ++j) host_add_normal(vertex_normals + 3 * (int64_t)f[j], &count[(size_t)f[j]], fn);
   }
   if (vertex_normals)
-    for (int64_t k = 0; k < n_vertices; ++k) {  // (a vertex no face names: 0 / 0, as in the reference)
-      float* n = vertex_normals + 3 * k;
-      const float d = static_cast<float>(count[(size_t)k]);
-      n[0] = n[0] / d;
-      n[1] = n[1] / d;
-      n[2] = n[2] / d;
-      host_normalize3(n);
+    for (int64_t k = 0; k < n_vertices; ++k)  // (a vertex no face names: 0 / 0, as in the reference)
+      host_finish_normal(vertex_normals + 3 * k, count[(size_t)k]);
+  return VCY_OK;
+}
+
+int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const int32_t* faces, int64_t face_begin,
+                               int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals) {
+  if (n_vertices < 0 || n_seam < 0 || face_begin < 0 || face_end < face_begin || (n_seam > 0 && !seam_vertex_ids) ||
+      (n_seam > 0 && (!vertices || !vertex_normals)) || (n_seam > 0 && face_end > face_begin && !faces)) {
+    set_error("vcy_mesh_normals_host_seam: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  if (n_seam == 0) return VCY_OK;
+  // the seam vertices of one plane are a small window of the merged numbering: a slot per id of that window
+  int64_t lo = seam_vertex_ids[0], hi = seam_vertex_ids[0];
+  for (int64_t k = 0; k < n_seam; ++k) {
+    const int64_t id = seam_vertex_ids[k];
+    if (id < 0 || id >= n_vertices) {
+      set_error("vcy_mesh_normals_host_seam: seam vertex %lld of %lld", (long long)id, (long long)n_vertices);
+      return VCY_ERR_INVALID_ARG;
     }
+    lo = std::min(lo, id);
+    hi = std::max(hi, id);
+  }
+  std::vector<int32_t> slot((size_t)(hi - lo + 1), -1);
+  for (int64_t k = 0; k < n_seam; ++k) slot[(size_t)(seam_vertex_ids[k] - lo)] = (int32_t)k;  // (a repeated id: one slot)
+  for (int64_t i = 3 * face_begin; i < 3 * face_end; ++i)
+    if (faces[i] < 0 || faces[i] >= n_vertices) {
+      set_error("vcy_mesh_normals_host_seam: face %lld names vertex %d of %lld", (long long)(i / 3), faces[i], (long long)n_vertices);
+      return VCY_ERR_INVALID_ARG;
+    }
+  std::vector<float> sum(3 * (size_t)n_seam, 0.0f);
+  std::vector<int> count((size_t)n_seam, 0);
+  for (int64_t i = face_begin; i < face_end; ++i) {  // ascending face index: the order of the reference's sum
+    const int32_t* f = faces + 3 * i;
+    bool named = false;
+    for (int j = 0; j < 3; ++j) named = named || (f[j] >= lo && f[j] <= hi && slot[(size_t)(f[j] - lo)] >= 0);
+    if (!named) continue;
+    float fn[3];
+    host_face_normal(vertices, f, fn);
+    for (int j = 0; j < 3; ++j) {
+      if (f[j] < lo || f[j] > hi) continue;
+      const int32_t k = slot[(size_t)(f[j] - lo)];
+      if (k >= 0) host_add_normal(&sum[3 * (size_t)k], &count[(size_t)k], fn);
+    }
+  }
+  for (int64_t k = 0; k < n_seam; ++k) {
+    const int32_t q = slot[(size_t)(seam_vertex_ids[k] - lo)];
+    float n[3] = {sum[3 * (size_t)q], sum[3 * (size_t)q + 1], sum[3 * (size_t)q + 2]};
+    host_finish_normal(n, count[(size_t)q]);
+    float* o = vertex_normals + 3 * seam_vertex_ids[k];
+    o[0] = n[0], o[1] = n[1], o[2] = n[2];
+  }
   return VCY_OK;
 }
 

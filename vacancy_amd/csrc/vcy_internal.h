@@ -223,8 +223,10 @@ int check_carve_views(vcy_ctx* ctx, int n_views, const vcy_view* views);  // arg
 int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy_ctx::carve_log, or -1 (vcy_api.hip)
 // mc_kernels.hip
 // `which` (VCY_NORMALS_*) != 0: the normals of the mesh as well, into `normals_out` (mc_normals.hip)
+// `layer_faces` != null (vcy_extract_iso_normals_slab): the faces of the first and of the last own cell layer; a context
+// that owns a z-slab then gets the slab instance of the vertex normals (seam vertices left at zero)
 int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int which = 0,
-                vcy_mesh_normals* normals_out = nullptr);
+                vcy_mesh_normals* normals_out = nullptr, int64_t* layer_faces = nullptr);
 // sdf2d.hip
 void host_distance_transform_l1(const uint8_t* mask, int w, int h, const int32_t* rmin,
                                 const int32_t* rmax, float* out);

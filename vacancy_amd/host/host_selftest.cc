@@ -148,6 +148,55 @@ int main(int argc, char* argv[]) {
     }
     return 0;
   }
+  if (argc > 5 && std::string(argv[2]) == "shardnormals") {
+    // needs a device: ShardedVoxelCarver::ExtractIsoSurface(with_normals) after the six bunny views, written out raw.
+    //   host_selftest <data dir> shardnormals <resolution> <slabs on device 0> <out dir> [iso level] [linear interp]
+    //   writes <out dir>/vertices.f32, faces.i32, normals.f32, face_normals.f32, prints SHARDNORMALS <slabs> <sizes>
+    vacancy::VoxelCarverOption option;
+    option.bb_min = Eigen::Vector3f(-250.000000f, -344.586151f, -129.982697f);
+    option.bb_max = Eigen::Vector3f(250.000000f, 150.542343f, 257.329224f);
+    for (int i = 0; i < 3; ++i) {  // (examples.cc:91-99)
+      option.bb_min[i] -= 20.0f;
+      option.bb_max[i] += 20.0f;
+    }
+    option.resolution = (float)std::atof(argv[3]);
+    const std::string out = argv[5];
+    const double iso = argc > 6 ? std::atof(argv[6]) : 0.0;
+    const bool interp = argc > 7 ? std::atoi(argv[7]) != 0 : true;
+    vacancy::ShardedVoxelCarver sh(option, {0}, std::atoi(argv[4]));
+    if (!sh.Init()) return 6;
+    std::FILE* fp = std::fopen((dir + "/tumpose.txt").c_str(), "r");
+    if (!fp) return 9;
+    int id;
+    double t[3], q[4];
+    for (size_t i = 0; i < 6 && std::fscanf(fp, "%d %lf %lf %lf %lf %lf %lf %lf", &id, &t[0], &t[1], &t[2], &q[0], &q[1], &q[2], &q[3]) == 8; ++i) {
+      Eigen::Translation3d tr;
+      tr.x() = t[0]; tr.y() = t[1]; tr.z() = t[2];
+      Eigen::Quaterniond qu;
+      qu.x() = q[0]; qu.y() = q[1]; qu.z() = q[2]; qu.w() = q[3];
+      vacancy::PinholeCamera cam(320, 240, tr * qu, Eigen::Vector2f(159.3f, 127.65f), Eigen::Vector2f(258.65f, 258.25f));
+      vacancy::Image1b sil;
+      if (!sil.Load(dir + "/mask_" + vacancy::zfill(i) + ".png")) return 4;
+      if (!sh.Carve(cam, sil)) return 7;
+    }
+    std::fclose(fp);
+    vacancy::Mesh mesh;
+    sh.ExtractIsoSurface(&mesh, iso, interp, true);
+    auto dump = [](const std::string& path, const void* p, size_t bytes) {
+      std::FILE* f = std::fopen(path.c_str(), "wb");
+      if (!f) return false;
+      if (bytes) std::fwrite(p, 1, bytes, f);
+      std::fclose(f);
+      return true;
+    };
+    bool ok = dump(out + "/vertices.f32", mesh.vertices().data(), 12 * mesh.vertices().size());
+    ok = ok && dump(out + "/faces.i32", mesh.vertex_indices().data(), 12 * mesh.vertex_indices().size());
+    ok = ok && dump(out + "/normals.f32", mesh.normals().data(), 12 * mesh.normals().size());
+    ok = ok && dump(out + "/face_normals.f32", mesh.face_normals().data(), 12 * mesh.face_normals().size());
+    std::printf("SHARDNORMALS %d %d %zu %zu %zu %zu %zu\n", ok ? 1 : 0, sh.slab_count(), mesh.vertices().size(),
+                mesh.vertex_indices().size(), mesh.normals().size(), mesh.face_normals().size(), mesh.normal_indices().size());
+    return ok ? 0 : 8;
+  }
   if (argc > 3 && std::string(argv[2]) == "normals") {
     // CPU only: Mesh::CalcNormal through the facade.   host_selftest <data dir> normals <dir>
     //   reads <dir>/vertices.f32 and <dir>/faces.i32, writes <dir>/normals.f32, face_normals.f32, normal_indices.i32,

@@ -2,6 +2,7 @@
 #include "vacancy/sharded_voxel_carver.h"
 
 #include <cstring>
+#include <array>
 #include <future>
 #include <limits>
 #include <string>
@@ -278,25 +279,37 @@ void ShardedVoxelCarver::ExtractVoxel(Mesh* mesh, bool inside_empty) {
   for (int64_t* p : ids) vcy_ids_free(p);
 }
 
-void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals) {
-  ExtractIsoSurface(mesh, iso_level, linear_interp);
-  if (with_normals) mesh->CalcNormal();
+void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp) {
+  ExtractIsoSurface(mesh, iso_level, linear_interp, false);
 }
 
-void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp) {
+// with_normals: every slab's normals come from its own device (vcy_extract_iso_normals_slab); the seam vertices -- those a
+// slab's foreign vertices are mapped to -- are finished on the host over the faces of the two cell layers that meet at
+// the seam (vcy_mesh_normals_host_seam).  The rule is the one of vacancy_amd.dist.merge_meshes.
+void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals) {
   mesh->Clear();
   const size_t ns = impl_->slabs.size();
   if (ns == 0) return;
   if (!ExchangeHalo()) return;
   std::vector<vcy_mesh> parts(ns);
+  std::vector<vcy_mesh_normals> normals(ns);
+  std::vector<std::array<int64_t, 2>> layer_faces(ns);
   std::vector<std::string> errors(ns);
   std::vector<std::future<int>> jobs;
-  for (size_t s = 0; s < ns; ++s)
-    jobs.push_back(std::async(std::launch::async, [this, s, iso_level, linear_interp, &parts, &errors]() {
-      const int rc = vcy_extract_iso(impl_->slabs[s], iso_level, linear_interp ? 1 : 0, &parts[s]);
+  for (size_t s = 0; s < ns; ++s) {
+    std::memset(&parts[s], 0, sizeof(vcy_mesh));
+    std::memset(&normals[s], 0, sizeof(vcy_mesh_normals));
+    layer_faces[s] = {0, 0};
+    jobs.push_back(std::async(std::launch::async, [this, s, iso_level, linear_interp, with_normals, &parts, &normals,
+                                                    &layer_faces, &errors]() {
+      const int rc = with_normals ? vcy_extract_iso_normals_slab(impl_->slabs[s], iso_level, linear_interp ? 1 : 0,
+                                                                 VCY_NORMALS_VERTEX | VCY_NORMALS_FACE, &parts[s],
+                                                                 &normals[s], layer_faces[s].data())
+                                  : vcy_extract_iso(impl_->slabs[s], iso_level, linear_interp ? 1 : 0, &parts[s]);
       if (rc != VCY_OK) errors[s] = vcy_last_error();
       return rc;
     }));
+  }
   bool ok = true;
   for (auto& j : jobs) ok = (j.get() == VCY_OK) && ok;
   for (const std::string& e : errors)
@@ -305,13 +318,21 @@ void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool li
     // stitch: a slab's first n_foreign vertices are owned by the slab below -> look them up by edge key
     std::vector<Eigen::Vector3f>* V = mesh->mutable_vertices();
     std::vector<Eigen::Vector3i>* F = mesh->mutable_vertex_indices();
+    std::vector<Eigen::Vector3f>* N = mesh->mutable_normals();
+    std::vector<Eigen::Vector3f>* FN = mesh->mutable_face_normals();
     std::unordered_map<std::pair<int64_t, int64_t>, int, KeyHash> prev;
+    struct Seam {
+      int64_t face_begin, face_end;
+      std::vector<int64_t> ids;
+    };
+    std::vector<Seam> seams;
     int64_t offset = 0;
     {
       size_t total_v = 0, total_f = 0;
       for (const vcy_mesh& m : parts) total_v += static_cast<size_t>(m.n_vertices - m.n_foreign_vertices), total_f += static_cast<size_t>(m.n_faces);
       V->reserve(total_v);
       F->reserve(total_f);
+      if (with_normals) N->reserve(total_v), FN->reserve(total_f);
     }
     for (size_t s = 0; s < ns && ok; ++s) {
       const vcy_mesh& m = parts[s];
@@ -332,6 +353,18 @@ void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool li
       F->resize(f0 + m.n_faces);
       for (int64_t i = 0; i < m.n_faces; ++i)
         (*F)[f0 + i] = Eigen::Vector3i(remap[m.faces[3 * i]], remap[m.faces[3 * i + 1]], remap[m.faces[3 * i + 2]]);
+      if (with_normals && ok) {
+        // the slab's normals with the merged numbering; its foreign entries go, like its foreign vertices
+        detail::CopyTriples(N, nown > 0 ? normals[s].vertex_normals + 3 * nfo : nullptr, static_cast<size_t>(nown), v0);
+        detail::CopyTriples(FN, normals[s].face_normals, static_cast<size_t>(m.n_faces), f0);
+        if (nfo > 0) {
+          Seam seam;
+          seam.face_begin = static_cast<int64_t>(f0) - layer_faces[s - 1][1];
+          seam.face_end = static_cast<int64_t>(f0) + layer_faces[s][0];
+          seam.ids.assign(remap.begin(), remap.begin() + nfo);
+          seams.push_back(std::move(seam));
+        }
+      }
       prev.clear();
       if (s + 1 < ns) {
         // Only vertices on this slab's top plane can be referenced from above: edges with both voxels in the slice below
@@ -345,9 +378,22 @@ void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool li
       }
       offset += nown;
     }
+    if (with_normals && ok) {
+      for (const Seam& seam : seams)
+        if (vcy_mesh_normals_host_seam(static_cast<int64_t>(V->size()), reinterpret_cast<const float*>(V->data()),
+                                       reinterpret_cast<const int32_t*>(F->data()), seam.face_begin, seam.face_end,
+                                       static_cast<int64_t>(seam.ids.size()), seam.ids.data(),
+                                       reinterpret_cast<float*>(N->data())) != VCY_OK) {
+          LOGE("sharded merge: %s\n", vcy_last_error());
+          ok = false;
+          break;
+        }
+      if (ok) mesh->set_normal_indices(mesh->vertex_indices());
+    }
   }
   if (!ok) mesh->Clear();
   for (vcy_mesh& m : parts) vcy_mesh_free(&m);
+  for (vcy_mesh_normals& n : normals) vcy_mesh_normals_free(&n);
 }
 
 }  // namespace vacancy

@@ -223,8 +223,9 @@ class ShardedVoxelCarver:
         return self.last_collective
 
     # -- ExtractIsoSurface (voxel_carver.cc:540-543): every slab on its device, then the merge by edge key
-    def extract_slabs(self, iso_level=0.0, linear_interp=True, repeat=1):
-        """[mesh of slab s] in z order (the last of `repeat` extractions each)."""
+    def extract_slabs(self, iso_level=0.0, linear_interp=True, repeat=1, normals=False):
+        """[mesh of slab s] in z order (the last of `repeat` extractions each).  normals=True: every slab's
+        ExtractIsoSurfaceSlab -- its normals from its own device, the seam vertices left for the merge."""
         self.exchange_halo()
         meshes = [None] * len(self.slabs)
         index = {id(c): s for s, c in enumerate(self.slabs)}
@@ -232,20 +233,23 @@ class ShardedVoxelCarver:
         def run(i, cs):
             for c in cs:
                 for _ in range(repeat):
-                    m = c.ExtractIsoSurface(iso_level, linear_interp)
+                    m = c.ExtractIsoSurfaceSlab(iso_level, linear_interp) if normals \
+                        else c.ExtractIsoSurface(iso_level, linear_interp)
                 meshes[index[id(c)]] = m
 
         self._per_device(run)
         return meshes
 
     def ExtractIsoSurface(self, iso_level=0.0, linear_interp=True, normals=False):
-        """normals=True: "normals" and "face_normals" of the MERGED mesh, by the serial host walk (mesh_normals_host,
-        = Mesh::CalcNormal): a vertex on a slab's boundary plane has faces in two slabs, so the slabs' devices cannot
-        finish the sum on their own.  The bits equal the single-context device result."""
-        mesh = vdist.merge_meshes(self.extract_slabs(iso_level, linear_interp))
+        """normals=True: "normals" and "face_normals" of the MERGED mesh, = Mesh::CalcNormal of it, and
+        "normals_device_ms" (the sum over the slabs).  Every slab computes its normals on its own device
+        (vcy_extract_iso_normals_slab); a vertex on a slab's boundary plane has faces in two slabs, so those -- a
+        plane's worth per seam -- are finished on the host by the merge (vacancy_amd.dist.merge_meshes).  The bits
+        equal the single-context device result."""
+        parts = self.extract_slabs(iso_level, linear_interp, normals=normals)
+        mesh = vdist.merge_meshes(parts)
         if normals:
-            from . import carver as _vc
-            mesh["normals"], mesh["face_normals"] = _vc.mesh_normals_host(mesh["vertices"], mesh["faces"])
+            mesh["normals_device_ms"] = float(sum(p["normals_device_ms"] for p in parts))
         return mesh
 
     # -- ExtractVoxel (voxel_carver.cc:530-538, extract_voxel.cc:258-317): the keep predicate and the compaction run on
