@@ -42,6 +42,17 @@ static bool LoadTumPoses(const std::string& path, std::vector<Eigen::Affine3d>* 
 }
 
 int main(int argc, char* argv[]) {
+  // --keep-largest (anywhere on the command line): before the final extraction, carve away every connected component
+  // of the hull but the largest (VoxelCarver::KeepLargestComponents) -- the floaters six views leave
+  bool keep_largest = false;
+  {
+    int n = 1;
+    for (int i = 1; i < argc; ++i) {
+      if (std::string(argv[i]) == "--keep-largest") keep_largest = true;
+      else argv[n++] = argv[i];
+    }
+    argc = n;
+  }
   const std::string data_dir = argc > 1 ? argv[1] : "../data/";
   const std::string out_dir = argc > 2 ? argv[2] : data_dir;
   const float resolution = argc > 3 ? (float)std::atof(argv[3]) : 10.0f;
@@ -144,6 +155,12 @@ int main(int argc, char* argv[]) {
   }
 
   // the last view once more with normals (computed on the device), as a binary PLY a viewer lights correctly
+  if (keep_largest) {
+    std::vector<vacancy::VoxelComponent> before, after;
+    if (!carver.LabelComponents(&before) || !carver.KeepLargestComponents(1) || !carver.LabelComponents(&after)) return 9;
+    std::printf("COMPONENTS before %zu after %zu largest %lld voxels\n", before.size(), after.size(),
+                before.empty() ? 0LL : static_cast<long long>(before[0].n_voxels));
+  }
   if (!poses.empty()) {
     vacancy::Mesh lit;
     carver.ExtractIsoSurface(&lit, 0.0, true, true);

@@ -3,6 +3,7 @@
 // the voxel grid lives in HBM behind the C-ABI of vacancy_hip.h instead of a std::vector<Voxel>.
 #pragma once
 
+#include <cstdint>
 #include <memory>
 #include <vector>
 
@@ -77,6 +78,14 @@ class VoxelGrid {
   int xy_slice_num_{0};
 };
 
+// One 6-connected component of the solid voxels (update_num >= 1 and sdf < iso_level): vcy_component of vacancy_hip.h.
+// No counterpart in the reference.
+struct VoxelComponent {
+  std::int64_t label{0};     // smallest voxel id (z*nx*ny + y*nx + x) of the component
+  std::int64_t n_voxels{0};
+  Eigen::Vector3i bb_min{0, 0, 0}, bb_max{0, 0, 0};  // inclusive voxel-index bounds
+};
+
 class VoxelCarver {
  public:
   VoxelCarver();
@@ -106,6 +115,15 @@ class VoxelCarver {
   // with_normals: the mesh's normals(), face_normals() and normal_indices() as well -- Mesh::CalcNormal() of the result,
   // computed on the device behind the extraction (vcy_extract_iso_normals), bit-equal to calling CalcNormal() afterwards
   void ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals);
+
+  // Connected components of the hull, labelled on the device (vcy_label_components): the list, largest first (ties:
+  // the lower label).  KeepLargestComponents (vcy_keep_components) carves away, in place, every component that is not
+  // among the `largest` largest (<= 0: any number) or has fewer than `min_voxels` voxels -- their voxels get
+  // sdf = fill_sdf (finite, >= iso_level), so the phantom volumes and specks of a hull of few views are gone from
+  // every later ExtractIsoSurface / ExtractVoxel, and further Carve() calls go on at full speed.  false + LOGE on
+  // an error.  ShardedVoxelCarver has no counterpart yet (the seam merge across z-slabs is not built).
+  bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
+  bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
 
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;

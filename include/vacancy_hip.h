@@ -304,6 +304,52 @@ int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vert
 int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const int32_t* faces, int64_t face_begin,
                                int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals);
 
+/* ---- connected components of the hull ------------------------------------ */
+
+/* 6-connected components of the SOLID voxels, labelled on the device (no reference counterpart: what a
+ * shape-from-silhouette user otherwise does on the host with the downloaded grid, to drop the phantom volumes and specks
+ * a visual hull of few views has).
+ *   solid voxel : update_num >= 1 && (double)sdf < iso_level -- marching cubes' own comparison (marching_cubes.cc:121-128);
+ *                 an untouched voxel (sdf = lowest(), update_num = 0) and a NaN are not solid;
+ *   adjacency   : the six axis neighbours inside the grid (the adjacency of marching cubes' edges);
+ *   label       : the smallest global voxel id (z*nx*ny + y*nx + x) of the component;
+ *   order       : n_voxels descending, ties by label ascending; "the k largest" are the first k of it.
+ * The results are therefore exact and independent of how the kernels were scheduled. */
+typedef struct vcy_component {   /* 40 bytes */
+  int64_t label;                 /* smallest global voxel id of the component */
+  int64_t n_voxels;
+  int32_t bb_min[3], bb_max[3];  /* inclusive voxel-index bounds, x y z */
+} vcy_component;
+
+/* Applies queued ("defer") views, labels, and returns the list in the order above (library-owned:
+ * vcy_components_free; *out = NULL and *n_out = 0 when no voxel is solid).  The state is not changed; a context
+ * nothing has been carved into since vcy_create / vcy_reset returns the empty list without its lazy fill being
+ * written.  Labels take 4 bytes per voxel of device memory (kept by the context): VCY_ERR_TOO_MANY_VOXELS above
+ * 2^31 - 1 voxels.  VCY_ERR_UNSUPPORTED, with the state untouched, for a context that does not own the whole grid
+ * (z_begin > 0 or z_end < nz): a component may continue in the neighbouring slab, and the merge across the seams is
+ * not built yet -- download the slabs and label on the host there. */
+int  vcy_label_components(vcy_ctx* ctx, double iso_level, vcy_component** out, int64_t* n_out);
+void vcy_components_free(vcy_component* components);
+/* label of every voxel of the LAST vcy_label_components / vcy_keep_components on this context,
+ * -1 for a voxel that is not solid; nx*ny*nz entries, reference order.
+ * For vcy_keep_components these are the labels BEFORE its removal.  VCY_ERR_INVALID_ARG before any labelling. */
+int  vcy_download_labels(vcy_ctx* ctx, int64_t* labels);
+/* Labels, then keeps a component iff (keep_largest <= 0 or its rank in the order above is below keep_largest) and
+ * n_voxels >= min_voxels.  Every voxel of every other component gets sdf = fill_sdf; update_num and every other
+ * byte of the state stay.  fill_sdf must be finite with (double)fill_sdf >= iso_level (VCY_ERR_INVALID_ARG
+ * otherwise): a removed voxel is then outside for marching cubes and so are all its axis neighbours (outside,
+ * removed too, or untouched -- and cells with an untouched corner are skipped), so fill_sdf is never interpolated.
+ * The brick minima stay what they were: valid ones are reduced again by the kernel that rewrites a brick, so brick
+ * skipping in vcy_extract_iso and the live list of the next carve survive -- which a vcy_download / vcy_upload round
+ * trip would lose.  removed_components / removed_voxels (either may be NULL): what went.
+ * VCY_ERR_UNSUPPORTED, state untouched, for a context that does not own the whole grid (see above). */
+int  vcy_keep_components(vcy_ctx* ctx, double iso_level, int keep_largest, int64_t min_voxels,
+                         float fill_sdf, int64_t* removed_components, int64_t* removed_voxels);
+/* Milliseconds between HIP events on the context's stream around the kernels of the last vcy_label_components /
+ * vcy_keep_components (solid bits, run labels, merge, flatten, statistics and, for the latter, the filter), the
+ * two short host waits for the number of roots and their sorted list included; 0 when nothing was launched. */
+int  vcy_last_components_ms(const vcy_ctx* ctx, float* device_ms);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and

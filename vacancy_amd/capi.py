@@ -91,6 +91,16 @@ class MeshNormals(C.Structure):
 VCY_NORMALS_VERTEX, VCY_NORMALS_FACE = 1, 2
 
 
+class Component(C.Structure):
+    """vcy_component: one 6-connected component of the solid voxels (vcy_label_components)."""
+    _fields_ = [
+        ("label", C.c_int64),
+        ("n_voxels", C.c_int64),
+        ("bb_min", C.c_int32 * 3),
+        ("bb_max", C.c_int32 * 3),
+    ]
+
+
 # vcy_mesh_arrays_fn: int (*)(void* user, int64 n_vertices, int64 n_faces, float** vertices, int32** faces)
 MeshArraysFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.POINTER(C.c_float)),
                            C.POINTER(C.POINTER(C.c_int32)))
@@ -152,6 +162,11 @@ def load():
                                                    P(C.c_int64)]),
         "vcy_mesh_normals_free": (None, [P(MeshNormals)]),
         "vcy_last_normals_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_label_components": (C.c_int, [vp, C.c_double, P(P(Component)), P(C.c_int64)]),
+        "vcy_components_free": (None, [P(Component)]),
+        "vcy_download_labels": (C.c_int, [vp, vp]),
+        "vcy_keep_components": (C.c_int, [vp, C.c_double, C.c_int, C.c_int64, C.c_float, P(C.c_int64), P(C.c_int64)]),
+        "vcy_last_components_ms": (C.c_int, [vp, P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_extract_voxel": (C.c_int, [vp, C.c_int, P(Mesh)]),

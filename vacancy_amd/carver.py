@@ -331,6 +331,53 @@ class VoxelCarver:
         self._lib.vcy_ids_free(p)
         return ids
 
+    # -- connected components of the hull (no reference counterpart; definitions: include/vacancy_hip.h)
+    def LabelComponents(self, iso_level=0.0, labels=False):
+        """vcy_label_components: the 6-connected components of the solid voxels (update_num >= 1 and sdf < iso_level),
+        labelled on the device.  Dict of numpy arrays, one row per component, n_voxels descending then label ascending:
+        "label" (int64, the component's smallest voxel id), "n_voxels" (int64), "bb_min" / "bb_max" (int32 [n, 3],
+        inclusive x y z); with labels=True also "labels" (int64 per voxel, -1 where not solid); "device_ms"."""
+        p, n = C.POINTER(capi.Component)(), C.c_int64(0)
+        rc = self._lib.vcy_label_components(self._ctx, iso_level, C.byref(p), C.byref(n))
+        if rc != 0:
+            raise RuntimeError(last_error())
+        rec = np.dtype([("label", np.int64), ("n_voxels", np.int64), ("bb_min", np.int32, 3), ("bb_max", np.int32, 3)])
+        assert rec.itemsize == C.sizeof(capi.Component)
+        if n.value:
+            arr = np.frombuffer(C.string_at(p, n.value * rec.itemsize), rec)
+            self._lib.vcy_components_free(p)
+        else:
+            arr = np.zeros(0, rec)
+        out = {k: np.ascontiguousarray(arr[k]) for k in ("label", "n_voxels", "bb_min", "bb_max")}
+        if labels:
+            out["labels"] = self.download_labels()
+        out["device_ms"] = self.last_components_ms()
+        return out
+
+    def KeepComponents(self, iso_level=0.0, largest=1, min_voxels=0, fill_sdf=1.0):
+        """vcy_keep_components: keeps the `largest` largest components (<= 0: any number) that have at least
+        `min_voxels` voxels; every voxel of every other component gets sdf = fill_sdf (finite, >= iso_level), in
+        place, with the brick minima kept current."""
+        rc_n, rv_n = C.c_int64(0), C.c_int64(0)
+        rc = self._lib.vcy_keep_components(self._ctx, iso_level, int(largest), int(min_voxels), fill_sdf,
+                                           C.byref(rc_n), C.byref(rv_n))
+        if rc != 0:
+            raise RuntimeError(last_error())
+        return {"removed_components": int(rc_n.value), "removed_voxels": int(rv_n.value),
+                "device_ms": self.last_components_ms()}
+
+    def download_labels(self):
+        """vcy_download_labels: the label of every voxel as of the last LabelComponents / KeepComponents."""
+        lab = np.empty(self.slab_voxels, np.int64)
+        if self._lib.vcy_download_labels(self._ctx, _p(lab)) != 0:
+            raise RuntimeError(last_error())
+        return lab
+
+    def last_components_ms(self):
+        ms = C.c_float()
+        self._lib.vcy_last_components_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     # -- state access
     def download(self):
         n = self.slab_voxels

@@ -510,6 +510,12 @@ void vcy_destroy(vcy_ctx* c) {
   (void)hipFree(c->d_mc_normals);
   if (c->ev_nrm_begin) (void)hipEventDestroy(c->ev_nrm_begin);
   if (c->ev_nrm_end) (void)hipEventDestroy(c->ev_nrm_end);
+  (void)hipFree(c->d_cc_labels);
+  (void)hipFree(c->d_cc_bits);
+  (void)hipFree(c->d_cc_roots);
+  if (c->h_cc_report) (void)hipHostFree(c->h_cc_report);
+  if (c->ev_cc_begin) (void)hipEventDestroy(c->ev_cc_begin);
+  if (c->ev_cc_end) (void)hipEventDestroy(c->ev_cc_end);
   (void)hipFree(c->d_mc_flags);
   if (c->h_mc_report) (void)hipHostFree(c->h_mc_report);
   (void)hipFree(c->d_mc_cells);

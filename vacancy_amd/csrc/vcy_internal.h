@@ -192,6 +192,21 @@ struct vcy_ctx {
   size_t mc_normals_bytes = 0;
   hipEvent_t ev_nrm_begin = nullptr, ev_nrm_end = nullptr;  // around the normals launches (vcy_last_normals_ms)
   float last_normals_device_ms = 0.0f;
+  // connected components (components.hip); everything grow-only
+  void* d_cc_labels = nullptr;        // int32 per voxel: the label (smallest voxel id of the component) or -1, of the last labelling
+  size_t cc_labels_bytes = 0;
+  void* d_cc_bits = nullptr;          // the solid bit of every voxel in 64-voxel words along x, and the root counter behind them
+  size_t cc_bits_bytes = 0;
+  void* d_cc_roots = nullptr;         // [statistics | sorted roots | removal flags] of up to cc_roots_cap components
+  size_t cc_roots_bytes = 0;
+  int cc_roots_cap = 0;
+  int cc_n_roots = 0;
+  void* h_cc_report = nullptr;        // 64 page-locked bytes the number of roots is read through
+  bool cc_labels_valid = false;       // vcy_download_labels has something to return ...
+  bool cc_labels_empty = false;       // ... namely -1 everywhere (the slab was fresh: nothing was launched)
+  hipEvent_t ev_cc_begin = nullptr, ev_cc_end = nullptr;
+  bool cc_timed = false;
+  float last_components_device_ms = 0.0f;
 
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
@@ -227,6 +242,7 @@ int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy
 // that owns a z-slab then gets the slab instance of the vertex normals (seam vertices left at zero)
 int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int which = 0,
                 vcy_mesh_normals* normals_out = nullptr, int64_t* layer_faces = nullptr);
+// components.hip: vcy_label_components, vcy_keep_components, vcy_download_labels, vcy_last_components_ms
 // sdf2d.hip
 void host_distance_transform_l1(const uint8_t* mask, int w, int h, const int32_t* rmin,
                                 const int32_t* rmax, float* out);

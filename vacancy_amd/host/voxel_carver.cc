@@ -321,6 +321,50 @@ void VoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_in
   LOGI("MarchingCubes with normals %02f\n", NowMs() - t0);
 }
 
+bool VoxelCarver::LabelComponents(std::vector<VoxelComponent>* components, double iso_level) {
+  components->clear();
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  vcy_component* list = nullptr;
+  std::int64_t n = 0;
+  const int rc = vcy_label_components(impl_->ctx, iso_level, &list, &n);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  components->resize(static_cast<size_t>(n));
+  for (std::int64_t i = 0; i < n; ++i) {
+    VoxelComponent& c = (*components)[static_cast<size_t>(i)];
+    c.label = list[i].label;
+    c.n_voxels = list[i].n_voxels;
+    for (int k = 0; k < 3; ++k) c.bb_min[k] = list[i].bb_min[k], c.bb_max[k] = list[i].bb_max[k];
+  }
+  vcy_components_free(list);
+  return true;
+}
+
+bool VoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  std::int64_t gone = 0, gone_voxels = 0;
+  const int rc = vcy_keep_components(impl_->ctx, iso_level, largest, min_voxels, fill_sdf, &gone, &gone_voxels);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  float ms = 0.0f;
+  vcy_last_components_ms(impl_->ctx, &ms);
+  LOGI("KeepLargestComponents removed %lld components, %lld voxels %02f\n", static_cast<long long>(gone),
+       static_cast<long long>(gone_voxels), static_cast<double>(ms));
+  return true;
+}
+
 void VoxelCarver::ExtractVoxel(Mesh* mesh, bool inside_empty) {
   mesh->Clear();
   if (!impl_->ctx) return;
