@@ -43,7 +43,8 @@ static bool LoadTumPoses(const std::string& path, std::vector<Eigen::Affine3d>* 
 
 int main(int argc, char* argv[]) {
   // --keep-largest (anywhere on the command line): before the final extraction, carve away every connected component
-  // of the hull but the largest (VoxelCarver::KeepLargestComponents) -- the floaters six views leave
+  // of the hull but the largest (VoxelCarver::KeepLargestComponents) -- the floaters six views leave; with slabs, the
+  // sharded run is filtered too (ShardedVoxelCarver::KeepLargestComponents) and its kept mesh compared
   bool keep_largest = false;
   {
     int n = 1;
@@ -160,6 +161,23 @@ int main(int argc, char* argv[]) {
     if (!carver.LabelComponents(&before) || !carver.KeepLargestComponents(1) || !carver.LabelComponents(&after)) return 9;
     std::printf("COMPONENTS before %zu after %zu largest %lld voxels\n", before.size(), after.size(),
                 before.empty() ? 0LL : static_cast<long long>(before[0].n_voxels));
+    if (sharded) {  // the same filter over the slabs: the same lists, and the kept mesh equals the single carver's
+      std::vector<vacancy::VoxelComponent> sbefore, safter;
+      if (!sharded->LabelComponents(&sbefore) || !sharded->KeepLargestComponents(1) || !sharded->LabelComponents(&safter)) return 9;
+      vacancy::Mesh kept, skept;
+      carver.ExtractIsoSurface(&kept, 0.0);
+      sharded->ExtractIsoSurface(&skept, 0.0);
+      bool same = sbefore.size() == before.size() && safter.size() == after.size() &&
+                  skept.vertices().size() == kept.vertices().size() && skept.vertex_indices().size() == kept.vertex_indices().size();
+      for (size_t k = 0; same && k < sbefore.size(); ++k) same = sbefore[k].label == before[k].label && sbefore[k].n_voxels == before[k].n_voxels;
+      for (size_t k = 0; same && k < skept.vertices().size(); ++k)
+        for (int a = 0; a < 3; ++a) same = same && skept.vertices()[k][a] == kept.vertices()[k][a];
+      for (size_t k = 0; same && k < skept.vertex_indices().size(); ++k)
+        for (int a = 0; a < 3; ++a) same = same && skept.vertex_indices()[k][a] == kept.vertex_indices()[k][a];
+      std::printf("COMPONENTSSHARDED slabs %d before %zu after %zu kept verts %zu faces %zu single verts %zu faces %zu identical %d\n",
+                  sharded->slab_count(), sbefore.size(), safter.size(), skept.vertices().size(), skept.vertex_indices().size(),
+                  kept.vertices().size(), kept.vertex_indices().size(), same ? 1 : 0);
+    }
   }
   if (!poses.empty()) {
     vacancy::Mesh lit;

@@ -52,6 +52,13 @@ class ShardedVoxelCarver {
   // kept voxels of all slabs are walked in z order by ONE drifting cube on the host -- the reference's arithmetic
   // (extract_voxel.cc:290-311), so the mesh equals a single VoxelCarver's array for array.
   void ExtractVoxel(Mesh* mesh, bool inside_empty = false);
+  // VoxelCarver::LabelComponents / KeepLargestComponents over the slabs: every slab labels its own slices on its device
+  // (vcy_label_components_slab), one plane of labels per seam and the lists of touching pieces go through the host, which
+  // joins the pieces (vcy_merge_components_host); the filter is every slab's own kernel (vcy_keep_components_slab), brick
+  // minima kept current per slab.  The list, and the state afterwards, equal a single VoxelCarver's.  The halos are
+  // stale after the filter as after a Carve(); the extractions exchange them before they read them.
+  bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
+  bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
 
  private:
   bool ExchangeHalo();

@@ -121,7 +121,7 @@ class VoxelCarver {
   // among the `largest` largest (<= 0: any number) or has fewer than `min_voxels` voxels -- their voxels get
   // sdf = fill_sdf (finite, >= iso_level), so the phantom volumes and specks of a hull of few views are gone from
   // every later ExtractIsoSurface / ExtractVoxel, and further Carve() calls go on at full speed.  false + LOGE on
-  // an error.  ShardedVoxelCarver has no counterpart yet (the seam merge across z-slabs is not built).
+  // an error.  ShardedVoxelCarver has the same two members (the pieces of the z-slabs are merged across the seams).
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
 

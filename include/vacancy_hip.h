@@ -278,7 +278,7 @@ int vcy_extract_iso_normals(vcy_ctx* ctx, double iso_level, int linear_interp, i
  * vertices of the slab above).  Their faces lie in two slabs and a float sum cannot be continued as a lump, so their
  * entries are zero here and the host that merges the slabs finishes them:
  *   1. concatenate the slabs' normals with the merged numbering (a slab's foreign entries dropped, like its vertices);
- *   2. per seam, vcy_mesh_normals_host_seam on the MERGED arrays with the face range
+ *   2. per seam, vcy_mesh_normals_seam_sum (or vcy_mesh_normals_host_seam) on the MERGED arrays with the face range
  *      [first face of the upper slab - layer_faces[1] of the lower slab, first face of the upper slab + layer_faces[0]
  *      of the upper slab) and the merged ids the upper slab's foreign vertices were mapped to by edge key.
  * layer_faces[0] / [1] = the numbers of faces of the slab's first / last own cell layer (both n_faces for a slab of one
@@ -303,6 +303,13 @@ int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vert
  * a vertex named by a face of the range outside [0, n_vertices), or a range that is not 0 <= face_begin <= face_end. */
 int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const int32_t* faces, int64_t face_begin,
                                int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals);
+/* The same finish from face normals that exist already: face_normals (3 floats per face of the MERGED mesh, the slabs'
+ * device results concatenated) instead of the positions.  For a mesh without NaN the two calls give the same bits.  A
+ * mesh over NaN voxels has NaN face normals of either sign; this call takes the devices' own and adds them as the
+ * vertex normals kernel does (of two NaNs the later term's), so that the seam vertices equal the whole-grid context's
+ * to the bit there as well.  The mergers of the sharded carvers use this one.  Errors as above. */
+int vcy_mesh_normals_seam_sum(int64_t n_vertices, const int32_t* faces, const float* face_normals, int64_t face_begin,
+                              int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals);
 
 /* ---- connected components of the hull ------------------------------------ */
 
@@ -326,12 +333,12 @@ typedef struct vcy_component {   /* 40 bytes */
  * nothing has been carved into since vcy_create / vcy_reset returns the empty list without its lazy fill being
  * written.  Labels take 4 bytes per voxel of device memory (kept by the context): VCY_ERR_TOO_MANY_VOXELS above
  * 2^31 - 1 voxels.  VCY_ERR_UNSUPPORTED, with the state untouched, for a context that does not own the whole grid
- * (z_begin > 0 or z_end < nz): a component may continue in the neighbouring slab, and the merge across the seams is
- * not built yet -- download the slabs and label on the host there. */
+ * (z_begin > 0 or z_end < nz): a component may continue in the neighbouring slab -- vcy_label_components_slab and the
+ * seam merge below are the calls for a grid cut into z-slabs. */
 int  vcy_label_components(vcy_ctx* ctx, double iso_level, vcy_component** out, int64_t* n_out);
 void vcy_components_free(vcy_component* components);
 /* label of every voxel of the LAST vcy_label_components / vcy_keep_components on this context,
- * -1 for a voxel that is not solid; nx*ny*nz entries, reference order.
+ * -1 for a voxel that is not solid; nx*ny*nz entries, reference order (a z-slab: nx*ny*(z_end - z_begin), global ids).
  * For vcy_keep_components these are the labels BEFORE its removal.  VCY_ERR_INVALID_ARG before any labelling. */
 int  vcy_download_labels(vcy_ctx* ctx, int64_t* labels);
 /* Labels, then keeps a component iff (keep_largest <= 0 or its rank in the order above is below keep_largest) and
@@ -342,13 +349,75 @@ int  vcy_download_labels(vcy_ctx* ctx, int64_t* labels);
  * The brick minima stay what they were: valid ones are reduced again by the kernel that rewrites a brick, so brick
  * skipping in vcy_extract_iso and the live list of the next carve survive -- which a vcy_download / vcy_upload round
  * trip would lose.  removed_components / removed_voxels (either may be NULL): what went.
- * VCY_ERR_UNSUPPORTED, state untouched, for a context that does not own the whole grid (see above). */
+ * VCY_ERR_UNSUPPORTED, state untouched, for a context that does not own the whole grid (see above;
+ * vcy_keep_components_slab is the filter of a z-slab). */
 int  vcy_keep_components(vcy_ctx* ctx, double iso_level, int keep_largest, int64_t min_voxels,
                          float fill_sdf, int64_t* removed_components, int64_t* removed_voxels);
 /* Milliseconds between HIP events on the context's stream around the kernels of the last vcy_label_components /
  * vcy_keep_components (solid bits, run labels, merge, flatten, statistics and, for the latter, the filter), the
  * two short host waits for the number of roots and their sorted list included; 0 when nothing was launched. */
 int  vcy_last_components_ms(const vcy_ctx* ctx, float* device_ms);
+
+/* ---- connected components of a grid cut into z-slabs ---------------------- */
+
+/* The same definitions for contexts that each own a z-slab [z_begin, z_end) of one grid (any devices, one process or
+ * one per GPU).  Every slab labels its own slices on its device; what crosses a seam is ONE plane of labels
+ * (nx * ny int64, through host memory) and a list of label pairs, never a slab's label volume; the host joins the
+ * pieces.  Per-voxel storage stays 32 bits per SLAB (VCY_ERR_TOO_MANY_VOXELS above 2^31 - 1 voxels in one slab) while
+ * everything that leaves a context is a 64-bit global voxel id, so a grid of more than 2^31 voxels can be labelled
+ * in slabs.  The merged list and the merged per-voxel labels equal what vcy_label_components returns on one context
+ * holding the whole grid, wherever the grid is cut.  Order of calls, slabs in z order s = 0 .. S - 1:
+ *   1. vcy_label_components_slab on every slab: the slab's own pieces with PROVISIONAL labels -- z_begin * nx * ny + the
+ *      smallest slab-local id of the piece, i.e. its smallest global id -- and boxes in global z;
+ *   2. vcy_component_top_plane on slabs 0 .. S - 2, vcy_component_seam_pairs on slabs 1 .. S - 1 with the plane of the
+ *      slab below: (label below, label above) for the pieces that touch across the seam;
+ *   3. vcy_merge_components_host (no GPU): the merged list and, per slab, the global label of every piece;
+ *   4. vcy_resolve_components_slab on every slab installs its map: vcy_download_labels then returns merged labels;
+ *   5. for the filter, vcy_keep_components_slab on every slab with the pieces that go.
+ * Steps 2, 4 and 5 speak about the state step 1 labelled: after a carve, vcy_upload or vcy_reset they return
+ * VCY_ERR_INVALID_ARG until the slab is labelled again.  A slab's halo below an upper slab is stale after step 5, as
+ * after a carve: exchange the halos (vcy_halo_allgather, ...) before the next extraction, which every sharded
+ * extractor does anyway. */
+
+/* vcy_label_components on the slices this context owns (any context: on a whole grid the list is exactly
+ * vcy_label_components').  Applies queued views; the state is not changed; a context nothing has been carved into
+ * since vcy_create / vcy_reset returns the empty list without its lazy fill being written.  Drops a map installed
+ * earlier: vcy_download_labels returns the provisional labels until step 4. */
+int  vcy_label_components_slab(vcy_ctx* ctx, double iso_level, vcy_component** out, int64_t* n_out);
+/* The provisional labels of this slab's last slice z_end - 1 (nx * ny entries, -1 where not solid): what the slab
+ * above needs.  VCY_ERR_INVALID_ARG before vcy_label_components_slab. */
+int  vcy_component_top_plane(vcy_ctx* ctx, int64_t* plane_labels);
+/* On the UPPER slab of a seam: `below_plane_labels` (host memory, nx * ny) is vcy_component_top_plane of the slab that
+ * ends at this context's z_begin.  Uploads it and compares it on the device with this slab's own labels of slice
+ * z_begin; returns 2 * n int64 -- (label below, label above) per pair, sorted, every pair once -- library-owned
+ * (vcy_seam_pairs_free; NULL and 0 when nothing touches).  VCY_ERR_INVALID_ARG for a context with z_begin == 0 (no seam
+ * below it) or one that has not been labelled.  vcy_last_components_ms afterwards: this call's device time. */
+int  vcy_component_seam_pairs(vcy_ctx* ctx, const int64_t* below_plane_labels, int64_t** pairs_out, int64_t* n_pairs_out);
+void vcy_seam_pairs_free(int64_t* pairs);
+/* The seam merge, host arithmetic only (no GPU needed).  `lists`: the slabs' lists of step 1 one behind the other in z
+ * order, n_lists[s] entries of slab s; `pairs`: the seams' pair lists one behind the other, n_pairs[s] pairs (2 int64
+ * each) for the seam between slabs s and s + 1 -- duplicates allowed, either array NULL when empty.  Union-find over the
+ * labels: a merged component's label is the smallest provisional label of its set (= its smallest global voxel id),
+ * n_voxels are summed, boxes joined.  merged_out: the list in the order of vcy_label_components (library-owned,
+ * vcy_components_free; NULL when empty); global_labels[i]: the merged label of entry i of `lists` (caller-allocated, sum
+ * of n_lists entries).  VCY_ERR_INVALID_ARG for a pair that names a label its slab did not report (first number: slab
+ * s, second: slab s + 1), a label a slab reports twice, or a negative count. */
+int  vcy_merge_components_host(int n_slabs, const vcy_component* lists, const int64_t* n_lists, const int64_t* pairs,
+                               const int64_t* n_pairs, vcy_component** merged_out, int64_t* n_merged_out,
+                               int64_t* global_labels);
+/* Installs this slab's part of the merge: n = the number of pieces step 1 reported, every one of them named once in
+ * provisional_labels, with its merged label.  VCY_ERR_INVALID_ARG, nothing installed, for another count, a label the
+ * slab did not report or names twice, or a merged label that is negative or above the piece's own. */
+int  vcy_resolve_components_slab(vcy_ctx* ctx, int64_t n, const int64_t* provisional_labels, const int64_t* global_labels);
+/* The filter of vcy_keep_components on a slab: every voxel of the listed pieces (provisional labels of step 1) gets
+ * sdf = fill_sdf, in place, over the slab's own 8 x 8 x 8 bricks; update_num and every other byte of the state stay;
+ * valid brick minima are reduced again in the bricks that changed and only there.  Which pieces go is the caller's
+ * decision on the MERGED list (the rule of vcy_keep_components).  fill_sdf: finite and not below the iso level of step
+ * 1, VCY_ERR_INVALID_ARG otherwise, as for a label the slab did not report or a slab that has not been labelled --
+ * state untouched in every such case.  vcy_download_labels afterwards: the labels from before the removal; a second
+ * filter needs a new labelling.  removed_voxels may be NULL.  vcy_last_components_ms: the filter's device time. */
+int  vcy_keep_components_slab(vcy_ctx* ctx, float fill_sdf, int64_t n_remove, const int64_t* remove_provisional_labels,
+                              int64_t* removed_voxels);
 
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 

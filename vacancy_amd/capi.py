@@ -167,8 +167,16 @@ def load():
         "vcy_download_labels": (C.c_int, [vp, vp]),
         "vcy_keep_components": (C.c_int, [vp, C.c_double, C.c_int, C.c_int64, C.c_float, P(C.c_int64), P(C.c_int64)]),
         "vcy_last_components_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_label_components_slab": (C.c_int, [vp, C.c_double, P(P(Component)), P(C.c_int64)]),
+        "vcy_component_top_plane": (C.c_int, [vp, vp]),
+        "vcy_component_seam_pairs": (C.c_int, [vp, vp, P(P(C.c_int64)), P(C.c_int64)]),
+        "vcy_seam_pairs_free": (None, [P(C.c_int64)]),
+        "vcy_merge_components_host": (C.c_int, [C.c_int, vp, vp, vp, vp, P(P(Component)), P(C.c_int64), vp]),
+        "vcy_resolve_components_slab": (C.c_int, [vp, C.c_int64, vp, vp]),
+        "vcy_keep_components_slab": (C.c_int, [vp, C.c_float, C.c_int64, vp, P(C.c_int64)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
+        "vcy_mesh_normals_seam_sum": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_extract_voxel": (C.c_int, [vp, C.c_int, P(Mesh)]),
         "vcy_extract_voxel_ids": (C.c_int, [vp, C.c_int, P(P(C.c_int64)), P(C.c_int64)]),
         "vcy_ids_free": (None, [P(C.c_int64)]),

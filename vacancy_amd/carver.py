@@ -60,6 +60,26 @@ def mesh_normals_host_seam(vertices, faces, face_begin, face_end, seam_vertex_id
     return vn
 
 
+def mesh_normals_seam_sum(n_vertices, faces, face_normals, face_begin, face_end, seam_vertex_ids, vertex_normals):
+    """vcy_mesh_normals_seam_sum: the seam finish from the merged mesh's face normals (the devices' own) instead of the
+    positions, IN PLACE in `vertex_normals` like mesh_normals_host_seam; of two NaN terms the later one's, as on the
+    device.  Serial, no GPU needed."""
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    fn = np.ascontiguousarray(face_normals, np.float32).reshape(-1, 3)
+    ids = np.ascontiguousarray(seam_vertex_ids, np.int64).reshape(-1)
+    vn = vertex_normals
+    if not (isinstance(vn, np.ndarray) and vn.dtype == np.float32 and vn.flags.c_contiguous and vn.flags.writeable
+            and vn.shape == (int(n_vertices), 3)):
+        raise ValueError("vertex_normals must be a writeable C-contiguous float32 array of the vertices' shape")
+    if face_end > len(f) or len(fn) != len(f):
+        raise ValueError("faces [%d, %d) of %d, %d face normals" % (face_begin, face_end, len(f), len(fn)))
+    rc = capi.load().vcy_mesh_normals_seam_sum(int(n_vertices), _p(f), _p(fn), int(face_begin), int(face_end), len(ids),
+                                               _p(ids), _p(vn))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return vn
+
+
 class VoxelCarver:
     def __init__(self, option=None, device_id=0, z_range=None):
         self._lib = capi.load()
@@ -337,18 +357,14 @@ class VoxelCarver:
         labelled on the device.  Dict of numpy arrays, one row per component, n_voxels descending then label ascending:
         "label" (int64, the component's smallest voxel id), "n_voxels" (int64), "bb_min" / "bb_max" (int32 [n, 3],
         inclusive x y z); with labels=True also "labels" (int64 per voxel, -1 where not solid); "device_ms"."""
+        return self._label(self._lib.vcy_label_components, iso_level, labels)
+
+    def _label(self, entry, iso_level, labels):
         p, n = C.POINTER(capi.Component)(), C.c_int64(0)
-        rc = self._lib.vcy_label_components(self._ctx, iso_level, C.byref(p), C.byref(n))
+        rc = entry(self._ctx, iso_level, C.byref(p), C.byref(n))
         if rc != 0:
             raise RuntimeError(last_error())
-        rec = np.dtype([("label", np.int64), ("n_voxels", np.int64), ("bb_min", np.int32, 3), ("bb_max", np.int32, 3)])
-        assert rec.itemsize == C.sizeof(capi.Component)
-        if n.value:
-            arr = np.frombuffer(C.string_at(p, n.value * rec.itemsize), rec)
-            self._lib.vcy_components_free(p)
-        else:
-            arr = np.zeros(0, rec)
-        out = {k: np.ascontiguousarray(arr[k]) for k in ("label", "n_voxels", "bb_min", "bb_max")}
+        out = components_to_dict(p, n.value)
         if labels:
             out["labels"] = self.download_labels()
         out["device_ms"] = self.last_components_ms()
@@ -365,6 +381,52 @@ class VoxelCarver:
             raise RuntimeError(last_error())
         return {"removed_components": int(rc_n.value), "removed_voxels": int(rv_n.value),
                 "device_ms": self.last_components_ms()}
+
+    # -- the same for a context that owns a z-slab; the order of the calls is in include/vacancy_hip.h, and
+    # vacancy_amd.dist.label_components_slabs / keep_components_slabs go through it
+    def LabelComponentsSlab(self, iso_level=0.0, labels=False):
+        """vcy_label_components_slab: the pieces of the slices this context owns, as LabelComponents returns them, with
+        provisional labels (the piece's smallest global voxel id) and boxes in global z."""
+        return self._label(self._lib.vcy_label_components_slab, iso_level, labels)
+
+    def component_top_plane(self):
+        """vcy_component_top_plane: provisional labels of the slab's last slice (int64 [nx * ny], -1 where not solid)."""
+        plane = np.empty(self.dims[0] * self.dims[1], np.int64)
+        if self._lib.vcy_component_top_plane(self._ctx, _p(plane)) != 0:
+            raise RuntimeError(last_error())
+        return plane
+
+    def component_seam_pairs(self, below_plane):
+        """vcy_component_seam_pairs: int64 [n, 2] of (label in the slab below, label in this slab) for the pieces that
+        touch across the seam at this slab's first slice; `below_plane` = component_top_plane() of the slab below."""
+        below = np.ascontiguousarray(below_plane, np.int64)
+        if below.size != self.dims[0] * self.dims[1]:
+            raise ValueError("the plane has %d entries, a slice of this grid %d" % (below.size, self.dims[0] * self.dims[1]))
+        p, n = C.POINTER(C.c_int64)(), C.c_int64(0)
+        if self._lib.vcy_component_seam_pairs(self._ctx, _p(below), C.byref(p), C.byref(n)) != 0:
+            raise RuntimeError(last_error())
+        if not n.value:
+            return np.zeros((0, 2), np.int64)
+        pairs = np.ctypeslib.as_array(p, shape=(n.value, 2)).copy()
+        self._lib.vcy_seam_pairs_free(p)
+        return pairs
+
+    def resolve_components(self, provisional, merged):
+        """vcy_resolve_components_slab: installs the merged label of every piece LabelComponentsSlab reported;
+        download_labels() then returns merged labels."""
+        a, b = np.ascontiguousarray(provisional, np.int64), np.ascontiguousarray(merged, np.int64)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("one merged label per provisional label")
+        if self._lib.vcy_resolve_components_slab(self._ctx, len(a), _p(a), _p(b)) != 0:
+            raise RuntimeError(last_error())
+
+    def KeepComponentsSlab(self, remove_provisional, fill_sdf=1.0):
+        """vcy_keep_components_slab: the voxels of the listed pieces get sdf = fill_sdf.  {"removed_voxels", "device_ms"}."""
+        a = np.ascontiguousarray(remove_provisional, np.int64).reshape(-1)
+        gone = C.c_int64(0)
+        if self._lib.vcy_keep_components_slab(self._ctx, fill_sdf, len(a), _p(a), C.byref(gone)) != 0:
+            raise RuntimeError(last_error())
+        return {"removed_voxels": int(gone.value), "device_ms": self.last_components_ms()}
 
     def download_labels(self):
         """vcy_download_labels: the label of every voxel as of the last LabelComponents / KeepComponents."""
@@ -513,6 +575,49 @@ class VoxelCarver:
         ms = C.c_float()
         self._lib.vcy_timer_end(self._ctx, C.byref(ms))
         return ms.value
+
+
+_COMPONENT_REC = np.dtype([("label", np.int64), ("n_voxels", np.int64), ("bb_min", np.int32, 3), ("bb_max", np.int32, 3)])
+assert _COMPONENT_REC.itemsize == C.sizeof(capi.Component)
+
+
+def components_to_dict(p, n):
+    """A library-owned vcy_component list as the dict of arrays LabelComponents returns; frees the list."""
+    if n:
+        arr = np.frombuffer(C.string_at(p, n * _COMPONENT_REC.itemsize), _COMPONENT_REC)
+        capi.load().vcy_components_free(p)
+    else:
+        arr = np.zeros(0, _COMPONENT_REC)
+    return {k: np.ascontiguousarray(arr[k]) for k in ("label", "n_voxels", "bb_min", "bb_max")}
+
+
+def merge_components_host(lists, pairs):
+    """vcy_merge_components_host (no GPU): `lists` = the slabs' LabelComponentsSlab dicts in z order, `pairs` = the seams'
+    int64 [n, 2] arrays (one fewer).  Returns (merged dict, [merged label of every piece of slab s])."""
+    lib = capi.load()
+    ns = len(lists)
+    if len(pairs) != max(0, ns - 1):
+        raise ValueError("%d slabs have %d seams, not %d" % (ns, max(0, ns - 1), len(pairs)))
+    counts = np.array([len(l["label"]) for l in lists], np.int64)
+    flat = np.zeros(int(counts.sum()), _COMPONENT_REC)
+    at = 0
+    for l in lists:
+        k = len(l["label"])
+        for key in ("label", "n_voxels", "bb_min", "bb_max"):
+            flat[key][at:at + k] = l[key]
+        at += k
+    pr = [np.ascontiguousarray(q, np.int64).reshape(-1, 2) for q in pairs]
+    pcounts = np.array([len(q) for q in pr], np.int64)
+    pflat = np.ascontiguousarray(np.concatenate(pr).reshape(-1) if pr else np.zeros(0, np.int64))
+    glob = np.full(len(flat), -1, np.int64)
+    p, n = C.POINTER(capi.Component)(), C.c_int64(0)
+    rc = lib.vcy_merge_components_host(ns, _p(flat), _p(counts), _p(pflat), _p(pcounts), C.byref(p), C.byref(n), _p(glob))
+    if rc != 0:
+        e = RuntimeError(last_error())
+        e.rc = rc
+        raise e
+    ends = np.cumsum(counts)
+    return components_to_dict(p, n.value), [glob[e - k:e].copy() for e, k in zip(ends, counts)]
 
 
 def carve_batch_silhouettes_sharded(carvers, views, silhouettes):

@@ -23,6 +23,17 @@
 //                   reduced again from what was read and written.
 // The host reads the number of roots once (page-locked), sorts the root list (real scenes: tens of roots) and, for the
 // filter, marks the slots to be removed.  Label storage: 4 bytes per voxel + 1 bit, so up to 2^31 - 1 voxels.
+//
+// A grid cut into z-slabs (vcy_label_components_slab and what follows it in vacancy_hip.h): every slab runs steps 1 - 5
+// over its own slices -- per-voxel storage stays a 32-bit slab-local index, everything reported is a 64-bit global id
+// (z_begin * nx * ny + the local one) --, then
+//   7. cc_seam_pairs   on the upper slab of a seam, one wave per 64-voxel word of its first plane: the labels of the lower
+//                      slab's top plane (nx * ny int64, through host memory) against its own; one (lower, upper) pair per
+//                      maximal stretch of x where both are solid -- inside such a stretch either side is one run, so one
+//                      piece.  One wave-aggregated atomicAdd per word for the output slots.
+// and the host joins the slabs' pieces (vcy_merge_components_host: union-find over the 64-bit provisional labels).  What
+// crosses a seam is that plane and the pairs, never a slab's label volume.  The filter on a slab is cc_filter over the
+// slab's own bricks with the removal flags the merged list gives.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -309,6 +320,45 @@ __global__ __launch_bounds__(256) void cc_filter_kernel(float* __restrict__ sdf,
   }
 }
 
+// One wave per 64-voxel word of the slab's first plane, a lane per voxel.  `below[v]`: the label the slab below gave the
+// voxel under v (global, -1: not solid); `label`: this slab's own (slab-local, -1: not solid).  A pair goes out at the
+// first voxel of every maximal stretch of x in which both are solid; the stretch that continues from the previous word
+// has gone out there (the carry, as in cc_merge_kernel).  *n_pairs counts every pair, stored or not: the host comes
+// again with a larger list when it did not fit.
+__global__ __launch_bounds__(256) void cc_seam_pairs_kernel(const int* __restrict__ label, const int64_t* __restrict__ below,
+                                                            int nx, int Wr, int nwords, int64_t id0, int64_t* __restrict__ pairs,
+                                                            unsigned int cap, unsigned int* __restrict__ n_pairs) {
+  const int lane = threadIdx.x & 63;
+  for (int wi = blockIdx.x * 4 + (threadIdx.x >> 6); wi < nwords; wi += gridDim.x * 4) {  // (uniform per wave)
+    const int y = wi / Wr, w = wi - y * Wr;
+    const int x = w * 64 + lane;
+    int own = -1;
+    int64_t low = -1;
+    if (x < nx) {
+      own = label[(int64_t)y * nx + x];
+      low = below[(int64_t)y * nx + x];
+    }
+    const u64 both = __ballot(own >= 0 && low >= 0);
+    if (both == 0ull) continue;
+    bool left = false;  // the voxel before the word: lane 0 looks
+    if (lane == 0 && w > 0) left = label[(int64_t)y * nx + x - 1] >= 0 && below[(int64_t)y * nx + x - 1] >= 0;
+    const u64 carry = __ballot(left) & 1ull;
+    const u64 starts = both & ~((both << 1) | carry);
+    if (starts == 0ull) continue;
+    const int first = __builtin_ctzll(starts);
+    unsigned int base = 0;
+    if (lane == first) base = atomicAdd(n_pairs, (unsigned int)__builtin_popcountll(starts));
+    base = __shfl(base, first, 64);
+    if ((starts >> lane) & 1ull) {
+      const unsigned int k = base + (unsigned int)__builtin_popcountll(starts & ((1ull << lane) - 1ull));
+      if (k < cap) {
+        pairs[2 * (int64_t)k] = low;
+        pairs[2 * (int64_t)k + 1] = id0 + own;
+      }
+    }
+  }
+}
+
 }  // namespace cc
 
 using cc::Stats;
@@ -332,9 +382,15 @@ bool whole_grid(const vcy_ctx* c) { return c->z0 == 0 && c->z1 == c->nz && c->ha
 // Steps 1 - 5.  `comps` in the order of the header (n_voxels descending, label ascending); `slot_of_comp[i]` = where
 // component i's root stands in the sorted root list the device holds (cc_roots).  The begin event is recorded here, the
 // end event by the caller.
+// Runs over the slices the context owns: on a z-slab the labels and the boxes are global (z_begin added), the pieces
+// those of the slab alone.
 static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* comps, std::vector<int>* slot_of_comp) {
   comps->clear();
   if (slot_of_comp) slot_of_comp->clear();
+  c->cc_slab_labelled = false;
+  c->cc_roots_host.clear();
+  c->cc_nvox_host.clear();
+  c->cc_global_host.clear();
   c->last_components_device_ms = 0.0f;
   c->cc_timed = false;
   { const int rcf = flush_pending(c); if (rcf != VCY_OK) return rcf; }
@@ -351,7 +407,7 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
     return VCY_ERR_TOO_MANY_VOXELS;
   }
   const int nx = c->nx, ny = c->ny, Wr = (nx + 63) / 64;
-  const int64_t nwords = (int64_t)Wr * ny * c->nz;
+  const int64_t nwords = (int64_t)Wr * ny * c->nz_local();
   { const int rc = grow(&c->d_cc_labels, &c->cc_labels_bytes, sizeof(int) * (size_t)n); if (rc != VCY_OK) return rc; }
   { const int rc = grow(&c->d_cc_bits, &c->cc_bits_bytes, sizeof(cc::u64) * (size_t)nwords + 64); if (rc != VCY_OK) return rc; }
   if (c->cc_roots_cap == 0) {
@@ -440,14 +496,19 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
     return roots[(size_t)a] < roots[(size_t)b];
   });
   comps->resize((size_t)n_roots);
+  const int64_t id0 = (int64_t)c->z0 * c->slice;
   for (size_t i = 0; i < order.size(); ++i) {
     const size_t s = (size_t)order[i];
     vcy_component& o = (*comps)[i];
-    o.label = roots[s];
+    o.label = id0 + roots[s];
     o.n_voxels = (int64_t)stats[s].n;
     for (int k = 0; k < 3; ++k) o.bb_min[k] = stats[s].mn[k], o.bb_max[k] = stats[s].mx[k];
+    o.bb_min[2] += c->z0, o.bb_max[2] += c->z0;
   }
   if (slot_of_comp) *slot_of_comp = order;
+  c->cc_nvox_host.resize((size_t)n_roots);
+  for (size_t s = 0; s < (size_t)n_roots; ++s) c->cc_nvox_host[s] = (int64_t)stats[s].n;
+  c->cc_roots_host.swap(roots);
   return VCY_OK;
 }
 
@@ -459,13 +520,74 @@ static int finish_timer(vcy_ctx* c) {
   return VCY_OK;
 }
 
+// Step 6 over the bricks of the owned slices (bricks are slab-local, as the fused carve's: z_begin need not be a multiple
+// of 8).  removed[slot]: in the order of the sorted root list; keep0: a slab-local root that stays, or -1.
+static int launch_filter(vcy_ctx* c, const std::vector<uint8_t>& removed, int keep0, float fill_sdf) {
+  const size_t nc = removed.size();
+  Stats* d_stats = (Stats*)c->d_cc_roots;
+  const int* d_roots = (const int*)(d_stats + c->cc_roots_cap);
+  uint8_t* d_removed = (uint8_t*)(d_roots + c->cc_roots_cap);
+  VCY_HIP_CHECK(hipMemcpyAsync(d_removed, removed.data(), nc, hipMemcpyHostToDevice, c->stream));
+  const int nzl = c->nz_local();
+  const int nbw = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (nzl + 7) / 8;
+  const int64_t nbricks = (int64_t)nbw * nby * nbz;
+  float* bmin = c->brick_min_valid && c->d_brick_min ? c->d_brick_min : nullptr;
+  hipLaunchKernelGGL(cc::cc_filter_kernel, dim3((unsigned)((nbricks + 3) / 4)), dim3(256), 0, c->stream, c->owned_slab_sdf(),
+                     (const int*)c->d_cc_labels, c->nx, c->ny, nzl, nbw, nby, nbricks, d_roots, (int)nc, d_removed, keep0,
+                     fill_sdf, bmin);
+  VCY_HIP_CHECK(hipGetLastError());
+  return VCY_OK;
+}
+
 static int check_owner(const vcy_ctx* c, const char* who) {
   if (whole_grid(c)) return VCY_OK;
-  // a component may continue in the neighbouring slab: the seam merge is not built yet
-  set_error("%s: the context owns z [%d, %d) of %d slices; components need the whole grid in one context", who, c->z0, c->z1,
-            c->nz);
+  // a component may continue in the neighbouring slab: vcy_label_components_slab and the seam merge are the calls for it
+  set_error("%s: the context owns z [%d, %d) of %d slices; components need the whole grid in one context "
+            "(a z-slab: vcy_label_components_slab)", who, c->z0, c->z1, c->nz);
   return VCY_ERR_UNSUPPORTED;
 }
+
+// where a slab-local root stands in the sorted root list, or -1
+static int host_slot_of(const vcy_ctx* c, int64_t root) {
+  const std::vector<int>& r = c->cc_roots_host;
+  if (root < 0 || root > 0x7fffffffLL) return -1;
+  const auto it = std::lower_bound(r.begin(), r.end(), (int)root);
+  return it != r.end() && *it == (int)root ? (int)(it - r.begin()) : -1;
+}
+
+// the seam calls need the labelling vcy_label_components_slab left, of the state as it is now
+static int check_slab_labelled(const vcy_ctx* c, const char* who) {
+  if (!c->cc_slab_labelled || !c->cc_labels_valid) {
+    set_error("%s: vcy_label_components_slab has not labelled this context", who);
+    return VCY_ERR_INVALID_ARG;
+  }
+  if (!c->pending.empty() || c->views_carved != c->cc_views_at_label) {
+    set_error("%s: views have been carved since vcy_label_components_slab: label again", who);
+    return VCY_ERR_INVALID_ARG;
+  }
+  return VCY_OK;
+}
+
+namespace {
+
+struct UnionFind {  // over indices; a set's root is its smallest index
+  std::vector<int64_t> p;
+  explicit UnionFind(size_t n) : p(n) {
+    for (size_t i = 0; i < n; ++i) p[i] = (int64_t)i;
+  }
+  int64_t find(int64_t i) {
+    while (p[(size_t)i] != i) i = p[(size_t)i] = p[(size_t)p[(size_t)i]];
+    return i;
+  }
+  void unite(int64_t a, int64_t b) {
+    a = find(a), b = find(b);
+    if (a == b) return;
+    if (a < b) p[(size_t)b] = a;
+    else p[(size_t)a] = b;
+  }
+};
+
+}  // namespace
 
 }  // namespace vcy
 
@@ -518,7 +640,21 @@ int vcy_download_labels(vcy_ctx* c, int64_t* labels) {
   std::vector<int> raw((size_t)n);
   VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
   VCY_HIP_CHECK(hipMemcpy(raw.data(), c->d_cc_labels, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; ++i) labels[i] = raw[(size_t)i];
+  if (!c->cc_global_host.empty()) {  // the merged labels (vcy_resolve_components_slab); neighbours mostly share a root
+    int last = -1;
+    int64_t last_global = -1;
+    for (int64_t i = 0; i < n; ++i) {
+      const int r = raw[(size_t)i];
+      if (r != last) {
+        last = r;
+        last_global = r < 0 ? -1 : c->cc_global_host[(size_t)host_slot_of(c, r)];
+      }
+      labels[i] = last_global;
+    }
+    return VCY_OK;
+  }
+  const int64_t id0 = (int64_t)c->z0 * c->slice;  // (0 on a whole grid)
+  for (int64_t i = 0; i < n; ++i) labels[i] = raw[(size_t)i] < 0 ? -1 : id0 + raw[(size_t)i];
   return VCY_OK;
 }
 
@@ -555,17 +691,8 @@ int vcy_keep_components(vcy_ctx* c, double iso_level, int keep_largest, int64_t 
     rv_n += comps[i].n_voxels;
   }
   if (rc_n > 0) {
-    Stats* d_stats = (Stats*)c->d_cc_roots;
-    const int* d_roots = (const int*)(d_stats + c->cc_roots_cap);
-    uint8_t* d_removed = (uint8_t*)(d_roots + c->cc_roots_cap);
-    VCY_HIP_CHECK(hipMemcpyAsync(d_removed, removed.data(), nc, hipMemcpyHostToDevice, c->stream));
-    const int nbw = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (c->nz + 7) / 8;
-    const int64_t nbricks = (int64_t)nbw * nby * nbz;
-    float* bmin = c->brick_min_valid && c->d_brick_min ? c->d_brick_min : nullptr;
-    hipLaunchKernelGGL(cc::cc_filter_kernel, dim3((unsigned)((nbricks + 3) / 4)), dim3(256), 0, c->stream, c->owned_slab_sdf(),
-                       (const int*)c->d_cc_labels, c->nx, c->ny, c->nz, nbw, nby, nbricks, d_roots, (int)nc, d_removed, keep0,
-                       fill_sdf, bmin);
-    VCY_HIP_CHECK(hipGetLastError());
+    const int rc = launch_filter(c, removed, keep0, fill_sdf);
+    if (rc != VCY_OK) return rc;
     // (the copy reads `removed` until the stream has passed it: finish_timer waits)
   }
   { const int rc = finish_timer(c); if (rc != VCY_OK) return rc; }
@@ -577,6 +704,319 @@ int vcy_keep_components(vcy_ctx* c, double iso_level, int keep_largest, int64_t 
 int vcy_last_components_ms(const vcy_ctx* c, float* device_ms) {
   if (!c || !device_ms) return VCY_ERR_INVALID_ARG;
   *device_ms = c->last_components_device_ms;
+  return VCY_OK;
+}
+
+/* ---- z-slabs ---------------------------------------------------------------------------------------------------- */
+
+int vcy_label_components_slab(vcy_ctx* c, double iso_level, vcy_component** out, int64_t* n_out) {
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  if (!out || !n_out) {
+    set_error("vcy_label_components_slab: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  *out = nullptr;
+  *n_out = 0;
+  VCY_HIP_CHECK(hipSetDevice(c->device));
+  std::vector<vcy_component> comps;
+  { const int rc = label_components(c, iso_level, &comps, nullptr); if (rc != VCY_OK) return rc; }
+  { const int rc = finish_timer(c); if (rc != VCY_OK) return rc; }
+  c->cc_slab_labelled = true;
+  c->cc_iso = iso_level;
+  c->cc_views_at_label = c->views_carved;
+  if (comps.empty()) return VCY_OK;
+  vcy_component* p = (vcy_component*)std::malloc(sizeof(vcy_component) * comps.size());
+  if (!p) {
+    set_error("vcy_label_components_slab: out of host memory");
+    return VCY_ERR_INTERNAL;
+  }
+  std::memcpy(p, comps.data(), sizeof(vcy_component) * comps.size());
+  *out = p;
+  *n_out = (int64_t)comps.size();
+  return VCY_OK;
+}
+
+int vcy_component_top_plane(vcy_ctx* c, int64_t* plane_labels) {
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  if (!plane_labels) {
+    set_error("vcy_component_top_plane: null pointer");
+    return VCY_ERR_INVALID_ARG;
+  }
+  { const int rc = check_slab_labelled(c, "vcy_component_top_plane"); if (rc != VCY_OK) return rc; }
+  const int64_t slice = c->slice;
+  if (c->cc_labels_empty || c->cc_n_roots == 0) {
+    for (int64_t i = 0; i < slice; ++i) plane_labels[i] = -1;
+    return VCY_OK;
+  }
+  VCY_HIP_CHECK(hipSetDevice(c->device));
+  std::vector<int> raw((size_t)slice);
+  const int64_t first = slice * (int64_t)(c->nz_local() - 1);
+  VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
+  VCY_HIP_CHECK(hipMemcpy(raw.data(), (const int*)c->d_cc_labels + first, sizeof(int) * (size_t)slice, hipMemcpyDeviceToHost));
+  const int64_t id0 = (int64_t)c->z0 * slice;
+  for (int64_t i = 0; i < slice; ++i) plane_labels[i] = raw[(size_t)i] < 0 ? -1 : id0 + raw[(size_t)i];
+  return VCY_OK;
+}
+
+int vcy_component_seam_pairs(vcy_ctx* c, const int64_t* below_plane_labels, int64_t** pairs_out, int64_t* n_pairs_out) {
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  if (!below_plane_labels || !pairs_out || !n_pairs_out) {
+    set_error("vcy_component_seam_pairs: null pointer");
+    return VCY_ERR_INVALID_ARG;
+  }
+  *pairs_out = nullptr;
+  *n_pairs_out = 0;
+  if (c->z0 == 0) {
+    set_error("vcy_component_seam_pairs: the context starts at slice 0: there is no seam below it");
+    return VCY_ERR_INVALID_ARG;
+  }
+  { const int rc = check_slab_labelled(c, "vcy_component_seam_pairs"); if (rc != VCY_OK) return rc; }
+  c->last_components_device_ms = 0.0f;
+  c->cc_timed = false;
+  if (c->cc_labels_empty || c->cc_n_roots == 0) return VCY_OK;  // nothing solid above the seam
+  VCY_HIP_CHECK(hipSetDevice(c->device));
+  const int nx = c->nx, ny = c->ny, Wr = (nx + 63) / 64;
+  const int nwords = Wr * ny;
+  const size_t plane_bytes = sizeof(int64_t) * (size_t)c->slice;
+  // a pair per stretch: a word of 64 voxels starts at most 32; the first guess is far smaller than that bound
+  size_t cap = std::max<size_t>(4096, (size_t)nwords * 2);
+  std::vector<int64_t> pairs;
+  unsigned int* h_report = (unsigned int*)c->h_cc_report;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    { const int rc = grow(&c->d_cc_seam, &c->cc_seam_bytes, plane_bytes + 64 + 2 * sizeof(int64_t) * cap); if (rc != VCY_OK) return rc; }
+    int64_t* d_below = (int64_t*)c->d_cc_seam;
+    unsigned int* d_n = (unsigned int*)((char*)c->d_cc_seam + plane_bytes);
+    int64_t* d_pairs = (int64_t*)((char*)c->d_cc_seam + plane_bytes + 64);
+    if (attempt == 0) {
+      VCY_HIP_CHECK(hipEventRecord(c->ev_cc_begin, c->stream));
+      c->cc_timed = true;
+    }
+    VCY_HIP_CHECK(hipMemcpyAsync(d_below, below_plane_labels, plane_bytes, hipMemcpyHostToDevice, c->stream));
+    VCY_HIP_CHECK(hipMemsetAsync(d_n, 0, 64, c->stream));
+    hipLaunchKernelGGL(cc::cc_seam_pairs_kernel, dim3((unsigned)std::min(2048, (nwords + 3) / 4)), dim3(256), 0, c->stream,
+                       (const int*)c->d_cc_labels, d_below, nx, Wr, nwords, (int64_t)c->z0 * c->slice, d_pairs,
+                       (unsigned int)cap, d_n);
+    VCY_HIP_CHECK(hipGetLastError());
+    VCY_HIP_CHECK(hipMemcpyAsync(h_report, d_n, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)h_report[0];
+    if (n > cap) {  // (a checkerboard of a plane: the list did not fit; once more into one that does)
+      cap = n;
+      continue;
+    }
+    pairs.resize(2 * n);
+    if (n) VCY_HIP_CHECK(hipMemcpy(pairs.data(), d_pairs, 2 * sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    break;
+  }
+  { const int rc = finish_timer(c); if (rc != VCY_OK) return rc; }
+  const size_t n = pairs.size() / 2;
+  if (n == 0) return VCY_OK;
+  // the order the atomics gave is not part of the result: sorted, every pair once
+  std::vector<std::pair<int64_t, int64_t>> uniq(n);
+  for (size_t i = 0; i < n; ++i) uniq[i] = {pairs[2 * i], pairs[2 * i + 1]};
+  std::sort(uniq.begin(), uniq.end());
+  uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  int64_t* p = (int64_t*)std::malloc(2 * sizeof(int64_t) * uniq.size());
+  if (!p) {
+    set_error("vcy_component_seam_pairs: out of host memory");
+    return VCY_ERR_INTERNAL;
+  }
+  for (size_t i = 0; i < uniq.size(); ++i) p[2 * i] = uniq[i].first, p[2 * i + 1] = uniq[i].second;
+  *pairs_out = p;
+  *n_pairs_out = (int64_t)uniq.size();
+  return VCY_OK;
+}
+
+void vcy_seam_pairs_free(int64_t* pairs) { std::free(pairs); }
+
+int vcy_resolve_components_slab(vcy_ctx* c, int64_t n, const int64_t* provisional_labels, const int64_t* global_labels) {
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  { const int rc = check_slab_labelled(c, "vcy_resolve_components_slab"); if (rc != VCY_OK) return rc; }
+  const size_t nr = c->cc_roots_host.size();
+  if (n < 0 || (n > 0 && (!provisional_labels || !global_labels)) || (size_t)n != nr) {
+    set_error("vcy_resolve_components_slab: the map has %lld entries, the slab reported %lld components", (long long)n,
+              (long long)nr);
+    return VCY_ERR_INVALID_ARG;
+  }
+  const int64_t id0 = (int64_t)c->z0 * c->slice;
+  std::vector<int64_t> global(nr, -1);
+  for (int64_t i = 0; i < n; ++i) {
+    const int slot = host_slot_of(c, provisional_labels[i] - id0);
+    if (slot < 0 || global[(size_t)slot] >= 0 || global_labels[i] < 0 || global_labels[i] > provisional_labels[i]) {
+      set_error("vcy_resolve_components_slab: entry %lld (%lld -> %lld): %s", (long long)i, (long long)provisional_labels[i],
+                (long long)global_labels[i],
+                slot < 0 ? "the slab reported no component with this label"
+                         : global[(size_t)slot] >= 0 ? "the label is named twice"
+                                                     : "a merged label is the smallest of its set: not negative, not above the piece's own");
+      return VCY_ERR_INVALID_ARG;  // (the installed map, if any, stays)
+    }
+    global[(size_t)slot] = global_labels[i];
+  }
+  c->cc_global_host.swap(global);
+  return VCY_OK;
+}
+
+int vcy_keep_components_slab(vcy_ctx* c, float fill_sdf, int64_t n_remove, const int64_t* remove_provisional_labels,
+                             int64_t* removed_voxels) {
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  if (removed_voxels) *removed_voxels = 0;
+  { const int rc = check_slab_labelled(c, "vcy_keep_components_slab"); if (rc != VCY_OK) return rc; }
+  if (!std::isfinite(fill_sdf) || !((double)fill_sdf >= c->cc_iso)) {
+    set_error("vcy_keep_components_slab: fill_sdf %g must be finite and not below the iso level %g of the labelling",
+              (double)fill_sdf, c->cc_iso);
+    return VCY_ERR_INVALID_ARG;
+  }
+  if (n_remove < 0 || (n_remove > 0 && !remove_provisional_labels)) {
+    set_error("vcy_keep_components_slab: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  const size_t nr = c->cc_roots_host.size();
+  const int64_t id0 = (int64_t)c->z0 * c->slice;
+  std::vector<uint8_t> removed(nr, 0);
+  int64_t rv_n = 0;
+  for (int64_t i = 0; i < n_remove; ++i) {
+    const int slot = host_slot_of(c, remove_provisional_labels[i] - id0);
+    if (slot < 0) {
+      set_error("vcy_keep_components_slab: the slab reported no component with the label %lld",
+                (long long)remove_provisional_labels[i]);
+      return VCY_ERR_INVALID_ARG;
+    }
+    if (!removed[(size_t)slot]) rv_n += c->cc_nvox_host[(size_t)slot];
+    removed[(size_t)slot] = 1;
+  }
+  c->last_components_device_ms = 0.0f;
+  c->cc_timed = false;
+  if (rv_n > 0) {
+    int keep0 = -1;  // the largest piece that stays
+    int64_t best = 0;
+    for (size_t s = 0; s < nr; ++s)
+      if (!removed[s] && c->cc_nvox_host[s] > best) best = c->cc_nvox_host[s], keep0 = c->cc_roots_host[s];
+    VCY_HIP_CHECK(hipSetDevice(c->device));
+    VCY_HIP_CHECK(hipEventRecord(c->ev_cc_begin, c->stream));
+    c->cc_timed = true;
+    { const int rc = launch_filter(c, removed, keep0, fill_sdf); if (rc != VCY_OK) return rc; }
+    { const int rc = finish_timer(c); if (rc != VCY_OK) return rc; }  // (waits: `removed` is read until then)
+    // the labels stay those from before the removal (vcy_download_labels), but no second filter may lean on them
+    c->cc_slab_labelled = false;
+  }
+  if (removed_voxels) *removed_voxels = rv_n;
+  return VCY_OK;
+}
+
+int vcy_merge_components_host(int n_slabs, const vcy_component* lists, const int64_t* n_lists, const int64_t* pairs,
+                              const int64_t* n_pairs, vcy_component** merged_out, int64_t* n_merged_out,
+                              int64_t* global_labels) {
+  if (merged_out) *merged_out = nullptr;
+  if (n_merged_out) *n_merged_out = 0;
+  if (n_slabs < 1 || !n_lists || !merged_out || !n_merged_out || (n_slabs > 1 && !n_pairs)) {
+    set_error("vcy_merge_components_host: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  std::vector<int64_t> first((size_t)n_slabs + 1, 0);  // slab s: entries [first[s], first[s + 1]) of `lists`
+  for (int s = 0; s < n_slabs; ++s) {
+    if (n_lists[s] < 0 || (s + 1 < n_slabs && n_pairs[s] < 0)) {
+      set_error("vcy_merge_components_host: a negative count");
+      return VCY_ERR_INVALID_ARG;
+    }
+    first[(size_t)s + 1] = first[(size_t)s] + n_lists[s];
+  }
+  const int64_t total = first[(size_t)n_slabs];
+  if (total == 0) {
+    for (int s = 0; s + 1 < n_slabs; ++s)
+      if (n_pairs[s] > 0) {
+        set_error("vcy_merge_components_host: seam %d has pairs, but no slab reported a component", s);
+        return VCY_ERR_INVALID_ARG;
+      }
+    return VCY_OK;
+  }
+  if (!lists || !global_labels) {
+    set_error("vcy_merge_components_host: null pointer");
+    return VCY_ERR_INVALID_ARG;
+  }
+  // entries ordered by label per slab: the lookup of a pair's two ends
+  std::vector<std::vector<std::pair<int64_t, int64_t>>> by_label((size_t)n_slabs);  // (label, entry)
+  for (int s = 0; s < n_slabs; ++s) {
+    auto& v = by_label[(size_t)s];
+    v.reserve((size_t)n_lists[s]);
+    for (int64_t i = first[(size_t)s]; i < first[(size_t)s + 1]; ++i) v.push_back({lists[i].label, i});
+    std::sort(v.begin(), v.end());
+    for (size_t i = 1; i < v.size(); ++i)
+      if (v[i].first == v[i - 1].first) {
+        set_error("vcy_merge_components_host: slab %d reports the label %lld twice", s, (long long)v[i].first);
+        return VCY_ERR_INVALID_ARG;
+      }
+  }
+  auto entry_of = [&](int s, int64_t label) -> int64_t {
+    const auto& v = by_label[(size_t)s];
+    const auto it = std::lower_bound(v.begin(), v.end(), std::make_pair(label, (int64_t)-1));
+    return it != v.end() && it->first == label ? it->second : -1;
+  };
+  UnionFind uf((size_t)total);
+  const int64_t* pr = pairs;
+  for (int s = 0; s + 1 < n_slabs; ++s) {
+    if (n_pairs[s] > 0 && !pairs) {
+      set_error("vcy_merge_components_host: null pointer");
+      return VCY_ERR_INVALID_ARG;
+    }
+    for (int64_t k = 0; k < n_pairs[s]; ++k, pr += 2) {
+      const int64_t a = entry_of(s, pr[0]), b = entry_of(s + 1, pr[1]);
+      if (a < 0 || b < 0) {
+        set_error("vcy_merge_components_host: pair %lld of seam %d names the label %lld, which slab %d did not report",
+                  (long long)k, s, (long long)(a < 0 ? pr[0] : pr[1]), a < 0 ? s : s + 1);
+        return VCY_ERR_INVALID_ARG;
+      }
+      uf.unite(a, b);
+    }
+  }
+  // per set: the smallest label, the sum, the joined box -- gathered at the set's root entry
+  std::vector<vcy_component> acc((size_t)total);
+  std::vector<char> seen((size_t)total, 0);
+  for (int64_t i = 0; i < total; ++i) {
+    const size_t r = (size_t)uf.find(i);
+    if (!seen[r]) {
+      seen[r] = 1;
+      acc[r] = lists[i];
+      continue;
+    }
+    vcy_component& o = acc[r];
+    o.label = std::min(o.label, lists[i].label);
+    o.n_voxels += lists[i].n_voxels;
+    for (int k = 0; k < 3; ++k) {
+      o.bb_min[k] = std::min(o.bb_min[k], lists[i].bb_min[k]);
+      o.bb_max[k] = std::max(o.bb_max[k], lists[i].bb_max[k]);
+    }
+  }
+  std::vector<vcy_component> merged;
+  for (int64_t i = 0; i < total; ++i)
+    if (uf.find(i) == i) merged.push_back(acc[(size_t)i]);
+  for (int64_t i = 0; i < total; ++i) global_labels[i] = acc[(size_t)uf.find(i)].label;
+  std::sort(merged.begin(), merged.end(), [](const vcy_component& a, const vcy_component& b) {
+    if (a.n_voxels != b.n_voxels) return a.n_voxels > b.n_voxels;
+    return a.label < b.label;
+  });
+  vcy_component* p = (vcy_component*)std::malloc(sizeof(vcy_component) * merged.size());
+  if (!p) {
+    set_error("vcy_merge_components_host: out of host memory");
+    return VCY_ERR_INTERNAL;
+  }
+  std::memcpy(p, merged.data(), sizeof(vcy_component) * merged.size());
+  *merged_out = p;
+  *n_merged_out = (int64_t)merged.size();
   return VCY_OK;
 }
 

@@ -210,6 +210,7 @@ int fill_state(vcy_ctx* c) {
   c->brick_min_valid = false;
   if (c->h_live_hint) c->h_live_hint[0] = c->h_live_hint[1] = 0;
   c->views_carved = 0;
+  c->cc_slab_labelled = false;  // (the seam calls of components.hip speak about the state that was labelled)
   c->halo_valid = false;
   c->cnt_implied = true;
   // counters start over at one byte (fresh: nothing to convert; the wide array is kept as the spare)
@@ -513,6 +514,7 @@ void vcy_destroy(vcy_ctx* c) {
   (void)hipFree(c->d_cc_labels);
   (void)hipFree(c->d_cc_bits);
   (void)hipFree(c->d_cc_roots);
+  (void)hipFree(c->d_cc_seam);
   if (c->h_cc_report) (void)hipHostFree(c->h_cc_report);
   if (c->ev_cc_begin) (void)hipEventDestroy(c->ev_cc_begin);
   if (c->ev_cc_end) (void)hipEventDestroy(c->ev_cc_end);
@@ -986,6 +988,7 @@ int vcy_upload(vcy_ctx* c, const float* sdf, const int32_t* update_num) {
   c->halo_valid = false;
   c->cnt_implied = false;  // arbitrary state from outside
   c->brick_min_valid = false;
+  c->cc_slab_labelled = false;
   return VCY_OK;
 }
 
@@ -1881,11 +1884,23 @@ int vcy_mesh_normals_host(int64_t n_vertices, int64_t n_faces, const float* vert
   return VCY_OK;
 }
 
-int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const int32_t* faces, int64_t face_begin,
-                               int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals) {
+namespace {
+// One term of a vertex's sum as mc_vertex_normals_kernel adds it.  For numbers this is host_add_normal.  Where the sum
+// and the term are both NaN (a mesh over NaN voxels) an adder returns one of its operands, and which one is not part of
+// the arithmetic: the kernel's add has the term as its first source and returns that one, x86 keeps the sum.  The two
+// NaNs can differ in their sign bit, so the seam finish names the kernel's choice.
+inline void device_add_normal(float* n, int* count, const float fn[3]) {
+  for (int k = 0; k < 3; ++k) n[k] = (std::isnan(n[k]) && std::isnan(fn[k])) ? fn[k] : n[k] + fn[k];
+  ++*count;
+}
+
+// The seam finish.  face_normals == nullptr: Mesh::CalcFaceNormal of the faces on the host and the host's sum;
+// otherwise the given rows (the devices' own face normals) and the device's sum.
+int seam_finish(const char* who, int64_t n_vertices, const float* vertices, const int32_t* faces, const float* face_normals,
+                int64_t face_begin, int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals) {
   if (n_vertices < 0 || n_seam < 0 || face_begin < 0 || face_end < face_begin || (n_seam > 0 && !seam_vertex_ids) ||
-      (n_seam > 0 && (!vertices || !vertex_normals)) || (n_seam > 0 && face_end > face_begin && !faces)) {
-    set_error("vcy_mesh_normals_host_seam: invalid argument");
+      (n_seam > 0 && ((!vertices && !face_normals) || !vertex_normals)) || (n_seam > 0 && face_end > face_begin && !faces)) {
+    set_error("%s: invalid argument", who);
     return VCY_ERR_INVALID_ARG;
   }
   if (n_seam == 0) return VCY_OK;
@@ -1894,7 +1909,7 @@ int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const 
   for (int64_t k = 0; k < n_seam; ++k) {
     const int64_t id = seam_vertex_ids[k];
     if (id < 0 || id >= n_vertices) {
-      set_error("vcy_mesh_normals_host_seam: seam vertex %lld of %lld", (long long)id, (long long)n_vertices);
+      set_error("%s: seam vertex %lld of %lld", who, (long long)id, (long long)n_vertices);
       return VCY_ERR_INVALID_ARG;
     }
     lo = std::min(lo, id);
@@ -1904,7 +1919,7 @@ int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const 
   for (int64_t k = 0; k < n_seam; ++k) slot[(size_t)(seam_vertex_ids[k] - lo)] = (int32_t)k;  // (a repeated id: one slot)
   for (int64_t i = 3 * face_begin; i < 3 * face_end; ++i)
     if (faces[i] < 0 || faces[i] >= n_vertices) {
-      set_error("vcy_mesh_normals_host_seam: face %lld names vertex %d of %lld", (long long)(i / 3), faces[i], (long long)n_vertices);
+      set_error("%s: face %lld names vertex %d of %lld", who, (long long)(i / 3), faces[i], (long long)n_vertices);
       return VCY_ERR_INVALID_ARG;
     }
   std::vector<float> sum(3 * (size_t)n_seam, 0.0f);
@@ -1915,11 +1930,18 @@ int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const 
     for (int j = 0; j < 3; ++j) named = named || (f[j] >= lo && f[j] <= hi && slot[(size_t)(f[j] - lo)] >= 0);
     if (!named) continue;
     float fn[3];
-    host_face_normal(vertices, f, fn);
+    if (face_normals)
+      fn[0] = face_normals[3 * i], fn[1] = face_normals[3 * i + 1], fn[2] = face_normals[3 * i + 2];
+    else
+      host_face_normal(vertices, f, fn);
     for (int j = 0; j < 3; ++j) {
       if (f[j] < lo || f[j] > hi) continue;
       const int32_t k = slot[(size_t)(f[j] - lo)];
-      if (k >= 0) host_add_normal(&sum[3 * (size_t)k], &count[(size_t)k], fn);
+      if (k < 0) continue;
+      if (face_normals)
+        device_add_normal(&sum[3 * (size_t)k], &count[(size_t)k], fn);
+      else
+        host_add_normal(&sum[3 * (size_t)k], &count[(size_t)k], fn);
     }
   }
   for (int64_t k = 0; k < n_seam; ++k) {
@@ -1930,6 +1952,31 @@ int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const 
     o[0] = n[0], o[1] = n[1], o[2] = n[2];
   }
   return VCY_OK;
+}
+}  // namespace
+
+int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const int32_t* faces, int64_t face_begin,
+                               int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals) {
+  if (n_seam > 0 && !vertices) {
+    set_error("vcy_mesh_normals_host_seam: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  return seam_finish("vcy_mesh_normals_host_seam", n_vertices, vertices, faces, nullptr, face_begin, face_end, n_seam,
+                     seam_vertex_ids, vertex_normals);
+}
+
+int vcy_mesh_normals_seam_sum(int64_t n_vertices, const int32_t* faces, const float* face_normals, int64_t face_begin,
+                              int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals) {
+  if (n_seam > 0 && face_end > face_begin && !face_normals) {
+    set_error("vcy_mesh_normals_seam_sum: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  if (n_seam > 0 && face_end == face_begin) {  // (no face: the host's 0 / 0, as vcy_mesh_normals_host_seam)
+    static const float none[3] = {0.0f, 0.0f, 0.0f};
+    face_normals = none;
+  }
+  return seam_finish("vcy_mesh_normals_seam_sum", n_vertices, nullptr, faces, face_normals, face_begin, face_end, n_seam,
+                     seam_vertex_ids, vertex_normals);
 }
 
 int vcy_last_extract_wall_ms(const vcy_ctx* c, float* wall_ms) {

@@ -207,6 +207,16 @@ struct vcy_ctx {
   hipEvent_t ev_cc_begin = nullptr, ev_cc_end = nullptr;
   bool cc_timed = false;
   float last_components_device_ms = 0.0f;
+  // ... of a z-slab (vcy_label_components_slab and what follows it): host copies of the last labelling, in the order of
+  // the sorted root list the device holds (the slot order of cc_filter_kernel)
+  std::vector<int> cc_roots_host;     // slab-local roots, ascending
+  std::vector<int64_t> cc_nvox_host;  // voxels of each root's piece
+  std::vector<int64_t> cc_global_host;  // the installed map (vcy_resolve_components_slab): global label per slot; empty: none
+  bool cc_slab_labelled = false;      // the last labelling was vcy_label_components_slab's: the seam calls may follow
+  double cc_iso = 0.0;                // ... at this iso level
+  int64_t cc_views_at_label = 0;      // ... with this many views applied (a carve in between makes the labels stale)
+  void* d_cc_seam = nullptr;          // seam pairs: [the lower slab's top plane, int64 per voxel | counter | pairs] (grow-only)
+  size_t cc_seam_bytes = 0;
 
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
@@ -242,7 +252,8 @@ int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy
 // that owns a z-slab then gets the slab instance of the vertex normals (seam vertices left at zero)
 int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int which = 0,
                 vcy_mesh_normals* normals_out = nullptr, int64_t* layer_faces = nullptr);
-// components.hip: vcy_label_components, vcy_keep_components, vcy_download_labels, vcy_last_components_ms
+// components.hip: vcy_label_components, vcy_keep_components, vcy_download_labels, vcy_last_components_ms, the _slab
+// entries of a z-slab context and the seam merge on the host (vcy_merge_components_host)
 // sdf2d.hip
 void host_distance_transform_l1(const uint8_t* mask, int w, int h, const int32_t* rmin,
                                 const int32_t* rmax, float* out);

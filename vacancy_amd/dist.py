@@ -10,6 +10,8 @@ per launch and still left the ranks 5 % apart.
 Marching cubes needs the two slices below each slab: ONE all-gather of every slab's last two
 slices (RCCL when the backend is nccl), after which every slab is extracted on its own GPU.
 The per-slab meshes are stitched on the host by edge key (merge_meshes).
+Connected components of the hull are labelled per slab on its GPU; one plane of labels per seam and the lists of label
+pairs travel, and every rank joins the pieces on the host (label_components_slabs, merge_components).
 """
 import ctypes as C
 
@@ -281,7 +283,7 @@ def merge_meshes(meshes):
     Parts that all carry "normals", "face_normals" and "layer_faces" (VoxelCarver.ExtractIsoSurfaceSlab) give
     "normals" and "face_normals" of the merged mesh as well, bit-equal to Mesh::CalcNormal of it: the slabs' normals
     concatenated with the merged numbering (foreign entries dropped), then per seam the seam finish
-    (vcy_mesh_normals_host_seam, on the host) for the vertices the upper slab's foreign vertices were mapped to, over
+    (vcy_mesh_normals_seam_sum, on the host, over the slabs' own face normals) for the vertices the upper slab's foreign vertices were mapped to, over
     the faces of the lower slab's last and the upper slab's first cell layer.  Without those keys the result has
     exactly the three arrays above.
     """
@@ -325,5 +327,93 @@ def merge_meshes(meshes):
         out["face_normals"] = np.ascontiguousarray(np.concatenate(fnorm), np.float32)
         from . import carver as _vc
         for begin, end, ids in seams:
-            _vc.mesh_normals_host_seam(out["vertices"], out["faces"], begin, end, ids, out["normals"])
+            _vc.mesh_normals_seam_sum(len(out["vertices"]), out["faces"], out["face_normals"], begin, end, ids, out["normals"])
     return out
+
+
+# ---- connected components of a grid in z-slabs (the order of the calls: include/vacancy_hip.h) ----------------------
+
+def merge_components(lists, pairs):
+    """The seam merge on the host (vcy_merge_components_host, no GPU): `lists` = every slab's LabelComponentsSlab dict
+    in z order, `pairs` = per seam the int64 [n, 2] array of (label below, label above), duplicates allowed.  Returns
+    (the merged list as VoxelCarver.LabelComponents returns it, [per slab: the merged label of each of its pieces])."""
+    from . import carver as _vc
+    return _vc.merge_components_host(lists, pairs)
+
+
+def _each(carvers, fn):
+    return [fn(i, c) for i, c in enumerate(carvers)]
+
+
+def _gather_by_slab(mine, world):
+    """{slab id: object} of every rank joined into one dict on every rank (Python objects through the process group)."""
+    if world == 1:
+        return dict(mine)
+    import torch.distributed as dist
+    parts = [None] * world
+    dist.all_gather_object(parts, mine)
+    out = {}
+    for part in parts:
+        out.update(part)
+    return out
+
+
+def label_components_slabs(carvers, rank=0, world=1, iso_level=0.0, each=_each):
+    """LabelComponents of a grid cut into z-slabs.  `carvers`: this rank's slab contexts ordered by slab id (slab ids
+    rank, rank + world, ...; one process holding every slab: rank 0 of 1).  Every slab labels its own slices on its
+    device; the lists, the slabs' top planes of labels (nx * ny int64 per seam) and the seams' pair lists are gathered
+    as Python objects -- never a slab's label volume --, every rank runs the same host merge and installs its slabs'
+    maps, so that download_labels() on a slab returns merged labels.  `each(carvers, fn)` runs fn(i, carver) for
+    every local slab and returns the results in order (ShardedVoxelCarver: a host thread per device).
+    Returns {"merged": the list as VoxelCarver.LabelComponents returns it, "lists", "maps": per slab of the GRID,
+    "device_ms": the sum over this rank's slabs}."""
+    k = len(carvers)
+    ids = [rank + i * world for i in range(k)]
+    count = world * k
+    ms = [0.0] * k
+
+    def label(i, c):
+        part = c.LabelComponentsSlab(iso_level)
+        ms[i] += part.pop("device_ms")
+        return part, (c.component_top_plane() if ids[i] + 1 < count else None)
+
+    labelled = _gather_by_slab(dict(zip(ids, each(carvers, label))), world)
+
+    def seam(i, c):
+        if ids[i] == 0:
+            return None
+        pairs = c.component_seam_pairs(labelled[ids[i] - 1][1])
+        ms[i] += c.last_components_ms()
+        return pairs
+
+    seams = _gather_by_slab(dict(zip(ids, each(carvers, seam))), world)
+    lists = [labelled[s][0] for s in range(count)]
+    merged, maps = merge_components(lists, [seams[s] for s in range(1, count)])
+    each(carvers, lambda i, c: c.resolve_components(lists[ids[i]]["label"], maps[ids[i]]))
+    return {"merged": merged, "lists": lists, "maps": maps, "device_ms": float(sum(ms))}
+
+
+def keep_components_slabs(carvers, rank=0, world=1, iso_level=0.0, largest=1, min_voxels=0, fill_sdf=1.0, each=_each):
+    """KeepComponents of a grid cut into z-slabs: label_components_slabs, the rule of vcy_keep_components on the merged
+    list (a component stays iff (largest <= 0 or its rank is below largest) and n_voxels >= min_voxels), then every
+    slab's own filter kernel over the pieces that go.  A slab's halo below an upper slab is stale afterwards, as after a
+    carve: every extraction path here exchanges halos first.  Returns {"removed_components", "removed_voxels" (of the
+    whole grid), "device_ms" (labelling, seams and filter, summed over this rank's slabs)}."""
+    import math
+    if not math.isfinite(fill_sdf) or not float(np.float32(fill_sdf)) >= float(iso_level):
+        raise RuntimeError("keep_components_slabs: fill_sdf %g must be finite and not below the iso level %g"
+                           % (fill_sdf, iso_level))
+    r = label_components_slabs(carvers, rank, world, iso_level, each)
+    merged = r["merged"]
+    n = len(merged["label"])
+    keep = (np.ones(n, bool) if largest <= 0 else np.arange(n) < largest) & (merged["n_voxels"] >= min_voxels)
+    gone = merged["label"][~keep]
+    ids = [rank + i * world for i in range(len(carvers))]
+
+    def drop(i, c):
+        mine = r["lists"][ids[i]]["label"][np.isin(r["maps"][ids[i]], gone)]
+        return c.KeepComponentsSlab(mine, fill_sdf)["device_ms"] if len(gone) else 0.0
+
+    ms = each(carvers, drop)
+    return {"removed_components": int((~keep).sum()), "removed_voxels": int(merged["n_voxels"][~keep].sum()),
+            "device_ms": r["device_ms"] + float(sum(ms))}

@@ -197,6 +197,60 @@ int main(int argc, char* argv[]) {
                 mesh.vertex_indices().size(), mesh.normals().size(), mesh.face_normals().size(), mesh.normal_indices().size());
     return ok ? 0 : 8;
   }
+  if (argc > 4 && std::string(argv[2]) == "shardcomponents") {
+    // needs a device: ShardedVoxelCarver::LabelComponents / KeepLargestComponents after the six bunny views, next to a
+    // single VoxelCarver.   host_selftest <data dir> shardcomponents <resolution> <slabs on device 0>
+    //   prints SHARDCOMPONENTS <slabs> <components> <lists equal> <components after> <lists after equal> <mesh identical>
+    vacancy::VoxelCarverOption option;
+    option.bb_min = Eigen::Vector3f(-250.000000f, -344.586151f, -129.982697f);
+    option.bb_max = Eigen::Vector3f(250.000000f, 150.542343f, 257.329224f);
+    for (int i = 0; i < 3; ++i) {  // (examples.cc:91-99)
+      option.bb_min[i] -= 20.0f;
+      option.bb_max[i] += 20.0f;
+    }
+    option.resolution = (float)std::atof(argv[3]);
+    vacancy::VoxelCarver one(option);
+    vacancy::ShardedVoxelCarver sh(option, {0}, std::atoi(argv[4]));
+    if (!one.Init() || !sh.Init()) return 6;
+    std::FILE* fp = std::fopen((dir + "/tumpose.txt").c_str(), "r");
+    if (!fp) return 9;
+    int id;
+    double t[3], q[4];
+    for (size_t i = 0; i < 6 && std::fscanf(fp, "%d %lf %lf %lf %lf %lf %lf %lf", &id, &t[0], &t[1], &t[2], &q[0], &q[1], &q[2], &q[3]) == 8; ++i) {
+      Eigen::Translation3d tr;
+      tr.x() = t[0]; tr.y() = t[1]; tr.z() = t[2];
+      Eigen::Quaterniond qu;
+      qu.x() = q[0]; qu.y() = q[1]; qu.z() = q[2]; qu.w() = q[3];
+      vacancy::PinholeCamera cam(320, 240, tr * qu, Eigen::Vector2f(159.3f, 127.65f), Eigen::Vector2f(258.65f, 258.25f));
+      vacancy::Image1b sil;
+      if (!sil.Load(dir + "/mask_" + vacancy::zfill(i) + ".png")) return 4;
+      if (!one.Carve(cam, sil) || !sh.Carve(cam, sil)) return 7;
+    }
+    std::fclose(fp);
+    auto same_lists = [](const std::vector<vacancy::VoxelComponent>& a, const std::vector<vacancy::VoxelComponent>& b) {
+      bool same = a.size() == b.size();
+      for (size_t i = 0; same && i < a.size(); ++i)
+        for (int k = 0; k < 3; ++k)
+          same = same && a[i].label == b[i].label && a[i].n_voxels == b[i].n_voxels && a[i].bb_min[k] == b[i].bb_min[k] &&
+                 a[i].bb_max[k] == b[i].bb_max[k];
+      return same;
+    };
+    std::vector<vacancy::VoxelComponent> a, b, a2, b2;
+    if (!one.LabelComponents(&a) || !sh.LabelComponents(&b)) return 10;
+    if (!one.KeepLargestComponents(1) || !sh.KeepLargestComponents(1)) return 11;
+    if (!one.LabelComponents(&a2) || !sh.LabelComponents(&b2)) return 12;
+    vacancy::Mesh ma, mb;
+    one.ExtractIsoSurface(&ma, 0.0);
+    sh.ExtractIsoSurface(&mb, 0.0);
+    bool same = ma.vertices().size() == mb.vertices().size() && ma.vertex_indices().size() == mb.vertex_indices().size();
+    for (size_t k = 0; same && k < ma.vertices().size(); ++k)
+      for (int c = 0; c < 3; ++c) same = same && ma.vertices()[k][c] == mb.vertices()[k][c];
+    for (size_t k = 0; same && k < ma.vertex_indices().size(); ++k)
+      for (int c = 0; c < 3; ++c) same = same && ma.vertex_indices()[k][c] == mb.vertex_indices()[k][c];
+    std::printf("SHARDCOMPONENTS %d %zu %d %zu %d %d\n", sh.slab_count(), b.size(), same_lists(a, b) ? 1 : 0, b2.size(),
+                same_lists(a2, b2) ? 1 : 0, same ? 1 : 0);
+    return 0;
+  }
   if (argc > 3 && std::string(argv[2]) == "normals") {
     // CPU only: Mesh::CalcNormal through the facade.   host_selftest <data dir> normals <dir>
     //   reads <dir>/vertices.f32 and <dir>/faces.i32, writes <dir>/normals.f32, face_normals.f32, normal_indices.i32,

@@ -1,6 +1,8 @@
 // ShardedVoxelCarver: z-slab sharding over the C-ABI contexts of include/vacancy_hip.h.
 #include "vacancy/sharded_voxel_carver.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <array>
 #include <future>
@@ -60,6 +62,14 @@ struct ShardedVoxelCarver::Impl {
   int64_t slice = 0;               // voxels per z slice of the grid (nx * ny)
   std::vector<vcy_ctx*> slabs;  // in z order
   bool peer_copy_halo = false;
+  // what LabelComponents and KeepLargestComponents share: every slab labelled, the seams paired, the pieces merged
+  struct Labelled {
+    std::vector<vcy_component> merged;   // the whole grid's list, in the order of vcy_label_components
+    std::vector<vcy_component> pieces;   // the slabs' lists one behind the other
+    std::vector<int64_t> counts;         // pieces per slab
+    std::vector<int64_t> global;         // merged label of every piece
+  };
+  bool LabelSlabs(double iso_level, Labelled* out);
   ~Impl() {
     for (vcy_ctx* c : slabs) vcy_destroy(c);
   }
@@ -244,6 +254,138 @@ bool ShardedVoxelCarver::ExchangeHalo() {
   return true;
 }
 
+namespace {
+// fn(s) for every slab on a host thread of its own (a context is single-threaded, different contexts are independent;
+// vcy_last_error() is per thread, so a failure's text comes back with it)
+template <typename Fn>
+bool ForEachSlab(size_t ns, const char* what, Fn fn) {
+  std::vector<std::future<std::string>> jobs;
+  for (size_t s = 0; s < ns; ++s)
+    jobs.push_back(std::async(std::launch::async, [s, &fn]() { return fn(s) == VCY_OK ? std::string() : std::string(vcy_last_error()); }));
+  bool ok = true;
+  for (auto& j : jobs) {
+    const std::string e = j.get();
+    if (!e.empty()) {
+      LOGE("sharded %s failed: %s\n", what, e.c_str());
+      ok = false;
+    }
+  }
+  return ok;
+}
+}  // namespace
+
+// The order of calls of include/vacancy_hip.h ("connected components of a grid cut into z-slabs"): every slab labels its
+// own slices on its device; per seam the lower slab's top plane of labels (nx * ny int64) goes through host memory to the
+// upper slab's device, which returns the pairs of pieces that touch; the host joins the pieces.  No slab's label volume
+// leaves its device.
+bool ShardedVoxelCarver::Impl::LabelSlabs(double iso_level, Labelled* out) {
+  const size_t ns = slabs.size();
+  if (ns == 0) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  std::vector<vcy_component*> lists(ns, nullptr);
+  std::vector<int64_t> counts(ns, 0);
+  std::vector<std::vector<int64_t>> planes(ns);
+  bool ok = ForEachSlab(ns, "LabelComponents", [&](size_t s) {
+    int rc = vcy_label_components_slab(slabs[s], iso_level, &lists[s], &counts[s]);
+    if (rc == VCY_OK && s + 1 < ns) {
+      planes[s].resize(static_cast<size_t>(slice));
+      rc = vcy_component_top_plane(slabs[s], planes[s].data());
+    }
+    return rc;
+  });
+  std::vector<int64_t*> pairs(ns, nullptr);  // [s]: the seam below slab s
+  std::vector<int64_t> n_pairs(ns, 0);
+  ok = ok && ForEachSlab(ns, "LabelComponents (seams)", [&](size_t s) {
+    return s == 0 ? static_cast<int>(VCY_OK) : vcy_component_seam_pairs(slabs[s], planes[s - 1].data(), &pairs[s], &n_pairs[s]);
+  });
+  if (ok) {
+    out->counts = counts;
+    out->pieces.clear();
+    std::vector<int64_t> all_pairs;
+    for (size_t s = 0; s < ns; ++s) {
+      out->pieces.insert(out->pieces.end(), lists[s], lists[s] + counts[s]);
+      if (s > 0) all_pairs.insert(all_pairs.end(), pairs[s], pairs[s] + 2 * n_pairs[s]);
+    }
+    out->global.assign(out->pieces.size(), -1);
+    vcy_component* merged = nullptr;
+    int64_t n_merged = 0;
+    if (vcy_merge_components_host(static_cast<int>(ns), out->pieces.data(), counts.data(), all_pairs.data(), n_pairs.data() + 1,
+                                  &merged, &n_merged, out->global.data()) != VCY_OK) {
+      LOGE("sharded LabelComponents failed: %s\n", vcy_last_error());
+      ok = false;
+    } else {
+      out->merged.assign(merged, merged + n_merged);
+      vcy_components_free(merged);
+    }
+  }
+  if (ok) {
+    std::vector<int64_t> first(ns + 1, 0);
+    for (size_t s = 0; s < ns; ++s) first[s + 1] = first[s] + counts[s];
+    ok = ForEachSlab(ns, "LabelComponents (resolve)", [&](size_t s) {
+      std::vector<int64_t> provisional(static_cast<size_t>(counts[s]));
+      for (int64_t i = 0; i < counts[s]; ++i) provisional[static_cast<size_t>(i)] = out->pieces[static_cast<size_t>(first[s] + i)].label;
+      return vcy_resolve_components_slab(slabs[s], counts[s], provisional.data(), out->global.data() + first[s]);
+    });
+  }
+  for (vcy_component* p : lists) vcy_components_free(p);
+  for (int64_t* p : pairs) vcy_seam_pairs_free(p);
+  return ok;
+}
+
+bool ShardedVoxelCarver::LabelComponents(std::vector<VoxelComponent>* components, double iso_level) {
+  components->clear();
+  Impl::Labelled l;
+  if (!impl_->LabelSlabs(iso_level, &l)) return false;
+  components->resize(l.merged.size());
+  for (size_t i = 0; i < l.merged.size(); ++i) {
+    VoxelComponent& c = (*components)[i];
+    c.label = l.merged[i].label;
+    c.n_voxels = l.merged[i].n_voxels;
+    for (int k = 0; k < 3; ++k) c.bb_min[k] = l.merged[i].bb_min[k], c.bb_max[k] = l.merged[i].bb_max[k];
+  }
+  return true;
+}
+
+// The rule of vcy_keep_components on the merged list, then every slab's own filter kernel over its pieces of the components
+// that go.  The two halo slices below every upper slab are stale afterwards, exactly as after a Carve(): ExtractIsoSurface
+// always, and ExtractVoxel whenever it reads the slice below a slab (inside_empty), call ExchangeHalo() before they
+// read them, so nothing has to be exchanged here.
+bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
+  if (!std::isfinite(fill_sdf) || !(static_cast<double>(fill_sdf) >= iso_level)) {
+    LOGE("KeepLargestComponents: fill_sdf %g must be finite and not below the iso level %g\n", static_cast<double>(fill_sdf),
+         iso_level);
+    return false;
+  }
+  Impl::Labelled l;
+  if (!impl_->LabelSlabs(iso_level, &l)) return false;
+  std::vector<int64_t> gone;  // merged labels, ascending
+  std::int64_t gone_voxels = 0;
+  for (size_t i = 0; i < l.merged.size(); ++i) {
+    const bool keep = (largest <= 0 || static_cast<std::int64_t>(i) < static_cast<std::int64_t>(largest)) &&
+                      l.merged[i].n_voxels >= min_voxels;
+    if (!keep) gone.push_back(l.merged[i].label), gone_voxels += l.merged[i].n_voxels;
+  }
+  std::sort(gone.begin(), gone.end());
+  if (!gone.empty()) {
+    const size_t ns = impl_->slabs.size();
+    std::vector<int64_t> first(ns + 1, 0);
+    for (size_t s = 0; s < ns; ++s) first[s + 1] = first[s] + l.counts[s];
+    const bool ok = ForEachSlab(ns, "KeepLargestComponents", [&](size_t s) {
+      std::vector<int64_t> mine;
+      for (int64_t i = first[s]; i < first[s + 1]; ++i)
+        if (std::binary_search(gone.begin(), gone.end(), l.global[static_cast<size_t>(i)]))
+          mine.push_back(l.pieces[static_cast<size_t>(i)].label);
+      return vcy_keep_components_slab(impl_->slabs[s], fill_sdf, static_cast<int64_t>(mine.size()), mine.data(), nullptr);
+    });
+    if (!ok) return false;
+  }
+  LOGI("KeepLargestComponents removed %lld components, %lld voxels\n", static_cast<long long>(gone.size()),
+       static_cast<long long>(gone_voxels));
+  return true;
+}
+
 void ShardedVoxelCarver::ExtractVoxel(Mesh* mesh, bool inside_empty) {
   mesh->Clear();
   const size_t ns = impl_->slabs.size();
@@ -285,7 +427,7 @@ void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool li
 
 // with_normals: every slab's normals come from its own device (vcy_extract_iso_normals_slab); the seam vertices -- those a
 // slab's foreign vertices are mapped to -- are finished on the host over the faces of the two cell layers that meet at
-// the seam (vcy_mesh_normals_host_seam).  The rule is the one of vacancy_amd.dist.merge_meshes.
+// the seam (vcy_mesh_normals_seam_sum, from the slabs' own face normals).  The rule is the one of vacancy_amd.dist.merge_meshes.
 void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals) {
   mesh->Clear();
   const size_t ns = impl_->slabs.size();
@@ -380,10 +522,10 @@ void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool li
     }
     if (with_normals && ok) {
       for (const Seam& seam : seams)
-        if (vcy_mesh_normals_host_seam(static_cast<int64_t>(V->size()), reinterpret_cast<const float*>(V->data()),
-                                       reinterpret_cast<const int32_t*>(F->data()), seam.face_begin, seam.face_end,
-                                       static_cast<int64_t>(seam.ids.size()), seam.ids.data(),
-                                       reinterpret_cast<float*>(N->data())) != VCY_OK) {
+        if (vcy_mesh_normals_seam_sum(static_cast<int64_t>(V->size()), reinterpret_cast<const int32_t*>(F->data()),
+                                      reinterpret_cast<const float*>(FN->data()), seam.face_begin, seam.face_end,
+                                      static_cast<int64_t>(seam.ids.size()), seam.ids.data(),
+                                      reinterpret_cast<float*>(N->data())) != VCY_OK) {
           LOGE("sharded merge: %s\n", vcy_last_error());
           ok = false;
           break;

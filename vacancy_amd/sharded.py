@@ -269,3 +269,35 @@ class ShardedVoxelCarver:
         import numpy as np
         from . import carver as _vc
         return _vc.voxel_cubes(self.option, np.concatenate(ids) if ids else np.zeros(0, np.int64))
+
+    # -- connected components of the hull over the slabs (no reference counterpart; include/vacancy_hip.h): every slab
+    # labels its slices on its device, one plane of labels per seam and the pair lists go through the host, the host
+    # joins the pieces (vacancy_amd.dist.label_components_slabs) -- exactly what VoxelCarver returns on the whole grid
+    def _each_slab(self, slabs, fn):
+        """dist's `each`: fn(i, slab) for the slabs in z order, the slabs of a device on that device's thread."""
+        index = {id(c): s for s, c in enumerate(slabs)}
+        out = [None] * len(slabs)
+
+        def run(i, cs):
+            for c in cs:
+                out[index[id(c)]] = fn(index[id(c)], c)
+
+        self._per_device(run)
+        return out
+
+    def LabelComponents(self, iso_level=0.0, labels=False):
+        """VoxelCarver.LabelComponents of the whole grid: the same dict keys; "labels" (labels=True) are the slabs'
+        merged labels concatenated in z order; "device_ms" is the sum over the slabs."""
+        r = vdist.label_components_slabs(self.slabs, 0, 1, iso_level, each=self._each_slab)
+        out = dict(r["merged"])
+        if labels:
+            import numpy as np
+            out["labels"] = np.concatenate(self._each_slab(self.slabs, lambda i, c: c.download_labels()))
+        out["device_ms"] = r["device_ms"]
+        return out
+
+    def KeepComponents(self, iso_level=0.0, largest=1, min_voxels=0, fill_sdf=1.0):
+        """VoxelCarver.KeepComponents of the whole grid, every slab filtered in place by its own device (brick minima kept
+        current per slab).  The halos go stale, as after a carve; extract_slabs and ExtractVoxel exchange them first."""
+        return vdist.keep_components_slabs(self.slabs, 0, 1, iso_level, largest, min_voxels, fill_sdf,
+                                           each=self._each_slab)
