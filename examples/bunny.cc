@@ -1,8 +1,11 @@
 // The reference's demo (examples.cc:75-152) on the MI355X path: 6 masks + TUM poses of data/
 // bunny, 10 mm voxels; per view carve -> marching cubes (interpolated and not), PLY out.
-// Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs]
+// Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs] [planned] [--keep-largest] [--render DIR]
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
+//   --render DIR (DIR must exist) writes DIR/hull_<view>.png, the silhouette of the carved hull as every input camera
+//   sees it, and prints per view how it agrees with the input silhouette: the three pixel counts and the IoU.
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -46,11 +49,18 @@ int main(int argc, char* argv[]) {
   // of the hull but the largest (VoxelCarver::KeepLargestComponents) -- the floaters six views leave; with slabs, the
   // sharded run is filtered too (ShardedVoxelCarver::KeepLargestComponents) and its kept mesh compared
   bool keep_largest = false;
+  std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
     for (int i = 1; i < argc; ++i) {
       if (std::string(argv[i]) == "--keep-largest") keep_largest = true;
-      else argv[n++] = argv[i];
+      else if (std::string(argv[i]) == "--render") {
+        if (i + 1 >= argc) {
+          std::fprintf(stderr, "--render needs a directory\n");
+          return 10;
+        }
+        render_dir = argv[++i];
+      } else argv[n++] = argv[i];
     }
     argc = n;
   }
@@ -153,6 +163,34 @@ int main(int argc, char* argv[]) {
     std::printf("RESULT view %zu verts %zu faces %zu nointerp_verts %zu nointerp_faces %zu vsum %.6f %.6f %.6f "
                 "voxel_verts %zu\n",
                 i, nv, nf, mesh.vertices().size(), mesh.vertex_indices().size(), sum[0], sum[1], sum[2], voxel_verts);
+  }
+
+  if (!render_dir.empty()) {  // what the hull looks like from every input camera (vcy_render_hull / vcy_hull_agreement)
+    std::vector<std::shared_ptr<vacancy::PinholeCamera>> cams;
+    std::vector<const vacancy::Camera*> cam_ptrs;
+    std::vector<vacancy::Image1b> sils(poses.size() < 6 ? poses.size() : 6);
+    for (size_t i = 0; i < sils.size(); ++i) {
+      cams.push_back(std::make_shared<vacancy::PinholeCamera>(width, height, poses[i], Eigen::Vector2f(159.3f, 127.65f),
+                                                              Eigen::Vector2f(258.65f, 258.25f)));
+      cam_ptrs.push_back(cams.back().get());
+      if (!sils[i].Load(data_dir + "/mask_" + vacancy::zfill(i) + ".png")) return 3;
+      vacancy::Image1f depth;
+      vacancy::Image1b hull;
+      if (!carver.RenderHull(*cams.back(), &depth, &hull)) return 11;
+      const std::string png = render_dir + "/hull_" + vacancy::zfill(i) + ".png";
+      if (!hull.WritePng(png)) {
+        std::fprintf(stderr, "cannot write %s (--render does not create its directory)\n", png.c_str());
+        return 11;
+      }
+    }
+    std::vector<std::array<std::int64_t, 3>> counts;
+    if (!carver.HullAgreement(cam_ptrs, sils, &counts)) return 11;
+    for (size_t i = 0; i < counts.size(); ++i) {
+      const long long both = counts[i][0], only_mask = counts[i][1], only_hull = counts[i][2];
+      const long long uni = both + only_mask + only_hull;
+      std::printf("RENDER view %zu mask&hull %lld mask-only %lld hull-only %lld IoU %.4f\n", i, both, only_mask, only_hull,
+                  uni ? static_cast<double>(both) / static_cast<double>(uni) : 1.0);
+    }
   }
 
   // the last view once more with normals (computed on the device), as a binary PLY a viewer lights correctly

@@ -59,6 +59,11 @@ class ShardedVoxelCarver {
   // stale after the filter as after a Carve(); the extractions exchange them before they read them.
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
+  // VoxelCarver::RenderHull / HullAgreement need the whole grid in one context (merging slabs by minimum depth needs a tie
+  // rule of its own): both log an error and return false.
+  bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);
+  bool HullAgreement(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
+                     std::vector<std::array<std::int64_t, 3>>* counts);
 
  private:
   bool ExchangeHalo();

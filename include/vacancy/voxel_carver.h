@@ -3,6 +3,7 @@
 // the voxel grid lives in HBM behind the C-ABI of vacancy_hip.h instead of a std::vector<Voxel>.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <vector>
@@ -124,6 +125,17 @@ class VoxelCarver {
   // an error.  ShardedVoxelCarver has the same two members (the pieces of the z-slabs are merged across the seams).
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
+
+  // The hull as camera `camera` sees it (vcy_render_hull: the first solid voxel on every pixel's ray, exact -- the
+  // definition is in vacancy_hip.h): depth = camera depth of the hit, +inf where the ray meets no solid voxel;
+  // silhouette (optional) = 255 where it does.  The images get the camera's width x height, the ROI is the whole image.
+  // HullAgreement (vcy_hull_agreement) renders every camera and compares with the input silhouettes (non-zero = object)
+  // on the device: per view the pixel counts {mask && hull, mask && !hull, !mask && hull}.  false + LOGE on an error.
+  bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr, double iso_level = 0.0);
+  bool HullAgreement(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
+                     std::vector<std::array<std::int64_t, 3>>* counts, double iso_level = 0.0);
+  bool HullAgreement(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
+                     std::vector<std::array<std::int64_t, 3>>* counts);
 
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;

@@ -419,6 +419,71 @@ int  vcy_resolve_components_slab(vcy_ctx* ctx, int64_t n, const int64_t* provisi
 int  vcy_keep_components_slab(vcy_ctx* ctx, float fill_sdf, int64_t n_remove, const int64_t* remove_provisional_labels,
                               int64_t* removed_voxels);
 
+/* ---- ray-cast of the hull into a view ------------------------------------- */
+
+/* What the hull looks like from a camera: per pixel, the first SOLID voxel on the pixel's ray (no reference counterpart:
+ * the reference's Camera carries ray_w / org_ray_w, camera.cc:164-261, and nothing uses them).  Every rule below is
+ * float arithmetic in a fixed order, so the images are exact and independent of how a kernel walks the grid.
+ *   solid voxel : update_num >= 1 && (double)sdf < iso_level, the predicate of vcy_label_components; an untouched voxel
+ *                 and a NaN are not solid.
+ *   cell        : voxel i of axis a is the interval between the planes P_a[i] and P_a[i + 1] of vcy_cell_planes.
+ *   ray         : of pixel (u, v), integer pixel coordinates -- where the carve samples data[w * v + u] --, the
+ *                 camera-space points the carve's own projection sends to that pixel, by camera depth t = z_c >= 0:
+ *                   pinhole  o_c = (0, 0, 0),  d_c = (((float)u - cx) / fx, ((float)v - cy) / fy, 1);
+ *                   ortho    o_c = ((float)u, (float)v, 0),  d_c = (0, 0, 1) -- the inverse of OrthoCamera::Project
+ *                            (camera.cc:196-212), which the carve uses, NOT the reference's org_ray_c, which is offset
+ *                            by half the image;
+ *                 world ray, with R[r][c] = w2c[4 * r + c] taken as orthonormal and t_w2c[r] = w2c[4 * r + 3]:
+ *                   q = o_c - t_w2c (q_2 = 0.0f - t_w2c[2]),
+ *                   o_a = R[0][a] * q_0 + R[1][a] * q_1 + R[2][a] * q_2,
+ *                   d_a = R[0][a] * d_c0 + R[1][a] * d_c1 + R[2][a] * 1.0f     (products summed left to right).
+ *                 A ray with a non-finite component of o or d is a miss.
+ *   crossing    : axis a has crossings when d_a != 0 and inv_a = 1.0f / d_a is finite; plane k is crossed at
+ *                 t_a(k) = (P_a[k] - o_a) * inv_a -- from the integer k, never accumulated; t_a is monotone in k.
+ *   start       : crossings with t < 0 lie behind the start (t == 0, of either sign, lies ahead).  On an axis with
+ *                 crossings the start cell is i_a = (number of planes behind, i.e. below the ray for d_a > 0) - 1 for
+ *                 d_a > 0 and (number of planes ahead) - 1 for d_a < 0; on an axis without, i_a = (number of k with
+ *                 P_a[k] <= o_a) - 1.  i_a = -1 and i_a = n_a are the two sides outside the grid.
+ *   path        : the crossings ahead, every axis in its direction of travel, merged by (t, axis) ascending; a
+ *                 crossing of axis a moves i_a by one.  Crossings with t = +inf are never reached.  The voxel path is
+ *                 a pure function of (o, d) and the plane tables.
+ *   hit         : the first state of the path (the start included) with all three i_a inside the grid and the voxel
+ *                 solid, for a pixel inside the view's ROI.  Pixels outside the ROI, and rays that meet no solid voxel,
+ *                 are misses.
+ *   outputs     : depth (float)  t of the crossing that entered the voxel (+0.0f for t == 0), 0 when the ray starts
+ *                                inside a solid voxel; +inf on a miss;
+ *                 voxel (int64)  global id of the hit voxel (z * nx * ny + y * nx + x); -1 on a miss;
+ *                 axis  (uint8)  0 / 1 / 2: the axis whose plane was crossed to enter, 3: started inside; 255 on a miss.
+ *                                -sign(d_axis) * e_axis is a flat normal for previews. */
+
+/* The planes between the cells of one axis (host arithmetic, no GPU): out[0 .. n], n = dims[axis] of vcy_compute_dims.
+ * With p = vcy_axis_positions: out[k] = (float)(((double)p[k - 1] + (double)p[k]) * 0.5) for 0 < k < n, and the outer
+ * two extrapolated by half the neighbouring pitch, out[0] = (float)((double)p[0] - ((double)p[1] - (double)p[0]) * 0.5),
+ * out[n] = (float)((double)p[n - 1] + ((double)p[n - 1] - (double)p[n - 2]) * 0.5); with n == 1 the half pitch is
+ * (double)resolution * 0.5.  The voxel pitch is diff / n, not `resolution` (voxel_carver.cc:315-326).
+ * VCY_ERR_INVALID_ARG for an empty axis or a table that is not strictly increasing (a box whose centres collide in float). */
+int vcy_cell_planes(const float bb_min[3], const float bb_max[3], float resolution, int axis, float* out);
+
+/* Ray-casts the hull into `n_views` views (one launch for up to 64 of them).  depth_host / voxel_host / axis_host: arrays
+ * of n_views pointers to row-major width * height images; any of the three arrays, or single entries, may be NULL.
+ * Only roi_min / roi_max, width, height, w2c, the intrinsics and is_ortho of a view are read.  Applies queued ("defer")
+ * views first; the state is not changed; a context nothing has been carved into since vcy_create / vcy_reset returns
+ * all-miss images without its lazy fill being written.  The solid bits (one per voxel) and the occupancy bits (one per
+ * 8 x 8 x 8 brick) are kept between calls and rebuilt when a carve, vcy_upload, vcy_reset or a component filter has come
+ * in between, or the iso level differs.  VCY_ERR_UNSUPPORTED, state untouched, for a context that does not own the whole
+ * grid.  VCY_ERR_INVALID_ARG for a non-finite w2c, fx or fy equal to 0 on a pinhole view, a width or height <= 0, or an
+ * ROI outside the image. */
+int vcy_render_hull(vcy_ctx* ctx, double iso_level, int n_views, const vcy_view* views, float* const* depth_host,
+                    int64_t* const* voxel_host, uint8_t* const* axis_host);
+/* Renders and compares with the silhouettes on the device; no image is downloaded.  masks_host[i]: width * height
+ * bytes, non-zero = object (the convention of vcy_carve_silhouette's callers).  counts[3 * i + 0 .. 2] = pixels of view
+ * i inside its ROI with {mask && hull, mask && !hull, !mask && hull}.  Errors as for vcy_render_hull. */
+int vcy_hull_agreement(vcy_ctx* ctx, double iso_level, int n_views, const vcy_view* views,
+                       const uint8_t* const* masks_host, int64_t* counts);
+/* Milliseconds between HIP events around the launches (bit planes when rebuilt, the ray-cast) of the last
+ * vcy_render_hull / vcy_hull_agreement, summed over its launches; copies of images are not included. */
+int vcy_last_render_ms(const vcy_ctx* ctx, float* device_ms);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and
@@ -569,6 +634,9 @@ int vcy_reset(vcy_ctx* ctx);
  * (a voxel's count cannot exceed that number), then widened in one pass to what voxel_max_update_num needs; 0 allocates
  * the final width at once.  Results are identical; "count_bytes" / "count_bytes_final" read the widths back.
  * "paircount" (default 0): 1 makes every fused launch count the (brick, view) pairs it processes (vcy_last_carve_pairs).
+ * "rayskip" (default 1): the rays of vcy_render_hull / vcy_hull_agreement step over 8 x 8 x 8 bricks without a solid voxel
+ * and jump to the plane through which they enter the grid; 0: every ray walks crossing by crossing.  Results identical
+ * (readable through vcy_get_param).
  * "inject_carve_failure" (test hook, default 0): the next `value` applications of views fail with
  * VCY_ERR_INTERNAL before anything is launched -- how the tests exercise the error contract of vcy_carve. */
 int vcy_set_param(vcy_ctx* ctx, const char* name, int value);

@@ -174,6 +174,10 @@ def load():
         "vcy_merge_components_host": (C.c_int, [C.c_int, vp, vp, vp, vp, P(P(Component)), P(C.c_int64), vp]),
         "vcy_resolve_components_slab": (C.c_int, [vp, C.c_int64, vp, vp]),
         "vcy_keep_components_slab": (C.c_int, [vp, C.c_float, C.c_int64, vp, P(C.c_int64)]),
+        "vcy_cell_planes": (C.c_int, [P(C.c_float), P(C.c_float), C.c_float, C.c_int, vp]),
+        "vcy_render_hull": (C.c_int, [vp, C.c_double, C.c_int, P(View), P(vp), P(vp), P(vp)]),
+        "vcy_hull_agreement": (C.c_int, [vp, C.c_double, C.c_int, P(View), P(vp), vp]),
+        "vcy_last_render_ms": (C.c_int, [vp, P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_mesh_normals_seam_sum": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),

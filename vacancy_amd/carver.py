@@ -440,6 +440,51 @@ class VoxelCarver:
         self._lib.vcy_last_components_ms(self._ctx, C.byref(ms))
         return ms.value
 
+    # -- ray-cast of the hull into views (no reference counterpart; definitions: include/vacancy_hip.h)
+    def RenderHull(self, views, iso_level=0.0, voxel_ids=False, axes=False):
+        """vcy_render_hull: per view, the first solid voxel (update_num >= 1 and sdf < iso_level) on every pixel's ray.
+        `views`: one vcy_view or a list (one launch).  Per view a dict: "depth" (float32 [height, width], camera depth of
+        the crossing that entered the voxel, +inf on a miss; depth < inf is the hull's silhouette); with voxel_ids=True
+        "voxel" (int64, global voxel id, -1 on a miss); with axes=True "axis" (uint8, 0 / 1 / 2 the entry axis, 3 started
+        inside, 255 on a miss).  A single view returns its dict, a list a list."""
+        single = isinstance(views, View)
+        vs = [views] if single else list(views)
+        n = len(vs)
+        out = [{"depth": np.empty((v.height, v.width), np.float32)} for v in vs]
+        for o, v in zip(out, vs):
+            if voxel_ids:
+                o["voxel"] = np.empty((v.height, v.width), np.int64)
+            if axes:
+                o["axis"] = np.empty((v.height, v.width), np.uint8)
+        arr = (View * n)(*vs)
+        dp = (C.c_void_p * n)(*[o["depth"].ctypes.data for o in out])
+        vp = (C.c_void_p * n)(*[o["voxel"].ctypes.data for o in out]) if voxel_ids else None
+        ap = (C.c_void_p * n)(*[o["axis"].ctypes.data for o in out]) if axes else None
+        if self._lib.vcy_render_hull(self._ctx, iso_level, n, arr, dp, vp, ap) != 0:
+            raise RuntimeError(last_error())
+        return out[0] if single else out
+
+    def HullAgreement(self, views, masks, iso_level=0.0):
+        """vcy_hull_agreement: renders the hull into `views` and compares it with the silhouettes `masks` (non-zero =
+        object) on the device.  int64 [n_views, 3]: pixels inside the ROI with (mask and hull, mask and not hull, hull
+        and not mask)."""
+        vs = list(views)
+        n = len(vs)
+        ms = [np.ascontiguousarray(m, np.uint8) for m in masks]
+        if len(ms) != n or any(m.shape != (v.height, v.width) for m, v in zip(ms, vs)):
+            raise ValueError("one height x width silhouette per view")
+        arr = (View * n)(*vs)
+        mp = (C.c_void_p * n)(*[m.ctypes.data for m in ms])
+        counts = np.zeros((n, 3), np.int64)
+        if self._lib.vcy_hull_agreement(self._ctx, iso_level, n, arr, mp, _p(counts)) != 0:
+            raise RuntimeError(last_error())
+        return counts
+
+    def last_render_ms(self):
+        ms = C.c_float()
+        self._lib.vcy_last_render_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     # -- state access
     def download(self):
         n = self.slab_voxels
@@ -579,6 +624,18 @@ class VoxelCarver:
 
 _COMPONENT_REC = np.dtype([("label", np.int64), ("n_voxels", np.int64), ("bb_min", np.int32, 3), ("bb_max", np.int32, 3)])
 assert _COMPONENT_REC.itemsize == C.sizeof(capi.Component)
+
+
+def cell_planes(option, axis):
+    """vcy_cell_planes: the dims[axis] + 1 planes between the cells of one axis (float32), host arithmetic, no GPU."""
+    lib = capi.load()
+    dims = (C.c_int32 * 3)()
+    if lib.vcy_compute_dims(option.bb_min, option.bb_max, option.resolution, dims) != 0:
+        raise RuntimeError(last_error())
+    out = np.empty(max(int(dims[axis]), 0) + 1, np.float32)
+    if lib.vcy_cell_planes(option.bb_min, option.bb_max, option.resolution, int(axis), _p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
 
 
 def components_to_dict(p, n):

@@ -215,6 +215,7 @@ int launch_carve(vcy_ctx* c, int n_views, const vcy_view* views, const float* co
     if (rcv != VCY_OK) return rcv;
   }
 
+  ++c->state_epoch;  // (whatever is launched below changes the state: vcy_render_hull builds its bit planes again)
   const bool fused = c->use_fused && fused_eligible(c, n_views, views);
   if (!fused) {
     int rcm = materialize(c);

@@ -379,6 +379,24 @@ bool whole_grid(const vcy_ctx* c) { return c->z0 == 0 && c->z1 == c->nz && c->ha
 
 }  // namespace
 
+// Step 1 (vcy_internal.h): also the first kernel of the ray-cast of the hull.
+int launch_solid_bits(vcy_ctx* c, double iso, unsigned long long* bits) {
+  const int nx = c->nx, Wr = (nx + 63) / 64;
+  const int64_t nwords = (int64_t)Wr * c->ny * c->nz_local();
+  const float* sdf = c->owned_slab_sdf();
+  const void* cnt = c->owned_slab_cnt();
+  const dim3 grid((unsigned)((nwords + 4 * cc::kBitsWordsPerWave - 1) / (4 * cc::kBitsWordsPerWave)));
+#define VCY_CC_BITS(T, IMPL) \
+  hipLaunchKernelGGL((cc::cc_bits_kernel<T, IMPL>), grid, dim3(256), 0, c->stream, sdf, (const T*)cnt, nx, Wr, nwords, iso, bits)
+  if (c->cnt_implied) VCY_CC_BITS(uint8_t, true);
+  else if (c->cnt_bytes == 1) VCY_CC_BITS(uint8_t, false);
+  else if (c->cnt_bytes == 2) VCY_CC_BITS(uint16_t, false);
+  else VCY_CC_BITS(uint32_t, false);
+#undef VCY_CC_BITS
+  VCY_HIP_CHECK(hipGetLastError());
+  return VCY_OK;
+}
+
 // Steps 1 - 5.  `comps` in the order of the header (n_voxels descending, label ascending); `slot_of_comp[i]` = where
 // component i's root stands in the sorted root list the device holds (cc_roots).  The begin event is recorded here, the
 // end event by the caller.
@@ -421,23 +439,11 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
   int* label = (int*)c->d_cc_labels;
   cc::u64* bits = (cc::u64*)c->d_cc_bits;
   unsigned int* d_nroots = (unsigned int*)(bits + nwords);  // (the 64 bytes behind the words)
-  const float* sdf = c->owned_slab_sdf();
-  const void* cnt = c->owned_slab_cnt();
 
   VCY_HIP_CHECK(hipEventRecord(c->ev_cc_begin, c->stream));
   c->cc_timed = true;
   VCY_HIP_CHECK(hipMemsetAsync(d_nroots, 0, 64, c->stream));
-  {
-    const dim3 grid((unsigned)((nwords + 4 * cc::kBitsWordsPerWave - 1) / (4 * cc::kBitsWordsPerWave)));
-#define VCY_CC_BITS(T, IMPL) \
-  hipLaunchKernelGGL((cc::cc_bits_kernel<T, IMPL>), grid, dim3(256), 0, c->stream, sdf, (const T*)cnt, nx, Wr, nwords, iso, bits)
-    if (c->cnt_implied) VCY_CC_BITS(uint8_t, true);
-    else if (c->cnt_bytes == 1) VCY_CC_BITS(uint8_t, false);
-    else if (c->cnt_bytes == 2) VCY_CC_BITS(uint16_t, false);
-    else VCY_CC_BITS(uint32_t, false);
-#undef VCY_CC_BITS
-    VCY_HIP_CHECK(hipGetLastError());
-  }
+  { const int rc = launch_solid_bits(c, iso, bits); if (rc != VCY_OK) return rc; }
   const unsigned word_blocks = (unsigned)((nwords + 255) / 256);
   hipLaunchKernelGGL(cc::cc_init_kernel, dim3((unsigned)std::min<int64_t>((nwords + 3) / 4, 1 << 20)), dim3(256), 0, c->stream,
                      bits, nx, Wr, nwords, label);
@@ -532,6 +538,7 @@ static int launch_filter(vcy_ctx* c, const std::vector<uint8_t>& removed, int ke
   const int nbw = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (nzl + 7) / 8;
   const int64_t nbricks = (int64_t)nbw * nby * nbz;
   float* bmin = c->brick_min_valid && c->d_brick_min ? c->d_brick_min : nullptr;
+  ++c->state_epoch;  // (solid voxels go: the bit planes of the ray-cast are stale)
   hipLaunchKernelGGL(cc::cc_filter_kernel, dim3((unsigned)((nbricks + 3) / 4)), dim3(256), 0, c->stream, c->owned_slab_sdf(),
                      (const int*)c->d_cc_labels, c->nx, c->ny, nzl, nbw, nby, nbricks, d_roots, (int)nc, d_removed, keep0,
                      fill_sdf, bmin);

@@ -207,6 +207,7 @@ int fill_state(vcy_ctx* c) {
   c->deferred_rc = VCY_OK;
   c->deferred_msg.clear();
   c->fresh = true;  // written lazily, see vcy_ctx::fresh
+  ++c->state_epoch;
   c->brick_min_valid = false;
   if (c->h_live_hint) c->h_live_hint[0] = c->h_live_hint[1] = 0;
   c->views_carved = 0;
@@ -515,6 +516,7 @@ void vcy_destroy(vcy_ctx* c) {
   (void)hipFree(c->d_cc_bits);
   (void)hipFree(c->d_cc_roots);
   (void)hipFree(c->d_cc_seam);
+  render_release(c);
   if (c->h_cc_report) (void)hipHostFree(c->h_cc_report);
   if (c->ev_cc_begin) (void)hipEventDestroy(c->ev_cc_begin);
   if (c->ev_cc_end) (void)hipEventDestroy(c->ev_cc_end);
@@ -666,6 +668,10 @@ int vcy_set_param(vcy_ctx* c, const char* name, int value) {
     c->mesh_keys = value != 0;
     return VCY_OK;
   }
+  if (std::strcmp(name, "rayskip") == 0) {
+    c->ray_skip = value != 0 ? 1 : 0;
+    return VCY_OK;
+  }
   if (std::strcmp(name, "mcdirect") == 0) {  // bytes (of the guessed mesh) up to which mc_emit writes host memory directly
     c->mc_direct_bytes = value < 0 ? 0 : (int64_t)value;
     return VCY_OK;
@@ -706,6 +712,7 @@ int vcy_get_param(vcy_ctx* c, const char* name, int* value) {
   else if (std::strcmp(name, "livesync") == 0) *value = c->live_sync ? 1 : 0;
   else if (std::strcmp(name, "brick_min_valid") == 0) *value = c->brick_min_valid && !c->fresh ? 1 : 0;
   else if (std::strcmp(name, "meshkeys") == 0) *value = c->mesh_keys ? 1 : 0;
+  else if (std::strcmp(name, "rayskip") == 0) *value = c->ray_skip;
   else if (std::strcmp(name, "lazycount") == 0) *value = c->lazy_count ? 1 : 0;
   else if (std::strcmp(name, "carvetimer") == 0) *value = c->time_carve ? 1 : 0;
   else if (std::strcmp(name, "carvelog_dropped") == 0) *value = c->carve_log_dropped;
@@ -961,6 +968,7 @@ int vcy_upload(vcy_ctx* c, const float* sdf, const int32_t* update_num) {
   { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
   VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
   const int64_t n = c->slab_voxels();
+  ++c->state_epoch;
   if (sdf)
     VCY_HIP_CHECK(hipMemcpy(c->owned_slab_sdf(), sdf, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
   if (update_num) {

@@ -218,6 +218,20 @@ struct vcy_ctx {
   void* d_cc_seam = nullptr;          // seam pairs: [the lower slab's top plane, int64 per voxel | counter | pairs] (grow-only)
   size_t cc_seam_bytes = 0;
 
+  // ray-cast of the hull (render.hip); everything grow-only
+  int64_t state_epoch = 0;            // bumped by everything that may change which voxels are solid: a carve, vcy_upload, the fill, the component filter
+  void* d_rn_bits = nullptr;          // [solid bit of every voxel, 64-voxel words along x | one bit per 8 x 8 x 8 brick that holds a solid voxel]
+  size_t rn_bits_bytes = 0;
+  bool rn_bits_valid = false;         // ... describe the state of epoch rn_epoch at the iso level rn_iso
+  int64_t rn_epoch = -1;
+  double rn_iso = 0.0;
+  float* d_rn_planes = nullptr;       // the cell planes of the three axes one behind the other (vcy_cell_planes), nx + ny + nz + 3 floats
+  void* d_rn_out = nullptr;           // view records, counters, images and silhouettes of one launch
+  size_t rn_out_bytes = 0;
+  hipEvent_t ev_rn_begin = nullptr, ev_rn_end = nullptr;
+  float last_render_device_ms = 0.0f;
+  int ray_skip = 1;                   // "rayskip": rays step over bricks without a solid voxel (0: crossing by crossing)
+
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
 
@@ -254,6 +268,11 @@ int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int 
                 vcy_mesh_normals* normals_out = nullptr, int64_t* layer_faces = nullptr);
 // components.hip: vcy_label_components, vcy_keep_components, vcy_download_labels, vcy_last_components_ms, the _slab
 // entries of a z-slab context and the seam merge on the host (vcy_merge_components_host)
+// the solid bit of every voxel of the owned slices in 64-voxel words along x, (nx + 63) / 64 words per row (cc_bits_kernel);
+// the state must be materialised.  Shared by the labelling and the ray-cast (render.hip).
+int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
+// render.hip: vcy_render_hull, vcy_hull_agreement, vcy_cell_planes, vcy_last_render_ms
+void render_release(vcy_ctx* ctx);  // frees what the ray-cast keeps on the context (vcy_destroy)
 // sdf2d.hip
 void host_distance_transform_l1(const uint8_t* mask, int w, int h, const int32_t* rmin,
                                 const int32_t* rmax, float* out);

@@ -1,5 +1,6 @@
 // CPU-only check of the facade's host utilities (no GPU calls): PNG decode of the bunny masks,
 // TUM pose -> w2c arithmetic.  Prints values that tests/test_host.py compares with fixtures.
+#include <array>
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -249,6 +250,45 @@ int main(int argc, char* argv[]) {
       for (int c = 0; c < 3; ++c) same = same && ma.vertex_indices()[k][c] == mb.vertex_indices()[k][c];
     std::printf("SHARDCOMPONENTS %d %zu %d %zu %d %d\n", sh.slab_count(), b.size(), same_lists(a, b) ? 1 : 0, b2.size(),
                 same_lists(a2, b2) ? 1 : 0, same ? 1 : 0);
+    return 0;
+  }
+  if (argc > 4 && std::string(argv[2]) == "shardrender") {
+    // needs a device: the ray-cast of the hull needs the whole grid in one context, so ShardedVoxelCarver::RenderHull /
+    // HullAgreement refuse, and VoxelCarver's own refuse bad arguments -- each with false and a logged error.
+    //   host_selftest <data dir> shardrender <resolution> <slabs on device 0>
+    //   prints SHARDRENDER <slabs> <sharded RenderHull> <sharded HullAgreement> <null depth> <count mismatch> <no list>
+    //          <before Init> <good call>
+    vacancy::VoxelCarverOption option;
+    option.bb_min = Eigen::Vector3f(-250.000000f, -344.586151f, -129.982697f);
+    option.bb_max = Eigen::Vector3f(250.000000f, 150.542343f, 257.329224f);
+    for (int i = 0; i < 3; ++i) {  // (examples.cc:91-99)
+      option.bb_min[i] -= 20.0f;
+      option.bb_max[i] += 20.0f;
+    }
+    option.resolution = (float)std::atof(argv[3]);
+    vacancy::VoxelCarver one(option), never(option);
+    vacancy::ShardedVoxelCarver sh(option, {0}, std::atoi(argv[4]));
+    if (!one.Init() || !sh.Init()) return 6;
+    vacancy::PinholeCamera cam(320, 240, Eigen::Affine3d::Identity(), Eigen::Vector2f(159.3f, 127.65f),
+                               Eigen::Vector2f(258.65f, 258.25f));
+    vacancy::Image1b sil;
+    if (!sil.Load(dir + "/mask_" + vacancy::zfill(0) + ".png")) return 4;
+    if (!one.Carve(cam, sil) || !sh.Carve(cam, sil)) return 7;
+    vacancy::Image1f depth;
+    vacancy::Image1b hull;
+    std::vector<std::array<std::int64_t, 3>> counts;
+    const std::vector<const vacancy::Camera*> cams{&cam};
+    const std::vector<vacancy::Image1b> sils{sil}, two{sil, sil};
+    const bool r0 = sh.RenderHull(cam, &depth, &hull);
+    const bool r1 = sh.HullAgreement(std::vector<vacancy::Camera>(), std::vector<vacancy::Image1b>(), &counts);
+    const bool r2 = one.RenderHull(cam, nullptr);
+    const bool r3 = one.HullAgreement(cams, two, &counts);
+    const bool r4 = one.HullAgreement(cams, sils, nullptr);
+    const bool r5 = never.RenderHull(cam, &depth) || never.HullAgreement(cams, sils, &counts);
+    const bool r6 = one.RenderHull(cam, &depth, &hull) && one.HullAgreement(cams, sils, &counts) && counts.size() == 1 &&
+                    depth.width() == 320 && hull.height() == 240;
+    std::printf("SHARDRENDER %d %d %d %d %d %d %d %d\n", sh.slab_count(), r0 ? 1 : 0, r1 ? 1 : 0, r2 ? 1 : 0, r3 ? 1 : 0,
+                r4 ? 1 : 0, r5 ? 1 : 0, r6 ? 1 : 0);
     return 0;
   }
   if (argc > 3 && std::string(argv[2]) == "normals") {

@@ -352,6 +352,17 @@ bool ShardedVoxelCarver::LabelComponents(std::vector<VoxelComponent>* components
 // that go.  The two halo slices below every upper slab are stale afterwards, exactly as after a Carve(): ExtractIsoSurface
 // always, and ExtractVoxel whenever it reads the slice below a slab (inside_empty), call ExchangeHalo() before they
 // read them, so nothing has to be exchanged here.
+bool ShardedVoxelCarver::RenderHull(const Camera&, Image1f*, Image1b*) {
+  LOGE("ShardedVoxelCarver::RenderHull: the ray-cast needs the whole grid in one context (VoxelCarver::RenderHull)\n");
+  return false;
+}
+
+bool ShardedVoxelCarver::HullAgreement(const std::vector<Camera>&, const std::vector<Image1b>&,
+                                       std::vector<std::array<std::int64_t, 3>>*) {
+  LOGE("ShardedVoxelCarver::HullAgreement: the ray-cast needs the whole grid in one context (VoxelCarver::HullAgreement)\n");
+  return false;
+}
+
 bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!std::isfinite(fill_sdf) || !(static_cast<double>(fill_sdf) >= iso_level)) {
     LOGE("KeepLargestComponents: fill_sdf %g must be finite and not below the iso level %g\n", static_cast<double>(fill_sdf),

@@ -346,6 +346,79 @@ bool VoxelCarver::LabelComponents(std::vector<VoxelComponent>* components, doubl
   return true;
 }
 
+bool VoxelCarver::RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette, double iso_level) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  const int w = camera.width(), h = camera.height();
+  bool known = true;
+  const vcy_view v = ToView(camera, Eigen::Vector2i(0, 0), Eigen::Vector2i(w - 1, h - 1), w, h, &known);
+  if (!known) return false;  // (ToView has logged the camera type)
+  if (!depth || w <= 0 || h <= 0) {
+    LOGE("VoxelCarver::RenderHull needs a depth image to fill and a camera with a size (%d x %d)\n", w, h);
+    return false;
+  }
+  depth->Init(w, h);
+  float* dp = depth->data_ptr()->data();
+  const int rc = vcy_render_hull(impl_->ctx, iso_level, 1, &v, &dp, nullptr, nullptr);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  if (silhouette) {
+    silhouette->Init(w, h);
+    std::vector<unsigned char>& s = *silhouette->data_ptr();
+    for (size_t i = 0; i < s.size(); ++i) s[i] = dp[i] < std::numeric_limits<float>::infinity() ? 255 : 0;
+  }
+  return true;
+}
+
+bool VoxelCarver::HullAgreement(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
+                                std::vector<std::array<std::int64_t, 3>>* counts, double iso_level) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (!counts || cameras.size() != silhouettes.size() || cameras.empty()) {
+    LOGE("VoxelCarver::HullAgreement needs one silhouette per camera, at least one, and a place for the counts (%zu cameras, "
+         "%zu silhouettes)\n", cameras.size(), silhouettes.size());
+    return false;
+  }
+  const int n = static_cast<int>(cameras.size());
+  std::vector<vcy_view> views(n);
+  std::vector<const uint8_t*> masks(n);
+  for (int i = 0; i < n; ++i) {
+    const Image1b& s = silhouettes[i];
+    bool known = true;
+    if (!cameras[i] || s.empty()) {
+      LOGE("VoxelCarver::HullAgreement: view %d has no camera or an empty silhouette\n", i);
+      return false;
+    }
+    views[i] = ToView(*cameras[i], Eigen::Vector2i(0, 0), Eigen::Vector2i(s.width() - 1, s.height() - 1), s.width(),
+                      s.height(), &known);
+    if (!known) return false;  // (ToView has logged the camera type)
+    masks[i] = s.data().data();
+  }
+  counts->assign(static_cast<size_t>(n), std::array<std::int64_t, 3>{{0, 0, 0}});
+  static_assert(sizeof(std::array<std::int64_t, 3>) == 3 * sizeof(std::int64_t), "packed array layout");
+  const int rc = vcy_hull_agreement(impl_->ctx, iso_level, n, views.data(), masks.data(), (*counts)[0].data());
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  return true;
+}
+
+bool VoxelCarver::HullAgreement(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
+                                std::vector<std::array<std::int64_t, 3>>* counts) {
+  std::vector<const Camera*> ptrs(cameras.size());
+  for (size_t i = 0; i < cameras.size(); ++i) ptrs[i] = &cameras[i];
+  return HullAgreement(ptrs, silhouettes, counts);
+}
+
 bool VoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!impl_->ctx) {
     LOGE("voxel grid has not been initialized\n");
