@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <memory>
 #include <sstream>
@@ -190,6 +191,20 @@ int main(int argc, char* argv[]) {
       const long long uni = both + only_mask + only_hull;
       std::printf("RENDER view %zu mask&hull %lld mask-only %lld hull-only %lld IoU %.4f\n", i, both, only_mask, only_hull,
                   uni ? static_cast<double>(both) / static_cast<double>(uni) : 1.0);
+    }
+    if (sharded) {  // the same through the slabs: every slab renders its own slices, the host merges (RenderHullSlabs)
+      bool same = true;
+      for (size_t i = 0; i < cams.size(); ++i) {
+        vacancy::Image1f one, merged;
+        if (!carver.RenderHull(*cams[i], &one) || !sharded->RenderHullSlabs(*cams[i], &merged)) return 11;
+        same = same && one.data().size() == merged.data().size() &&
+               std::memcmp(one.data().data(), merged.data().data(), sizeof(float) * one.data().size()) == 0;
+      }
+      std::vector<std::array<std::int64_t, 3>> scounts;
+      if (!sharded->HullAgreementSlabs(cam_ptrs, sils, &scounts)) return 11;
+      same = same && scounts == counts;
+      std::printf("RENDERSHARDED slabs %d views %zu depth and counts identical %d\n", sharded->slab_count(), cams.size(), same ? 1 : 0);
+      if (!same) return 12;
     }
   }
 

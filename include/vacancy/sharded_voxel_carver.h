@@ -59,11 +59,21 @@ class ShardedVoxelCarver {
   // stale after the filter as after a Carve(); the extractions exchange them before they read them.
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
-  // VoxelCarver::RenderHull / HullAgreement need the whole grid in one context (merging slabs by minimum depth needs a tie
-  // rule of its own): both log an error and return false.
+  // VoxelCarver::RenderHull / HullAgreement over the slabs: RenderHullSlabs / HullAgreementSlabs below.  These two older
+  // names keep logging an error and returning false.
   bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);
   bool HullAgreement(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
                      std::vector<std::array<std::int64_t, 3>>* counts);
+  // Every slab renders the image of its own slices on its device (vcy_render_hull_slab: the global path, hits only in
+  // the owned slices; no halo exchange), a host thread per slab; the host merges by the rule of vcy_render_merge_host --
+  // per pixel the hit of the first slab in the ray's direction of travel along z, NOT the smallest depth, which two slabs
+  // can share.  The images equal VoxelCarver::RenderHull's bit for bit wherever the grid is cut.  HullAgreementSlabs
+  // brings one hit bit per pixel and slab to the host and counts there (vcy_hull_agreement_host).
+  bool RenderHullSlabs(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr, double iso_level = 0.0);
+  bool HullAgreementSlabs(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
+                          std::vector<std::array<std::int64_t, 3>>* counts, double iso_level = 0.0);
+  bool HullAgreementSlabs(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
+                          std::vector<std::array<std::int64_t, 3>>* counts, double iso_level = 0.0);
 
  private:
   bool ExchangeHalo();

@@ -471,7 +471,7 @@ int vcy_cell_planes(const float bb_min[3], const float bb_max[3], float resoluti
  * all-miss images without its lazy fill being written.  The solid bits (one per voxel) and the occupancy bits (one per
  * 8 x 8 x 8 brick) are kept between calls and rebuilt when a carve, vcy_upload, vcy_reset or a component filter has come
  * in between, or the iso level differs.  VCY_ERR_UNSUPPORTED, state untouched, for a context that does not own the whole
- * grid.  VCY_ERR_INVALID_ARG for a non-finite w2c, fx or fy equal to 0 on a pinhole view, a width or height <= 0, or an
+ * grid (such a context renders through vcy_render_hull_slab, below).  VCY_ERR_INVALID_ARG for a non-finite w2c, fx or fy equal to 0 on a pinhole view, a width or height <= 0, or an
  * ROI outside the image. */
 int vcy_render_hull(vcy_ctx* ctx, double iso_level, int n_views, const vcy_view* views, float* const* depth_host,
                     int64_t* const* voxel_host, uint8_t* const* axis_host);
@@ -480,8 +480,47 @@ int vcy_render_hull(vcy_ctx* ctx, double iso_level, int n_views, const vcy_view*
  * i inside its ROI with {mask && hull, mask && !hull, !mask && hull}.  Errors as for vcy_render_hull. */
 int vcy_hull_agreement(vcy_ctx* ctx, double iso_level, int n_views, const vcy_view* views,
                        const uint8_t* const* masks_host, int64_t* counts);
+/* ---- ... of a grid cut into z-slabs ----
+ * Everything refers to the definitions above: the global planes of vcy_cell_planes, the path as the merge by (t, axis) of
+ * three monotone crossing sequences, t, the entry axis and the -0 -> 0 rule.
+ *   slab image : the image of a context that owns the slices [z0, z1) is the whole-grid image of the state in which every
+ *                voxel outside [z0, z1) is not solid.  The ray walks the GLOBAL path: plane tables, integer plane indices
+ *                and start cells are global, t_a(k) is computed from the global k by the same float expression; a voxel
+ *                can only be a hit where z0 <= i_z < z1; the voxel id is the global id (i_z * ny + i_y) * nx + i_x; depth
+ *                and entry axis are those of the global path at that cell.  The halo slices below z0 are never read: no
+ *                halo exchange is needed before a render.
+ *   merge rule : along a ray i_z is monotone -- it rises when s_z > 0, falls when s_z < 0 and is constant when s_z == 0,
+ *                s_z being the sign the walk forms: d_z = R[0][2] * d_c0 + R[1][2] * d_c1 + R[2][2] * 1.0f, and the axis
+ *                moves iff d_z != 0 && isfinite(1.0f / d_z).  The ray visits the slabs in that order, and the whole-grid
+ *                hit is the hit of the FIRST slab in the ray's direction of travel along z that has one: the lowest slab
+ *                with voxel >= 0 for s_z > 0, the highest for s_z < 0; for s_z == 0 at most one slab can hit.  Depth,
+ *                voxel id and axis come from that slab, +inf / -1 / 255 when no slab hit.
+ *                Depth is NOT the key: two consecutive states of a path can carry the same t -- an x crossing and a z
+ *                crossing at equal t sort by axis -- and lie in different slabs.
+ *   hit bits   : one bit per pixel, rows of (width + 63) / 64 64-bit words; bit u & 63 of word [v][u >> 6] is set iff
+ *                pixel (u, v) lies in the ROI and its ray hits a solid voxel of the slab; every other bit, the padding
+ *                of a row included, is 0.  The OR of the slabs' bits is the whole grid's silhouette.
+ * Per view and slab, depth (4 B / pixel), or the hit bits alone (1 bit / pixel) for the agreement, cross to the host. */
+
+/* vcy_render_hull for ANY context: the slab image of the slices the context owns (on a context that owns the whole grid
+ * the first three images equal vcy_render_hull's).  hits_host: n_views pointers to (width + 63) / 64 * height 64-bit
+ * words each, or NULL, single entries too.  Arguments, errors, the 64 views per launch, the kept bit planes (of the
+ * owned slices, bricks counted from z0) and vcy_last_render_ms as for vcy_render_hull; a fresh slab renders all misses
+ * and all-zero hit bits without its lazy fill being written. */
+int vcy_render_hull_slab(vcy_ctx* ctx, double iso_level, int n_views, const vcy_view* views, float* const* depth_host,
+                         int64_t* const* voxel_host, uint8_t* const* axis_host, uint64_t* const* hits_host);
+/* The merge rule on the host (no GPU, no context).  depth / voxel / axis: n_slabs pointers each to the slabs' images of
+ * `view`, slabs in ascending z.  `voxel` is required (it says which slab hit); depth and axis may be NULL as a whole,
+ * and then their output is not written; voxel_out may be NULL.  VCY_ERR_INVALID_ARG for n_slabs <= 0, a NULL where an
+ * image is required, or a view vcy_render_hull would refuse. */
+int vcy_render_merge_host(const vcy_view* view, int n_slabs, const float* const* depth, const int64_t* const* voxel,
+                          const uint8_t* const* axis, float* depth_out, int64_t* voxel_out, uint8_t* axis_out);
+/* vcy_hull_agreement from the slabs' hit bits (host only): ORs hits[0 .. n_slabs - 1] and counts, inside the view's ROI,
+ * {mask && hull, mask && !hull, !mask && hull}; mask as for vcy_hull_agreement.  Errors as above. */
+int vcy_hull_agreement_host(const vcy_view* view, int n_slabs, const uint64_t* const* hits, const uint8_t* mask,
+                            int64_t counts[3]);
 /* Milliseconds between HIP events around the launches (bit planes when rebuilt, the ray-cast) of the last
- * vcy_render_hull / vcy_hull_agreement, summed over its launches; copies of images are not included. */
+ * vcy_render_hull / vcy_render_hull_slab / vcy_hull_agreement, summed over its launches; copies of images are not included. */
 int vcy_last_render_ms(const vcy_ctx* ctx, float* device_ms);
 
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */

@@ -177,6 +177,9 @@ def load():
         "vcy_cell_planes": (C.c_int, [P(C.c_float), P(C.c_float), C.c_float, C.c_int, vp]),
         "vcy_render_hull": (C.c_int, [vp, C.c_double, C.c_int, P(View), P(vp), P(vp), P(vp)]),
         "vcy_hull_agreement": (C.c_int, [vp, C.c_double, C.c_int, P(View), P(vp), vp]),
+        "vcy_render_hull_slab": (C.c_int, [vp, C.c_double, C.c_int, P(View), P(vp), P(vp), P(vp), P(vp)]),
+        "vcy_render_merge_host": (C.c_int, [P(View), C.c_int, P(vp), P(vp), P(vp), vp, vp, vp]),
+        "vcy_hull_agreement_host": (C.c_int, [P(View), C.c_int, P(vp), vp, vp]),
         "vcy_last_render_ms": (C.c_int, [vp, P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),

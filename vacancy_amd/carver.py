@@ -480,6 +480,30 @@ class VoxelCarver:
             raise RuntimeError(last_error())
         return counts
 
+    def RenderHullSlab(self, views, iso_level=0.0, voxel_ids=False, axes=False, hits=False):
+        """vcy_render_hull_slab: RenderHull of the slices this context owns -- the whole-grid image of the state in which
+        no voxel outside them is solid (global voxel ids, depths and axes of the global path) --, on any context.  With
+        hits=True "hits": uint64 [height, (width + 63) // 64], bit u & 63 of word u >> 6 set where the pixel lies in the
+        ROI and hits.  The slabs' images are merged by render_merge_host, their hit bits compared by
+        hull_agreement_host."""
+        single = isinstance(views, View)
+        vs = [views] if single else list(views)
+        n = len(vs)
+        out = [{"depth": np.empty((v.height, v.width), np.float32)} for v in vs]
+        for o, v in zip(out, vs):
+            if voxel_ids:
+                o["voxel"] = np.empty((v.height, v.width), np.int64)
+            if axes:
+                o["axis"] = np.empty((v.height, v.width), np.uint8)
+            if hits:
+                o["hits"] = np.empty((v.height, (v.width + 63) // 64), np.uint64)
+        arr = (View * n)(*vs)
+        ptrs = [(C.c_void_p * n)(*[o[k].ctypes.data for o in out]) if on else None
+                for k, on in (("depth", True), ("voxel", voxel_ids), ("axis", axes), ("hits", hits))]
+        if self._lib.vcy_render_hull_slab(self._ctx, iso_level, n, arr, *ptrs) != 0:
+            raise RuntimeError(last_error())
+        return out[0] if single else out
+
     def last_render_ms(self):
         ms = C.c_float()
         self._lib.vcy_last_render_ms(self._ctx, C.byref(ms))
@@ -845,3 +869,40 @@ def distance_transform_l1(mask, roi_min=None, roi_max=None):
     if rc != 0:
         raise RuntimeError(last_error())
     return out
+
+
+def render_merge_host(view, parts):
+    """vcy_render_merge_host: the slabs' images of one view (RenderHullSlab dicts in ascending z; "voxel" is required,
+    "depth" and "axis" are merged when every slab has them) merged into the whole grid's: the hit of the first slab in
+    the ray's direction of travel along z that has one.  No GPU."""
+    lib = capi.load()
+    n = len(parts)
+    if n == 0 or any("voxel" not in p for p in parts):
+        raise ValueError("render_merge_host needs the voxel ids of at least one slab")
+    shape = (view.height, view.width)
+    keep = {k: [np.ascontiguousarray(p[k], t) for p in parts] for k, t in
+            (("depth", np.float32), ("voxel", np.int64), ("axis", np.uint8)) if all(k in p for p in parts)}
+    if any(a.shape != shape for arrs in keep.values() for a in arrs):
+        raise ValueError("every slab image is height x width of the view")
+    out = {k: np.empty(shape, arrs[0].dtype) for k, arrs in keep.items()}
+    ptr = {k: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) for k, arrs in keep.items()}
+    if lib.vcy_render_merge_host(C.byref(view), n, ptr.get("depth"), ptr["voxel"], ptr.get("axis"),
+                                 _p(out["depth"]) if "depth" in out else None, _p(out["voxel"]),
+                                 _p(out["axis"]) if "axis" in out else None) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def hull_agreement_host(view, hits, mask):
+    """vcy_hull_agreement_host: int64 [3] = pixels inside the ROI with (mask and hull, mask and not hull, hull and not
+    mask), the hull being the OR of the slabs' hit bits (`hits`: uint64 [height, (width + 63) // 64] per slab).  No GPU."""
+    lib = capi.load()
+    hs = [np.ascontiguousarray(h, np.uint64) for h in hits]
+    m = np.ascontiguousarray(mask, np.uint8)
+    if not hs or any(h.shape != (view.height, (view.width + 63) // 64) for h in hs) or m.shape != (view.height, view.width):
+        raise ValueError("hit bits of height x (width + 63) // 64 words per slab and a height x width silhouette")
+    counts = np.zeros(3, np.int64)
+    hp = (C.c_void_p * len(hs))(*[h.ctypes.data for h in hs])
+    if lib.vcy_hull_agreement_host(C.byref(view), len(hs), hp, _p(m), _p(counts)) != 0:
+        raise RuntimeError(last_error())
+    return counts

@@ -22,6 +22,14 @@
 //   entry    outside the grid, E is the LATEST of the planes through which the out-of-range axes come into range; no
 //            state before E lies inside the grid, and the other axes are counted up to E in the same way.
 // Both compare the same floats as the flat walk, so "rayskip" 0 and 1 give the same bits.
+//
+// z-slabs (vcy_render_hull_slab, the SLAB instances of rn_cast).  A context that owns the slices [z0, z1) renders the
+// whole-grid image of the state in which no voxel outside its slices is solid: the ray walks the GLOBAL path -- global
+// plane tables, plane indices and start cells --, "inside" is narrowed to z0 <= i_z < z1, the entry jump takes plane z0
+// or z1 as the plane through which z comes into range, and the bricks are counted from z0 (brick planes at z0 + 8k,
+// capped at z1), as the bit planes and the occupancy bits of a slab are.  The halo slices are never read.  The same
+// instances pack one hit bit per pixel: a wave's ballot is its tile's eight row bytes, stored by eight lanes.  The
+// images of the slabs are merged on the host (render_merge.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -41,6 +49,7 @@ struct Grid {
   int Wr;            // bit words per voxel row
   int nbx, nby;      // bricks along x and y
   int empty;         // nothing has been carved: every ray is a miss, no bit plane exists
+  int z0, z1;        // the owned slices (SLAB instances only; bits and occ start at slice z0)
   const u64* bits;
   const u64* occ;
   const float* planes;
@@ -55,6 +64,7 @@ struct View {          // one per view of a launch, in device memory
   long long* voxel;
   uint8_t* axis;
   const uint8_t* mask;  // agreement only
+  uint8_t* hits;        // SLAB instances only, may be null: rows of (w + 63) / 64 64-bit words, bit u & 63 of word u >> 6
 };
 
 __global__ __launch_bounds__(256) void rn_occupancy_kernel(const u64* __restrict__ bits, int ny, int nz, int Wr, int nbx,
@@ -143,8 +153,10 @@ __device__ __forceinline__ void jump(const float* P, const Grid& g, Axis (&ax)[3
   }
 }
 
-template <bool LDS, bool SKIP, bool AGREE>
+template <bool LDS, bool SKIP, bool AGREE, bool SLAB>
 __global__ __launch_bounds__(256) void rn_cast_kernel(Grid g, const View* __restrict__ views, u64* __restrict__ counts) {
+  static_assert(!(AGREE && SLAB), "the slabs' silhouettes are compared on the host, from their hit bits");
+  const int zlo = SLAB ? g.z0 : 0, zhi = SLAB ? g.z1 : g.n[2];  // the slices a voxel can be hit in
   extern __shared__ float s_planes[];
   const View& v = views[blockIdx.z];
   if ((int)blockIdx.x * 16 >= v.w || (int)blockIdx.y * 16 >= v.h) return;  // (uniform: the launch is sized for the largest view)
@@ -190,10 +202,11 @@ __global__ __launch_bounds__(256) void rn_cast_kernel(Grid g, const View* __rest
       int64_t brick_seen = -1;
       bool brick_live = false;
       for (;;) {
-        const bool inside = ax[0].i >= 0 && ax[0].i < g.n[0] && ax[1].i >= 0 && ax[1].i < g.n[1] && ax[2].i >= 0 && ax[2].i < g.n[2];
+        const bool inside = ax[0].i >= 0 && ax[0].i < g.n[0] && ax[1].i >= 0 && ax[1].i < g.n[1] && ax[2].i >= zlo && ax[2].i < zhi;
         if (inside) {
+          const int zl = ax[2].i - zlo;  // (slice within the bit planes)
           if (SKIP) {
-            const int64_t b = ((int64_t)(ax[2].i >> 3) * g.nby + (ax[1].i >> 3)) * g.nbx + (ax[0].i >> 3);
+            const int64_t b = ((int64_t)(zl >> 3) * g.nby + (ax[1].i >> 3)) * g.nbx + (ax[0].i >> 3);
             if (b != brick_seen) {
               brick_seen = b;
               brick_live = (g.occ[b >> 6] >> (b & 63)) & 1ull;
@@ -204,7 +217,8 @@ __global__ __launch_bounds__(256) void rn_cast_kernel(Grid g, const View* __rest
               float tE = INFINITY;
 #pragma unroll
               for (int a = 0; a < 3; ++a) {
-                kE[a] = ax[a].s > 0 ? min((ax[a].i | 7) + 1, g.n[a]) : (ax[a].i & ~7);
+                if (SLAB && a == 2) kE[a] = ax[a].s > 0 ? min(zlo + (zl | 7) + 1, zhi) : zlo + (zl & ~7);  // bricks from z0
+                else kE[a] = ax[a].s > 0 ? min((ax[a].i | 7) + 1, g.n[a]) : (ax[a].i & ~7);
                 m[a] = ax[a].s > 0 ? kE[a] - 1 - ax[a].i : ax[a].i - kE[a];
                 if (ax[a].s != 0) {
                   const float t = cross_t(P, g.off[a], kE[a], ax[a]);
@@ -218,7 +232,7 @@ __global__ __launch_bounds__(256) void rn_cast_kernel(Grid g, const View* __rest
               continue;
             }
           }
-          const u64 word = g.bits[((int64_t)ax[2].i * g.n[1] + ax[1].i) * g.Wr + (ax[0].i >> 6)];
+          const u64 word = g.bits[((int64_t)zl * g.n[1] + ax[1].i) * g.Wr + (ax[0].i >> 6)];
           if ((word >> (ax[0].i & 63)) & 1ull) {
             depth = t_in == 0.0f ? 0.0f : t_in;
             voxel = ((long long)ax[2].i * g.n[1] + ax[1].i) * g.n[0] + ax[0].i;
@@ -229,7 +243,7 @@ __global__ __launch_bounds__(256) void rn_cast_kernel(Grid g, const View* __rest
           bool gone = false, waiting = false;
 #pragma unroll
           for (int a = 0; a < 3; ++a) {
-            const bool below = ax[a].i < 0, above = ax[a].i >= g.n[a];
+            const bool below = ax[a].i < (a == 2 ? zlo : 0), above = ax[a].i >= (a == 2 ? zhi : g.n[a]);
             gone = gone || (below && ax[a].s <= 0) || (above && ax[a].s >= 0);
             waiting = waiting || below || above;
           }
@@ -240,9 +254,10 @@ __global__ __launch_bounds__(256) void rn_cast_kernel(Grid g, const View* __rest
             float tE = -INFINITY;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-              kE[a] = ax[a].s > 0 ? 0 : g.n[a];
-              m[a] = ax[a].s > 0 ? g.n[a] - ax[a].i : ax[a].i + 1;
-              if (ax[a].i < 0 || ax[a].i >= g.n[a]) {
+              const int lo = a == 2 ? zlo : 0, hi = a == 2 ? zhi : g.n[a];
+              kE[a] = ax[a].s > 0 ? lo : hi;
+              m[a] = ax[a].s > 0 ? g.n[a] - ax[a].i : ax[a].i + 1;  // (every plane ahead: an axis that is not E may be far past its own entry)
+              if (ax[a].i < lo || ax[a].i >= hi) {
                 const float t = cross_t(P, g.off[a], kE[a], ax[a]);
                 if (t >= tE) tE = t, aE = a;  // (ties: the higher axis is the later one)
               }
@@ -277,6 +292,17 @@ __global__ __launch_bounds__(256) void rn_cast_kernel(Grid g, const View* __rest
     if (v.voxel) v.voxel[px] = voxel;
     if (v.axis) v.axis[px] = (uint8_t)axis;
   }
+  if (SLAB) {
+    // the tile's hit bits: byte r of the ballot is row r, bit c of it column c; lanes 0 .. 7 store a row byte each, and
+    // behind the last tile of a row of tiles the lanes 8 j + r clear byte j of what is left of the row's last word
+    const u64 hb = __ballot(in_roi && voxel >= 0);
+    if (v.hits) {
+      const int x0 = blockIdx.x * 16 + (wave & 1) * 8, y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane & 7), j = lane >> 3;
+      const int row_bytes = ((v.w + 63) >> 6) * 8, at = (x0 >> 3) + j;
+      if (x0 < v.w && y < v.h && at < row_bytes && (j == 0 || x0 + 8 >= v.w))
+        v.hits[(int64_t)y * row_bytes + at] = j == 0 ? (uint8_t)(hb >> ((lane & 7) * 8)) : (uint8_t)0;
+    }
+  }
   if (AGREE) {
     const bool mask = in_roi && v.mask[(int64_t)w * v.w + u] != 0;
     const bool hull = voxel >= 0;
@@ -309,6 +335,8 @@ int grow(void** p, size_t* have, size_t want) {
 
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
+size_t hit_bytes(const vcy_view& v) { return (((size_t)v.width + 63) / 64) * 8 * (size_t)v.height; }  // packed hit bits of a view
+
 int cell_planes(const float bb_min[3], const float bb_max[3], float resolution, int axis, int n, float* out) {
   std::vector<float> p((size_t)n);
   { const int rc = vcy_axis_positions(bb_min, bb_max, resolution, axis, p.data()); if (rc != VCY_OK) return rc; }
@@ -326,42 +354,20 @@ int cell_planes(const float bb_min[3], const float bb_max[3], float resolution, 
   return VCY_OK;
 }
 
-int check_render_view(const vcy_view* v, int i) {
-  if (v->width <= 0 || v->height <= 0) {
-    set_error("view %d: invalid image size %d x %d", i, v->width, v->height);
-    return VCY_ERR_INVALID_ARG;
-  }
-  if (v->roi_min[0] < 0 || v->roi_min[1] < 0 || v->roi_max[0] >= v->width || v->roi_max[1] >= v->height ||
-      v->roi_min[0] > v->roi_max[0] || v->roi_min[1] > v->roi_max[1]) {
-    set_error("view %d: ROI [%d,%d]-[%d,%d] outside the %dx%d image", i, v->roi_min[0], v->roi_min[1], v->roi_max[0],
-              v->roi_max[1], v->width, v->height);
-    return VCY_ERR_INVALID_ARG;
-  }
-  for (int k = 0; k < 12; ++k)
-    if (!std::isfinite(v->w2c[k])) {
-      set_error("view %d: w2c is not finite", i);
-      return VCY_ERR_INVALID_ARG;
-    }
-  if (!v->is_ortho && (v->fx == 0.0f || v->fy == 0.0f)) {
-    set_error("view %d: a pinhole view needs fx and fy other than 0", i);
-    return VCY_ERR_INVALID_ARG;
-  }
-  return VCY_OK;
-}
-
 // Bit planes of the current state at `iso`, when the kept ones describe another state.
 int ensure_bits(vcy_ctx* c, double iso) {
   if (c->rn_bits_valid && c->rn_epoch == c->state_epoch && c->rn_iso == iso) return VCY_OK;
   c->rn_bits_valid = false;
   const int Wr = (c->nx + 63) / 64;
-  const int64_t nwords = (int64_t)Wr * c->ny * c->nz;
-  const int nbx = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (c->nz + 7) / 8;
+  const int nzl = c->nz_local();  // (launch_solid_bits covers the owned slices; bricks are counted from z0)
+  const int64_t nwords = (int64_t)Wr * c->ny * nzl;
+  const int nbx = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (nzl + 7) / 8;
   const int64_t nbricks = (int64_t)nbx * nby * nbz, nocc = (nbricks + 63) / 64;
   { const int rc = grow(&c->d_rn_bits, &c->rn_bits_bytes, sizeof(rn::u64) * (size_t)(nwords + nocc)); if (rc != VCY_OK) return rc; }
   rn::u64* bits = (rn::u64*)c->d_rn_bits;
   { const int rc = launch_solid_bits(c, iso, bits); if (rc != VCY_OK) return rc; }
   hipLaunchKernelGGL(rn::rn_occupancy_kernel, dim3((unsigned)((nocc * 64 + 255) / 256)), dim3(256), 0, c->stream, bits, c->ny,
-                     c->nz, Wr, nbx, nby, nbricks, bits + nwords);
+                     nzl, Wr, nbx, nby, nbricks, bits + nwords);
   VCY_HIP_CHECK(hipGetLastError());
   c->rn_bits_valid = true;
   c->rn_epoch = c->state_epoch;
@@ -390,9 +396,11 @@ int ensure_planes(vcy_ctx* c) {
   return VCY_OK;
 }
 
-// vcy_render_hull (masks == null) and vcy_hull_agreement (masks, counts) behind their argument checks
+// vcy_render_hull (masks == null), vcy_hull_agreement (masks, counts) and vcy_render_hull_slab (slab: any context, hit
+// bits) behind their argument checks
 int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* const* depth, int64_t* const* voxel,
-           uint8_t* const* axis, const uint8_t* const* masks, int64_t* counts, const char* who) {
+           uint8_t* const* axis, const uint8_t* const* masks, int64_t* counts, const char* who, bool slab = false,
+           uint64_t* const* hits = nullptr) {
   if (n_views <= 0 || !views || (masks && !counts)) {
     set_error("%s: invalid argument", who);
     return VCY_ERR_INVALID_ARG;
@@ -409,8 +417,8 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
     set_error("voxel grid has not been initialized");
     return VCY_ERR_NOT_INITIALIZED;
   }
-  if (!(c->z0 == 0 && c->z1 == c->nz && c->halo_lo == 0)) {
-    // merging slabs by minimum depth needs a tie rule of its own
+  if (!slab && !(c->z0 == 0 && c->z1 == c->nz && c->halo_lo == 0)) {
+    // (the slabs' images are merged by vcy_render_merge_host; these two entry points keep to the whole grid)
     set_error("%s: the context owns z [%d, %d) of %d slices; the ray-cast needs the whole grid in one context", who, c->z0,
               c->z1, c->nz);
     return VCY_ERR_UNSUPPORTED;
@@ -429,6 +437,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
   g.Wr = (c->nx + 63) / 64;
   g.nbx = (c->nx + 7) / 8, g.nby = (c->ny + 7) / 8;
   g.empty = c->fresh ? 1 : 0;  // nothing carved since the fill: no voxel is solid, and the lazy fill stays lazy
+  g.z0 = c->z0, g.z1 = c->z1;
   g.planes = c->d_rn_planes;
   const bool lds = g.total <= rn::kLdsPlanes;
   const bool skip = c->ray_skip != 0;
@@ -439,7 +448,8 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
     const int m = std::min(rn::kMaxViewsPerLaunch, n_views - first);
     // [view records | counters | per view: depth, voxel ids, axes, silhouette]
     std::vector<rn::View> rec((size_t)m);
-    std::vector<size_t> at_depth((size_t)m, 0), at_voxel((size_t)m, 0), at_axis((size_t)m, 0), at_mask((size_t)m, 0);
+    std::vector<size_t> at_depth((size_t)m, 0), at_voxel((size_t)m, 0), at_axis((size_t)m, 0), at_mask((size_t)m, 0),
+        at_hits((size_t)m, 0);
     size_t bytes = align16(sizeof(rn::View) * (size_t)m);
     const size_t at_counts = bytes;
     bytes += align16(sizeof(rn::u64) * 3 * (size_t)m);
@@ -451,6 +461,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
       if (voxel && voxel[first + i]) at_voxel[(size_t)i] = bytes, bytes += align16(px * sizeof(int64_t));
       if (axis && axis[first + i]) at_axis[(size_t)i] = bytes, bytes += align16(px);
       if (masks) at_mask[(size_t)i] = bytes, bytes += align16(px);
+      if (hits && hits[first + i]) at_hits[(size_t)i] = bytes, bytes += align16(hit_bytes(v));
       wmax = std::max(wmax, v.width), hmax = std::max(hmax, v.height);
     }
     { const int rc = grow(&c->d_rn_out, &c->rn_out_bytes, bytes); if (rc != VCY_OK) return rc; }
@@ -469,6 +480,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
       r.voxel = at_voxel[(size_t)i] ? (long long*)(base + at_voxel[(size_t)i]) : nullptr;
       r.axis = at_axis[(size_t)i] ? (uint8_t*)(base + at_axis[(size_t)i]) : nullptr;
       r.mask = masks ? (const uint8_t*)(base + at_mask[(size_t)i]) : nullptr;
+      r.hits = at_hits[(size_t)i] ? (uint8_t*)(base + at_hits[(size_t)i]) : nullptr;
       if (masks)
         VCY_HIP_CHECK(hipMemcpyAsync(base + at_mask[(size_t)i], masks[first + i], (size_t)v.width * (size_t)v.height,
                                      hipMemcpyHostToDevice, c->stream));
@@ -482,14 +494,19 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
       const int rc = ensure_bits(c, iso);
       if (rc != VCY_OK) return rc;
       g.bits = (const rn::u64*)c->d_rn_bits;
-      g.occ = g.bits + (int64_t)g.Wr * c->ny * c->nz;
+      g.occ = g.bits + (int64_t)g.Wr * c->ny * c->nz_local();
     }
     const dim3 grid((unsigned)((wmax + 15) / 16), (unsigned)((hmax + 15) / 16), (unsigned)m);
     const size_t shmem = lds ? sizeof(float) * (size_t)g.total : 0;
     const rn::View* d_views = (const rn::View*)base;
 #define VCY_RN_CAST(L, S, A) \
-  hipLaunchKernelGGL((rn::rn_cast_kernel<L, S, A>), grid, dim3(256), shmem, c->stream, g, d_views, d_counts)
-    if (masks) {
+  hipLaunchKernelGGL((rn::rn_cast_kernel<L, S, A, false>), grid, dim3(256), shmem, c->stream, g, d_views, d_counts)
+#define VCY_RN_CAST_SLAB(L, S) \
+  hipLaunchKernelGGL((rn::rn_cast_kernel<L, S, false, true>), grid, dim3(256), shmem, c->stream, g, d_views, d_counts)
+    if (slab) {
+      if (lds) { if (skip) VCY_RN_CAST_SLAB(true, true); else VCY_RN_CAST_SLAB(true, false); }
+      else { if (skip) VCY_RN_CAST_SLAB(false, true); else VCY_RN_CAST_SLAB(false, false); }
+    } else if (masks) {
       if (lds) { if (skip) VCY_RN_CAST(true, true, true); else VCY_RN_CAST(true, false, true); }
       else { if (skip) VCY_RN_CAST(false, true, true); else VCY_RN_CAST(false, false, true); }
     } else {
@@ -497,6 +514,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
       else { if (skip) VCY_RN_CAST(false, true, false); else VCY_RN_CAST(false, false, false); }
     }
 #undef VCY_RN_CAST
+#undef VCY_RN_CAST_SLAB
     VCY_HIP_CHECK(hipGetLastError());
     VCY_HIP_CHECK(hipEventRecord(c->ev_rn_end, c->stream));
 
@@ -509,6 +527,8 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
         VCY_HIP_CHECK(hipMemcpyAsync(voxel[first + i], base + at_voxel[(size_t)i], px * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
       if (at_axis[(size_t)i])
         VCY_HIP_CHECK(hipMemcpyAsync(axis[first + i], base + at_axis[(size_t)i], px, hipMemcpyDeviceToHost, c->stream));
+      if (at_hits[(size_t)i])
+        VCY_HIP_CHECK(hipMemcpyAsync(hits[first + i], base + at_hits[(size_t)i], hit_bytes(v), hipMemcpyDeviceToHost, c->stream));
     }
     if (masks)
       VCY_HIP_CHECK(hipMemcpyAsync(counts + 3 * (size_t)first, d_counts, sizeof(rn::u64) * 3 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
@@ -563,6 +583,12 @@ int vcy_cell_planes(const float bb_min[3], const float bb_max[3], float resoluti
 int vcy_render_hull(vcy_ctx* c, double iso_level, int n_views, const vcy_view* views, float* const* depth_host,
                     int64_t* const* voxel_host, uint8_t* const* axis_host) {
   return render(c, iso_level, n_views, views, depth_host, voxel_host, axis_host, nullptr, nullptr, "vcy_render_hull");
+}
+
+int vcy_render_hull_slab(vcy_ctx* c, double iso_level, int n_views, const vcy_view* views, float* const* depth_host,
+                         int64_t* const* voxel_host, uint8_t* const* axis_host, uint64_t* const* hits_host) {
+  return render(c, iso_level, n_views, views, depth_host, voxel_host, axis_host, nullptr, nullptr, "vcy_render_hull_slab", true,
+                hits_host);
 }
 
 int vcy_hull_agreement(vcy_ctx* c, double iso_level, int n_views, const vcy_view* views, const uint8_t* const* masks_host,

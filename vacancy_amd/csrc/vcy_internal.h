@@ -271,8 +271,10 @@ int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int 
 // the solid bit of every voxel of the owned slices in 64-voxel words along x, (nx + 63) / 64 words per row (cc_bits_kernel);
 // the state must be materialised.  Shared by the labelling and the ray-cast (render.hip).
 int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
-// render.hip: vcy_render_hull, vcy_hull_agreement, vcy_cell_planes, vcy_last_render_ms
+// render.hip: vcy_render_hull, vcy_hull_agreement, vcy_render_hull_slab, vcy_cell_planes, vcy_last_render_ms
 void render_release(vcy_ctx* ctx);  // frees what the ray-cast keeps on the context (vcy_destroy)
+// render_merge.hip (host code only): vcy_render_merge_host, vcy_hull_agreement_host, and the view checks of the ray-cast
+int check_render_view(const vcy_view* v, int i);
 // sdf2d.hip
 void host_distance_transform_l1(const uint8_t* mask, int w, int h, const int32_t* rmin,
                                 const int32_t* rmax, float* out);

@@ -417,3 +417,71 @@ def keep_components_slabs(carvers, rank=0, world=1, iso_level=0.0, largest=1, mi
     ms = each(carvers, drop)
     return {"removed_components": int((~keep).sum()), "removed_voxels": int(merged["n_voxels"][~keep].sum()),
             "device_ms": r["device_ms"] + float(sum(ms))}
+
+
+# ---- ray-cast of the hull of a grid in z-slabs (the slab image and the merge rule: include/vacancy_hip.h) -----------
+
+def _as_views(views):
+    from .capi import View
+    single = isinstance(views, View)
+    return single, ([views] if single else list(views))
+
+
+def render_hull_slabs(carvers, rank=0, world=1, views=(), iso_level=0.0, voxel_ids=False, axes=False, each=_each,
+                      render=None):
+    """RenderHull of a grid cut into z-slabs.  `carvers` as for label_components_slabs.  Every slab renders its own
+    image of every view on its device (RenderHullSlab; no halo exchange), the images -- depth, voxel ids and, with
+    axes=True, entry axes -- are gathered as Python objects, and rank 0 merges them on the host by the rule of
+    vcy_render_merge_host.  Returns what VoxelCarver.RenderHull returns (plus "device_ms" per view list: the sum over
+    this rank's slabs) on rank 0, None elsewhere.  `render(i, carver, views)` replaces the slab's render (tests)."""
+    from . import carver as _vc
+    single, vs = _as_views(views)
+    k = len(carvers)
+    ids = [rank + i * world for i in range(k)]
+    ms = [0.0] * k
+
+    def cast(i, c):
+        if render is not None:
+            return render(i, c, vs)
+        parts = c.RenderHullSlab(vs, iso_level, voxel_ids=True, axes=axes)
+        ms[i] = c.last_render_ms()
+        return parts
+
+    images = _gather_by_slab(dict(zip(ids, each(carvers, cast))), world)
+    if rank != 0:
+        return None
+    out = []
+    for j, v in enumerate(vs):
+        m = _vc.render_merge_host(v, [images[s][j] for s in range(world * k)])
+        if not voxel_ids:
+            del m["voxel"]
+        if not axes:
+            m.pop("axis", None)
+        m["device_ms"] = float(sum(ms))
+        out.append(m)
+    return out[0] if single else out
+
+
+def hull_agreement_slabs(carvers, rank=0, world=1, views=(), masks=(), iso_level=0.0, each=_each, render=None):
+    """HullAgreement of a grid cut into z-slabs: every slab renders its packed hit bits (one bit per pixel crosses to
+    the host, no image), they are gathered, and rank 0 ORs them and counts against the silhouettes
+    (vcy_hull_agreement_host).  int64 [n_views, 3] as VoxelCarver.HullAgreement on rank 0, None elsewhere."""
+    from . import carver as _vc
+    vs = list(views)
+    ms = list(masks)
+    if len(ms) != len(vs):
+        raise ValueError("one height x width silhouette per view")
+    k = len(carvers)
+    ids = [rank + i * world for i in range(k)]
+
+    def cast(i, c):
+        parts = render(i, c, vs) if render is not None else c.RenderHullSlab(vs, iso_level, hits=True)
+        return [p["hits"] for p in parts]
+
+    bits = _gather_by_slab(dict(zip(ids, each(carvers, cast))), world)
+    if rank != 0:
+        return None
+    counts = np.zeros((len(vs), 3), np.int64)
+    for j, (v, m) in enumerate(zip(vs, ms)):
+        counts[j] = _vc.hull_agreement_host(v, [bits[s][j] for s in range(world * k)], m)
+    return counts

@@ -252,6 +252,56 @@ int main(int argc, char* argv[]) {
                 same_lists(a2, b2) ? 1 : 0, same ? 1 : 0);
     return 0;
   }
+  if (argc > 4 && std::string(argv[2]) == "slabrender") {
+    // needs a device: ShardedVoxelCarver::RenderHullSlabs / HullAgreementSlabs after the six bunny views, next to a single
+    // VoxelCarver's RenderHull / HullAgreement.   host_selftest <data dir> slabrender <resolution> <slabs on device 0>
+    //   prints SLABRENDER <slabs> <depth bytes equal> <silhouette equal> <counts equal>
+    vacancy::VoxelCarverOption option;
+    option.bb_min = Eigen::Vector3f(-250.000000f, -344.586151f, -129.982697f);
+    option.bb_max = Eigen::Vector3f(250.000000f, 150.542343f, 257.329224f);
+    for (int i = 0; i < 3; ++i) {  // (examples.cc:91-99)
+      option.bb_min[i] -= 20.0f;
+      option.bb_max[i] += 20.0f;
+    }
+    option.resolution = (float)std::atof(argv[3]);
+    vacancy::VoxelCarver one(option);
+    vacancy::ShardedVoxelCarver sh(option, {0}, std::atoi(argv[4]));
+    if (!one.Init() || !sh.Init()) return 6;
+    std::FILE* fp = std::fopen((dir + "/tumpose.txt").c_str(), "r");
+    if (!fp) return 9;
+    int id;
+    double t[3], q[4];
+    std::vector<vacancy::PinholeCamera> cams;
+    std::vector<vacancy::Image1b> sils;
+    for (size_t i = 0; i < 6 && std::fscanf(fp, "%d %lf %lf %lf %lf %lf %lf %lf", &id, &t[0], &t[1], &t[2], &q[0], &q[1], &q[2], &q[3]) == 8; ++i) {
+      Eigen::Translation3d tr;
+      tr.x() = t[0]; tr.y() = t[1]; tr.z() = t[2];
+      Eigen::Quaterniond qu;
+      qu.x() = q[0]; qu.y() = q[1]; qu.z() = q[2]; qu.w() = q[3];
+      cams.emplace_back(320, 240, tr * qu, Eigen::Vector2f(159.3f, 127.65f), Eigen::Vector2f(258.65f, 258.25f));
+      vacancy::Image1b sil;
+      if (!sil.Load(dir + "/mask_" + vacancy::zfill(i) + ".png")) return 4;
+      if (!one.Carve(cams.back(), sil) || !sh.Carve(cams.back(), sil)) return 7;
+      sils.push_back(sil);
+    }
+    std::fclose(fp);
+    bool depth_same = !cams.empty(), sil_same = !cams.empty(), counts_same = !cams.empty();
+    for (size_t i = 0; i < cams.size(); ++i) {
+      vacancy::Image1f da, db;
+      vacancy::Image1b ha, hb;
+      if (!one.RenderHull(cams[i], &da, &ha) || !sh.RenderHullSlabs(cams[i], &db, &hb)) return 10;
+      depth_same = depth_same && da.data().size() == db.data().size() &&
+                   std::memcmp(da.data().data(), db.data().data(), sizeof(float) * da.data().size()) == 0;
+      sil_same = sil_same && ha.data() == hb.data();
+      std::vector<std::array<std::int64_t, 3>> ca, cb;
+      const std::vector<const vacancy::Camera*> ptr{&cams[i]};
+      const std::vector<vacancy::Image1b> s1{sils[i]};
+      if (!one.HullAgreement(ptr, s1, &ca) || !sh.HullAgreementSlabs(ptr, s1, &cb)) return 11;
+      counts_same = counts_same && ca == cb && ca.size() == 1 && ca[0][0] > 0;
+    }
+    std::printf("SLABRENDER %d %d %d %d\n", sh.slab_count(), depth_same ? 1 : 0, sil_same ? 1 : 0, counts_same ? 1 : 0);
+    return 0;
+  }
   if (argc > 4 && std::string(argv[2]) == "shardrender") {
     // needs a device: the ray-cast of the hull needs the whole grid in one context, so ShardedVoxelCarver::RenderHull /
     // HullAgreement refuse, and VoxelCarver's own refuse bad arguments -- each with false and a logged error.

@@ -363,6 +363,110 @@ bool ShardedVoxelCarver::HullAgreement(const std::vector<Camera>&, const std::ve
   return false;
 }
 
+// The ray-cast over the slabs (include/vacancy_hip.h, "... of a grid cut into z-slabs"): every slab renders the image of
+// its own slices on its device -- no halo exchange --, the depth and voxel-id images come to the host, and
+// vcy_render_merge_host takes, per pixel, the hit of the first slab in the ray's direction of travel along z.
+bool ShardedVoxelCarver::RenderHullSlabs(const Camera& camera, Image1f* depth, Image1b* silhouette, double iso_level) {
+  const size_t ns = impl_->slabs.size();
+  if (ns == 0) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  const int w = camera.width(), h = camera.height();
+  bool known = true;
+  const vcy_view v = MakeView(camera, w, h, &known);
+  if (!known) return false;  // (MakeView has logged the camera type)
+  if (!depth || w <= 0 || h <= 0) {
+    LOGE("ShardedVoxelCarver::RenderHullSlabs needs a depth image to fill and a camera with a size (%d x %d)\n", w, h);
+    return false;
+  }
+  const size_t px = static_cast<size_t>(w) * static_cast<size_t>(h);
+  std::vector<std::vector<float>> depths(ns, std::vector<float>(px));
+  std::vector<std::vector<int64_t>> voxels(ns, std::vector<int64_t>(px));
+  if (!ForEachSlab(ns, "RenderHullSlabs", [&](size_t s) {
+        float* dp = depths[s].data();
+        int64_t* vp = voxels[s].data();
+        return vcy_render_hull_slab(impl_->slabs[s], iso_level, 1, &v, &dp, &vp, nullptr, nullptr);
+      }))
+    return false;
+  std::vector<const float*> dps(ns);
+  std::vector<const int64_t*> vps(ns);
+  for (size_t s = 0; s < ns; ++s) dps[s] = depths[s].data(), vps[s] = voxels[s].data();
+  depth->Init(w, h);
+  float* out = depth->data_ptr()->data();
+  if (vcy_render_merge_host(&v, static_cast<int>(ns), dps.data(), vps.data(), nullptr, out, nullptr, nullptr) != VCY_OK) {
+    LOGE("sharded RenderHullSlabs failed: %s\n", vcy_last_error());
+    return false;
+  }
+  if (silhouette) {
+    silhouette->Init(w, h);
+    std::vector<unsigned char>& sil = *silhouette->data_ptr();
+    for (size_t i = 0; i < sil.size(); ++i) sil[i] = out[i] < std::numeric_limits<float>::infinity() ? 255 : 0;
+  }
+  return true;
+}
+
+// ... and the comparison with the silhouettes: one hit bit per pixel and slab comes to the host, which ORs and counts
+// (vcy_hull_agreement_host).
+bool ShardedVoxelCarver::HullAgreementSlabs(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
+                                            std::vector<std::array<std::int64_t, 3>>* counts, double iso_level) {
+  std::vector<const Camera*> ptrs(cameras.size());
+  for (size_t i = 0; i < cameras.size(); ++i) ptrs[i] = &cameras[i];
+  return HullAgreementSlabs(ptrs, silhouettes, counts, iso_level);
+}
+
+bool ShardedVoxelCarver::HullAgreementSlabs(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
+                                            std::vector<std::array<std::int64_t, 3>>* counts, double iso_level) {
+  const size_t ns = impl_->slabs.size();
+  if (ns == 0) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (!counts || cameras.size() != silhouettes.size() || cameras.empty()) {
+    LOGE("ShardedVoxelCarver::HullAgreementSlabs needs one silhouette per camera, at least one, and a place for the counts "
+         "(%zu cameras, %zu silhouettes)\n", cameras.size(), silhouettes.size());
+    return false;
+  }
+  const int n = static_cast<int>(cameras.size());
+  std::vector<vcy_view> views(static_cast<size_t>(n));
+  std::vector<size_t> words(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    const Image1b& sil = silhouettes[static_cast<size_t>(i)];
+    bool known = true;
+    if (!cameras[static_cast<size_t>(i)] || sil.empty()) {
+      LOGE("ShardedVoxelCarver::HullAgreementSlabs: view %d has no camera or an empty silhouette\n", i);
+      return false;
+    }
+    views[static_cast<size_t>(i)] = MakeView(*cameras[static_cast<size_t>(i)], sil.width(), sil.height(), &known);
+    if (!known) return false;  // (MakeView has logged the camera type)
+    words[static_cast<size_t>(i)] = (static_cast<size_t>(sil.width()) + 63) / 64 * static_cast<size_t>(sil.height());
+  }
+  std::vector<std::vector<std::vector<uint64_t>>> hits(ns);  // [slab][view]
+  if (!ForEachSlab(ns, "HullAgreementSlabs", [&](size_t s) {
+        hits[s].resize(static_cast<size_t>(n));
+        std::vector<uint64_t*> ptrs(static_cast<size_t>(n));
+        for (int i = 0; i < n; ++i) {
+          hits[s][static_cast<size_t>(i)].resize(words[static_cast<size_t>(i)]);
+          ptrs[static_cast<size_t>(i)] = hits[s][static_cast<size_t>(i)].data();
+        }
+        return vcy_render_hull_slab(impl_->slabs[s], iso_level, n, views.data(), nullptr, nullptr, nullptr, ptrs.data());
+      }))
+    return false;
+  counts->assign(static_cast<size_t>(n), std::array<std::int64_t, 3>{{0, 0, 0}});
+  for (int i = 0; i < n; ++i) {
+    std::vector<const uint64_t*> of_view(ns);
+    for (size_t s = 0; s < ns; ++s) of_view[s] = hits[s][static_cast<size_t>(i)].data();
+    int64_t c[3] = {0, 0, 0};
+    if (vcy_hull_agreement_host(&views[static_cast<size_t>(i)], static_cast<int>(ns), of_view.data(),
+                                silhouettes[static_cast<size_t>(i)].data().data(), c) != VCY_OK) {
+      LOGE("sharded HullAgreementSlabs failed: %s\n", vcy_last_error());
+      return false;
+    }
+    (*counts)[static_cast<size_t>(i)] = {{c[0], c[1], c[2]}};
+  }
+  return true;
+}
+
 bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!std::isfinite(fill_sdf) || !(static_cast<double>(fill_sdf) >= iso_level)) {
     LOGE("KeepLargestComponents: fill_sdf %g must be finite and not below the iso level %g\n", static_cast<double>(fill_sdf),

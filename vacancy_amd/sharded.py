@@ -301,3 +301,14 @@ class ShardedVoxelCarver:
         current per slab).  The halos go stale, as after a carve; extract_slabs and ExtractVoxel exchange them first."""
         return vdist.keep_components_slabs(self.slabs, 0, 1, iso_level, largest, min_voxels, fill_sdf,
                                            each=self._each_slab)
+
+    # -- the ray-cast of the hull over the slabs (include/vacancy_hip.h): every slab renders its own slices on its device
+    # -- no halo exchange --, depth images (or, for the agreement, one hit bit per pixel) go through the host, which
+    # merges them by the rule of vcy_render_merge_host: exactly what VoxelCarver returns on the whole grid
+    def RenderHull(self, views, iso_level=0.0, voxel_ids=False, axes=False):
+        """VoxelCarver.RenderHull of the whole grid: the same dicts, plus "device_ms" (the sum over the slabs)."""
+        return vdist.render_hull_slabs(self.slabs, 0, 1, views, iso_level, voxel_ids, axes, each=self._each_slab)
+
+    def HullAgreement(self, views, masks, iso_level=0.0):
+        """VoxelCarver.HullAgreement of the whole grid, from the slabs' packed hit bits."""
+        return vdist.hull_agreement_slabs(self.slabs, 0, 1, views, masks, iso_level, each=self._each_slab)
