@@ -335,14 +335,11 @@ int prepare_views(vcy_ctx* c, int n_views, const ViewParams* vp, bool need_bound
     }
   }
   // staging buffer owned by the context, grown on demand
-  if (c->fused_scratch_bytes < c2_bytes + fv_bytes) {
-    VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->d_fused_scratch) VCY_HIP_CHECK(hipFree(c->d_fused_scratch));
-    c->d_fused_scratch = nullptr;
-    c->fused_scratch_bytes = 0;
-    c->fused_cache_valid = false;
-    VCY_HIP_CHECK(hipMalloc(&c->d_fused_scratch, c2_bytes + fv_bytes));
-    c->fused_scratch_bytes = c2_bytes + fv_bytes;
+  {
+    const size_t had = c->fused_scratch_bytes;
+    const int rcg = grow_device(&c->d_fused_scratch, &c->fused_scratch_bytes, c2_bytes + fv_bytes, c->stream);
+    if (rcg != VCY_OK || c->fused_scratch_bytes != had) c->fused_cache_valid = false;  // (the buffer moved)
+    if (rcg != VCY_OK) return rcg;
   }
   float* d_c2 = (float*)c->d_fused_scratch;
   FusedView* d_views = (FusedView*)((char*)c->d_fused_scratch + c2_bytes);
@@ -614,14 +611,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
     const int64_t cap = rec_cap;
     chunk_layers = (int)std::max<int64_t>(1, std::min<int64_t>(nbz, cap / std::max<int64_t>(per_layer, 1)));
     const size_t need = (size_t)(per_layer * chunk_layers);
-    if (c->records_bytes < need) {
-      VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-      if (c->d_records) (void)hipFree(c->d_records);
-      c->d_records = nullptr;
-      c->records_bytes = 0;
-      VCY_HIP_CHECK(hipMalloc(&c->d_records, need));
-      c->records_bytes = need;
-    }
+    { const int rcg = grow_device(&c->d_records, &c->records_bytes, need, c->stream); if (rcg != VCY_OK) return rcg; }
   }
   if (c->count_pairs) {  // "paircount" 1: one counter per brick layer of the slab, cleared by every launch
     if (c->pair_count_layers < nbz) {
@@ -690,14 +680,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
       list_entry_words = one_view && c->list_records != 0 ? kLiveEntryWords : 0;
       const size_t need = list_entry_words ? sizeof(int) * (2 + (size_t)nwg * kLiveEntryWords) : sizeof(int) * ((size_t)nwg + 1);  // (the hint below: a race with its copy is benign, it only
       // decides whether the NEXT launch lists its workgroups; with several chunks it reflects the last one)
-      if (c->wg_list_bytes < need) {
-        VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->d_wg_list) (void)hipFree(c->d_wg_list);
-        c->d_wg_list = nullptr;
-        c->wg_list_bytes = 0;
-        VCY_HIP_CHECK(hipMalloc(&c->d_wg_list, need));
-        c->wg_list_bytes = need;
-      }
+      { const int rcg = grow_device((void**)&c->d_wg_list, &c->wg_list_bytes, need, c->stream); if (rcg != VCY_OK) return rcg; }
       VCY_HIP_CHECK(hipMemsetAsync(c->d_wg_list, 0, sizeof(int), c->stream));
       hipLaunchKernelGGL(live_workgroups_kernel, dim3((unsigned)((nwg + kLiveThreads - 1) / kLiveThreads)), dim3(kLiveThreads), 0, c->stream, recs, nbricks,
                          n_views, have_min ? bmin : nullptr, m.trunc, units_x, nby, nbw, nwg, c->d_wg_list, unit_bricks,

@@ -365,16 +365,6 @@ using cc::Stats;
 
 namespace {
 
-int grow(void** p, size_t* have, size_t want) {
-  if (*have >= want) return VCY_OK;
-  if (*p) VCY_HIP_CHECK(hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  VCY_HIP_CHECK(hipMalloc(p, want));
-  *have = want;
-  return VCY_OK;
-}
-
 bool whole_grid(const vcy_ctx* c) { return c->z0 == 0 && c->z1 == c->nz && c->halo_lo == 0; }
 
 }  // namespace
@@ -426,10 +416,10 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
   }
   const int nx = c->nx, ny = c->ny, Wr = (nx + 63) / 64;
   const int64_t nwords = (int64_t)Wr * ny * c->nz_local();
-  { const int rc = grow(&c->d_cc_labels, &c->cc_labels_bytes, sizeof(int) * (size_t)n); if (rc != VCY_OK) return rc; }
-  { const int rc = grow(&c->d_cc_bits, &c->cc_bits_bytes, sizeof(cc::u64) * (size_t)nwords + 64); if (rc != VCY_OK) return rc; }
+  { const int rc = grow_device(&c->d_cc_labels, &c->cc_labels_bytes, sizeof(int) * (size_t)n, c->stream, false); if (rc != VCY_OK) return rc; }
+  { const int rc = grow_device(&c->d_cc_bits, &c->cc_bits_bytes, sizeof(cc::u64) * (size_t)nwords + 64, c->stream, false); if (rc != VCY_OK) return rc; }
   if (c->cc_roots_cap == 0) {
-    const int rc = grow(&c->d_cc_roots, &c->cc_roots_bytes, (size_t)(1 << 16) * (sizeof(int) + sizeof(Stats) + 1));
+    const int rc = grow_device(&c->d_cc_roots, &c->cc_roots_bytes, (size_t)(1 << 16) * (sizeof(int) + sizeof(Stats) + 1), c->stream, false);
     if (rc != VCY_OK) return rc;
     c->cc_roots_cap = 1 << 16;
   }
@@ -462,7 +452,7 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
   c->cc_labels_empty = false;
   if (n_roots == 0) return VCY_OK;
   if (n_roots > c->cc_roots_cap) {  // (thousands of specks: the list did not fit; once more into a larger one)
-    const int rc = grow(&c->d_cc_roots, &c->cc_roots_bytes, (size_t)n_roots * (sizeof(int) + sizeof(Stats) + 1));
+    const int rc = grow_device(&c->d_cc_roots, &c->cc_roots_bytes, (size_t)n_roots * (sizeof(int) + sizeof(Stats) + 1), c->stream, false);
     if (rc != VCY_OK) {
       c->cc_roots_cap = 0;
       return rc;
@@ -799,7 +789,7 @@ int vcy_component_seam_pairs(vcy_ctx* c, const int64_t* below_plane_labels, int6
   std::vector<int64_t> pairs;
   unsigned int* h_report = (unsigned int*)c->h_cc_report;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    { const int rc = grow(&c->d_cc_seam, &c->cc_seam_bytes, plane_bytes + 64 + 2 * sizeof(int64_t) * cap); if (rc != VCY_OK) return rc; }
+    { const int rc = grow_device(&c->d_cc_seam, &c->cc_seam_bytes, plane_bytes + 64 + 2 * sizeof(int64_t) * cap, c->stream, false); if (rc != VCY_OK) return rc; }
     int64_t* d_below = (int64_t*)c->d_cc_seam;
     unsigned int* d_n = (unsigned int*)((char*)c->d_cc_seam + plane_bytes);
     int64_t* d_pairs = (int64_t*)((char*)c->d_cc_seam + plane_bytes + 64);

@@ -1,5 +1,6 @@
-// What the marching-cubes translation units share (mc_kernels.hip: the extraction chain; mc_normals.hip: the
-// normals behind it): the cell-word layout, the case tables' shape, VertexInterp and the block scan.  Everything
+// What the marching-cubes translation units share (mc_kernels.hip: the kernels of the extraction chain and their
+// launches; mc_normals.hip: the normals behind it; mc_extract.hip: the host driver of both): the cell-word layout,
+// the case tables' shape, VertexInterp, the block scan, and the launch structs the driver fills.  The device code
 // here has internal linkage or is inline, so each translation unit gets its own copy and no relocatable device
 // code is needed.
 #pragma once
@@ -8,6 +9,7 @@
 
 #include <cstdint>
 
+struct vcy_ctx;
 namespace vcy {
 namespace mc {
 
@@ -159,6 +161,66 @@ __device__ __forceinline__ void vertex_interp(double iso, const float pa[3], con
 #pragma unroll
   for (int k = 0; k < 3; ++k) out[k] = (float)((double)pa[k] + mu * ((double)pb[k] - (double)pa[k]));
 }
+
+// ---- mc_kernels.hip: the launches of the extraction chain, in the order the driver enqueues them ----------------
+// Every pointer is device memory unless said otherwise.  Each launch returns VCY_OK or a VCY_ERR_* with the error set.
+void build_tables(McTables* t);  // (host) the case tables the kernels read
+
+// mc_sweep_kernel's geometry (see the kernel), planned by the driver because it shapes the cell-word arrays (Yc)
+struct SweepParams {
+  int R;           // cell rows per workgroup
+  int K;           // 256-word blocks per step = R * Wr / 256
+  int groups;      // row groups per layer = Yc / R
+  int layers;      // cell layers per workgroup
+  int dl;          // cells whose max corner lies in stored slice s form layer li = s + dl
+  int cnt_slices;  // READS_CNT: update_num is read for the stored slices below this one (all of them)
+  int wshift;      // log2 Wr
+};
+constexpr int kSweepMaxK = 4;
+#ifndef VCY_SWEEP_TARGET_WGS
+#define VCY_SWEEP_TARGET_WGS 1024
+#endif
+
+// What a chained scan needs from its caller: the publication flags of ONE scan slot (kChainedScanMaxChunks words), the
+// slot's ticket counter and how many tickets have been drawn from it so far (advanced by the launch).
+constexpr int kChainedScanMaxChunks = 1024;
+struct ChainedScanSlot {
+  uint32_t* flags;
+  uint32_t* ticket;
+  uint32_t* tickets_drawn;  // (host)
+  uint32_t epoch;
+};
+
+// What the three launches take.  launch_cell_search: the bit planes (mc_bits_kernel, or mc_bits_bricks_kernel over the
+// owned slices when the context's brick minima allow) and mc_active_kernel -- or, with `sweep`, mc_sweep_kernel alone -- then the scan
+// of the per-block cell counts; it sets p->in / ok / tc to the planes the later passes read (a whole grid whose state
+// implies TC == OK gets no third plane: p->tc == p->ok).  launch_owners: mc_compact, mc_owner and the scan of their
+// per-block counts.  launch_emit: mc_emit.  The kernels behind the search read the number of cells and the totals from
+// device memory and stay inside the three capacities.
+struct ChainLaunch {
+  const McTables* T;
+  const SweepParams* sweep;                    // null: bit planes in memory
+  u64 *in, *ok, *tc, *ghost;                   // planes [slice][y][Wr]; the sweep: `in` and IN / OK / TC of one slice in `ghost`
+  u64* act;                                    // [nwords]
+  uint32_t* word_cell_off;                     // [nwords]
+  u64* block_cells;                            // [nblocks + 1] per block of kWordsPerBlock cell words, scanned in place
+  unsigned nblocks;
+  u64 *scan_scratch, *ncells_dev;              // ncells_dev receives the number of active cells
+  int64_t cap_cells, cap_verts, cap_faces;     // (the last two: mc_emit only, like verts .. report)
+  unsigned cell_blocks;                        // blocks of 256 list entries = (cap_cells + 255) / 256
+  u64* cell_list;                              // the three below: [cap_cells]
+  uint32_t* info;
+  uint16_t* nbr_active;
+  u64* block_offs;                             // [cell_blocks + 1] (vertices << 32 | triangles), scanned in place
+  u64 *cell_scan_scratch, *grand_total_dev;
+  float* verts;                                // verts / keys / faces: device staging, or page-locked HOST arrays (the
+  long long* keys;                             // direct path); keys may be null
+  int* faces;
+  u64* report;  // 64 page-locked host bytes: cells, ghost cells, (vertices << 32 | triangles), foreign vertices
+};
+int launch_cell_search(const vcy_ctx* c, McParams* p, const ChainLaunch& a, const ChainedScanSlot& slot);  // on c->stream
+int launch_owners(hipStream_t stream, const McParams& p, const ChainLaunch& a, const ChainedScanSlot& slot);
+int launch_emit(hipStream_t stream, const McParams& p, const ChainLaunch& a);
 
 // mc_normals.hip: Mesh::CalcFaceNormal + Mesh::CalcNormal (reference mesh.cc:197-240) of the mesh mc_emit has just
 // been enqueued for, behind it on the same stream.  Every pointer is device memory; `verts` / `faces` are the DEVICE

@@ -1,4 +1,6 @@
-// K2-K4: marching cubes on the device slab, reproducing the reference's serial scan.
+// K2-K4: marching cubes on the device slab, reproducing the reference's serial scan.  This file holds the kernels and,
+// at its end, the launches the host driver (extract_iso, mc_extract.hip) calls: launch_cell_search, launch_owners,
+// launch_emit (declared in mc_common.h) -- which kernel instance a pass takes is decided there, next to the kernels.
 //
 // Replaces MarchingCubes() (reference src/vacancy/marching_cubes.cc:63-228).  The reference
 // walks cells z,y,x from 1, deduplicates vertices with a std::map keyed by the voxel-id pair
@@ -30,12 +32,9 @@
 //
 // Memory-bound, no MFMA: 4 B (sdf) per cell algorithmic; real traffic = one read of sdf +
 // update_num, everything else is 1 bit per voxel/cell, plus 12 B per vertex/triangle out.
-#include <chrono>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <utility>
-#include <vector>
 
 #include "mc_common.h"
 #include "vcy_internal.h"
@@ -52,28 +51,6 @@ const char* const kCaseStrings[256] = {
 #include "vacancy_mc_cases.inc"
 };
 
-
-void build_tables(McTables* t) {
-  std::memset(t, 0, sizeof(*t));
-  for (int c = 0; c < 256; ++c) {
-    const char* s = kCaseStrings[c];
-    int n = 0;
-    for (; s[n]; ++n) t->tri[c][n] = (int8_t)((s[n] <= '9') ? s[n] - '0' : s[n] - 'a' + 10);
-    for (int k = n; k < 16; ++k) t->tri[c][k] = -1;
-    t->ntri[c] = (uint8_t)(n / 3);
-    // creation order: triangles in table order, corners j=0..2 read entry i+(2-j)
-    // (marching_cubes.cc:199-206)
-    uint16_t seen = 0;
-    for (int i = 0; i < n; i += 3)
-      for (int j = 0; j < 3; ++j) {
-        const int e = t->tri[c][i + (2 - j)];
-        if (!(seen & (1 << e))) {
-          t->prec[c][e] = seen;
-          seen |= (uint16_t)(1 << e);
-        }
-      }
-  }
-}
 
 __device__ const int8_t kKeyA[12] = {0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3};
 __device__ const int8_t kKeyB[12] = {1, 2, 2, 3, 5, 6, 6, 7, 4, 5, 6, 7};
@@ -114,7 +91,7 @@ constexpr int kBitsWordsPerWave = VCY_BITS_WORDS;
 
 // TC_FROM_OK: the state has only ever been written by the grid fill and the carve kernels, where
 // update_num == 0 implies sdf == lowest(); then OK(corner 6) already implies TC(corner 6) and the TC
-// plane may be any superset of OK -- OK itself, without reading update_num at all (see extract_iso).
+// plane may be any superset of OK -- OK itself, without reading update_num at all (see launch_cell_search).
 template <typename CountT, bool ISO_F32, bool TC_FROM_OK>
 __global__ __launch_bounds__(256) void mc_bits_kernel(const float* __restrict__ sdf,
                                                       const CountT* __restrict__ cnt, int nx, int Wr,
@@ -177,7 +154,7 @@ __global__ __launch_bounds__(256) void mc_bits_kernel(const float* __restrict__ 
   if (lane < kBitsWordsPerWave && first + lane < nwords) {
     in[first + lane] = m_in;
     ok[first + lane] = m_ok;
-    if (tc != nullptr) tc[first + lane] = m_tc;  // null: the TC plane is the OK plane itself (extract_iso)
+    if (tc != nullptr) tc[first + lane] = m_tc;  // null: the TC plane is the OK plane itself (launch_cell_search)
   }
 }
 
@@ -549,24 +526,12 @@ __global__ __launch_bounds__(256) void mc_active_kernel(McParams p, u64* __restr
 // once plus the row shared by two row groups (1 / R) and the slice shared by two z chunks (1 / layers).
 // update_num: READS_CNT reads it next to sdf (state set by vcy_upload); otherwise OK implies TC, except for the
 // ghost layer of a slab, whose max corners lie in the slab below: those TC words come in `tc_ghost`.
-struct SweepParams {
-  int R;           // cell rows per workgroup
-  int K;           // 256-word blocks per step = R * Wr / 256
-  int groups;      // row groups per layer = Yc / R
-  int layers;      // cell layers per workgroup
-  int dl;          // cells whose max corner lies in stored slice s form layer li = s + dl
-  int cnt_slices;  // READS_CNT: update_num is read for the stored slices below this one (all of them)
-  int wshift;      // log2 Wr
-};
-constexpr int kSweepMaxK = 4;
+// (SweepParams, kSweepMaxK: mc_common.h -- the driver plans the geometry)
 constexpr int kSweepBatch = 16;
 #ifndef VCY_SWEEP_SETS
 #define VCY_SWEEP_SETS 2
 #endif
 constexpr int kSweepSets = VCY_SWEEP_SETS;  // register sets of kSweepBatch requests in flight per wave
-#ifndef VCY_SWEEP_TARGET_WGS
-#define VCY_SWEEP_TARGET_WGS 1024
-#endif
 
 // lane K of the result = the scalar `sval`, the other lanes keep `old` (the lane select must be an immediate: a
 // second scalar register would be a second constant-bus operand)
@@ -904,7 +869,6 @@ __global__ __launch_bounds__(256) void add_chunk_offsets_kernel(u64* __restrict_
 // launched workgroup draws exactly one).  Publication is (sum, epoch): the epoch grows with every scan of a context, so
 // the flags are never cleared either.  Every chunk reads all its predecessors -- quadratic, which is why this form is
 // only taken up to kChainedScanMaxChunks.
-constexpr int kChainedScanMaxChunks = 1024;
 __global__ __launch_bounds__(256) void scan_chained_kernel(u64* __restrict__ data, int64_t n, u64* __restrict__ chunk_sums,
                                                            uint32_t* __restrict__ chunk_flags, uint32_t epoch,
                                                            u64* __restrict__ total, uint32_t* __restrict__ ticket,
@@ -959,15 +923,6 @@ __global__ __launch_bounds__(256) void scan_chained_kernel(u64* __restrict__ dat
   }
   if (chunk == (int)gridDim.x - 1 && threadIdx.x == 255) *total = run;  // (the last element's inclusive value)
 }
-
-// What a chained scan needs from its caller: the publication flags of ONE scan slot (kChainedScanMaxChunks words), the
-// slot's ticket counter and how many tickets have been drawn from it so far (advanced here).
-struct ChainedScanSlot {
-  uint32_t* flags;
-  uint32_t* ticket;
-  uint32_t* tickets_drawn;  // (host)
-  uint32_t epoch;
-};
 
 // in-place exclusive scan; *d_total (device) receives the grand total.  `scratch` holds the chunk
 // sums of every level (n/1024 + n/1024^2 + ... + a few elements).
@@ -1269,207 +1224,82 @@ int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long lo
   return exclusive_scan_u64(d, n, d_total, scratch, stream);
 }
 
-// ---- host driver ----------------------------------------------------------------------------
+// ---- launches (declared in mc_common.h; the host driver: mc_extract.hip) ---------------------------------
 
-int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int which, vcy_mesh_normals* normals_out,
-                int64_t* layer_faces) {
-  out->n_vertices = out->n_faces = out->n_foreign_vertices = 0;
-  out->vertices = nullptr;  // an empty mesh has no arrays
-  out->faces = nullptr;
-  out->edge_keys = nullptr;
-  if (c->halo_lo && !c->halo_valid) {
-    set_error("halo slices not installed: call vcy_halo_pack / all-gather / vcy_halo_unpack first");
-    return VCY_ERR_NOT_INITIALIZED;
+void mc::build_tables(McTables* t) {
+  std::memset(t, 0, sizeof(*t));
+  for (int c = 0; c < 256; ++c) {
+    const char* s = kCaseStrings[c];
+    int n = 0;
+    for (; s[n]; ++n) t->tri[c][n] = (int8_t)((s[n] <= '9') ? s[n] - '0' : s[n] - 'a' + 10);
+    for (int k = n; k < 16; ++k) t->tri[c][k] = -1;
+    t->ntri[c] = (uint8_t)(n / 3);
+    // creation order: triangles in table order, corners j=0..2 read entry i+(2-j)
+    // (marching_cubes.cc:199-206)
+    uint16_t seen = 0;
+    for (int i = 0; i < n; i += 3)
+      for (int j = 0; j < 3; ++j) {
+        const int e = t->tri[c][i + (2 - j)];
+        if (!(seen & (1 << e))) {
+          t->prec[c][e] = seen;
+          seen |= (uint16_t)(1 << e);
+        }
+      }
   }
-  McParams p;
-  p.sdf = c->d_sdf;
-  p.cnt = c->d_cnt;
-  p.px = c->d_px;
-  p.py = c->d_py;
-  p.pz = c->d_pz;
-  p.nx = c->nx;
-  p.ny = c->ny;
-  p.nslices = c->halo_lo + c->nz_local();
-  p.Wr = (c->nx + 63) / 64;
-  p.Y = c->ny - 1;
-  p.zc0 = std::max(c->z0, 1);
-  p.L = c->z1 - p.zc0;
-  p.zs0 = c->z0 - c->halo_lo;
-  p.has_ghost = c->halo_lo > 0 ? 1 : 0;
-  p.iso = iso;
-  p.linear = linear_interp;
-  c->last_extract_device_ms = 0.0f;
-  c->last_normals_device_ms = 0.0f;
-  if (normals_out == nullptr) which = 0;
-  if (layer_faces) layer_faces[0] = layer_faces[1] = 0;
-  if (c->nx < 2 || p.Y <= 0 || p.L <= 0) return VCY_OK;  // no cells (reference loops do not run)
-  // One sweep (mc_sweep_kernel) needs a voxel row that is a power-of-two number of whole words.  It moves 2 % fewer
-  // bytes than the bit planes in memory (mc_bits + mc_active) but is not faster anywhere (sweep / planes, one box:
-  // 256^3 0.172 / 0.133 ms, 512^3 0.291 / 0.260, 1024^3 1.26-1.27 / 1.23-1.24, 2048^3 9.55 / 9.18), so it is
-  // taken only on request ("mcsweep" 1).
-  const bool sweep = c->mc_sweep && c->nx == p.Wr * 64 && (p.Wr & (p.Wr - 1)) == 0 && p.Wr <= 32;
-  SweepParams q{};
-  p.Yc = p.Y;
-  if (sweep) {
-    q.R = std::max(32, kWordsPerBlock / p.Wr);
-    q.K = q.R * p.Wr / kWordsPerBlock;  // <= kSweepMaxK
-    p.Yc = (p.Y + q.R - 1) / q.R * q.R;
-    q.groups = p.Yc / q.R;
-    // enough workgroups to fill the GPU, few enough that the slice two z chunks share stays a small part
-    const int64_t want = ((int64_t)(p.L + 1) * q.groups + VCY_SWEEP_TARGET_WGS - 1) / VCY_SWEEP_TARGET_WGS;
-    q.layers = (int)std::min<int64_t>(std::max<int64_t>(want, 8), 64);
-    q.dl = p.zs0 - p.zc0 + 1;
-    q.cnt_slices = c->cnt_implied ? 0 : p.nslices;
-    while ((1 << q.wshift) < p.Wr) ++q.wshift;
-  }
-  const int64_t ghost_words = (int64_t)p.Yc * p.Wr;
-  p.G = (ghost_words + kWordsPerBlock - 1) / kWordsPerBlock * kWordsPerBlock;
-  p.nwords = p.G + (int64_t)p.L * p.Yc * p.Wr;
-  {
-    auto make_div = [](uint32_t d) {
-      FastDiv f;
-      uint32_t l = 0;
-      while ((1ull << l) < d) ++l;  // ceil(log2 d)
-      f.d = d;
-      f.m = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
-      f.s1 = l < 1 ? l : 1;
-      f.s2 = l < 1 ? 0 : l - 1;
-      return f;
-    };
-    p.small32 = p.nwords < 0xffffffffLL && (int64_t)p.Yc * p.Wr < 0x7fffffffLL ? 1 : 0;
-    p.div_row = make_div((uint32_t)p.Wr);
-    p.div_layer = make_div(p.small32 ? (uint32_t)((int64_t)p.Yc * p.Wr) : 1u);
-  }
-  const int64_t nblocks64 = (p.nwords + kWordsPerBlock - 1) / kWordsPerBlock;
-  const int64_t vox_rows = (int64_t)p.nslices * c->ny;
-  const int64_t vox_words = vox_rows * p.Wr;
-  if (nblocks64 > 0x7fffffffLL || (vox_words + 3) / 4 > 0x7fffffffLL) {
-    set_error("too many cells for one launch");
-    return VCY_ERR_TOO_MANY_VOXELS;
-  }
-  const unsigned nblocks = (unsigned)nblocks64;
-  hipStream_t s = c->stream;
+}
 
-  if (!c->d_mc_tables) {
-    McTables h;
-    build_tables(&h);
-    VCY_HIP_CHECK(hipMalloc(&c->d_mc_tables, sizeof(McTables)));
-    VCY_HIP_CHECK(hipMemcpy(c->d_mc_tables, &h, sizeof(McTables), hipMemcpyHostToDevice));
-  }
-  const McTables* T = (const McTables*)c->d_mc_tables;
+namespace {
 
-  // scratch, cached in the context (grown on demand): bit planes, ACT, per-word offsets, block counts
-  // (3 bits per voxel + 12.5 B per 64 cells: 0.9 GB at 1024^3)
-  auto align = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t sz_plane = align(sizeof(u64) * (size_t)vox_words);
-  const size_t sz_act = align(sizeof(u64) * (size_t)p.nwords);
-  const size_t sz_woff = align(sizeof(uint32_t) * (size_t)p.nwords);
-  const size_t sz_counts = align(sizeof(u64) * ((size_t)nblocks + 1));
-  const size_t sz_scan = align(sizeof(u64) * ((size_t)nblocks / 1024 + 64) * 2);
-  const size_t sz_ghost = sweep ? align(sizeof(u64) * 3 * (size_t)c->ny * p.Wr) : 0;  // IN / OK / TC of one slice
-  const size_t need = (sweep ? 1 : 3) * sz_plane + sz_ghost + sz_act + sz_woff + sz_counts + sz_scan + 256;
-  if (c->mc_scratch_bytes < need) {
-    VCY_HIP_CHECK(hipStreamSynchronize(s));
-    if (c->d_mc_scratch) VCY_HIP_CHECK(hipFree(c->d_mc_scratch));
-    c->d_mc_scratch = nullptr;
-    c->mc_scratch_bytes = 0;
-    VCY_HIP_CHECK(hipMalloc(&c->d_mc_scratch, need));
-    c->mc_scratch_bytes = need;
-  }
-  char* base = (char*)c->d_mc_scratch;
-  u64* d_in = (u64*)base;                     base += sz_plane;
-  u64* d_ok = (u64*)base;                     base += sweep ? 0 : sz_plane;  // (the sweep keeps OK / TC in LDS)
-  u64* d_tc = (u64*)base;                     base += sweep ? 0 : sz_plane;
-  u64* d_ghost = (u64*)base;                  base += sz_ghost;
-  u64* d_act = (u64*)base;                    base += sz_act;
-  uint32_t* d_woff = (uint32_t*)base;         base += sz_woff;
-  u64* d_wcounts = (u64*)base;                base += sz_counts;
-  u64* d_scan = (u64*)base;                   base += sz_scan;
-  // publication flags of the chained scans (scan_chained_kernel): an allocation of their own, zeroed once -- they
-  // must never hold a FUTURE epoch, so they do not live in scratch whose layout changes with the extraction
-  if (!c->d_mc_flags) {
-    // [2 slots][kChainedScanMaxChunks] flags, then the two ticket counters
-    const size_t fbytes = sizeof(uint32_t) * (2 * (size_t)kChainedScanMaxChunks + 2);
-    VCY_HIP_CHECK(hipMalloc(&c->d_mc_flags, fbytes));
-    VCY_HIP_CHECK(hipMemsetAsync(c->d_mc_flags, 0, fbytes, s));
-    c->mc_scan_epoch = 0;
-    c->mc_scan_tickets[0] = c->mc_scan_tickets[1] = 0;
-  }
-  uint32_t* d_flags = (uint32_t*)c->d_mc_flags;
-  auto scan_slot = [&](int which) {
-    ChainedScanSlot sl;
-    sl.flags = d_flags + which * kChainedScanMaxChunks;
-    sl.ticket = d_flags + 2 * kChainedScanMaxChunks + which;
-    sl.tickets_drawn = &c->mc_scan_tickets[which];
-    sl.epoch = ++c->mc_scan_epoch;
-    return sl;
-  };
-  u64* d_total = (u64*)base;
-  p.in = d_in;
-  p.ok = d_ok;
-  p.tc = d_tc;
-
-  float* d_verts = nullptr;
-  long long* d_keys = nullptr;
-  int* d_faces = nullptr;
-  auto cleanup = [&]() {};
-#define MC_TRY(expr)                                                               \
-  do {                                                                             \
-    hipError_t _e = (expr);                                                        \
-    if (_e != hipSuccess) {                                                        \
-      set_error("%s failed: %s", #expr, hipGetErrorString(_e));                    \
-      cleanup();                                                                   \
-      return VCY_ERR_HIP;                                                          \
-    }                                                                              \
-  } while (0)
-
-  // the extraction has its own event pair: vcy_timer_begin / _end may bracket it
-  if (!c->ev_mc_begin) {
-    MC_TRY(hipEventCreate(&c->ev_mc_begin));
-    MC_TRY(hipEventCreate(&c->ev_mc_end));
-  }
-  MC_TRY(hipEventRecord(c->ev_mc_begin, s));
-  const bool iso_f32 = (double)(float)iso == iso;
-  // the halo slices come from another context: their update_num is read; the owned slices need it
-  // only if the state was ever set from outside (vcy_upload), see mc_bits_kernel
-  auto launch_bits = [&](int64_t word0, int64_t nw, bool tc_from_ok, u64* o_in, u64* o_ok, u64* o_tc) {
-    if (nw <= 0) return;
-    const unsigned blocks = (unsigned)((nw + 4 * kBitsWordsPerWave - 1) / (4 * kBitsWordsPerWave));
-    const float* sdf0 = c->d_sdf + word0 * 64;  // whole rows: only used when nx == Wr * 64 or word0 == 0
-    const char* cnt0 = (const char*)c->d_cnt + word0 * 64 * c->cnt_bytes;
+// the halo slices come from another context: their update_num is read; the owned slices need it
+// only if the state was ever set from outside (vcy_upload), see mc_bits_kernel
+void launch_bits(hipStream_t s, const McParams& p, int cnt_bytes, int64_t word0, int64_t nw, bool tc_from_ok, u64* o_in,
+                 u64* o_ok, u64* o_tc) {
+  if (nw <= 0) return;
+  const bool iso_f32 = (double)(float)p.iso == p.iso;
+  const unsigned blocks = (unsigned)((nw + 4 * kBitsWordsPerWave - 1) / (4 * kBitsWordsPerWave));
+  const float* sdf0 = p.sdf + word0 * 64;  // whole rows: only used when nx == Wr * 64 or word0 == 0
+  const char* cnt0 = (const char*)p.cnt + word0 * 64 * cnt_bytes;
 #define VCY_BITS(CT, F32, TCOK)                                                                          \
   hipLaunchKernelGGL((mc_bits_kernel<CT, F32, TCOK>), dim3(blocks), dim3(256), 0, s, sdf0, (const CT*)cnt0, \
-                     c->nx, p.Wr, nw, iso, o_in, o_ok, o_tc)
+                     p.nx, p.Wr, nw, p.iso, o_in, o_ok, o_tc)
 #define VCY_BITS_F(CT, TCOK)                                                    \
   do {                                                                          \
     if (iso_f32) VCY_BITS(CT, true, TCOK); else VCY_BITS(CT, false, TCOK);      \
   } while (0)
-    if (tc_from_ok) {
-      if (c->cnt_bytes == 1) VCY_BITS_F(uint8_t, true);
-      else if (c->cnt_bytes == 2) VCY_BITS_F(uint16_t, true);
-      else VCY_BITS_F(uint32_t, true);
-    } else {
-      if (c->cnt_bytes == 1) VCY_BITS_F(uint8_t, false);
-      else if (c->cnt_bytes == 2) VCY_BITS_F(uint16_t, false);
-      else VCY_BITS_F(uint32_t, false);
-    }
+  if (tc_from_ok) {
+    if (cnt_bytes == 1) VCY_BITS_F(uint8_t, true);
+    else if (cnt_bytes == 2) VCY_BITS_F(uint16_t, true);
+    else VCY_BITS_F(uint32_t, true);
+  } else {
+    if (cnt_bytes == 1) VCY_BITS_F(uint8_t, false);
+    else if (cnt_bytes == 2) VCY_BITS_F(uint16_t, false);
+    else VCY_BITS_F(uint32_t, false);
+  }
 #undef VCY_BITS_F
 #undef VCY_BITS
-  };
-  if (sweep) {
-    const bool reads_cnt = q.cnt_slices > 0;
-    // TC words of the slice the ghost layer's max corners lie in (stored slice 1), from its update_num
-    const u64* d_tc_ghost = nullptr;
-    if (!reads_cnt && c->halo_lo > 0) {
-      const int64_t row_words = (int64_t)c->ny * p.Wr;
-      launch_bits(row_words, row_words, false, d_ghost, d_ghost + row_words, d_ghost + 2 * row_words);
-      d_tc_ghost = d_ghost + 2 * row_words;
-    }
-    const unsigned chunks = (unsigned)((p.L + 1 + q.layers - 1) / q.layers);
-    const size_t lds = sizeof(u64) * 2 * (reads_cnt ? 3 : 2) * (size_t)(q.R + 1) * p.Wr;
+}
+
+// One sweep (mc_sweep_kernel) needs a voxel row that is a power-of-two number of whole words.  It moves 2 % fewer
+// bytes than the bit planes in memory (mc_bits + mc_active) but is not faster anywhere (sweep / planes, one box:
+// 256^3 0.172 / 0.133 ms, 512^3 0.291 / 0.260, 1024^3 1.26-1.27 / 1.23-1.24, 2048^3 9.55 / 9.18), so it is
+// taken only on request ("mcsweep" 1).
+void launch_sweep(const vcy_ctx* c, const McParams& p, const ChainLaunch& a) {
+  hipStream_t s = c->stream;
+  const SweepParams& q = *a.sweep;
+  const bool iso_f32 = (double)(float)p.iso == p.iso;
+  const bool reads_cnt = q.cnt_slices > 0;
+  // TC words of the slice the ghost layer's max corners lie in (stored slice 1), from its update_num
+  const u64* d_tc_ghost = nullptr;
+  if (!reads_cnt && c->halo_lo > 0) {
+    const int64_t row_words = (int64_t)p.ny * p.Wr;
+    launch_bits(s, p, c->cnt_bytes, row_words, row_words, false, a.ghost, a.ghost + row_words, a.ghost + 2 * row_words);
+    d_tc_ghost = a.ghost + 2 * row_words;
+  }
+  const unsigned chunks = (unsigned)((p.L + 1 + q.layers - 1) / q.layers);
+  const size_t lds = sizeof(u64) * 2 * (reads_cnt ? 3 : 2) * (size_t)(q.R + 1) * p.Wr;
 #define VCY_SWEEP(CT, F32, RC, KM)                                                                                   \
-  hipLaunchKernelGGL((mc_sweep_kernel<CT, F32, RC, KM>), dim3(chunks * (unsigned)q.groups), dim3(256), lds, s, p, q, d_act, \
-                     d_woff, d_wcounts, d_in, d_tc_ghost)
+  hipLaunchKernelGGL((mc_sweep_kernel<CT, F32, RC, KM>), dim3(chunks * (unsigned)q.groups), dim3(256), lds, s, p, q, a.act, \
+                     a.word_cell_off, a.block_cells, a.in, d_tc_ghost)
 #define VCY_SWEEP_K(CT, F32, RC)                      \
   do {                                                \
     if (q.K <= 1) VCY_SWEEP(CT, F32, RC, 1);          \
@@ -1480,371 +1310,91 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
   do {                                                                            \
     if (iso_f32) VCY_SWEEP_K(CT, true, RC); else VCY_SWEEP_K(CT, false, RC);      \
   } while (0)
-    if (reads_cnt) {
-      if (c->cnt_bytes == 1) VCY_SWEEP_F(uint8_t, true);
-      else if (c->cnt_bytes == 2) VCY_SWEEP_F(uint16_t, true);
-      else VCY_SWEEP_F(uint32_t, true);
-    } else {
-      VCY_SWEEP_F(uint16_t, false);  // (update_num is not read)
-    }
+  if (reads_cnt) {
+    if (c->cnt_bytes == 1) VCY_SWEEP_F(uint8_t, true);
+    else if (c->cnt_bytes == 2) VCY_SWEEP_F(uint16_t, true);
+    else VCY_SWEEP_F(uint32_t, true);
+  } else {
+    VCY_SWEEP_F(uint16_t, false);  // (update_num is not read)
+  }
 #undef VCY_SWEEP_F
 #undef VCY_SWEEP_K
 #undef VCY_SWEEP
-  } else {
-    const int64_t halo_words = (int64_t)c->halo_lo * c->ny * p.Wr;
-    // a whole grid whose state implies TC == OK: no third plane at all
-    const bool alias_tc = c->cnt_implied && c->nx == p.Wr * 64 && c->halo_lo == 0;
-    if (alias_tc) {
-      p.tc = d_ok;
-      d_tc = nullptr;
-    }
-    if (c->cnt_implied && c->nx == p.Wr * 64) {
-      launch_bits(0, halo_words, false, d_in, d_ok, d_tc);
-      const int nbw = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (c->nz_local() + 7) / 8;
-      // (rows of 16 words and more: at 512^3 -- 8 words, 4096 brick rows -- the dense pass is the faster one, 0.197 against
-      // 0.210 ms per extraction in the default mode, 0.233 against 0.271 after a weighted-average carve; "mcskip" 2 forces
-      // the brick rows on any size for the tests)
-      if (c->mc_skip && (p.Wr >= 16 || c->mc_skip > 1) && c->brick_min_valid && !c->fresh && c->d_brick_min &&
-          nbw <= kBricksMaxNbw && nbz <= 65535) {
-        // the owned slices, bricks the carve kernels left entirely outside the surface not read ("mcskip")
-        const float* sdf0 = c->d_sdf + halo_words * 64;
-        u64* o_tc = d_tc ? d_tc + halo_words : nullptr;
-        if (iso_f32)
-          hipLaunchKernelGGL((mc_bits_bricks_kernel<true>), dim3((unsigned)nby, (unsigned)nbz), dim3(256), 0, s, sdf0, c->ny,
-                             c->nz_local(), p.Wr, iso, d_in + halo_words, d_ok + halo_words, o_tc, c->d_brick_min, nbw, nby);
-        else
-          hipLaunchKernelGGL((mc_bits_bricks_kernel<false>), dim3((unsigned)nby, (unsigned)nbz), dim3(256), 0, s, sdf0, c->ny,
-                             c->nz_local(), p.Wr, iso, d_in + halo_words, d_ok + halo_words, o_tc, c->d_brick_min, nbw, nby);
-      } else {
-        launch_bits(halo_words, vox_words - halo_words, true, d_in + halo_words, d_ok + halo_words,
-                    d_tc ? d_tc + halo_words : nullptr);
-      }
-    } else {
-      launch_bits(0, vox_words, false, d_in, d_ok, d_tc);
-    }
-    hipLaunchKernelGGL(mc_active_kernel, dim3((nblocks + kActiveBlocks - 1) / kActiveBlocks), dim3(256), 0, s, p, d_act,
-                       d_woff, d_wcounts, (int64_t)nblocks);
-  }
-  MC_TRY(hipGetLastError());
-  int rc;
-  {
-    const ChainedScanSlot sl = scan_slot(0);
-    rc = exclusive_scan_u64(d_wcounts, nblocks, d_total, d_scan, s, &sl);
-  }
-  if (rc != VCY_OK) return rc;
-
-  // ---- the surface cells ------------------------------------------------------------------------
-  // How much comes next is data: the number of active cells sizes the list and the owner info, the numbers of
-  // vertices and triangles the output arrays.  The kernels read those counts from device memory, so with the
-  // sizes of this context's previous extraction as a guess (plus a quarter) the whole chain is enqueued
-  // without the host reading anything back; the counts are fetched once at the end, and if a guess was too
-  // small the chain runs again with the exact sizes -- which is also the path of the first extraction.
-  struct CellBuffers {
-    u64* list; uint32_t* info; uint16_t* nact; u64* counts; u64* scan; u64* total; unsigned blocks;
-  };
-  auto cell_buffers = [&](int64_t cap_cells, CellBuffers* b) -> int {
-    b->blocks = (unsigned)((cap_cells + 255) / 256);
-    const size_t sz_list = align(sizeof(u64) * (size_t)cap_cells);
-    const size_t sz_info = align(sizeof(uint32_t) * (size_t)cap_cells);
-    const size_t sz_nact = align(sizeof(uint16_t) * (size_t)cap_cells);
-    const size_t sz_cc = align(sizeof(u64) * ((size_t)b->blocks + 1));
-    const size_t sz_cs = align(sizeof(u64) * ((size_t)b->blocks / 1024 + 64) * 2);
-    const size_t need2 = sz_list + sz_info + sz_nact + sz_cc + sz_cs + 256;
-    if (c->mc_cells_bytes < need2) {
-      MC_TRY(hipStreamSynchronize(s));
-      if (c->d_mc_cells) MC_TRY(hipFree(c->d_mc_cells));
-      c->d_mc_cells = nullptr;
-      c->mc_cells_bytes = 0;
-      MC_TRY(hipMalloc(&c->d_mc_cells, need2));
-      c->mc_cells_bytes = need2;
-    }
-    char* b2 = (char*)c->d_mc_cells;
-    b->list = (u64*)b2;                   b2 += sz_list;
-    b->info = (uint32_t*)b2;              b2 += sz_info;
-    b->nact = (uint16_t*)b2;              b2 += sz_nact;
-    b->counts = (u64*)b2;                 b2 += sz_cc;
-    b->scan = (u64*)b2;                   b2 += sz_cs;
-    b->total = (u64*)b2;
-    return VCY_OK;
-  };
-  // active cells -> list -> owner info + (vertices, triangles) per block -> offsets
-  auto enqueue_owners = [&](const CellBuffers& b, int64_t cap_cells) -> int {
-    hipLaunchKernelGGL(mc_compact_kernel, dim3((nblocks + kCompactBlocks - 1) / kCompactBlocks), dim3(256), 0, s, p, d_act,
-                       d_woff, d_wcounts, d_total, (int64_t)nblocks, b.list, cap_cells);
-    hipLaunchKernelGGL(mc_owner_kernel, dim3(b.blocks), dim3(256), 0, s, p, T, d_act, b.list, d_total, cap_cells, b.info,
-                       b.nact, b.counts);
-    MC_TRY(hipGetLastError());
-    const ChainedScanSlot sl = scan_slot(1);
-    return exclusive_scan_u64(b.counts, b.blocks, b.total, b.scan, s, &sl);
-  };
-  // The counts come back through 64 bytes of page-locked memory that mc_emit writes itself (see the kernel).
-  if (!c->h_mc_report) {
-    MC_TRY(hipHostMalloc((void**)&c->h_mc_report, 64, hipHostMallocPortable | hipHostMallocMapped));
-    std::memset((void*)c->h_mc_report, 0, 64);
-  }
-  volatile u64* report = (volatile u64*)c->h_mc_report;
-  const bool timing = c->mc_timing != 0;
-  double t_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto now_us = []() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  const double t_begin = timing ? now_us() : 0.0;
-  // Output arrays.  A mesh of up to "mcdirect" bytes (default 32 MiB) is written by mc_emit STRAIGHT into the page-locked
-  // host arrays the caller receives (whole rows of dwords over PCIe while other blocks still compute): the call is then
-  // one enqueue and one wait.  Larger meshes are staged in device memory and copied with exact sizes after the counts
-  // are known (over-copying the guess's headroom would cost more than the second wait).  The kernel's stores cross PCIe
-  // at 50 GB/s where the copy engine reaches 54, and what they overlap is the 65 us of emit arithmetic: 0.22 -> 0.20 ms
-  // for a 5 MB mesh, 0.65 -> 0.62 for 23 MB (512^3), nothing for 92 MB (1024^3) -- profiles/r06/mc_wall.txt.
-  bool direct = false;
-  auto release_host = [&]() {
-    mesh_host_free(out->vertices);
-    mesh_host_free(out->faces);
-    mesh_host_free(out->edge_keys);
-    out->vertices = nullptr, out->faces = nullptr, out->edge_keys = nullptr;
-  };
-  auto enqueue_emit = [&](const CellBuffers& b, int64_t cap_cells, int64_t cap_v, int64_t cap_f) -> int {
-    const size_t sz_v = align(sizeof(float) * 3 * (size_t)std::max<int64_t>(cap_v, 1));
-    const size_t sz_k = align(sizeof(long long) * 2 * (size_t)std::max<int64_t>(cap_v, 1));
-    const size_t sz_f = align(sizeof(int) * 3 * (size_t)std::max<int64_t>(cap_f, 1));
-    direct = false;
-    // (with normals the mesh is staged on the device: mc_face_normals reads the emitted arrays, and must not read them
-    // back over PCIe)
-    if (which == 0 && layer_faces == nullptr && (int64_t)(sz_v + sz_f + (c->mesh_keys ? sz_k : 0)) <= c->mc_direct_bytes) {
-      bool pinned = true, pk = true, pf = true;
-      out->vertices = (float*)mesh_host_alloc(sz_v, &pinned);
-      out->faces = (int32_t*)mesh_host_alloc(sz_f, &pf);
-      if (c->mesh_keys) out->edge_keys = (int64_t*)mesh_host_alloc(sz_k, &pk);
-      direct = out->vertices && out->faces && (!c->mesh_keys || out->edge_keys) && pinned && pf && pk;
-      if (!direct) release_host();
-    }
-    if (direct) {
-      d_verts = out->vertices;
-      d_keys = c->mesh_keys ? (long long*)out->edge_keys : nullptr;
-      d_faces = (int*)out->faces;
-    } else {
-      if (c->mc_out_bytes < sz_v + sz_k + sz_f) {
-        MC_TRY(hipStreamSynchronize(s));
-        if (c->d_mc_out) MC_TRY(hipFree(c->d_mc_out));
-        c->d_mc_out = nullptr;
-        c->mc_out_bytes = 0;
-        MC_TRY(hipMalloc(&c->d_mc_out, sz_v + sz_k + sz_f));
-        c->mc_out_bytes = sz_v + sz_k + sz_f;
-      }
-      d_verts = (float*)c->d_mc_out;
-      d_keys = c->mesh_keys ? (long long*)((char*)c->d_mc_out + sz_v) : nullptr;
-      d_faces = (int*)((char*)c->d_mc_out + sz_v + sz_k);
-    }
-    hipLaunchKernelGGL(mc_emit_kernel, dim3(b.blocks), dim3(256), 0, s, p, T, d_act, b.list, d_total, cap_cells, d_woff,
-                       d_wcounts, b.info, b.nact, b.counts, b.total, cap_v, cap_f, d_verts, d_keys, d_faces,
-                       d_wcounts + p.G / kWordsPerBlock, (u64*)c->h_mc_report);
-    MC_TRY(hipGetLastError());
-    return VCY_OK;
-  };
-  // Normals (vcy_extract_iso_normals): two more launches behind mc_emit, behind the same capacity checks (they read
-  // the counts themselves), enqueued again with the chain when a guess was too small.  Their own event pair:
-  // last_extract_device_ms stays "the mesh kernels".
-  float* d_vn = nullptr;
-  float* d_fn = nullptr;
-  bool normals_timed = false;
-  auto enqueue_normals = [&](const CellBuffers& b, int64_t cap_cells, int64_t cap_v, int64_t cap_f) -> int {
-    const size_t sz_vn = (which & VCY_NORMALS_VERTEX) ? align(sizeof(float) * 3 * (size_t)std::max<int64_t>(cap_v, 1)) : 0;
-    const size_t sz_fn = (which & VCY_NORMALS_FACE) ? align(sizeof(float) * 3 * (size_t)std::max<int64_t>(cap_f, 1)) : 0;
-    if (c->mc_normals_bytes < sz_vn + sz_fn) {
-      MC_TRY(hipStreamSynchronize(s));
-      if (c->d_mc_normals) MC_TRY(hipFree(c->d_mc_normals));
-      c->d_mc_normals = nullptr;
-      c->mc_normals_bytes = 0;
-      MC_TRY(hipMalloc(&c->d_mc_normals, sz_vn + sz_fn));
-      c->mc_normals_bytes = sz_vn + sz_fn;
-    }
-    d_vn = sz_vn ? (float*)c->d_mc_normals : nullptr;
-    d_fn = sz_fn ? (float*)((char*)c->d_mc_normals + sz_vn) : nullptr;
-    if (!c->ev_nrm_begin) {
-      MC_TRY(hipEventCreate(&c->ev_nrm_begin));
-      MC_TRY(hipEventCreate(&c->ev_nrm_end));
-    }
-    NormalsLaunch a;
-    a.T = T;
-    a.act = d_act;
-    a.cell_list = b.list;
-    a.ncells_dev = d_total;
-    a.cap_cells = cap_cells;
-    a.info = b.info;
-    a.block_offs = b.counts;
-    a.grand_total_dev = b.total;
-    a.cap_verts = cap_v;
-    a.cap_faces = cap_f;
-    a.verts = d_verts;
-    a.faces = d_faces;
-    a.vertex_normals = d_vn;
-    a.face_normals = d_fn;
-    // a z-slab (vcy_extract_iso_normals_slab): the seam vertices are left to the host, the layer counts it needs come
-    // back in the report block, behind the four words of mc_emit
-    a.slab = (c->z0 != 0 || c->z1 != c->nz || c->halo_lo != 0) ? 1 : 0;
-    a.open_top = c->z1 < c->nz ? 1 : 0;
-    a.word_cell_off = d_woff;
-    a.block_cell_offs = d_wcounts;
-    a.ghost_cells_dev = d_wcounts + p.G / kWordsPerBlock;
-    a.report = layer_faces ? (u64*)c->h_mc_report + 4 : nullptr;
-    MC_TRY(hipEventRecord(c->ev_nrm_begin, s));
-    MC_TRY(launch_normals(s, p, a));
-    MC_TRY(hipEventRecord(c->ev_nrm_end, s));
-    normals_timed = true;
-    return VCY_OK;
-  };
-  // number of active cells, and how many of them are ghost cells (words below G)
-  int64_t ncells = 0, nghost = 0, nv = 0, nf = 0, nforeign = 0, first_layer_faces = 0, last_layer_faces = 0;
-  CellBuffers cb{};
-  bool done = false, end_recorded = false;
-  auto with_headroom = [](int64_t v) { return v + v / 4 + 4096; };  // the next view's mesh is a little different
-  auto read_report = [&]() {
-    ncells = (int64_t)report[0];
-    nghost = (int64_t)report[1];
-    nv = (int64_t)(report[2] >> 32);
-    nf = (int64_t)(report[2] & 0xFFFFFFFFull);
-    nforeign = (int64_t)report[3];
-    first_layer_faces = (int64_t)report[4];  // (written by the normals' layer count, when asked for)
-    last_layer_faces = (int64_t)report[5];
-  };
-  if (timing) t_ph[0] = now_us();
-  if (c->mc_hint_cells > 0) {
-    const int64_t cap_cells = with_headroom(c->mc_hint_cells);
-    const int64_t cap_v = with_headroom(c->mc_hint_verts), cap_f = with_headroom(c->mc_hint_faces);
-    rc = cell_buffers(cap_cells, &cb);
-    if (rc == VCY_OK) rc = enqueue_owners(cb, cap_cells);
-    if (rc == VCY_OK) rc = enqueue_emit(cb, cap_cells, cap_v, cap_f);
-    if (rc != VCY_OK) {
-      release_host();
-      return rc;
-    }
-    // (the end of the kernels: last_extract_device_ms is "kernels only")
-    MC_TRY(hipEventRecord(c->ev_mc_end, s));
-    end_recorded = true;
-    if (which != 0 || layer_faces) {
-      rc = enqueue_normals(cb, cap_cells, cap_v, cap_f);
-      if (rc != VCY_OK) return rc;
-    }
-    if (timing) t_ph[1] = now_us();
-    MC_TRY(hipStreamSynchronize(s));  // the ONE wait of an extraction whose mesh went straight to host memory
-    if (timing) t_ph[2] = now_us();
-    read_report();
-    done = ncells <= cap_cells && nv <= cap_v && nf <= cap_f;
-    if (ncells == 0) nv = nf = 0;
-    if (!done) release_host();
-  }
-  if (!done) {
-    // first extraction of a context, or a guess that was too small: the counts first, then buffers of the right size
-    MC_TRY(hipMemcpyAsync((void*)&report[0], d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
-    MC_TRY(hipMemcpyAsync((void*)&report[1], d_wcounts + p.G / kWordsPerBlock, sizeof(u64), hipMemcpyDeviceToHost, s));
-    MC_TRY(hipStreamSynchronize(s));
-    ncells = (int64_t)report[0];
-    nghost = (int64_t)report[1];
-    nv = nf = nforeign = 0;
-    if (ncells > 0xFFFFFFFFLL) {
-      set_error("too many surface cells");
-      return VCY_ERR_TOO_MANY_VOXELS;
-    }
-    if (ncells > 0) {
-      // (buffers sized with the same headroom as the guesses, so that the next extraction does not reallocate)
-      const int64_t cap_cells = with_headroom(ncells);
-      rc = cell_buffers(cap_cells, &cb);
-      if (rc == VCY_OK) rc = enqueue_owners(cb, cap_cells);
-      if (rc != VCY_OK) return rc;
-      MC_TRY(hipMemcpyAsync((void*)&report[2], cb.total, sizeof(u64), hipMemcpyDeviceToHost, s));
-      MC_TRY(hipStreamSynchronize(s));
-      nv = (int64_t)(report[2] >> 32);
-      nf = (int64_t)(report[2] & 0xFFFFFFFFull);
-      rc = enqueue_emit(cb, cap_cells, with_headroom(nv), with_headroom(nf));
-      if (rc != VCY_OK) {
-        release_host();
-        return rc;
-      }
-      MC_TRY(hipEventRecord(c->ev_mc_end, s));
-      end_recorded = true;
-      if (which != 0 || layer_faces) {
-        rc = enqueue_normals(cb, cap_cells, with_headroom(nv), with_headroom(nf));
-        if (rc != VCY_OK) return rc;
-      }
-      MC_TRY(hipStreamSynchronize(s));
-      read_report();
-    } else {
-      end_recorded = false;
-    }
-  }
-  if (ncells > 0) out->n_foreign_vertices = nforeign;
-  c->mc_hint_cells = ncells;
-  c->mc_hint_verts = nv;
-  c->mc_hint_faces = nf;
-  if (!end_recorded) MC_TRY(hipEventRecord(c->ev_mc_end, s));
-  MC_TRY(hipEventSynchronize(c->ev_mc_end));
-  MC_TRY(hipEventElapsedTime(&c->last_extract_device_ms, c->ev_mc_begin, c->ev_mc_end));
-  if (timing) t_ph[3] = now_us();
-
-  if (direct && ncells > 0 && (nv > 0 || nf > 0)) {
-    // the arrays are already where the caller reads them; an empty side has no array
-    if (nv == 0) {
-      mesh_host_free(out->vertices);
-      mesh_host_free(out->edge_keys);
-      out->vertices = nullptr, out->edge_keys = nullptr;
-    }
-    if (nf == 0) {
-      mesh_host_free(out->faces);
-      out->faces = nullptr;
-    }
-  } else {
-    if (direct) release_host();  // (an empty mesh)
-    // the mesh arrays: page-locked host buffers, three DMAs in flight on the context's stream
-    if (nv > 0) {
-      out->vertices = (float*)mesh_host_alloc(sizeof(float) * 3 * (size_t)nv);
-      if (c->mesh_keys) out->edge_keys = (int64_t*)mesh_host_alloc(sizeof(int64_t) * 2 * (size_t)nv);
-    }
-    if (nf > 0) out->faces = (int32_t*)mesh_host_alloc(sizeof(int32_t) * 3 * (size_t)nf);
-    if ((nv > 0 && (!out->vertices || (c->mesh_keys && !out->edge_keys))) || (nf > 0 && !out->faces)) {
-      set_error("out of host memory for the mesh");
-      return VCY_ERR_INTERNAL;
-    }
-    if (nv > 0) {
-      MC_TRY(hipMemcpyAsync(out->vertices, d_verts, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, s));
-      if (c->mesh_keys)
-        MC_TRY(hipMemcpyAsync(out->edge_keys, d_keys, sizeof(long long) * 2 * (size_t)nv, hipMemcpyDeviceToHost, s));
-    }
-    if (nf > 0) MC_TRY(hipMemcpyAsync(out->faces, d_faces, sizeof(int) * 3 * (size_t)nf, hipMemcpyDeviceToHost, s));
-    if (which != 0 && ncells > 0) {
-      // (the caller -- vcy_extract_iso_normals -- releases both structs when this function fails)
-      if ((which & VCY_NORMALS_VERTEX) && nv > 0) {
-        normals_out->vertex_normals = (float*)mesh_host_alloc(sizeof(float) * 3 * (size_t)nv);
-        if (!normals_out->vertex_normals) {
-          set_error("out of host memory for the normals");
-          return VCY_ERR_INTERNAL;
-        }
-        MC_TRY(hipMemcpyAsync(normals_out->vertex_normals, d_vn, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, s));
-      }
-      if ((which & VCY_NORMALS_FACE) && nf > 0) {
-        normals_out->face_normals = (float*)mesh_host_alloc(sizeof(float) * 3 * (size_t)nf);
-        if (!normals_out->face_normals) {
-          set_error("out of host memory for the normals");
-          return VCY_ERR_INTERNAL;
-        }
-        MC_TRY(hipMemcpyAsync(normals_out->face_normals, d_fn, sizeof(float) * 3 * (size_t)nf, hipMemcpyDeviceToHost, s));
-      }
-    }
-    if (nv > 0 || nf > 0) MC_TRY(hipStreamSynchronize(s));
-    if (normals_timed && ncells > 0) MC_TRY(hipEventSynchronize(c->ev_nrm_end));
-    if (normals_timed && ncells > 0) MC_TRY(hipEventElapsedTime(&c->last_normals_device_ms, c->ev_nrm_begin, c->ev_nrm_end));
-  }
-  out->n_vertices = nv;
-  out->n_faces = nf;
-  if (layer_faces && ncells > 0 && nf > 0) layer_faces[0] = first_layer_faces, layer_faces[1] = last_layer_faces;
-  if (timing) {
-    t_ph[4] = now_us();
-    fprintf(stderr, "[vcy mc timing] setup %.1f us | enqueue %.1f | wait %.1f | events %.1f | mesh to host %.1f | total %.1f "
-                    "(direct %d, %lld cells, %lld v, %lld f, kernels %.1f us)\n",
-            t_ph[0] - t_begin, t_ph[1] - t_ph[0], t_ph[2] - t_ph[1], t_ph[3] - t_ph[2], t_ph[4] - t_ph[3], t_ph[4] - t_begin,
-            direct ? 1 : 0, (long long)ncells, (long long)nv, (long long)nf, c->last_extract_device_ms * 1e3);
-  }
-#undef MC_TRY
-  cleanup();
-  return VCY_OK;
 }
 
+// bit planes in memory, then mc_active_kernel
+void launch_planes(const vcy_ctx* c, McParams& p, const ChainLaunch& a) {
+  hipStream_t s = c->stream;
+  const bool whole_words = p.nx == p.Wr * 64;
+  const int64_t vox_words = (int64_t)p.nslices * p.ny * p.Wr;
+  const int64_t halo_words = (int64_t)c->halo_lo * p.ny * p.Wr;
+  u64* d_tc = a.tc;
+  // a whole grid whose state implies TC == OK: no third plane at all
+  if (c->cnt_implied && whole_words && c->halo_lo == 0) {
+    p.tc = a.ok;
+    d_tc = nullptr;
+  }
+  if (c->cnt_implied && whole_words) {
+    launch_bits(s, p, c->cnt_bytes, 0, halo_words, false, a.in, a.ok, d_tc);
+    const int nbw = (p.nx + 7) / 8, nby = (p.ny + 7) / 8, nbz = (c->nz_local() + 7) / 8;
+    // (rows of 16 words and more: at 512^3 -- 8 words, 4096 brick rows -- the dense pass is the faster one, 0.197 against
+    // 0.210 ms per extraction in the default mode, 0.233 against 0.271 after a weighted-average carve; "mcskip" 2 forces
+    // the brick rows on any size for the tests)
+    if (c->mc_skip && (p.Wr >= 16 || c->mc_skip > 1) && c->brick_min_valid && !c->fresh && c->d_brick_min &&
+        nbw <= kBricksMaxNbw && nbz <= 65535) {
+      // the owned slices, bricks the carve kernels left entirely outside the surface not read ("mcskip")
+      const float* sdf0 = p.sdf + halo_words * 64;
+      u64* o_tc = d_tc ? d_tc + halo_words : nullptr;
+      if ((double)(float)p.iso == p.iso)
+        hipLaunchKernelGGL((mc_bits_bricks_kernel<true>), dim3((unsigned)nby, (unsigned)nbz), dim3(256), 0, s, sdf0, p.ny,
+                           c->nz_local(), p.Wr, p.iso, a.in + halo_words, a.ok + halo_words, o_tc, c->d_brick_min, nbw, nby);
+      else
+        hipLaunchKernelGGL((mc_bits_bricks_kernel<false>), dim3((unsigned)nby, (unsigned)nbz), dim3(256), 0, s, sdf0, p.ny,
+                           c->nz_local(), p.Wr, p.iso, a.in + halo_words, a.ok + halo_words, o_tc, c->d_brick_min, nbw, nby);
+    } else {
+      launch_bits(s, p, c->cnt_bytes, halo_words, vox_words - halo_words, true, a.in + halo_words, a.ok + halo_words,
+                  d_tc ? d_tc + halo_words : nullptr);
+    }
+  } else {
+    launch_bits(s, p, c->cnt_bytes, 0, vox_words, false, a.in, a.ok, d_tc);
+  }
+  hipLaunchKernelGGL(mc_active_kernel, dim3((a.nblocks + kActiveBlocks - 1) / kActiveBlocks), dim3(256), 0, s, p, a.act,
+                     a.word_cell_off, a.block_cells, (int64_t)a.nblocks);
+}
+
+}  // namespace
+
+int mc::launch_cell_search(const vcy_ctx* c, McParams* p, const ChainLaunch& a, const ChainedScanSlot& slot) {
+  p->in = a.in;
+  p->ok = a.ok;
+  p->tc = a.tc;
+  if (a.sweep) launch_sweep(c, *p, a);
+  else launch_planes(c, *p, a);
+  VCY_HIP_CHECK(hipGetLastError());
+  return exclusive_scan_u64(a.block_cells, a.nblocks, a.ncells_dev, a.scan_scratch, c->stream, &slot);
+}
+
+// active cells -> list -> owner info + (vertices, triangles) per block -> offsets
+int mc::launch_owners(hipStream_t s, const McParams& p, const ChainLaunch& a, const ChainedScanSlot& slot) {
+  hipLaunchKernelGGL(mc_compact_kernel, dim3((a.nblocks + kCompactBlocks - 1) / kCompactBlocks), dim3(256), 0, s, p, a.act,
+                     a.word_cell_off, a.block_cells, a.ncells_dev, (int64_t)a.nblocks, a.cell_list, a.cap_cells);
+  hipLaunchKernelGGL(mc_owner_kernel, dim3(a.cell_blocks), dim3(256), 0, s, p, a.T, a.act, a.cell_list, a.ncells_dev,
+                     a.cap_cells, a.info, a.nbr_active, a.block_offs);
+  VCY_HIP_CHECK(hipGetLastError());
+  return exclusive_scan_u64(a.block_offs, a.cell_blocks, a.grand_total_dev, a.cell_scan_scratch, s, &slot);
+}
+
+// Output arrays.  A mesh of up to "mcdirect" bytes (default 32 MiB) is written by mc_emit STRAIGHT into the page-locked
+// host arrays the caller receives (whole rows of dwords over PCIe while other blocks still compute): the call is then
+// one enqueue and one wait.  Larger meshes are staged in device memory and copied with exact sizes after the counts
+// are known (over-copying the guess's headroom would cost more than the second wait).  The kernel's stores cross PCIe
+// at 50 GB/s where the copy engine reaches 54, and what they overlap is the 65 us of emit arithmetic: 0.22 -> 0.20 ms
+// for a 5 MB mesh, 0.65 -> 0.62 for 23 MB (512^3), nothing for 92 MB (1024^3) -- profiles/r06/mc_wall.txt.
+int mc::launch_emit(hipStream_t s, const McParams& p, const ChainLaunch& a) {
+  hipLaunchKernelGGL(mc_emit_kernel, dim3(a.cell_blocks), dim3(256), 0, s, p, a.T, a.act, a.cell_list, a.ncells_dev,
+                     a.cap_cells, a.word_cell_off, a.block_cells, a.info, a.nbr_active, a.block_offs, a.grand_total_dev,
+                     a.cap_verts, a.cap_faces, a.verts, a.keys, a.faces, a.block_cells + p.G / kWordsPerBlock, a.report);
+  VCY_HIP_CHECK(hipGetLastError());
+  return VCY_OK;
+}
 }  // namespace vcy

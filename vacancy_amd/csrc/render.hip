@@ -323,16 +323,6 @@ constexpr int kLdsPlanes = 12288;  // floats: the three tables of up to 4095 vox
 
 namespace {
 
-int grow(void** p, size_t* have, size_t want) {
-  if (*have >= want) return VCY_OK;
-  if (*p) VCY_HIP_CHECK(hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  VCY_HIP_CHECK(hipMalloc(p, want));
-  *have = want;
-  return VCY_OK;
-}
-
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 size_t hit_bytes(const vcy_view& v) { return (((size_t)v.width + 63) / 64) * 8 * (size_t)v.height; }  // packed hit bits of a view
@@ -363,7 +353,7 @@ int ensure_bits(vcy_ctx* c, double iso) {
   const int64_t nwords = (int64_t)Wr * c->ny * nzl;
   const int nbx = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (nzl + 7) / 8;
   const int64_t nbricks = (int64_t)nbx * nby * nbz, nocc = (nbricks + 63) / 64;
-  { const int rc = grow(&c->d_rn_bits, &c->rn_bits_bytes, sizeof(rn::u64) * (size_t)(nwords + nocc)); if (rc != VCY_OK) return rc; }
+  { const int rc = grow_device(&c->d_rn_bits, &c->rn_bits_bytes, sizeof(rn::u64) * (size_t)(nwords + nocc), c->stream, false); if (rc != VCY_OK) return rc; }
   rn::u64* bits = (rn::u64*)c->d_rn_bits;
   { const int rc = launch_solid_bits(c, iso, bits); if (rc != VCY_OK) return rc; }
   hipLaunchKernelGGL(rn::rn_occupancy_kernel, dim3((unsigned)((nocc * 64 + 255) / 256)), dim3(256), 0, c->stream, bits, c->ny,
@@ -464,7 +454,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
       if (hits && hits[first + i]) at_hits[(size_t)i] = bytes, bytes += align16(hit_bytes(v));
       wmax = std::max(wmax, v.width), hmax = std::max(hmax, v.height);
     }
-    { const int rc = grow(&c->d_rn_out, &c->rn_out_bytes, bytes); if (rc != VCY_OK) return rc; }
+    { const int rc = grow_device(&c->d_rn_out, &c->rn_out_bytes, bytes, c->stream, false); if (rc != VCY_OK) return rc; }
     char* base = (char*)c->d_rn_out;
     for (int i = 0; i < m; ++i) {
       const vcy_view& v = views[first + i];

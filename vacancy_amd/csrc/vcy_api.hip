@@ -1,5 +1,5 @@
 // C-ABI entry points of libvacancy_hip.so: lifetime, state access, halo, helpers.
-// The carving and extraction kernels live in carve_kernels.hip / mc_kernels.hip.
+// The carving and extraction kernels live in carve_kernels.hip / mc_kernels.hip (the extraction's host driver: mc_extract.hip).
 #include <algorithm>
 #include <cstdarg>
 #include <cstring>
@@ -86,6 +86,18 @@ void mesh_host_free(void* p) {
     return;
   }
   std::free(p);  // not ours (never happens for meshes this library returned)
+}
+
+int grow_device(void** p, size_t* have, size_t want, hipStream_t wait_for, bool wait) {
+  if (*have >= want) return VCY_OK;
+  if (wait) VCY_HIP_CHECK(hipStreamSynchronize(wait_for));
+  void* old = *p;
+  *p = nullptr;
+  *have = 0;
+  if (old) VCY_HIP_CHECK(hipFree(old));
+  VCY_HIP_CHECK(hipMalloc(p, want));  // (a failed hipMalloc leaves *p as it is: null)
+  *have = want;
+  return VCY_OK;
 }
 
 // sdf = lowest(), update_num = 0 over slab + halo (reference voxel_carver.cc:339, Voxel ctor)
@@ -1092,14 +1104,7 @@ int vcy_halo_copy_from(vcy_ctx* c, vcy_ctx* below) {
     // slab's width behind the copy -- widening is exact, narrowing saturates, and halo counters are only ever read as
     // `update_num >= 1` (convert_counts_kernel).
     const size_t tmp_need = (size_t)(2 * s) * below->cnt_bytes;
-    if (c->halo_tmp_bytes < tmp_need) {
-      VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-      (void)hipFree(c->d_halo_tmp);
-      c->d_halo_tmp = nullptr;
-      c->halo_tmp_bytes = 0;
-      VCY_HIP_CHECK(hipMalloc(&c->d_halo_tmp, tmp_need));
-      c->halo_tmp_bytes = tmp_need;
-    }
+    { const int rcg = grow_device(&c->d_halo_tmp, &c->halo_tmp_bytes, tmp_need, c->stream); if (rcg != VCY_OK) return rcg; }
     VCY_HIP_CHECK(hipMemcpyPeerAsync(c->d_halo_tmp, c->device, cnt_src, below->device, tmp_need, c->stream));
     const int rcc = convert_counts(c->stream, c->d_halo_tmp, below->cnt_bytes, c->d_cnt, c->cnt_bytes, 2 * s);
     if (rcc != VCY_OK) return rcc;
@@ -1306,13 +1311,7 @@ int vcy_carve_silhouette(vcy_ctx* c, const vcy_view* view, const uint8_t* mask, 
   const size_t off_scr = (npx + 255) / 256 * 256;
   const size_t need = off_scr + device_make_sdf_scratch_bytes(view->width, view->height);
   VCY_HIP_CHECK(hipStreamSynchronize(c->stream));  // the staging may still feed the previous call's kernels
-  if (c->sil_scratch_bytes < need) {
-    if (c->d_sil_scratch) VCY_HIP_CHECK(hipFree(c->d_sil_scratch));
-    c->d_sil_scratch = nullptr;
-    c->sil_scratch_bytes = 0;
-    VCY_HIP_CHECK(hipMalloc(&c->d_sil_scratch, need));
-    c->sil_scratch_bytes = need;
-  }
+  { const int rcg = grow_device(&c->d_sil_scratch, &c->sil_scratch_bytes, need, c->stream, false); if (rcg != VCY_OK) return rcg; }
   char* d = (char*)c->d_sil_scratch;
   float* d_img = nullptr;
   size_t cap = 0;
@@ -1409,14 +1408,7 @@ int vcy_make_sdf_batch_device(vcy_ctx* c, int n_views, const vcy_view* views, co
   const size_t sz_scr = (device_make_sdf_scratch_bytes(1, (int)max_px) + 255) / 256 * 256;
   // staging of the streamed entry point, grown on demand (page-locking 64 MB per call would cost more than the work)
   const size_t need_dev = (size_t)group * (sz_mask + sz_scr), need_pin = (size_t)group * sz_mask;
-  if (c->stream_pool_bytes < need_dev) {
-    VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->d_stream_pool) VCY_HIP_CHECK(hipFree(c->d_stream_pool));
-    c->d_stream_pool = nullptr;
-    c->stream_pool_bytes = 0;
-    VCY_HIP_CHECK(hipMalloc(&c->d_stream_pool, need_dev));
-    c->stream_pool_bytes = need_dev;
-  }
+  { const int rcg = grow_device(&c->d_stream_pool, &c->stream_pool_bytes, need_dev, c->stream); if (rcg != VCY_OK) return rcg; }
   if (c->pinned_bytes < need_pin) {
     if (c->aux_stream) VCY_HIP_CHECK(hipStreamSynchronize(c->aux_stream));
     if (c->h_pinned) VCY_HIP_CHECK(hipHostFree(c->h_pinned));
@@ -1496,14 +1488,7 @@ int vcy_carve_batch_silhouettes(vcy_ctx* c, int n_views, const vcy_view* views,
     }
     return e != hipSuccess;
   };
-  if (c->stream_pool_bytes < total) {
-    VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->d_stream_pool) VCY_HIP_CHECK(hipFree(c->d_stream_pool));
-    c->d_stream_pool = nullptr;
-    c->stream_pool_bytes = 0;
-    VCY_HIP_CHECK(hipMalloc(&c->d_stream_pool, total));
-    c->stream_pool_bytes = total;
-  }
+  { const int rcg = grow_device(&c->d_stream_pool, &c->stream_pool_bytes, total, c->stream); if (rcg != VCY_OK) return rcg; }
   // page-locked staging: pageable memory would be copied through the runtime's own bounce buffer by
   // one thread; here a few host threads fill it and the DMA engine takes it from there
   const size_t pinned_total = 2 * (size_t)per_set * sz_mask;
@@ -1730,6 +1715,23 @@ int vcy_make_sdf(const uint8_t* mask, int w, int h, const int32_t rmin[2], const
   return VCY_OK;
 }
 
+// What the extraction entry points share once their arguments are checked: the device, the views still pending, the
+// call, empty structs after a failure, and the wall time (call entry -> mesh arrays in host memory).
+static int timed_extract(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int which,
+                         vcy_mesh_normals* normals_out, int64_t* layer_faces) {
+  VCY_HIP_CHECK(hipSetDevice(c->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
+  const int rc = extract_iso(c, iso, linear_interp, out, which, normals_out, layer_faces);
+  if (rc != VCY_OK) {
+    vcy_mesh_free(out);
+    if (normals_out) vcy_mesh_normals_free(normals_out);
+    if (layer_faces) layer_faces[0] = layer_faces[1] = 0;
+  }
+  c->last_extract_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
 int vcy_extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
   if (!c) {
     set_error("voxel grid has not been initialized");
@@ -1737,13 +1739,7 @@ int vcy_extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out) {
   }
   if (!out) return VCY_ERR_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));
-  VCY_HIP_CHECK(hipSetDevice(c->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
-  const int rc = extract_iso(c, iso, linear_interp, out);
-  if (rc != VCY_OK) vcy_mesh_free(out);  // (whatever host arrays a failed extraction had already taken from the pool)
-  c->last_extract_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  return timed_extract(c, iso, linear_interp, out, 0, nullptr, nullptr);
 }
 
 int vcy_extract_iso_normals(vcy_ctx* c, double iso, int linear_interp, int which, vcy_mesh* out,
@@ -1765,16 +1761,7 @@ int vcy_extract_iso_normals(vcy_ctx* c, double iso, int linear_interp, int which
     return VCY_ERR_UNSUPPORTED;
   }
   if (which == 0) return vcy_extract_iso(c, iso, linear_interp, out);
-  VCY_HIP_CHECK(hipSetDevice(c->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
-  const int rc = extract_iso(c, iso, linear_interp, out, which, normals_out);
-  if (rc != VCY_OK) {
-    vcy_mesh_free(out);
-    vcy_mesh_normals_free(normals_out);
-  }
-  c->last_extract_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  return timed_extract(c, iso, linear_interp, out, which, normals_out, nullptr);
 }
 
 int vcy_extract_iso_normals_slab(vcy_ctx* c, double iso, int linear_interp, int which, vcy_mesh* out,
@@ -1797,17 +1784,7 @@ int vcy_extract_iso_normals_slab(vcy_ctx* c, double iso, int linear_interp, int 
               "the edge keys (vcy_set_param \"meshkeys\" 1)", c->z0, c->z1, c->nz);
     return VCY_ERR_INVALID_ARG;
   }
-  VCY_HIP_CHECK(hipSetDevice(c->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
-  const int rc = extract_iso(c, iso, linear_interp, out, which, normals_out, layer_faces);
-  if (rc != VCY_OK) {
-    vcy_mesh_free(out);
-    vcy_mesh_normals_free(normals_out);
-    layer_faces[0] = layer_faces[1] = 0;
-  }
-  c->last_extract_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  return timed_extract(c, iso, linear_interp, out, which, normals_out, layer_faces);
 }
 
 void vcy_mesh_normals_free(vcy_mesh_normals* n) {

@@ -171,10 +171,10 @@ struct vcy_ctx {
   float stream_wall_ms = 0.0f;
   void* h_pinned = nullptr;           // page-locked staging of the silhouettes, two sets
   size_t pinned_bytes = 0;
-  void* d_mc_tables = nullptr;        // marching-cubes case tables (mc_kernels.hip)
+  void* d_mc_tables = nullptr;        // marching-cubes case tables (mc_extract.hip)
   void* d_mc_scratch = nullptr;       // bit planes, active words, offsets, per-cell info
   size_t mc_scratch_bytes = 0;
-  void* d_mc_flags = nullptr;         // publication flags of the chained scans (mc_kernels.hip, scan_chained_kernel)
+  void* d_mc_flags = nullptr;         // publication flags of the chained scans (mc_kernels.hip scan_chained_kernel)
   uint32_t mc_scan_epoch = 0;         // ... and the epoch of the last scan (flags never hold a later one)
   void* h_mc_report = nullptr;        // 64 page-locked bytes mc_emit reports an extraction's counts in (extract_iso)
   int64_t mc_direct_bytes = (int64_t)32 << 20;  // "mcdirect": meshes guessed up to this size are written by mc_emit straight into host memory
@@ -260,7 +260,8 @@ int selftest_fused(hipStream_t stream);
 int flush_pending(vcy_ctx* ctx, bool from_carve = false);   // applies vcy_ctx::pending (no-op when empty)
 int check_carve_views(vcy_ctx* ctx, int n_views, const vcy_view* views);  // argument checks of the carve entry points (vcy_api.hip)
 int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy_ctx::carve_log, or -1 (vcy_api.hip)
-// mc_kernels.hip
+// mc_extract.hip: the host driver of the marching-cubes extraction (its kernels and their launches: mc_kernels.hip,
+// mc_normals.hip; what the three share: mc_common.h)
 // `which` (VCY_NORMALS_*) != 0: the normals of the mesh as well, into `normals_out` (mc_normals.hip)
 // `layer_faces` != null (vcy_extract_iso_normals_slab): the faces of the first and of the last own cell layer; a context
 // that owns a z-slab then gets the slab instance of the vertex normals (seam vertices left at zero)
@@ -290,6 +291,10 @@ int device_make_sdf_batch(hipStream_t stream, int n, const uint8_t* const* masks
 // host arrays of returned meshes (page-locked pool, vcy_api.hip); released by vcy_mesh_free
 void* mesh_host_alloc(size_t bytes, bool* pinned_out = nullptr);
 void mesh_host_free(void* p);
+// A device buffer cached in the context, grow-only: at least `want` bytes behind *p.  Before the old buffer is freed
+// the work on `wait_for` is waited for, unless the caller knows that nothing in flight uses it (`wait` false).  A
+// failed allocation leaves *p == nullptr and *have == 0.  (vcy_api.hip)
+int grow_device(void** p, size_t* have, size_t want, hipStream_t wait_for, bool wait = true);
 // utility kernels (vcy_api.hip)
 int ensure_count_width(vcy_ctx* ctx, int64_t max_count);  // d_cnt wide enough for counts up to max_count (vcy_api.hip)
 int count_width_for(const vcy_ctx* ctx, int64_t max_count);
