@@ -79,6 +79,17 @@ class VoxelGrid {
   int xy_slice_num_{0};
 };
 
+// How ColorMesh combines the photographs that see a vertex: vcy_color_option of vacancy_hip.h, where the rule is
+// defined.  No counterpart in the reference.
+enum class ColorMode { kMean = 0, kWeighted = 1, kBest = 2 };
+struct ColorOption {
+  ColorMode mode{ColorMode::kWeighted};                 // kWeighted: by |cos| between the normal and the viewing ray
+  SdfInterpolation interp{SdfInterpolation::kBilinear};
+  float depth_tolerance{-1.0f};                         // world units; < 0: 1.5 * the carver's resolution
+  float min_cos{0.0f};                                  // kWeighted, kBest: a view contributes iff its weight > min_cos
+  Eigen::Vector3f fallback = Eigen::Vector3f(128.0f, 128.0f, 128.0f);  // colour of a vertex no view sees
+};
+
 // One 6-connected component of the solid voxels (update_num >= 1 and sdf < iso_level): vcy_component of vacancy_hip.h.
 // No counterpart in the reference.
 struct VoxelComponent {
@@ -136,6 +147,14 @@ class VoxelCarver {
                      std::vector<std::array<std::int64_t, 3>>* counts, double iso_level = 0.0);
   bool HullAgreement(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
                      std::vector<std::array<std::int64_t, 3>>* counts);
+
+  // Fills mesh->vertex_colors() (float RGB in 0 .. 255, what WritePly emits) from the photographs, on the device
+  // (vcy_color_vertices): a view colours a vertex it sees -- whose camera depth is at most the hull's depth at its pixel,
+  // ray-cast here at iso_level, + depth_tolerance.  photos[i] belongs to cameras[i] and gives the view its size; the ROI
+  // is the whole image.  Computes the mesh's normals (CalcNormal) if it has none and the mode needs them.
+  // false + LOGE on an error, the colours then stay as they were.
+  bool ColorMesh(Mesh* mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
+                 const ColorOption& option = ColorOption(), double iso_level = 0.0);
 
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;

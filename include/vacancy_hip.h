@@ -523,6 +523,76 @@ int vcy_hull_agreement_host(const vcy_view* view, int n_slabs, const uint64_t* c
  * vcy_render_hull / vcy_render_hull_slab / vcy_hull_agreement, summed over its launches; copies of images are not included. */
 int vcy_last_render_ms(const vcy_ctx* ctx, float* device_ms);
 
+/* ---- colour of vertices from the input photographs ------------------------ */
+
+/* What colour a point of the surface has in the photographs that see it (no reference counterpart: the reference's Mesh
+ * carries vertex_colors_ and nothing fills them).  Inputs: n_vertices points p (float xyz, world; any points, not only an
+ * extraction's vertices), optionally one float normal n per point, n_views views, per view a photograph
+ * uint8 [height][width][3] (RGB, row-major; the sizes may differ between views) and a depth image float [height][width]
+ * with vcy_render_hull's meaning (camera depth, +inf on a miss), and a vcy_color_option.  All arithmetic is float, every
+ * product and every sum rounded on its own (no FMA), division and square root correctly rounded.
+ * Per vertex the accumulators start at S_c = 0, W = 0, n_used = 0, w_best = -1, best_view = -1; then, for each view i in
+ * ascending order, with R[r][c] = w2c[4 * r + c], t[r] = w2c[4 * r + 3]:
+ *   1. projection : the carve's own, pc[r] = t[r] + (R[r][0] * px + (R[r][1] * py + R[r][2] * pz)); the view is skipped
+ *                   if pc[2] < 0; pinhole u = fx / pc[2] * pc[0] + cx, w = fy / pc[2] * pc[1] + cy; ortho u = pc[0],
+ *                   w = pc[1].
+ *   2. ROI test   : the carve's in its complement form, inside iff u >= (float)roi_min[0] && w >= (float)roi_min[1] &&
+ *                   u <= (float)roi_max[0] && w <= (float)roi_max[1]: NaN coordinates are outside.  Skipped when outside.
+ *   3. occlusion  : the depth pixel is the carve's nearest-neighbour pixel, xi = (int)roundf(u), yi = (int)roundf(w)
+ *                   (halves away from zero), each clamped into the ROI.  The view sees the vertex iff
+ *                   pc[2] <= depth[yi][xi] + depth_tolerance -- one float add, one compare; a depth of +inf always sees
+ *                   it, a NaN depth never.  Skipped when it does not.
+ *   4. sample     : per channel c, of the texels converted (float)uint8.  VCY_INTERP_NN: the texel (xi, yi).
+ *                   VCY_INTERP_BILINEAR: x0 = (int)floorf(u), x1 = x0 + 1, then x0 = max(x0, roi_min[0]),
+ *                   x1 = min(x1, roi_max[0]), the same for y; lu = u - (float)x0, lv = w - (float)y0;
+ *                   sample_c = (((1 - lu) * (1 - lv) * s00 + lu * (1 - lv) * s10) + (1 - lu) * lv * s01) + lu * lv * s11
+ *                   with s00 = texel (x0, y0), s10 = (x1, y0), s01 = (x0, y1), s11 = (x1, y1), products left to right.
+ *   5. weight     : VCY_COLOR_MEAN: wt = 1; normals and min_cos are not read.  Otherwise the camera-space normal
+ *                   nc[r] = R[r][0] * nx + (R[r][1] * ny + R[r][2] * nz); pinhole
+ *                   len = sqrtf((pc0 * pc0 + pc1 * pc1) + pc2 * pc2), cos = ((nc0 * pc0 + nc1 * pc1) + nc2 * pc2) / len;
+ *                   ortho cos = nc[2]; wt = fabsf(cos) -- the absolute value is deliberate: marching cubes' winding
+ *                   fixes the sign of Mesh::CalcNormal, and faces that point away are removed by the occlusion test, not
+ *                   by the sign.  The view contributes iff wt > min_cos; a NaN weight (the normal of a vertex no face
+ *                   names) never does.
+ *   6. accumulate : S_c += wt * sample_c, W += wt, n_used += 1; if wt > w_best (strict: the lowest index wins a tie)
+ *                   w_best = wt, best_view = i, best_c = sample_c.
+ * Result: VCY_COLOR_MEAN and VCY_COLOR_WEIGHTED rgb_c = S_c / W, VCY_COLOR_BEST rgb_c = best_c; with n_used == 0
+ * rgb = fallback.  rgb is float in 0 .. 255, not rounded -- the convention of Mesh::vertex_colors_. */
+enum { VCY_COLOR_MEAN = 0, VCY_COLOR_WEIGHTED = 1, VCY_COLOR_BEST = 2 };
+typedef struct vcy_color_option {
+  int32_t mode;            /* VCY_COLOR_MEAN, VCY_COLOR_WEIGHTED, VCY_COLOR_BEST */
+  int32_t interp;          /* VCY_INTERP_NN / VCY_INTERP_BILINEAR, the carve's two samplers */
+  float   depth_tolerance; /* world units, >= 0 and finite */
+  float   min_cos;         /* modes 1, 2: a view contributes iff its weight > min_cos; finite, >= 0 */
+  float   fallback[3];     /* colour of a vertex no view contributes to */
+} vcy_color_option;
+
+/* The definition above, serial, on the host (no GPU, no context).  vertices / normals: 3 floats per vertex (normals may
+ * be NULL in VCY_COLOR_MEAN); photos / depth: n_views pointers each, all required.  rgb_out: 3 * n_vertices floats;
+ * n_used_out, best_view_out: n_vertices int32 each (best_view -1 when no view contributes), either may be NULL.
+ * n_vertices == 0 is VCY_OK and writes nothing.  VCY_ERR_INVALID_ARG, nothing written, for a NULL required pointer,
+ * n_views <= 0, a view vcy_render_hull would refuse, an unknown mode or interp, a negative or non-finite depth_tolerance or
+ * min_cos, or NULL normals in modes 1 and 2. */
+int vcy_color_vertices_host(int64_t n_vertices, const float* vertices, const float* normals, int n_views,
+                            const vcy_view* views, const uint8_t* const* photos, const float* const* depth,
+                            const vcy_color_option* option, float* rgb_out, int32_t* n_used_out, int32_t* best_view_out);
+/* The same on the device, bit for bit (one lane per vertex, the view loop inside the lane; views in chunks of 64 with the
+ * accumulators carried between them, so any n_views >= 1).  depth_host != NULL: the depth images are uploaded and used as
+ * given, iso_level is ignored and the context only names the device and the stream -- any context will do, a z-slab
+ * included: this is how a sharded caller colours (with the merged depth of vcy_render_merge_host), and where a depth
+ * sensor's image goes.  depth_host == NULL: the library ray-casts the hull itself at iso_level, every view with its own
+ * ROI, and the depth images stay in device memory (none crosses to the host or back); this applies queued ("defer") views
+ * first, as the render does, and needs a context that owns the whole grid -- VCY_ERR_UNSUPPORTED otherwise.  The state is
+ * never changed; a fresh context renders all misses without its lazy fill being written.  Arguments and errors as for
+ * the host function. */
+int vcy_color_vertices(vcy_ctx* ctx, double iso_level, int64_t n_vertices, const float* vertices, const float* normals,
+                       int n_views, const vcy_view* views, const uint8_t* const* photos_host, const float* const* depth_host,
+                       const vcy_color_option* option, float* rgb_out, int32_t* n_used_out, int32_t* best_view_out);
+/* Milliseconds between HIP events around the colouring launches (the packing of the photographs to one dword per texel
+ * and the colouring kernel) of the last vcy_color_vertices, summed over its chunks of views.  Copies and the ray-cast are
+ * not included; the ray-cast of a call without depth images is in vcy_last_render_ms. */
+int vcy_last_color_ms(const vcy_ctx* ctx, float* device_ms);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and

@@ -89,6 +89,22 @@ class MeshNormals(C.Structure):
 
 
 VCY_NORMALS_VERTEX, VCY_NORMALS_FACE = 1, 2
+VCY_COLOR_MEAN, VCY_COLOR_WEIGHTED, VCY_COLOR_BEST = 0, 1, 2
+
+
+class ColorOption(C.Structure):
+    """vcy_color_option: how vcy_color_vertices combines the views that see a vertex."""
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("interp", C.c_int32),
+        ("depth_tolerance", C.c_float),
+        ("min_cos", C.c_float),
+        ("fallback", C.c_float * 3),
+    ]
+
+    def __init__(self, mode=VCY_COLOR_WEIGHTED, interp=VCY_INTERP_BILINEAR, depth_tolerance=0.0, min_cos=0.0,
+                 fallback=(128.0, 128.0, 128.0)):
+        super().__init__(mode, interp, depth_tolerance, min_cos, (C.c_float * 3)(*fallback))
 
 
 class Component(C.Structure):
@@ -181,6 +197,10 @@ def load():
         "vcy_render_merge_host": (C.c_int, [P(View), C.c_int, P(vp), P(vp), P(vp), vp, vp, vp]),
         "vcy_hull_agreement_host": (C.c_int, [P(View), C.c_int, P(vp), vp, vp]),
         "vcy_last_render_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_color_vertices_host": (C.c_int, [C.c_int64, vp, vp, C.c_int, P(View), P(vp), P(vp), P(ColorOption), vp, vp, vp]),
+        "vcy_color_vertices": (C.c_int, [vp, C.c_double, C.c_int64, vp, vp, C.c_int, P(View), P(vp), P(vp), P(ColorOption),
+                                         vp, vp, vp]),
+        "vcy_last_color_ms": (C.c_int, [vp, P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_mesh_normals_seam_sum": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),

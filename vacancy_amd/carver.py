@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import CarverOption, Mesh, UpdateOption, View, make_view  # noqa: F401
+from .capi import CarverOption, ColorOption, Mesh, UpdateOption, View, make_view  # noqa: F401
 
 
 def _p(a):
@@ -78,6 +78,47 @@ def mesh_normals_seam_sum(n_vertices, faces, face_normals, face_begin, face_end,
     if rc != 0:
         raise RuntimeError(last_error())
     return vn
+
+
+def _color_args(vertices, views, photos, normals, depth, mode, interp, depth_tolerance, min_cos, fallback):
+    """The arrays and ctypes arguments vcy_color_vertices and vcy_color_vertices_host share; the first element keeps every
+    array alive for the call."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    vs = list(views)
+    n = len(vs)
+    ph = [np.ascontiguousarray(p, np.uint8) for p in photos]
+    if len(ph) != n or any(p.shape != (w.height, w.width, 3) for p, w in zip(ph, vs)):
+        raise ValueError("one height x width x 3 uint8 photograph per view")
+    nr = None
+    if normals is not None:
+        nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if nr.shape != v.shape:
+            raise ValueError("one normal per vertex")
+    dp = None
+    if depth is not None:
+        dp = [np.ascontiguousarray(d, np.float32) for d in depth]
+        if len(dp) != n or any(d.shape != (w.height, w.width) for d, w in zip(dp, vs)):
+            raise ValueError("one height x width float32 depth image per view")
+    opt = ColorOption(mode, interp, depth_tolerance, min_cos, fallback)
+    out = {"rgb": np.zeros((len(v), 3), np.float32), "n_used": np.zeros(len(v), np.int32),
+           "best_view": np.zeros(len(v), np.int32)}
+    arr = (View * max(n, 1))(*vs)
+    pp = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in ph])
+    dpp = (C.c_void_p * n)(*[d.ctypes.data for d in dp]) if dp is not None else None
+    args = (len(v), _p(v), _p(nr) if nr is not None else None, n, arr, pp, dpp, C.byref(opt), _p(out["rgb"]),
+            _p(out["n_used"]), _p(out["best_view"]))
+    return (v, nr, ph, dp, opt, arr, pp, dpp), args, out
+
+
+def color_vertices_host(vertices, views, photos, depth, normals=None, mode=capi.VCY_COLOR_WEIGHTED,
+                        interp=capi.VCY_INTERP_BILINEAR, depth_tolerance=0.0, min_cos=0.0, fallback=(128, 128, 128)):
+    """vcy_color_vertices_host: the colour of every vertex from the photographs of the views that see it (definition:
+    include/vacancy_hip.h), serial, no GPU needed.  `depth`: one float32 depth image per view with RenderHull's meaning.
+    Returns {"rgb": float32 [n, 3] in 0 .. 255, "n_used": int32 [n], "best_view": int32 [n], -1 where no view contributes}."""
+    keep, args, out = _color_args(vertices, views, photos, normals, depth, mode, interp, depth_tolerance, min_cos, fallback)
+    if capi.load().vcy_color_vertices_host(*args) != 0:
+        raise RuntimeError(last_error())
+    return out
 
 
 class VoxelCarver:
@@ -508,6 +549,26 @@ class VoxelCarver:
         ms = C.c_float()
         self._lib.vcy_last_render_ms(self._ctx, C.byref(ms))
         return ms.value
+
+    # -- colour of vertices from the photographs (no reference counterpart; definition: include/vacancy_hip.h)
+    def ColorVertices(self, vertices, views, photos, normals=None, depth=None, mode=capi.VCY_COLOR_WEIGHTED,
+                      interp=capi.VCY_INTERP_BILINEAR, depth_tolerance=None, min_cos=0.0, fallback=(128, 128, 128),
+                      iso_level=0.0):
+        """vcy_color_vertices: per vertex the mean (VCY_COLOR_MEAN), the mean weighted by |cos| between normal and viewing
+        ray (VCY_COLOR_WEIGHTED) or the most frontal sample (VCY_COLOR_BEST) of the photographs of the views that see it.
+        A view sees a vertex whose camera depth is at most the hull's depth at its pixel + depth_tolerance (default: 1.5
+        voxels).  `depth`: one image per view (RenderHull's, a merged slab render, a sensor's) -- any context will do then;
+        None: the hull is ray-cast here at `iso_level` and the depth never leaves the device (whole-grid contexts only).
+        Returns {"rgb": float32 [n, 3] in 0 .. 255, "n_used", "best_view" (-1: none): int32 [n], "device_ms"}."""
+        if depth_tolerance is None:
+            depth_tolerance = 1.5 * self.option.resolution
+        keep, args, out = _color_args(vertices, views, photos, normals, depth, mode, interp, depth_tolerance, min_cos, fallback)
+        if self._lib.vcy_color_vertices(self._ctx, iso_level, *args) != 0:
+            raise RuntimeError(last_error())
+        ms = C.c_float()
+        self._lib.vcy_last_color_ms(self._ctx, C.byref(ms))
+        out["device_ms"] = ms.value
+        return out
 
     # -- state access
     def download(self):

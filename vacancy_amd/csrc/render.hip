@@ -387,11 +387,12 @@ int ensure_planes(vcy_ctx* c) {
 }
 
 // vcy_render_hull (masks == null), vcy_hull_agreement (masks, counts) and vcy_render_hull_slab (slab: any context, hit
-// bits) behind their argument checks
+// bits) behind their argument checks; depth_dev (render_depth_device: one launch's views): the depth image of every view
+// stays in vcy_ctx::d_rn_out, is not copied to the host, and its device address is handed back
 int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* const* depth, int64_t* const* voxel,
            uint8_t* const* axis, const uint8_t* const* masks, int64_t* counts, const char* who, bool slab = false,
-           uint64_t* const* hits = nullptr) {
-  if (n_views <= 0 || !views || (masks && !counts)) {
+           uint64_t* const* hits = nullptr, const float** depth_dev = nullptr) {
+  if (n_views <= 0 || !views || (masks && !counts) || (depth_dev && (depth || n_views > rn::kMaxViewsPerLaunch))) {
     set_error("%s: invalid argument", who);
     return VCY_ERR_INVALID_ARG;
   }
@@ -447,7 +448,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
     for (int i = 0; i < m; ++i) {
       const vcy_view& v = views[first + i];
       const size_t px = (size_t)v.width * (size_t)v.height;
-      if (depth && depth[first + i]) at_depth[(size_t)i] = bytes, bytes += align16(px * sizeof(float));
+      if ((depth && depth[first + i]) || depth_dev) at_depth[(size_t)i] = bytes, bytes += align16(px * sizeof(float));
       if (voxel && voxel[first + i]) at_voxel[(size_t)i] = bytes, bytes += align16(px * sizeof(int64_t));
       if (axis && axis[first + i]) at_axis[(size_t)i] = bytes, bytes += align16(px);
       if (masks) at_mask[(size_t)i] = bytes, bytes += align16(px);
@@ -511,7 +512,8 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
     for (int i = 0; i < m; ++i) {
       const vcy_view& v = views[first + i];
       const size_t px = (size_t)v.width * (size_t)v.height;
-      if (at_depth[(size_t)i])
+      if (depth_dev) depth_dev[first + i] = (const float*)(base + at_depth[(size_t)i]);
+      else if (at_depth[(size_t)i])
         VCY_HIP_CHECK(hipMemcpyAsync(depth[first + i], base + at_depth[(size_t)i], px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
       if (at_voxel[(size_t)i])
         VCY_HIP_CHECK(hipMemcpyAsync(voxel[first + i], base + at_voxel[(size_t)i], px * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -541,6 +543,10 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
 }
 
 }  // namespace
+
+int render_depth_device(vcy_ctx* c, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who) {
+  return render(c, iso, n_views, views, nullptr, nullptr, nullptr, nullptr, nullptr, who, false, nullptr, depth_dev);
+}
 
 void render_release(vcy_ctx* c) {
   (void)hipFree(c->d_rn_bits);

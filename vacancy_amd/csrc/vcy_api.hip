@@ -529,6 +529,7 @@ void vcy_destroy(vcy_ctx* c) {
   (void)hipFree(c->d_cc_roots);
   (void)hipFree(c->d_cc_seam);
   render_release(c);
+  color_release(c);
   if (c->h_cc_report) (void)hipHostFree(c->h_cc_report);
   if (c->ev_cc_begin) (void)hipEventDestroy(c->ev_cc_begin);
   if (c->ev_cc_end) (void)hipEventDestroy(c->ev_cc_end);

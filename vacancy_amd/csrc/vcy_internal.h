@@ -232,6 +232,12 @@ struct vcy_ctx {
   float last_render_device_ms = 0.0f;
   int ray_skip = 1;                   // "rayskip": rays step over bricks without a solid voxel (0: crossing by crossing)
 
+  // colours of vertices (color.hip); grow-only
+  void* d_cl_buf = nullptr;           // view records, vertices, normals, results, carried accumulators and the images of one chunk of views
+  size_t cl_buf_bytes = 0;
+  hipEvent_t ev_cl_begin = nullptr, ev_cl_end = nullptr;
+  float last_color_device_ms = 0.0f;
+
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
 
@@ -274,6 +280,11 @@ int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int 
 int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
 // render.hip: vcy_render_hull, vcy_hull_agreement, vcy_render_hull_slab, vcy_cell_planes, vcy_last_render_ms
 void render_release(vcy_ctx* ctx);  // frees what the ray-cast keeps on the context (vcy_destroy)
+// vcy_render_hull's depth images of up to 64 views (one launch), left in device memory: depth_dev[i] points into
+// vcy_ctx::d_rn_out and holds until the context next renders; waits for the launch; vcy_last_render_ms as for the render
+int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who);
+// color.hip: vcy_color_vertices, vcy_color_vertices_host, vcy_last_color_ms
+void color_release(vcy_ctx* ctx);   // frees what the colouring keeps on the context (vcy_destroy)
 // render_merge.hip (host code only): vcy_render_merge_host, vcy_hull_agreement_host, and the view checks of the ray-cast
 int check_render_view(const vcy_view* v, int i);
 // sdf2d.hip

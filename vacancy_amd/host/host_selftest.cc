@@ -1,5 +1,6 @@
 // CPU-only check of the facade's host utilities (no GPU calls): PNG decode of the bunny masks,
 // TUM pose -> w2c arithmetic.  Prints values that tests/test_host.py compares with fixtures.
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <chrono>
@@ -339,6 +340,81 @@ int main(int argc, char* argv[]) {
                     depth.width() == 320 && hull.height() == 240;
     std::printf("SHARDRENDER %d %d %d %d %d %d %d %d\n", sh.slab_count(), r0 ? 1 : 0, r1 ? 1 : 0, r2 ? 1 : 0, r3 ? 1 : 0,
                 r4 ? 1 : 0, r5 ? 1 : 0, r6 ? 1 : 0);
+    return 0;
+  }
+  if (argc > 3 && std::string(argv[2]) == "colormesh") {
+    // needs a device: VoxelCarver::ColorMesh on the synthetic sphere scene (vacancy_amd/synth.py: an N^3 grid, cameras on a
+    // Fibonacci sphere at distance 2 N, a sphere of radius 0.35 N) with a photograph of one constant colour per view.
+    //   host_selftest <data dir> colormesh <out dir>
+    //   writes <out>/colored.ply (ASCII), prints one VIEWCOLOR <r> <g> <b> per view, FALLBACK <r> <g> <b> and
+    //   COLORMESH <ok> <vertices> <colours> <colours of the kBest run that are no view's colour> <bad calls refused>
+    const int n = 24, n_views = 8, w = 48, h = 40;
+    vacancy::VoxelCarverOption option;
+    option.bb_min = Eigen::Vector3f(-0.5f * n, -0.5f * n, -0.5f * n);
+    option.bb_max = Eigen::Vector3f(0.5f * n, 0.5f * n, 0.5f * n);
+    option.resolution = 1.0f;
+    vacancy::VoxelCarver carver(option), never(option);
+    if (!carver.Init()) return 3;
+    const double radius = 0.35 * n, dist = 2.0 * n, lim = radius * radius / (dist * dist - radius * radius);
+    std::vector<std::shared_ptr<vacancy::Camera>> cams;
+    std::vector<const vacancy::Camera*> cam_ptrs;
+    std::vector<vacancy::Image1b> sils;
+    std::vector<vacancy::Image3b> photos;
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < n_views; ++i) {
+      const double y = 1.0 - 2.0 * (i + 0.5) / n_views, r = std::sqrt(std::max(0.0, 1.0 - y * y));
+      const double phi = i * pi * (3.0 - std::sqrt(5.0));
+      const Eigen::Vector3d pos(dist * r * std::cos(phi), dist * y, dist * r * std::sin(phi));
+      std::shared_ptr<vacancy::PinholeCamera> cam(
+          new vacancy::PinholeCamera(w, h, vacancy::c2w(pos, Eigen::Vector3d(0.0, 0.0, 0.0), Eigen::Vector3d(0.0, 1.0, 0.0)), 60.0f));
+      vacancy::Image1b sil(w, h);
+      vacancy::Image3b photo(w, h);
+      for (int v = 0; v < h; ++v)
+        for (int u = 0; u < w; ++u) {
+          const double du = (u - cam->principal_point()[0]) / cam->focal_length()[0];
+          const double dv = (v - cam->principal_point()[1]) / cam->focal_length()[1];
+          sil.at(u, v, 0) = du * du + dv * dv <= lim ? 255 : 0;
+          photo.at(u, v, 0) = (unsigned char)(30 + 25 * i), photo.at(u, v, 1) = (unsigned char)(220 - 20 * i);
+          photo.at(u, v, 2) = (unsigned char)(60 + (i * 37) % 120);
+        }
+      std::printf("VIEWCOLOR %d %d %d\n", 30 + 25 * i, 220 - 20 * i, 60 + (i * 37) % 120);
+      cams.push_back(cam);
+      cam_ptrs.push_back(cam.get());
+      sils.push_back(sil);
+      photos.push_back(photo);
+    }
+    if (!carver.Carve(cam_ptrs, sils)) return 7;
+    vacancy::Mesh mesh;
+    carver.ExtractIsoSurface(&mesh);
+    vacancy::ColorOption copt;  // kWeighted, bilinear, 1.5 voxels of tolerance
+    copt.fallback = Eigen::Vector3f(100.0f, 150.0f, 90.0f);
+    std::printf("FALLBACK 100 150 90\n");
+    bool ok = carver.ColorMesh(&mesh, cam_ptrs, photos, copt);
+    ok = ok && !mesh.normals().empty() && mesh.WritePly(std::string(argv[3]) + "/colored.ply");
+    const size_t nv = mesh.vertices().size(), nc = mesh.vertex_colors().size();
+    // kBest with the NN sampler: every colour is one view's colour, or the fallback
+    vacancy::Mesh best = mesh;
+    copt.mode = vacancy::ColorMode::kBest;
+    copt.interp = vacancy::SdfInterpolation::kNn;
+    ok = ok && carver.ColorMesh(&best, cam_ptrs, photos, copt) && best.vertex_colors().size() == nv;
+    size_t foreign = 0;
+    for (const Eigen::Vector3f& c : best.vertex_colors()) {
+      bool known = c[0] == 100.0f && c[1] == 150.0f && c[2] == 90.0f;
+      for (int i = 0; i < n_views; ++i)
+        known = known || (c[0] == (float)(30 + 25 * i) && c[1] == (float)(220 - 20 * i) && c[2] == (float)(60 + (i * 37) % 120));
+      foreign += known ? 0 : 1;
+    }
+    // refused, the colours untouched: no photographs, one photograph too few, a null mesh, a carver without a grid
+    int refused = 0;
+    std::vector<vacancy::Image3b> fewer(photos.begin(), photos.end() - 1);
+    refused += carver.ColorMesh(&best, cam_ptrs, fewer, copt) ? 0 : 1;
+    refused += carver.ColorMesh(&best, std::vector<const vacancy::Camera*>(), std::vector<vacancy::Image3b>(), copt) ? 0 : 1;
+    refused += carver.ColorMesh(nullptr, cam_ptrs, photos, copt) ? 0 : 1;
+    refused += never.ColorMesh(&best, cam_ptrs, photos, copt) ? 0 : 1;
+    copt.min_cos = -1.0f;
+    refused += carver.ColorMesh(&best, cam_ptrs, photos, copt) ? 0 : 1;
+    ok = ok && best.vertex_colors().size() == nv;
+    std::printf("COLORMESH %d %zu %zu %zu %d\n", ok ? 1 : 0, nv, nc, foreign, refused);
     return 0;
   }
   if (argc > 3 && std::string(argv[2]) == "normals") {

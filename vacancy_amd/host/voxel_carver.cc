@@ -419,6 +419,55 @@ bool VoxelCarver::HullAgreement(const std::vector<Camera>& cameras, const std::v
   return HullAgreement(ptrs, silhouettes, counts);
 }
 
+bool VoxelCarver::ColorMesh(Mesh* mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
+                            const ColorOption& option, double iso_level) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (!mesh || cameras.size() != photos.size() || cameras.empty()) {
+    LOGE("VoxelCarver::ColorMesh needs a mesh and one photograph per camera, at least one (%zu cameras, %zu photographs)\n",
+         cameras.size(), photos.size());
+    return false;
+  }
+  const int n = static_cast<int>(cameras.size());
+  std::vector<vcy_view> views(n);
+  std::vector<const uint8_t*> data(n);
+  for (int i = 0; i < n; ++i) {
+    const Image3b& p = photos[i];
+    bool known = true;
+    if (!cameras[i] || p.empty()) {
+      LOGE("VoxelCarver::ColorMesh: view %d has no camera or an empty photograph\n", i);
+      return false;
+    }
+    views[i] = ToView(*cameras[i], Eigen::Vector2i(0, 0), Eigen::Vector2i(p.width() - 1, p.height() - 1), p.width(),
+                      p.height(), &known);
+    if (!known) return false;  // (ToView has logged the camera type)
+    data[i] = p.data().data();
+  }
+  vcy_color_option o;
+  o.mode = static_cast<int32_t>(option.mode);
+  o.interp = static_cast<int32_t>(option.interp);
+  o.depth_tolerance = option.depth_tolerance < 0.0f ? 1.5f * impl_->option.resolution : option.depth_tolerance;
+  o.min_cos = option.min_cos;
+  for (int k = 0; k < 3; ++k) o.fallback[k] = option.fallback[k];
+  const size_t nv = mesh->vertices().size();
+  if (option.mode != ColorMode::kMean && mesh->normals().size() != nv) mesh->CalcNormal();
+  const float* normals = option.mode != ColorMode::kMean ? reinterpret_cast<const float*>(mesh->normals().data()) : nullptr;
+  static_assert(sizeof(Eigen::Vector3f) == 3 * sizeof(float), "packed vector layout");
+  std::vector<Eigen::Vector3f> colors(nv);
+  const int rc = vcy_color_vertices(impl_->ctx, iso_level, static_cast<int64_t>(nv),
+                                    reinterpret_cast<const float*>(mesh->vertices().data()), normals, n, views.data(),
+                                    data.data(), nullptr, &o, reinterpret_cast<float*>(colors.data()), nullptr, nullptr);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  mesh->set_vertex_colors(colors);
+  return true;
+}
+
 bool VoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!impl_->ctx) {
     LOGE("voxel grid has not been initialized\n");
