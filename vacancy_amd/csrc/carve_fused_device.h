@@ -269,16 +269,19 @@ __device__ __forceinline__ void raw_tile_wait() { asm volatile("s_waitcnt vmcnt(
 
 // min over the wave (NaN operands are ignored, like the `dist > s` test ignores them): six DPP
 // v_min_f32 (row reduction, then row_bcast 15 / 31) and one readlane.  Written in assembly because
-// the compiler expands a DPP move + canonicalise + min per step; the s_nop covers the VALU-write ->
-// DPP-read hazard the assembler does not see inside an asm block.
+// the compiler expands a DPP move + canonicalise + min per step.  ONE block: the s_nop 1 in front of every
+// step is the VALU-write -> DPP-read hazard (two wait states), which the assembler does not see inside an
+// asm block -- and as six blocks the compiler, which does not see into them either, put an s_nop of its own
+// around every one.
 __device__ __forceinline__ float wave_min(float v) {
-#define VCY_DPP_MIN(CTRL) asm volatile("s_nop 1\n\tv_min_f32_dpp %0, %0, %0 " CTRL : "+v"(v))
-  VCY_DPP_MIN("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf");
-  VCY_DPP_MIN("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf");
-  VCY_DPP_MIN("row_half_mirror row_mask:0xf bank_mask:0xf");
-  VCY_DPP_MIN("row_mirror row_mask:0xf bank_mask:0xf");  // every lane of a 16-lane row holds the row minimum
-  VCY_DPP_MIN("row_bcast:15 row_mask:0xa bank_mask:0xf");  // rows 1, 3 <- min(own, row 0 / 2)
-  VCY_DPP_MIN("row_bcast:31 row_mask:0xc bank_mask:0xf");  // rows 2, 3 <- min(own, row 1): lane 63 = all
+#define VCY_DPP_MIN(CTRL) "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 " CTRL "\n\t"
+  asm volatile(VCY_DPP_MIN("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
+               VCY_DPP_MIN("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+               VCY_DPP_MIN("row_half_mirror row_mask:0xf bank_mask:0xf")
+               VCY_DPP_MIN("row_mirror row_mask:0xf bank_mask:0xf")      // every lane of a 16-lane row holds the row minimum
+               VCY_DPP_MIN("row_bcast:15 row_mask:0xa bank_mask:0xf")    // rows 1, 3 <- min(own, row 0 / 2)
+               VCY_DPP_MIN("row_bcast:31 row_mask:0xc bank_mask:0xf")    // rows 2, 3 <- min(own, row 1): lane 63 = all
+               : "+v"(v));
 #undef VCY_DPP_MIN
   return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), 63));
 }

@@ -605,6 +605,79 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
 #endif
   // ---- views ------------------------------------------------------------------------------
   int n_processed = 0;  // (wave-uniform: an SGPR; only read with "paircount" on)
+  const bool is_ortho = GEN && mode.ortho != 0, is_nn = GEN && mode.interp == VCY_INTERP_NN;
+  // What a view's run works with, set by begin_view() for the view `vi`: its parameters, this brick's record of x
+  // products, the next live view (whose tile is in flight), the tile's geometry, c1 + c2 of this lane.
+  // (the view records are read-only for the whole launch: the constant address space keeps their fields in scalar
+  // loads -- through a plain pointer that is carried from one loop to the other they became vector loads with a
+  // vmcnt(0) wait in front of every run)
+  typedef const ViewParams __attribute__((address_space(4))) cview;
+  cview* vp = nullptr;
+  cfloat_ptr c0 = nullptr;
+  int vnext = vi_end;
+  float pitchf = 0.0f;
+  int base = 0, big_pitch = 0;
+  const lds_float* rawcur = nullptr;
+  float h12x = 0.0f, h12y = 0.0f, h12z = 0.0f;
+  auto begin_view = [&]() {
+    const int vv = kRows ? (vi & 7) : vi;  // the view of pair vi
+    const ViewParams& v = views[vv].v;
+    vp = (cview*)&v;
+    // this view's record of the wave brick's x products: (x, y) pairs at [2 k], z at [16 + k]
+    c0 = (cfloat_ptr)(c0_all + ((size_t)vv * (nxp / WX) + (x_first / WX)) * kC0Stride);
+    // stage this view's tile (wave-private: program order is enough)
+    VCY_SETPRIO(3);
+    wave_lds_fence();
+    if (kRaw) {
+      raw_tile_wait();  // this view's pixels have landed in raw_buf(cur)
+    } else {
+      tile_fill(v, tile_of(vi), lane, (float*)tile);
+    }
+    wave_lds_fence();
+    // the next live view's tile is fetched while this one is computed
+    vnext = next_view(live, vi);
+    if (kRaw && vnext < vi_end) raw_prefetch(views[kRows ? (vnext & 7) : vnext].v, tile_of(vnext), lane, raw_buf(cur ^ 1));
+    ++n_processed;
+    pitchf = tile_of(vi).pitchf;
+    base = tile_of(vi).base;
+    big_pitch = kRaw ? 16 : (int)pitchf;  // pixels per row of the big tile
+    rawcur = (const lds_float*)raw_buf(cur);
+    // c1 + c2 of this lane's (y, z): the inner sum of pc = t + (c0 + (c1 + c2)) (voxel_carver.cc:453)
+    h12x = vp->r[0][1] * py + vp->r[0][2] * pz, h12y = vp->r[1][1] * py + vp->r[1][2] * pz;
+    h12z = vp->r[2][1] * py + vp->r[2][2] * pz;
+    VCY_SETPRIO(0);
+    VCY_PT(1);
+  };
+  // Behind a view's run: what the views that follow ask of the state, and the step to the next live view.
+  auto end_view = [&](bool brick_moved) {
+    VCY_SETPRIO(3);
+    if (brick_moved) VCY_PT_COUNT(11);
+    none_touched = false;  // (a checked view may have touched only some voxels)
+    if (!kOne) refresh_all_touched();  // (only the views that follow ask)
+
+    // state moved: some of the remaining views may have become droppable (min(sdf) only grows)
+    // (an unchanged brick leaves every bound comparison as it was)
+    if (!kOne && want_bound && UPDATE == VCY_UPDATE_MAX && brick_moved) {
+      live = live_views();
+      const int v2 = next_view(live, vi);
+      if (v2 != vnext) {
+        vnext = v2;
+        // (the dropped view's pixels may still be arriving in that buffer: loads complete in order)
+        if (kRaw && vnext < vi_end) raw_prefetch(views[kRows ? (vnext & 7) : vnext].v, tile_of(vnext), lane, raw_buf(cur ^ 1));
+      }
+    }
+    vi = vnext;
+    cur ^= 1;
+    VCY_PT(5);
+  };
+  // TileInfo::sure of the view end_view() stepped to when it is another select-free run of the brick in registers
+  // (bit 0 set), else 0.
+  auto next_fast_bits = [&]() -> int {
+    if (kOne || vi >= vi_end) return 0;
+    if (kRows && (vi >> 3) != jc) return 0;  // (the pair belongs to another brick of the segment)
+    const int bits = __builtin_amdgcn_readfirstlane(tile_of(vi).sure);
+    return (bits & 1) != 0 ? bits : 0;
+  };
   while (vi < vi_end) {
     if constexpr (kRows) {
       if ((vi >> 3) != jc) {  // (uniform) the next pair belongs to another brick of the segment
@@ -622,28 +695,8 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
         }
       }
     }
-    const int vv = kRows ? (vi & 7) : vi;  // the view of pair vi
-    const ViewParams& v = views[vv].v;
-    // this view's record of the wave brick's x products: (x, y) pairs at [2 k], z at [16 + k]
-    cfloat_ptr c0 = (cfloat_ptr)(c0_all + ((size_t)vv * (nxp / WX) + (x_first / WX)) * kC0Stride);
-    // stage this view's tile (wave-private: program order is enough)
-    VCY_SETPRIO(3);
-    wave_lds_fence();
-    if (kRaw) {
-      raw_tile_wait();  // this view's pixels have landed in raw_buf(cur)
-    } else {
-      tile_fill(v, tile_of(vi), lane, (float*)tile);
-    }
-    wave_lds_fence();
-    // the next live view's tile is fetched while this one is computed
-    int vnext = next_view(live, vi);
-    if (kRaw && vnext < vi_end) raw_prefetch(views[kRows ? (vnext & 7) : vnext].v, tile_of(vnext), lane, raw_buf(cur ^ 1));
-    ++n_processed;
-    const float pitchf = tile_of(vi).pitchf;
-    const int base = tile_of(vi).base;
-    const int big_pitch = kRaw ? 16 : (int)pitchf;  // pixels per row of the big tile
+    begin_view();
     // the four taps of the sample whose upper left pixel is tile element idx
-    const lds_float* rawcur = (const lds_float*)raw_buf(cur);
     auto quad_at = [&](unsigned idx) -> float4 {
       if constexpr (kRaw) {
         const lds_float* p = rawcur + idx;
@@ -655,21 +708,15 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       }
     };
 
-    const float lo_x = tile_of(vi).lo_x, hi_x = tile_of(vi).hi_x;
-    const float lo_y = tile_of(vi).lo_y, hi_y = tile_of(vi).hi_y;
-    const bool is_ortho = GEN && mode.ortho != 0, is_nn = GEN && mode.interp == VCY_INTERP_NN;
-    // c1 + c2 of this lane's (y, z): the inner sum of pc = t + (c0 + (c1 + c2)) (voxel_carver.cc:453)
-    const float h12x = v.r[0][1] * py + v.r[0][2] * pz, h12y = v.r[1][1] * py + v.r[1][2] * pz;
-    const float h12z = v.r[2][1] * py + v.r[2][2] * pz;
-    VCY_SETPRIO(0);
-    VCY_PT(1);
-
     // Straight-line fast path for the 8 voxels of this thread (no divergent control flow, so
     // the eight LDS reads and the arithmetic interleave); voxels the tile does not cover are
     // only recorded here and handled below.  SURE: the prologue has proved that every voxel of the
     // brick samples inside this tile (TileInfo::sure), so the per-voxel tests are compiled out.
     auto carve_view = [&](auto sure_tag) {
       constexpr bool SURE = decltype(sure_tag)::value;
+      cview& v = *vp;
+      const float lo_x = tile_of(vi).lo_x, hi_x = tile_of(vi).hi_x;
+      const float lo_y = tile_of(vi).lo_y, hi_y = tile_of(vi).hi_y;
       bool slow[WX];
       bool any_slow = false;
       bool moved = false;  // some voxel of this lane changed
@@ -719,7 +766,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
         for (int k = 0; k < WX; ++k) {
           if (slow[k]) {
             float dist = 0.0f;
-            bool ok = sample_generic(&v, mode, g.px[min(x_first + k, g.nx - 1)], py, pz, &dist);
+            bool ok = sample_generic((const ViewParams*)vp, mode, g.px[min(x_first + k, g.nx - 1)], py, pz, &dist);
             if (CHECKMAX) ok = ok && !(n[k] > (NT)g.max_update_num);
             moved = apply_sample<UPDATE>(ok, dist, g.weight, s[k], n[k]) || moved;
           }
@@ -756,6 +803,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       constexpr bool FIRST = decltype(first_tag)::value;
       constexpr bool NOTRUNC = decltype(notrunc_tag)::value;
       constexpr bool UNIFORM = decltype(uniform_tag)::value;
+      cview& v = *vp;
       // the brick's common weights, in VGPRs (uniform values; opaque to the compiler so that they are not
       // folded back into scalar operands): (fn * sdf + dist) * (1 / (fn + 1)), voxel_carver.cc:88-95
       float fn_v = 0.0f, inv_v = 0.0f, wgt_v = 1.0f;
@@ -853,7 +901,6 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     const bool sure = (sure_bits & 1) != 0, never_truncated = (sure_bits & 2) != 0;
     // (Branch weights: the checked loops below are the rare ones in the kernels that have a select-free loop;
     // the register allocator then spills there, if anywhere, and not in the loops that do the work.)
-    constexpr bool kHasFast = kFastMax || kFastWa || kFastWaGeneral;
     const bool fast_first = kFastMax && sure && none_touched;
     const bool fast_next = (kFastMax && sure && all_touched) || (kFastWa && sure && implied);
     // general weights: every voxel updated by this view and all counts equal -- a first touch stores the sample
@@ -868,8 +915,32 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       }
       VCY_PT(2);
       VCY_PT_COUNT(7);
-    } else if (__builtin_expect_with_probability(fast_next, kHasFast && !kFastWaGeneral, 0.9)) {
-      // weighted average: no truncation test when it cannot fire, and brick-wide weights while the counts agree
+    } else if (kFastMax && __builtin_expect_with_probability(fast_next || fast_first, 1, 0.99)) {
+      // kMax, select-free.  The first touch of an untouched brick (FIRST, a plain store of the samples: it leaves the
+      // brick touched everywhere) and the runs of every `sure` view that follows are a loop of their own: the state --
+      // s[], n[] -- is carried by that loop's back edge alone and stays in the registers the update chains work on.
+      // (As one of five paths that met behind the view, the run ended with 16 register moves into the set the other
+      // paths leave the state in, and the loop latch moved all 16 back: 32 of 328 vector instructions per pair,
+      // profiles/view_loop.)  A view that is not `sure` leaves the loop and comes back in through the checked paths below.
+      // run(): one select-free run and the step to the view behind it; is that view another one of this loop?
+      auto run = [&](auto first_tag) -> bool {
+        brick_moved = carve_view_fast(first_tag, std::false_type{}, std::false_type{});
+        VCY_PT(2);
+        VCY_PT_COUNT(7);
+        end_view(brick_moved);
+        if (!all_touched || (next_fast_bits() & 1) == 0) return false;
+        begin_view();
+        return true;
+      };
+      bool more = true;
+      if (fast_first) more = run(std::true_type{});
+      while (more) more = run(std::false_type{});
+      continue;
+    } else if (kFastWa && __builtin_expect_with_probability(fast_next, 1, 0.9)) {
+      // weighted average: no truncation test when it cannot fire, and brick-wide weights while the counts agree.
+      // (One pass through the outer loop per view.  Loops of their own for the three flavours, like kMax has above, take
+      // the 25 register moves per pair out of these runs too, but the allocator then spills inside them: scratch 64 ->
+      // 112 bytes, 25.6 -> 33.5 ms per step in --mode tsdf -- profiles/view_loop/README.md.)
       const bool all_updated = kFastWa && (!TRUNC || never_truncated);
       if (kFastWa && all_updated && uniform_cnt) {
         brick_moved = carve_view_fast(std::false_type{}, std::true_type{}, std::true_type{});
@@ -879,10 +950,6 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
         if (kFastWa) leave_uniform();
         brick_moved = carve_view_fast(std::false_type{}, std::false_type{}, std::false_type{});
       }
-      VCY_PT(2);
-      VCY_PT_COUNT(7);
-    } else if (__builtin_expect_with_probability(fast_first, kHasFast, 0.99)) {
-      brick_moved = carve_view_fast(std::true_type{}, std::false_type{}, std::false_type{});
       VCY_PT(2);
       VCY_PT_COUNT(7);
     } else if (sure) {
@@ -896,25 +963,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       VCY_PT(4);
       VCY_PT_COUNT(9);
     }
-    VCY_SETPRIO(3);
-    if (brick_moved) VCY_PT_COUNT(11);
-    none_touched = false;  // (a checked view may have touched only some voxels)
-    if (!kOne) refresh_all_touched();  // (only the views that follow ask)
-
-    // state moved: some of the remaining views may have become droppable (min(sdf) only grows)
-    // (an unchanged brick leaves every bound comparison as it was)
-    if (!kOne && want_bound && UPDATE == VCY_UPDATE_MAX && brick_moved) {
-      live = live_views();
-      const int v2 = next_view(live, vi);
-      if (v2 != vnext) {
-        vnext = v2;
-        // (the dropped view's pixels may still be arriving in that buffer: loads complete in order)
-        if (kRaw && vnext < vi_end) raw_prefetch(views[kRows ? (vnext & 7) : vnext].v, tile_of(vnext), lane, raw_buf(cur ^ 1));
-      }
-    }
-    vi = vnext;
-    cur ^= 1;
-    VCY_PT(5);
+    end_view(brick_moved);
   }
 
   // ---- write back what changed (update_num grows with every change) ----------------------------
