@@ -1,7 +1,7 @@
 """update_num at the edges of its three storage widths, against the CPU oracle bit for bit.
 
 A context keeps every voxel's update_num in 1, 2 or 4 bytes: one byte on a fresh grid, widened when the views applied
-or the counts uploaded could need more (count_width_for / set_count_width, vcy_api.hip), up to the width that
+or the counts uploaded could need more (count_width_for / set_count_width, vcy_state.hip), up to the width that
 voxel_max_update_num + 1 needs (a voxel is skipped once update_num > max, voxel_carver.cc:447-450).  Every kernel that
 reads or writes the counters has one branch per width, and halo slices travel at the final ("wire") width and are
 narrowed -- saturating -- into a narrower receiver.  Every case below asserts count_bytes before and after the

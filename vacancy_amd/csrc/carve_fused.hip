@@ -243,16 +243,15 @@ int div_level(vcy_ctx* c, float n) {
   auto it = g_div_cache.find(key);
   if (it != g_div_cache.end()) return it->second;
   int level = 0;
-  unsigned* d_bad = nullptr;
+  DeviceBuf<unsigned> d_bad;
   unsigned h_bad[2] = {1u, 1u};
-  if (hipMalloc(&d_bad, 2 * sizeof(unsigned)) == hipSuccess) {
+  if (d_bad.alloc(2 * sizeof(unsigned)) == hipSuccess) {
     hipError_t e = hipMemsetAsync(d_bad, 0, 2 * sizeof(unsigned), c->stream);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(div_verify_kernel, dim3((1u << 23) / 256u, 121u), dim3(256), 0, c->stream, n, d_bad);
       e = hipMemcpyAsync(h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_bad);
     if (e == hipSuccess) level = h_bad[0] == 0 ? 2 : (h_bad[1] == 0 ? 1 : 0);
     else (void)hipGetLastError();
   } else {
@@ -325,21 +324,17 @@ int prepare_views(vcy_ctx* c, int n_views, const ViewParams* vp, bool need_bound
   if (need_bound) {
     size_t total = 0;
     for (int vi = 0; vi < n_views; ++vi) total += ((size_t)planes * vp[vi].width * vp[vi].height + 3) & ~(size_t)3;
-    if (c->wmax_bytes < total * sizeof(float)) {
+    if (c->d_wmax.bytes() < total * sizeof(float)) {
       VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-      if (c->d_wmax) (void)hipFree(c->d_wmax);
-      c->d_wmax = nullptr;
-      c->wmax_bytes = 0;
-      if (hipMalloc(&c->d_wmax, total * sizeof(float)) == hipSuccess) c->wmax_bytes = total * sizeof(float);
-      else { c->d_wmax = nullptr; (void)hipGetLastError(); }
+      if (c->d_wmax.alloc(total * sizeof(float)) != hipSuccess) (void)hipGetLastError();  // (best effort: the kernel scans the footprints)
     }
   }
   // staging buffer owned by the context, grown on demand
   {
-    const size_t had = c->fused_scratch_bytes;
-    const int rcg = grow_device(&c->d_fused_scratch, &c->fused_scratch_bytes, c2_bytes + fv_bytes, c->stream);
-    if (rcg != VCY_OK || c->fused_scratch_bytes != had) c->fused_cache_valid = false;  // (the buffer moved)
-    if (rcg != VCY_OK) return rcg;
+    const size_t had = c->d_fused_scratch.bytes();
+    const hipError_t eg = c->d_fused_scratch.grow(c2_bytes + fv_bytes, c->stream);
+    if (eg != hipSuccess || c->d_fused_scratch.bytes() != had) c->fused_cache_valid = false;  // (the buffer moved)
+    VCY_HIP_CHECK(eg);
   }
   float* d_c2 = (float*)c->d_fused_scratch;
   FusedView* d_views = (FusedView*)((char*)c->d_fused_scratch + c2_bytes);
@@ -360,19 +355,16 @@ int prepare_views(vcy_ctx* c, int n_views, const ViewParams* vp, bool need_bound
     // views queues behind the previous one like any other work on the stream (round 5; until then this path waited
     // for the stream twice and uploaded the c0 records, 0.5 MB at 1024^3 x 32, from a host vector).
     static_assert(kC0Stride == 32 && WX == 8, "c0_records_kernel's record layout");
-    if (c->fused_stage_bytes < fv_bytes) {
+    if (c->h_fused_stage[1].bytes() < fv_bytes) {  // (the second is allocated last, after both events: where it is large enough, everything is there)
       for (int q = 0; q < 2; ++q) {
         if (c->ev_fused_stage[q]) (void)hipEventSynchronize(c->ev_fused_stage[q]);
-        if (c->h_fused_stage[q]) (void)hipHostFree(c->h_fused_stage[q]);
-        c->h_fused_stage[q] = nullptr;
+        (void)c->h_fused_stage[q].reset();
       }
-      c->fused_stage_bytes = 0;
       const size_t room = fv_bytes + fv_bytes / 2 + 4096;
       for (int q = 0; q < 2; ++q) {
-        VCY_HIP_CHECK(hipHostMalloc(&c->h_fused_stage[q], room, hipHostMallocDefault));
-        if (!c->ev_fused_stage[q]) VCY_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fused_stage[q], hipEventDisableTiming));
+        VCY_HIP_CHECK(c->ev_fused_stage[q].ensure(hipEventDisableTiming));
+        VCY_HIP_CHECK(c->h_fused_stage[q].alloc(room));
       }
-      c->fused_stage_bytes = room;
     }
     c->fused_stage_idx ^= 1;
     VCY_HIP_CHECK(hipEventSynchronize(c->ev_fused_stage[c->fused_stage_idx]));  // (the copy of two launches ago: long made)
@@ -545,10 +537,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
   // nothing is dropped before the state is read and marching cubes reads every brick
   if (!c->d_brick_min) {
     const size_t bytes = sizeof(float) * (size_t)nbw * nby * nbz;
-    if (hipMalloc(&c->d_brick_min, bytes) != hipSuccess) {
-      c->d_brick_min = nullptr;
-      (void)hipGetLastError();
-    }
+    if (c->d_brick_min.alloc(bytes) != hipSuccess) (void)hipGetLastError();
     c->brick_min_valid = false;
   }
   if (!c->cnt_implied) c->brick_min_valid = false;
@@ -611,17 +600,10 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
     const int64_t cap = rec_cap;
     chunk_layers = (int)std::max<int64_t>(1, std::min<int64_t>(nbz, cap / std::max<int64_t>(per_layer, 1)));
     const size_t need = (size_t)(per_layer * chunk_layers);
-    { const int rcg = grow_device(&c->d_records, &c->records_bytes, need, c->stream); if (rcg != VCY_OK) return rcg; }
+    VCY_HIP_CHECK(c->d_records.grow(need, c->stream));
   }
   if (c->count_pairs) {  // "paircount" 1: one counter per brick layer of the slab, cleared by every launch
-    if (c->pair_count_layers < nbz) {
-      VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-      if (c->d_pair_count) (void)hipFree(c->d_pair_count);
-      c->d_pair_count = nullptr;
-      c->pair_count_layers = 0;
-      VCY_HIP_CHECK(hipMalloc(&c->d_pair_count, sizeof(unsigned long long) * (size_t)nbz));
-      c->pair_count_layers = nbz;
-    }
+    VCY_HIP_CHECK(c->d_pair_count.grow(sizeof(unsigned long long) * (size_t)nbz, c->stream));
     VCY_HIP_CHECK(hipMemsetAsync(c->d_pair_count, 0, sizeof(unsigned long long) * (size_t)nbz, c->stream));
     c->pair_count_views = n_views;
   }
@@ -680,7 +662,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
       list_entry_words = one_view && c->list_records != 0 ? kLiveEntryWords : 0;
       const size_t need = list_entry_words ? sizeof(int) * (2 + (size_t)nwg * kLiveEntryWords) : sizeof(int) * ((size_t)nwg + 1);  // (the hint below: a race with its copy is benign, it only
       // decides whether the NEXT launch lists its workgroups; with several chunks it reflects the last one)
-      { const int rcg = grow_device((void**)&c->d_wg_list, &c->wg_list_bytes, need, c->stream); if (rcg != VCY_OK) return rcg; }
+      VCY_HIP_CHECK(c->d_wg_list.grow(need, c->stream));
       VCY_HIP_CHECK(hipMemsetAsync(c->d_wg_list, 0, sizeof(int), c->stream));
       hipLaunchKernelGGL(live_workgroups_kernel, dim3((unsigned)((nwg + kLiveThreads - 1) / kLiveThreads)), dim3(kLiveThreads), 0, c->stream, recs, nbricks,
                          n_views, have_min ? bmin : nullptr, m.trunc, units_x, nby, nbw, nwg, c->d_wg_list, unit_bricks,
@@ -688,10 +670,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
       launch_grid = groups_of((unsigned)nwg);  // (every unit started unless the count below arrives)
       VCY_HIP_CHECK(hipGetLastError());
       wgl = c->d_wg_list;
-      if (!c->h_live_hint && hipHostMalloc((void**)&c->h_live_hint, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        c->h_live_hint = nullptr;
-        (void)hipGetLastError();
-      }
+      if (!c->h_live_hint && c->h_live_hint.alloc(2 * sizeof(int)) != hipSuccess) (void)hipGetLastError();
       if (c->h_live_hint) {
         c->h_live_hint[1] = nwg;
         (void)hipMemcpyAsync(&c->h_live_hint[0], c->d_wg_list, sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -825,8 +804,8 @@ int plan_layer_pairs(vcy_ctx* c, int n_views, const ViewParams* vp, int stride, 
   ModeParams m{u.voxel_update, u.sdf_interp, u.update_outside, u.use_truncation ? 1 : 0, c->fused_ortho ? 1 : 0, 0};
   const int sxn = (nbw + stride - 1) / stride, syn = (nby + stride - 1) / stride;
   const int64_t nsample = (int64_t)sxn * syn * nbz;
-  unsigned long long* d_out = nullptr;
-  VCY_HIP_CHECK(hipMalloc(&d_out, sizeof(unsigned long long) * (size_t)nbz));
+  DeviceBuf<unsigned long long> d_out;
+  VCY_HIP_CHECK(d_out.alloc(sizeof(unsigned long long) * (size_t)nbz));
   std::vector<unsigned long long> h((size_t)nbz, 0ull);
   hipError_t e = hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * (size_t)nbz, c->stream);
   if (e == hipSuccess) {
@@ -842,7 +821,6 @@ int plan_layer_pairs(vcy_ctx* c, int n_views, const ViewParams* vp, int stride, 
   }
   if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, sizeof(unsigned long long) * (size_t)nbz, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_out);
   if (e != hipSuccess) {
     set_error("slab planner: %s", hipGetErrorString(e));
     return VCY_ERR_HIP;
@@ -862,16 +840,15 @@ __global__ void selftest_rcp_count_kernel(int* n_bad) {
 
 // Device-side identities the fast paths of the fused kernel rest on; VCY_OK when all hold.
 int selftest_fused(hipStream_t stream) {
-  int* d_bad = nullptr;
+  DeviceBuf<int> d_bad;
   int h_bad = -1;
-  VCY_HIP_CHECK(hipMalloc(&d_bad, sizeof(int)));
+  VCY_HIP_CHECK(d_bad.alloc(sizeof(int)));
   hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(selftest_rcp_count_kernel, dim3(256), dim3(256), 0, stream, d_bad);
     e = hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(d_bad);
   if (e != hipSuccess) {
     set_error("self test failed to run: %s", hipGetErrorString(e));
     return VCY_ERR_HIP;

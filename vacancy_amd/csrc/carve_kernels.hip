@@ -122,8 +122,8 @@ static int resolve_views(vcy_ctx* c, int n_views, const vcy_view* views, const f
   // max over the whole SDF buffer (voxel_carver.cc:436); only update_outside = kMax reads it
   std::vector<float> max_sdf((size_t)n_views, 0.0f);
   if (u.update_outside == VCY_OUTSIDE_MAX) {
-    float* d_max = nullptr;
-    VCY_HIP_CHECK(hipMalloc(&d_max, sizeof(float) * (size_t)n_views * (1 + kMaxReduceBlocks)));
+    DeviceBuf<float> d_max;
+    VCY_HIP_CHECK(d_max.alloc(sizeof(float) * (size_t)n_views * (1 + kMaxReduceBlocks)));
     float* d_part = d_max + n_views;
     for (int i = 0; i < n_views; ++i) {
       const int64_t npx = (int64_t)views[i].width * views[i].height;
@@ -135,7 +135,6 @@ static int resolve_views(vcy_ctx* c, int n_views, const vcy_view* views, const f
     hipError_t e = hipMemcpyAsync(max_sdf.data(), d_max, sizeof(float) * (size_t)n_views,
                                   hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_max);
     if (e != hipSuccess) {
       set_error("max reduce failed: %s", hipGetErrorString(e));
       return VCY_ERR_HIP;
@@ -171,13 +170,10 @@ int flush_pending(vcy_ctx* c, bool from_carve) {
   }
   c->halo_valid = halo_valid;
   // stream order: a buffer handed out again is only written after this launch
-  for (auto& t : todo) c->sdf_pool.emplace_back(t.d_sdf, t.bytes);
+  for (auto& t : todo) c->sdf_pool.push_back(std::move(t.d_sdf));
   // image sizes that keep changing would let idle buffers pile up: keep at most two queues' worth
-  // (hipFree waits for the device, so a buffer still read by the launch above is safe to free)
-  while (c->sdf_pool.size() > 64) {
-    (void)hipFree(c->sdf_pool.front().first);
-    c->sdf_pool.erase(c->sdf_pool.begin());
-  }
+  // (freeing a buffer waits for the device, so one still read by the launch above is safe to free)
+  while (c->sdf_pool.size() > 64) c->sdf_pool.erase(c->sdf_pool.begin());
   return rc;
 }
 

@@ -336,8 +336,8 @@ int color_device(vcy_ctx* c, double iso, int64_t n, const float* vertices, const
                  float* rgb_out, int32_t* n_used_out, int32_t* best_view_out) {
   VCY_HIP_CHECK(hipSetDevice(c->device));
   c->last_color_device_ms = 0.0f;
-  if (!c->ev_cl_begin) VCY_HIP_CHECK(hipEventCreate(&c->ev_cl_begin));
-  if (!c->ev_cl_end) VCY_HIP_CHECK(hipEventCreate(&c->ev_cl_end));
+  VCY_HIP_CHECK(c->ev_cl_begin.ensure());
+  VCY_HIP_CHECK(c->ev_cl_end.ensure());
   const bool with_normals = o.mode != VCY_COLOR_MEAN;
   const int n_chunks = (n_views + cl::kMaxViewsPerLaunch - 1) / cl::kMaxViewsPerLaunch;
 
@@ -361,7 +361,7 @@ int color_device(vcy_ctx* c, double iso, int64_t n, const float* vertices, const
     }
     image_bytes = std::max(image_bytes, b);
   }
-  { const int rc = grow_device(&c->d_cl_buf, &c->cl_buf_bytes, at_images + image_bytes, c->stream, false); if (rc != VCY_OK) return rc; }
+  VCY_HIP_CHECK(c->d_cl_buf.grow(at_images + image_bytes, c->stream, false));
   char* base = (char*)c->d_cl_buf;
 
   VCY_HIP_CHECK(hipMemcpyAsync(base + at_vtx, vertices, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
@@ -461,12 +461,6 @@ int color_device(vcy_ctx* c, double iso, int64_t n, const float* vertices, const
 }
 
 }  // namespace
-
-void color_release(vcy_ctx* c) {
-  (void)hipFree(c->d_cl_buf);
-  if (c->ev_cl_begin) (void)hipEventDestroy(c->ev_cl_begin);
-  if (c->ev_cl_end) (void)hipEventDestroy(c->ev_cl_end);
-}
 
 }  // namespace vcy
 

@@ -416,16 +416,15 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
   }
   const int nx = c->nx, ny = c->ny, Wr = (nx + 63) / 64;
   const int64_t nwords = (int64_t)Wr * ny * c->nz_local();
-  { const int rc = grow_device(&c->d_cc_labels, &c->cc_labels_bytes, sizeof(int) * (size_t)n, c->stream, false); if (rc != VCY_OK) return rc; }
-  { const int rc = grow_device(&c->d_cc_bits, &c->cc_bits_bytes, sizeof(cc::u64) * (size_t)nwords + 64, c->stream, false); if (rc != VCY_OK) return rc; }
+  VCY_HIP_CHECK(c->d_cc_labels.grow(sizeof(int) * (size_t)n, c->stream, false));
+  VCY_HIP_CHECK(c->d_cc_bits.grow(sizeof(cc::u64) * (size_t)nwords + 64, c->stream, false));
   if (c->cc_roots_cap == 0) {
-    const int rc = grow_device(&c->d_cc_roots, &c->cc_roots_bytes, (size_t)(1 << 16) * (sizeof(int) + sizeof(Stats) + 1), c->stream, false);
-    if (rc != VCY_OK) return rc;
+    VCY_HIP_CHECK(c->d_cc_roots.grow((size_t)(1 << 16) * (sizeof(int) + sizeof(Stats) + 1), c->stream, false));
     c->cc_roots_cap = 1 << 16;
   }
-  if (!c->h_cc_report) VCY_HIP_CHECK(hipHostMalloc(&c->h_cc_report, 64, hipHostMallocDefault));
-  if (!c->ev_cc_begin) VCY_HIP_CHECK(hipEventCreate(&c->ev_cc_begin));
-  if (!c->ev_cc_end) VCY_HIP_CHECK(hipEventCreate(&c->ev_cc_end));
+  if (!c->h_cc_report) VCY_HIP_CHECK(c->h_cc_report.alloc(64));
+  VCY_HIP_CHECK(c->ev_cc_begin.ensure());
+  VCY_HIP_CHECK(c->ev_cc_end.ensure());
   int* label = (int*)c->d_cc_labels;
   cc::u64* bits = (cc::u64*)c->d_cc_bits;
   unsigned int* d_nroots = (unsigned int*)(bits + nwords);  // (the 64 bytes behind the words)
@@ -452,11 +451,9 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
   c->cc_labels_empty = false;
   if (n_roots == 0) return VCY_OK;
   if (n_roots > c->cc_roots_cap) {  // (thousands of specks: the list did not fit; once more into a larger one)
-    const int rc = grow_device(&c->d_cc_roots, &c->cc_roots_bytes, (size_t)n_roots * (sizeof(int) + sizeof(Stats) + 1), c->stream, false);
-    if (rc != VCY_OK) {
-      c->cc_roots_cap = 0;
-      return rc;
-    }
+    const hipError_t eg = c->d_cc_roots.grow((size_t)n_roots * (sizeof(int) + sizeof(Stats) + 1), c->stream, false);
+    if (eg != hipSuccess) c->cc_roots_cap = 0;
+    VCY_HIP_CHECK(eg);
     c->cc_roots_cap = (int)n_roots;
     VCY_HIP_CHECK(hipMemsetAsync(d_nroots, 0, 64, c->stream));
     hipLaunchKernelGGL(cc::cc_collect_kernel, dim3(voxel_blocks), dim3(256), 0, c->stream, label, n, (int*)c->d_cc_roots,
@@ -789,7 +786,7 @@ int vcy_component_seam_pairs(vcy_ctx* c, const int64_t* below_plane_labels, int6
   std::vector<int64_t> pairs;
   unsigned int* h_report = (unsigned int*)c->h_cc_report;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    { const int rc = grow_device(&c->d_cc_seam, &c->cc_seam_bytes, plane_bytes + 64 + 2 * sizeof(int64_t) * cap, c->stream, false); if (rc != VCY_OK) return rc; }
+    VCY_HIP_CHECK(c->d_cc_seam.grow(plane_bytes + 64 + 2 * sizeof(int64_t) * cap, c->stream, false));
     int64_t* d_below = (int64_t*)c->d_cc_seam;
     unsigned int* d_n = (unsigned int*)((char*)c->d_cc_seam + plane_bytes);
     int64_t* d_pairs = (int64_t*)((char*)c->d_cc_seam + plane_bytes + 64);

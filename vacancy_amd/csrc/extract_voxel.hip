@@ -113,18 +113,6 @@ struct HostIds {
   }
 };
 
-// (grow-only device scratch kept by the context: an extraction per view allocated and freed twice per call)
-static int xv_reserve(void** buf, size_t* cap, size_t need, hipStream_t s) {
-  using namespace vcy;
-  if (*cap >= need) return VCY_OK;
-  VCY_HIP_CHECK(hipStreamSynchronize(s));
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr, *cap = 0;
-  VCY_HIP_CHECK(hipMalloc(buf, need + need / 8));
-  *cap = need + need / 8;
-  return VCY_OK;
-}
-
 // Kept voxel ids of this context's slab, GLOBAL ids in scan order (device predicate + compaction).
 static int kept_voxel_ids(vcy_ctx* c, int inside_empty, HostIds* out_ids) {
   using namespace vcy;
@@ -150,9 +138,11 @@ static int kept_voxel_ids(vcy_ctx* c, int inside_empty, HostIds* out_ids) {
     const size_t sz_bits = align(sizeof(u64) * (size_t)nblocks * 4);
     const size_t sz_counts = align(sizeof(u64) * ((size_t)nblocks + 1));
     const size_t sz_scan = align(sizeof(u64) * ((size_t)nblocks / 1024 + 64) * 2);
+    // (grow-only device scratch kept by the context, an eighth of headroom whenever it has to grow: an extraction per
+    // view allocated and freed twice per call)
     {
-      const int rcs = xv_reserve(&c->d_xv_scratch, &c->xv_scratch_bytes, sz_bits + sz_counts + sz_scan + 256, s);
-      if (rcs != VCY_OK) return rcs;
+      const size_t need = sz_bits + sz_counts + sz_scan + 256;
+      if (c->d_xv_scratch.bytes() < need) VCY_HIP_CHECK(c->d_xv_scratch.grow(need + need / 8, s));
     }
     char* d_scratch = (char*)c->d_xv_scratch;
     u64* d_bits = (u64*)d_scratch;
@@ -193,7 +183,8 @@ static int kept_voxel_ids(vcy_ctx* c, int inside_empty, HostIds* out_ids) {
       rc = VCY_ERR_TOO_MANY_VOXELS;
     }
     if (rc == VCY_OK && kept > 0) {
-      rc = xv_reserve(&c->d_xv_ids, &c->xv_ids_bytes, sizeof(int64_t) * (size_t)kept, s);
+      const size_t need = sizeof(int64_t) * (size_t)kept;
+      if (c->d_xv_ids.bytes() < need) XV_TRY(c->d_xv_ids.grow(need + need / 8, s));
       d_ids = (int64_t*)c->d_xv_ids;
       if (rc == VCY_OK) {
         ids.p = (int64_t*)mesh_host_alloc(sizeof(int64_t) * (size_t)kept);
@@ -523,7 +514,7 @@ static int extract_voxel_impl(vcy_ctx* c, int inside_empty, vcy_mesh* out, vcy_m
   if (xv_timing()) std::fprintf(stderr, "vcy xv: kept voxel ids (device predicate + compaction + D2H) %.2f ms\n", xv_now() - t_a);
   std::vector<float> py((size_t)c->ny);
   VCY_HIP_CHECK(hipMemcpy(py.data(), c->d_py, sizeof(float) * (size_t)c->ny, hipMemcpyDeviceToHost));
-  return cubes_from_ids(c->h_px, py.data(), c->h_pz, c->nx, c->ny, c->opt.resolution, ids.p, ids.n, out, arrays, user);
+  return cubes_from_ids(c->h_px.data(), py.data(), c->h_pz.data(), c->nx, c->ny, c->opt.resolution, ids.p, ids.n, out, arrays, user);
 }
 
 extern "C" int vcy_extract_voxel(vcy_ctx* c, int inside_empty, vcy_mesh* out) {

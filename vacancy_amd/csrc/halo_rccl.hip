@@ -545,9 +545,9 @@ int vcy_carve_batch_silhouettes_sharded(vcy_ctx* const* slabs, int n_slabs, int 
       }
     for (vcy_ctx* c : mine) {  // the timing record of vcy_last_stream_ms, per slab
       while (failed.load() == VCY_OK && (int)c->stream_events.size() < 4 * n_chunks) {
-        hipEvent_t ev = nullptr;
-        if (!hip_ok(hipEventCreate(&ev), "hipEventCreate")) break;
-        c->stream_events.push_back(ev);
+        Event ev;
+        if (!hip_ok(ev.ensure(), "hipEventCreate")) break;
+        c->stream_events.push_back(std::move(ev));
       }
       c->stream_timed_chunks = 0;
     }

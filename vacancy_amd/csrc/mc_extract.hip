@@ -158,7 +158,7 @@ struct Extraction {
     if (!c->d_mc_tables) {
       McTables h;
       build_tables(&h);
-      VCY_HIP_CHECK(hipMalloc(&c->d_mc_tables, sizeof(McTables)));
+      VCY_HIP_CHECK(c->d_mc_tables.alloc(sizeof(McTables)));
       VCY_HIP_CHECK(hipMemcpy(c->d_mc_tables, &h, sizeof(McTables), hipMemcpyHostToDevice));
     }
     chain.T = (const McTables*)c->d_mc_tables;
@@ -173,7 +173,7 @@ struct Extraction {
     const size_t sz_scan = align256(sizeof(u64) * ((size_t)nblocks / 1024 + 64) * 2);
     const size_t sz_ghost = sweep ? align256(sizeof(u64) * 3 * (size_t)c->ny * p.Wr) : 0;  // IN / OK / TC of one slice
     const size_t need = (sweep ? 1 : 3) * sz_plane + sz_ghost + sz_act + sz_woff + sz_counts + sz_scan + 256;
-    { const int rc = grow_device(&c->d_mc_scratch, &c->mc_scratch_bytes, need, s); if (rc != VCY_OK) return rc; }
+    VCY_HIP_CHECK(c->d_mc_scratch.grow(need, s));
     char* base = (char*)c->d_mc_scratch;
     chain.in = (u64*)base;                     base += sz_plane;
     chain.ok = (u64*)base;                     base += sweep ? 0 : sz_plane;  // (the sweep keeps OK / TC in LDS)
@@ -189,19 +189,17 @@ struct Extraction {
     if (!c->d_mc_flags) {
       // [2 slots][kChainedScanMaxChunks] flags, then the two ticket counters
       const size_t fbytes = sizeof(uint32_t) * (2 * (size_t)kChainedScanMaxChunks + 2);
-      VCY_HIP_CHECK(hipMalloc(&c->d_mc_flags, fbytes));
+      VCY_HIP_CHECK(c->d_mc_flags.alloc(fbytes));
       VCY_HIP_CHECK(hipMemsetAsync(c->d_mc_flags, 0, fbytes, s));
       c->mc_scan_epoch = 0;
       c->mc_scan_tickets[0] = c->mc_scan_tickets[1] = 0;
     }
     // the extraction has its own event pair: vcy_timer_begin / _end may bracket it
-    if (!c->ev_mc_begin) {
-      VCY_HIP_CHECK(hipEventCreate(&c->ev_mc_begin));
-      VCY_HIP_CHECK(hipEventCreate(&c->ev_mc_end));
-    }
+    VCY_HIP_CHECK(c->ev_mc_begin.ensure());
+    VCY_HIP_CHECK(c->ev_mc_end.ensure());
     // The counts come back through 64 bytes of page-locked memory that mc_emit writes itself (see the kernel).
     if (!c->h_mc_report) {
-      VCY_HIP_CHECK(hipHostMalloc((void**)&c->h_mc_report, 64, hipHostMallocPortable | hipHostMallocMapped));
+      VCY_HIP_CHECK(c->h_mc_report.alloc(64));  // (portable + mapped: vcy_ctx::h_mc_report)
       std::memset((void*)c->h_mc_report, 0, 64);
     }
     report = (volatile u64*)c->h_mc_report;
@@ -223,7 +221,7 @@ struct Extraction {
     const size_t sz_cc = align256(sizeof(u64) * ((size_t)chain.cell_blocks + 1));
     const size_t sz_cs = align256(sizeof(u64) * ((size_t)chain.cell_blocks / 1024 + 64) * 2);
     const size_t need = sz_list + sz_info + sz_nact + sz_cc + sz_cs + 256;
-    { const int rc = grow_device(&c->d_mc_cells, &c->mc_cells_bytes, need, s); if (rc != VCY_OK) return rc; }
+    VCY_HIP_CHECK(c->d_mc_cells.grow(need, s));
     char* b = (char*)c->d_mc_cells;
     chain.cell_list = (u64*)b;             b += sz_list;
     chain.info = (uint32_t*)b;             b += sz_info;
@@ -259,7 +257,7 @@ struct Extraction {
       }
       host.release_mesh();
     }
-    { const int rc = grow_device(&c->d_mc_out, &c->mc_out_bytes, sz_v + sz_k + sz_f, s); if (rc != VCY_OK) return rc; }
+    VCY_HIP_CHECK(c->d_mc_out.grow(sz_v + sz_k + sz_f, s));
     chain.verts = (float*)c->d_mc_out;
     chain.keys = c->mesh_keys ? (long long*)((char*)c->d_mc_out + sz_v) : nullptr;
     chain.faces = (int*)((char*)c->d_mc_out + sz_v + sz_k);
@@ -274,13 +272,11 @@ struct Extraction {
         (which & VCY_NORMALS_VERTEX) ? align256(sizeof(float) * 3 * (size_t)std::max<int64_t>(chain.cap_verts, 1)) : 0;
     const size_t sz_fn =
         (which & VCY_NORMALS_FACE) ? align256(sizeof(float) * 3 * (size_t)std::max<int64_t>(chain.cap_faces, 1)) : 0;
-    { const int rc = grow_device(&c->d_mc_normals, &c->mc_normals_bytes, sz_vn + sz_fn, s); if (rc != VCY_OK) return rc; }
+    VCY_HIP_CHECK(c->d_mc_normals.grow(sz_vn + sz_fn, s));
     d_vn = sz_vn ? (float*)c->d_mc_normals : nullptr;
     d_fn = sz_fn ? (float*)((char*)c->d_mc_normals + sz_vn) : nullptr;
-    if (!c->ev_nrm_begin) {
-      VCY_HIP_CHECK(hipEventCreate(&c->ev_nrm_begin));
-      VCY_HIP_CHECK(hipEventCreate(&c->ev_nrm_end));
-    }
+    VCY_HIP_CHECK(c->ev_nrm_begin.ensure());
+    VCY_HIP_CHECK(c->ev_nrm_end.ensure());
     NormalsLaunch a;
     a.T = chain.T;
     a.act = chain.act;

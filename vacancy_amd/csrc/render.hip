@@ -353,7 +353,7 @@ int ensure_bits(vcy_ctx* c, double iso) {
   const int64_t nwords = (int64_t)Wr * c->ny * nzl;
   const int nbx = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (nzl + 7) / 8;
   const int64_t nbricks = (int64_t)nbx * nby * nbz, nocc = (nbricks + 63) / 64;
-  { const int rc = grow_device(&c->d_rn_bits, &c->rn_bits_bytes, sizeof(rn::u64) * (size_t)(nwords + nocc), c->stream, false); if (rc != VCY_OK) return rc; }
+  VCY_HIP_CHECK(c->d_rn_bits.grow(sizeof(rn::u64) * (size_t)(nwords + nocc), c->stream, false));
   rn::u64* bits = (rn::u64*)c->d_rn_bits;
   { const int rc = launch_solid_bits(c, iso, bits); if (rc != VCY_OK) return rc; }
   hipLaunchKernelGGL(rn::rn_occupancy_kernel, dim3((unsigned)((nocc * 64 + 255) / 256)), dim3(256), 0, c->stream, bits, c->ny,
@@ -375,14 +375,13 @@ int ensure_planes(vcy_ctx* c) {
     if (rc != VCY_OK) return rc;
     at += (size_t)n[a] + 1;
   }
-  float* d = nullptr;
-  VCY_HIP_CHECK(hipMalloc(&d, sizeof(float) * all.size()));
+  DeviceBuf<float> d;
+  VCY_HIP_CHECK(d.alloc(sizeof(float) * all.size()));
   if (hipMemcpy(d, all.data(), sizeof(float) * all.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
     set_error("vcy_render_hull: the copy of the plane tables failed");
     return VCY_ERR_HIP;
   }
-  c->d_rn_planes = d;
+  c->d_rn_planes = std::move(d);
   return VCY_OK;
 }
 
@@ -418,8 +417,8 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
   c->last_render_device_ms = 0.0f;
   { const int rc = flush_pending(c); if (rc != VCY_OK) return rc; }
   { const int rc = ensure_planes(c); if (rc != VCY_OK) return rc; }
-  if (!c->ev_rn_begin) VCY_HIP_CHECK(hipEventCreate(&c->ev_rn_begin));
-  if (!c->ev_rn_end) VCY_HIP_CHECK(hipEventCreate(&c->ev_rn_end));
+  VCY_HIP_CHECK(c->ev_rn_begin.ensure());
+  VCY_HIP_CHECK(c->ev_rn_end.ensure());
 
   rn::Grid g{};
   g.n[0] = c->nx, g.n[1] = c->ny, g.n[2] = c->nz;
@@ -455,7 +454,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
       if (hits && hits[first + i]) at_hits[(size_t)i] = bytes, bytes += align16(hit_bytes(v));
       wmax = std::max(wmax, v.width), hmax = std::max(hmax, v.height);
     }
-    { const int rc = grow_device(&c->d_rn_out, &c->rn_out_bytes, bytes, c->stream, false); if (rc != VCY_OK) return rc; }
+    VCY_HIP_CHECK(c->d_rn_out.grow(bytes, c->stream, false));
     char* base = (char*)c->d_rn_out;
     for (int i = 0; i < m; ++i) {
       const vcy_view& v = views[first + i];
@@ -546,14 +545,6 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
 
 int render_depth_device(vcy_ctx* c, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who) {
   return render(c, iso, n_views, views, nullptr, nullptr, nullptr, nullptr, nullptr, who, false, nullptr, depth_dev);
-}
-
-void render_release(vcy_ctx* c) {
-  (void)hipFree(c->d_rn_bits);
-  (void)hipFree(c->d_rn_planes);
-  (void)hipFree(c->d_rn_out);
-  if (c->ev_rn_begin) (void)hipEventDestroy(c->ev_rn_begin);
-  if (c->ev_rn_end) (void)hipEventDestroy(c->ev_rn_end);
 }
 
 }  // namespace vcy

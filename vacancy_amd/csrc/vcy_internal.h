@@ -32,6 +32,8 @@ constexpr float kInvalidSdf = -3.402823466e+38f;
 
 }  // namespace vcy
 
+#include "vcy_resources.h"  // DeviceBuf, PinnedBuf, Event, Stream: what owns the context's resources
+
 // The device-resident voxel grid of one z-slab.
 //
 // Layout (structure of arrays, the reference's 40-byte AoS Voxel is never materialised):
@@ -44,9 +46,11 @@ constexpr float kInvalidSdf = -3.402823466e+38f;
 struct vcy_ctx {
   int device = 0;
   bool counted = false;               // registered in the process-wide context count (vcy_create succeeded)
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+  // Members are destroyed in reverse order of declaration and a stream must outlive everything that was used on it:
+  // the two streams come first, every buffer and event after them.
+  vcy::Stream stream;
+  vcy::Stream aux_stream;             // producer stream of the streamed batch (uploads + SDF build)
+  vcy::Event ev_begin, ev_end;
 
   vcy_carver_option opt{};
   int nx = 0, ny = 0, nz = 0;  // global dims
@@ -69,20 +73,14 @@ struct vcy_ctx {
   int cnt_bytes_wire = 1;
   bool lazy_count = true;
 
-  float* d_sdf = nullptr;      // includes halo slices
-  void* d_cnt = nullptr;
-  void* d_cnt_spare = nullptr;        // the counter array of the OTHER width, kept once it exists (set_count_width): a
-  size_t cnt_spare_cap = 0;           // reset / carve cycle across the 256th view then allocates and frees nothing
-  size_t cnt_cap = 0;                 // bytes allocated behind d_cnt
-  void* d_xv_scratch = nullptr;       // ExtractVoxel: keep bits, block counts, scan scratch (grow-only)
-  size_t xv_scratch_bytes = 0;
-  void* d_xv_ids = nullptr;           // ExtractVoxel: the kept voxel ids before their copy to the host (grow-only)
-  size_t xv_ids_bytes = 0;
-  void* d_halo_tmp = nullptr;         // two slices of a neighbour's counters at ITS width (vcy_halo_copy_from)
-  size_t halo_tmp_bytes = 0;
-  float* d_px = nullptr;
-  float* d_py = nullptr;
-  float* d_pz = nullptr;
+  vcy::DeviceBuf<float> d_sdf;        // includes halo slices
+  vcy::DeviceBuf<> d_cnt;
+  vcy::DeviceBuf<> d_cnt_spare;       // the counter array of the OTHER width, kept once it exists (set_count_width): a
+                                      // reset / carve cycle across the 256th view then allocates and frees nothing
+  vcy::DeviceBuf<> d_xv_scratch;      // ExtractVoxel: keep bits, block counts, scan scratch (grow-only)
+  vcy::DeviceBuf<> d_xv_ids;          // ExtractVoxel: the kept voxel ids before their copy to the host (grow-only)
+  vcy::DeviceBuf<> d_halo_tmp;        // two slices of a neighbour's counters at ITS width (vcy_halo_copy_from)
+  vcy::DeviceBuf<float> d_px, d_py, d_pz;
 
   bool mesh_keys = true;              // vcy_extract_iso also returns the edge key of every vertex (vcy_set_param "meshkeys")
   int list_records = 1;               // "listrecords": the live list of a one-view launch carries the footprint records and per-wave live bits (0: workgroup ids only)
@@ -100,13 +98,11 @@ struct vcy_ctx {
   // `for each view: Carve()` loop then costs one pass over the grid instead of one per view.
   struct PendingView {
     vcy_view view;
-    float* d_sdf;   // private device copy of the SDF image
-    size_t bytes;
+    vcy::DeviceBuf<float> d_sdf;  // private device copy of the SDF image
   };
   std::vector<PendingView> pending;
-  std::vector<std::pair<float*, size_t>> sdf_pool;  // idle image buffers
-  void* d_sil_scratch = nullptr;      // staging of vcy_carve_silhouette (mask + transform scratch)
-  size_t sil_scratch_bytes = 0;
+  std::vector<vcy::DeviceBuf<float>> sdf_pool;  // idle image buffers
+  vcy::DeviceBuf<> d_sil_scratch;     // staging of vcy_carve_silhouette (mask + transform scratch)
   bool defer = true;                  // vcy_set_param("defer", 0): apply every view at once
   // A queued view that failed to apply inside a call that cannot report it to a Carve() caller (an
   // extraction, a download ...) is remembered: the NEXT carve entry point returns it (then clears it).
@@ -116,19 +112,17 @@ struct vcy_ctx {
   int last_div_level = 0;             // division variant of the last fused launch (vcy_get_param "div_level")
   bool use_short_div = true;          // vcy_set_param("shortdiv", 0): always the full division sequence
   bool use_fused = true;              // vcy_set_option("fused", 0) forces the per-view kernel
-  float* h_px = nullptr;              // host copy of the x axis table (c0 tables of the fused carve)
+  std::vector<float> h_px;            // host copy of the x axis table (c0 tables of the fused carve)
   float h_px_min = 0, h_px_max = 0, h_py_min = 0, h_py_max = 0;  // extreme voxel centres
-  float* h_pz = nullptr;              // host copy of d_pz (per-view z tables of the fused carve)
-  void* d_fused_scratch = nullptr;    // view blocks + z tables of the fused carve kernel
-  size_t fused_scratch_bytes = 0;
+  std::vector<float> h_pz;            // host copy of d_pz (per-view z tables of the fused carve)
+  vcy::DeviceBuf<> d_fused_scratch;   // view blocks + z tables of the fused carve kernel
   bool cnt_implied = true;            // update_num == 0 implies sdf == lowest(): no vcy_upload since the fill
-  float* d_brick_min = nullptr;       // min(sdf) of every 8x8x8 wave brick of the slab [bz][by][bxw], kept by the fused carve
+  vcy::DeviceBuf<float> d_brick_min;  // min(sdf) of every 8x8x8 wave brick of the slab [bz][by][bxw], kept by the fused carve
   bool brick_min_valid = false;       // ... and current: no write to the state since has bypassed the fused kernel
-  int* d_wg_list = nullptr;           // live workgroups of a carve launch of few views ([0] = count), live_workgroups_kernel
-  size_t wg_list_bytes = 0;
+  vcy::DeviceBuf<int> d_wg_list;      // live workgroups of a carve launch of few views ([0] = count), live_workgroups_kernel
   bool time_carve = false;            // vcy_set_param("carvetimer", 1): events around pre-pass and carve kernel of every fused launch
   struct CarveStamp {                 // one chunk of one fused launch
-    hipEvent_t ev[3];                 // before window maxima / pre-pass, before the carve kernel, after it
+    vcy::Event ev[3];                 // before window maxima / pre-pass, before the carve kernel, after it
     bool first_chunk;
   };
   std::vector<CarveStamp> carve_log;  // event triplets, created on demand (vcy_carve_log, vcy_last_carve_ms)
@@ -136,24 +130,21 @@ struct vcy_ctx {
   int carve_log_last = 0;             // index of the first chunk of the last launch
   int carve_log_dropped = 0;          // chunks that found the log full since it was cleared (vcy_get_param "carvelog_dropped")
   bool carve_log_last_dropped = false;  // ... the last launch among them: vcy_last_carve_ms has nothing to report
-  int* h_live_hint = nullptr;         // page-locked {live workgroups, workgroups} of the last listed launch (a hint, see launch_carve_fused)
+  vcy::PinnedBuf<int> h_live_hint;    // page-locked {live workgroups, workgroups} of the last listed launch (a hint, see launch_carve_fused)
   int64_t live_list_age = 0;
   bool use_live_list = true;          // vcy_set_param("livelist", 0): every workgroup is launched and decides for itself
   bool live_sync = true;              // vcy_set_param("livesync", 0): the carve kernel of a listed launch starts every workgroup instead of waiting for the list's length
   int coop_store = -1;                // vcy_set_param("coopstore"): write-back of a workgroup's bricks through LDS in whole row segments; -1 = where it pays (launch_carve_fused), 0 / 1 = never / whenever possible
   bool count_pairs = false;           // vcy_set_param("paircount", 1): the fused kernel counts the (brick, view) pairs it processes
-  unsigned long long* d_pair_count = nullptr;  // ... per brick layer of the slab, of the last fused launch (vcy_last_carve_pairs)
-  int pair_count_layers = 0, pair_count_views = 0;
+  vcy::DeviceBuf<unsigned long long> d_pair_count;  // ... per brick layer of the slab, of the last fused launch (vcy_last_carve_pairs)
+  int pair_count_views = 0;
   int64_t record_bytes_max = 0;       // vcy_set_param("recordbytes", n): footprint records per launch chunk (0: 2 GiB)
   int prologue_mode = 0;              // vcy_set_param("prologue"): 0 / 2 footprint records from the pre-pass (chunked); 1 footprints in the carve kernel's prologue (slower at every shape measured)
-  void* d_records = nullptr;          // footprint records of one fused launch, 8 bytes per (wave brick, view)
-  size_t records_bytes = 0;
-  float* d_wmax = nullptr;            // window-maximum planes of the views of one fused launch
-  size_t wmax_bytes = 0;
+  vcy::DeviceBuf<> d_records;         // footprint records of one fused launch, 8 bytes per (wave brick, view)
+  vcy::DeviceBuf<float> d_wmax;       // window-maximum planes of the views of one fused launch
   bool fused_ortho = false;           // projection model of the launch being prepared
-  void* h_fused_stage[2] = {nullptr, nullptr};  // page-locked staging of the view blocks, taken in turn (prepare_views)
-  hipEvent_t ev_fused_stage[2] = {nullptr, nullptr};  // "the copy out of staging buffer q has been made"
-  size_t fused_stage_bytes = 0;
+  vcy::PinnedBuf<> h_fused_stage[2];  // page-locked staging of the view blocks, taken in turn (prepare_views)
+  vcy::Event ev_fused_stage[2];       // "the copy out of staging buffer q has been made"
   int fused_stage_idx = 0;
   bool fused_cache_valid = false;     // d_fused_scratch holds what these view parameters give (launch_carve_fused)
   std::vector<char> fused_cache_vp;   // the ViewParams of the launch that filled it
@@ -162,49 +153,39 @@ struct vcy_ctx {
   bool fused_cache_bound = false, fused_cache_lower = false, fused_cache_ortho = false, fused_cache_samef = true;
   int fused_cache_max_quads = 0;
   int fused_cache_z[2] = {0, 0};
-  void* d_stream_pool = nullptr;      // staging of vcy_carve_batch_silhouettes (masks, SDFs, scratch)
-  size_t stream_pool_bytes = 0;
-  hipStream_t aux_stream = nullptr;   // producer stream of the streamed batch (uploads + SDF build)
-  hipEvent_t ev_ready[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr}, ev_uploaded[2] = {nullptr, nullptr};
-  std::vector<hipEvent_t> stream_events;  // four per chunk of the last streamed batch (vcy_last_stream_ms)
+  vcy::DeviceBuf<> d_stream_pool;     // staging of vcy_carve_batch_silhouettes (masks, SDFs, scratch)
+  vcy::Event ev_ready[2], ev_consumed[2], ev_uploaded[2];
+  std::vector<vcy::Event> stream_events;  // four per chunk of the last streamed batch (vcy_last_stream_ms)
   int stream_timed_chunks = 0;
   float stream_wall_ms = 0.0f;
-  void* h_pinned = nullptr;           // page-locked staging of the silhouettes, two sets
-  size_t pinned_bytes = 0;
-  void* d_mc_tables = nullptr;        // marching-cubes case tables (mc_extract.hip)
-  void* d_mc_scratch = nullptr;       // bit planes, active words, offsets, per-cell info
-  size_t mc_scratch_bytes = 0;
-  void* d_mc_flags = nullptr;         // publication flags of the chained scans (mc_kernels.hip scan_chained_kernel)
+  vcy::PinnedBuf<> h_pinned;          // page-locked staging of the silhouettes, two sets
+  vcy::DeviceBuf<> d_mc_tables;       // marching-cubes case tables (mc_extract.hip)
+  vcy::DeviceBuf<> d_mc_scratch;      // bit planes, active words, offsets, per-cell info
+  vcy::DeviceBuf<> d_mc_flags;        // publication flags of the chained scans (mc_kernels.hip scan_chained_kernel)
   uint32_t mc_scan_epoch = 0;         // ... and the epoch of the last scan (flags never hold a later one)
-  void* h_mc_report = nullptr;        // 64 page-locked bytes mc_emit reports an extraction's counts in (extract_iso)
+  vcy::PinnedBuf<void, hipHostMallocPortable | hipHostMallocMapped> h_mc_report;  // 64 page-locked bytes mc_emit reports an extraction's counts in (extract_iso)
   int64_t mc_direct_bytes = (int64_t)32 << 20;  // "mcdirect": meshes guessed up to this size are written by mc_emit straight into host memory
   int mc_timing = 0;                  // "mctiming" 1 (or VCY_MC_TIMING=1): host-side phases of every extraction on stderr
   uint32_t mc_scan_tickets[2] = {0, 0};  // chunk tickets drawn so far from the two scan slots' counters (scan_chained_kernel)
-  void* d_mc_cells = nullptr;         // per-active-cell arrays of the extraction
-  size_t mc_cells_bytes = 0;
-  void* d_mc_out = nullptr;           // device staging of the extracted mesh
-  size_t mc_out_bytes = 0;
+  vcy::DeviceBuf<> d_mc_cells;        // per-active-cell arrays of the extraction
+  vcy::DeviceBuf<> d_mc_out;          // device staging of the extracted mesh
   int64_t mc_hint_cells = 0, mc_hint_verts = 0, mc_hint_faces = 0;  // sizes of the last extraction (extract_iso)
   float last_extract_device_ms = 0.0f;
   float last_extract_wall_ms = 0.0f;  // call entry -> mesh arrays in host memory
-  hipEvent_t ev_mc_begin = nullptr, ev_mc_end = nullptr;  // the extraction's own timer
-  void* d_mc_normals = nullptr;       // device staging of the normals of vcy_extract_iso_normals (grow-only)
-  size_t mc_normals_bytes = 0;
-  hipEvent_t ev_nrm_begin = nullptr, ev_nrm_end = nullptr;  // around the normals launches (vcy_last_normals_ms)
+  vcy::Event ev_mc_begin, ev_mc_end;  // the extraction's own timer
+  vcy::DeviceBuf<> d_mc_normals;      // device staging of the normals of vcy_extract_iso_normals (grow-only)
+  vcy::Event ev_nrm_begin, ev_nrm_end;  // around the normals launches (vcy_last_normals_ms)
   float last_normals_device_ms = 0.0f;
   // connected components (components.hip); everything grow-only
-  void* d_cc_labels = nullptr;        // int32 per voxel: the label (smallest voxel id of the component) or -1, of the last labelling
-  size_t cc_labels_bytes = 0;
-  void* d_cc_bits = nullptr;          // the solid bit of every voxel in 64-voxel words along x, and the root counter behind them
-  size_t cc_bits_bytes = 0;
-  void* d_cc_roots = nullptr;         // [statistics | sorted roots | removal flags] of up to cc_roots_cap components
-  size_t cc_roots_bytes = 0;
-  int cc_roots_cap = 0;
+  vcy::DeviceBuf<> d_cc_labels;       // int32 per voxel: the label (smallest voxel id of the component) or -1, of the last labelling
+  vcy::DeviceBuf<> d_cc_bits;         // the solid bit of every voxel in 64-voxel words along x, and the root counter behind them
+  vcy::DeviceBuf<> d_cc_roots;        // [statistics | sorted roots | removal flags] of up to cc_roots_cap components
+  int cc_roots_cap = 0;               // (a count of components, not of bytes)
   int cc_n_roots = 0;
-  void* h_cc_report = nullptr;        // 64 page-locked bytes the number of roots is read through
+  vcy::PinnedBuf<> h_cc_report;       // 64 page-locked bytes the number of roots is read through
   bool cc_labels_valid = false;       // vcy_download_labels has something to return ...
   bool cc_labels_empty = false;       // ... namely -1 everywhere (the slab was fresh: nothing was launched)
-  hipEvent_t ev_cc_begin = nullptr, ev_cc_end = nullptr;
+  vcy::Event ev_cc_begin, ev_cc_end;
   bool cc_timed = false;
   float last_components_device_ms = 0.0f;
   // ... of a z-slab (vcy_label_components_slab and what follows it): host copies of the last labelling, in the order of
@@ -215,27 +196,23 @@ struct vcy_ctx {
   bool cc_slab_labelled = false;      // the last labelling was vcy_label_components_slab's: the seam calls may follow
   double cc_iso = 0.0;                // ... at this iso level
   int64_t cc_views_at_label = 0;      // ... with this many views applied (a carve in between makes the labels stale)
-  void* d_cc_seam = nullptr;          // seam pairs: [the lower slab's top plane, int64 per voxel | counter | pairs] (grow-only)
-  size_t cc_seam_bytes = 0;
+  vcy::DeviceBuf<> d_cc_seam;         // seam pairs: [the lower slab's top plane, int64 per voxel | counter | pairs] (grow-only)
 
   // ray-cast of the hull (render.hip); everything grow-only
   int64_t state_epoch = 0;            // bumped by everything that may change which voxels are solid: a carve, vcy_upload, the fill, the component filter
-  void* d_rn_bits = nullptr;          // [solid bit of every voxel, 64-voxel words along x | one bit per 8 x 8 x 8 brick that holds a solid voxel]
-  size_t rn_bits_bytes = 0;
+  vcy::DeviceBuf<> d_rn_bits;         // [solid bit of every voxel, 64-voxel words along x | one bit per 8 x 8 x 8 brick that holds a solid voxel]
   bool rn_bits_valid = false;         // ... describe the state of epoch rn_epoch at the iso level rn_iso
   int64_t rn_epoch = -1;
   double rn_iso = 0.0;
-  float* d_rn_planes = nullptr;       // the cell planes of the three axes one behind the other (vcy_cell_planes), nx + ny + nz + 3 floats
-  void* d_rn_out = nullptr;           // view records, counters, images and silhouettes of one launch
-  size_t rn_out_bytes = 0;
-  hipEvent_t ev_rn_begin = nullptr, ev_rn_end = nullptr;
+  vcy::DeviceBuf<float> d_rn_planes;  // the cell planes of the three axes one behind the other (vcy_cell_planes), nx + ny + nz + 3 floats
+  vcy::DeviceBuf<> d_rn_out;          // view records, counters, images and silhouettes of one launch
+  vcy::Event ev_rn_begin, ev_rn_end;
   float last_render_device_ms = 0.0f;
   int ray_skip = 1;                   // "rayskip": rays step over bricks without a solid voxel (0: crossing by crossing)
 
   // colours of vertices (color.hip); grow-only
-  void* d_cl_buf = nullptr;           // view records, vertices, normals, results, carried accumulators and the images of one chunk of views
-  size_t cl_buf_bytes = 0;
-  hipEvent_t ev_cl_begin = nullptr, ev_cl_end = nullptr;
+  vcy::DeviceBuf<> d_cl_buf;          // view records, vertices, normals, results, carried accumulators and the images of one chunk of views
+  vcy::Event ev_cl_begin, ev_cl_end;
   float last_color_device_ms = 0.0f;
 
   // upper bound on any voxel's update_num (each carved view adds at most one)
@@ -264,7 +241,7 @@ int plan_z_slabs(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* 
                  float brick_cost, int32_t* z_bounds, double* layer_cost, int max_layers, int* n_layers);  // carve_kernels.hip
 int selftest_fused(hipStream_t stream);
 int flush_pending(vcy_ctx* ctx, bool from_carve = false);   // applies vcy_ctx::pending (no-op when empty)
-int check_carve_views(vcy_ctx* ctx, int n_views, const vcy_view* views);  // argument checks of the carve entry points (vcy_api.hip)
+int check_carve_views(vcy_ctx* ctx, int n_views, const vcy_view* views);  // argument checks of the carve entry points (vcy_carve.hip)
 int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy_ctx::carve_log, or -1 (vcy_api.hip)
 // mc_extract.hip: the host driver of the marching-cubes extraction (its kernels and their launches: mc_kernels.hip,
 // mc_normals.hip; what the three share: mc_common.h)
@@ -279,12 +256,10 @@ int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int 
 // the state must be materialised.  Shared by the labelling and the ray-cast (render.hip).
 int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
 // render.hip: vcy_render_hull, vcy_hull_agreement, vcy_render_hull_slab, vcy_cell_planes, vcy_last_render_ms
-void render_release(vcy_ctx* ctx);  // frees what the ray-cast keeps on the context (vcy_destroy)
 // vcy_render_hull's depth images of up to 64 views (one launch), left in device memory: depth_dev[i] points into
 // vcy_ctx::d_rn_out and holds until the context next renders; waits for the launch; vcy_last_render_ms as for the render
 int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who);
 // color.hip: vcy_color_vertices, vcy_color_vertices_host, vcy_last_color_ms
-void color_release(vcy_ctx* ctx);   // frees what the colouring keeps on the context (vcy_destroy)
 // render_merge.hip (host code only): vcy_render_merge_host, vcy_hull_agreement_host, and the view checks of the ray-cast
 int check_render_view(const vcy_view* v, int i);
 // sdf2d.hip
@@ -299,15 +274,21 @@ size_t device_make_sdf_scratch_bytes(int w, int h);
 int device_make_sdf_batch(hipStream_t stream, int n, const uint8_t* const* masks_dev, const vcy_view* views,
                           bool normalize, bool truncate, float band, char* scratch, size_t scratch_stride,
                           float* const* sdf_dev);
-// host arrays of returned meshes (page-locked pool, vcy_api.hip); released by vcy_mesh_free
+// vcy_api.hip: the error string (set_error above), vcy_version, vcy_create / vcy_destroy, dims and axis positions, the
+// stream, vcy_set_param / vcy_get_param, timers, the carve log and pair-count readers, the self test, and the device
+// memory handed to callers (vcy_sdf_upload, vcy_device_alloc / _free, vcy_memcpy_*)
+// vcy_carve.hip: the carve entry points (vcy_carve*, vcy_make_sdf*, vcy_carve_batch_silhouettes, vcy_last_stream_ms),
+// the queue of pending views, the slab planner's wrappers and the two host SDF wrappers
+// vcy_mesh.hip: the vcy_extract_iso* wrappers, vcy_mesh_free / vcy_mesh_normals_free, the extraction's timers, the
+// normals and seam functions of the host (vcy_mesh_normals_host*, vcy_mesh_normals_seam_sum), and the
+// host arrays of returned meshes (page-locked pool); released by vcy_mesh_free
 void* mesh_host_alloc(size_t bytes, bool* pinned_out = nullptr);
 void mesh_host_free(void* p);
-// A device buffer cached in the context, grow-only: at least `want` bytes behind *p.  Before the old buffer is freed
-// the work on `wait_for` is waited for, unless the caller knows that nothing in flight uses it (`wait` false).  A
-// failed allocation leaves *p == nullptr and *have == 0.  (vcy_api.hip)
-int grow_device(void** p, size_t* have, size_t want, hipStream_t wait_for, bool wait = true);
-// utility kernels (vcy_api.hip)
-int ensure_count_width(vcy_ctx* ctx, int64_t max_count);  // d_cnt wide enough for counts up to max_count (vcy_api.hip)
+void mesh_pool_trim();  // frees the pool's idle buffers (vcy_destroy, when the last context goes)
+// vcy_state.hip: counter widths, the lazy fill, vcy_reset, download / upload / positions / voxels, vcy_state_equal and
+// the vcy_halo_* functions
+int ensure_count_width(vcy_ctx* ctx, int64_t max_count);  // d_cnt wide enough for counts up to max_count
+int set_count_width(vcy_ctx* ctx, int bytes);  // d_cnt at `bytes` per counter, what it holds converted (vcy_set_param "lazycount")
 int count_width_for(const vcy_ctx* ctx, int64_t max_count);
 int convert_counts(hipStream_t stream, const void* src, int src_bytes, void* dst, int dst_bytes, int64_t n);  // saturating
 int fill_state(vcy_ctx* ctx);   // marks the slab fresh (lazy)
