@@ -20,7 +20,7 @@
  *     [z_begin, z_end) of the global grid (the whole grid when world size is 1).
  *     Every stage runs per slab -- carve, SDF producer, marching cubes, ExtractVoxel,
  *     mesh normals; what spans two slabs (shared-plane vertices, the normals of the
- *     vertices on a seam plane) is stitched on the host that merges the slabs' results.
+ *     vertices on a seam plane) is stitched on the host by vcy_merge_meshes_host.
  *   - there is NO CPU fallback: if no HIP device is usable, vcy_create fails.
  */
 #ifndef VACANCY_HIP_H_
@@ -276,8 +276,8 @@ int vcy_extract_iso_normals(vcy_ctx* ctx, double iso_level, int linear_interp, i
  * vertices: those on x- or y-axis edges in the plane of slice z_begin - 1 that cells of the slab below own (this slab's
  * first n_foreign_vertices) and, when z_end < nz, those on such edges in the plane of slice z_end - 1 (the foreign
  * vertices of the slab above).  Their faces lie in two slabs and a float sum cannot be continued as a lump, so their
- * entries are zero here and the host that merges the slabs finishes them:
- *   1. concatenate the slabs' normals with the merged numbering (a slab's foreign entries dropped, like its vertices);
+ * entries are zero here and vcy_merge_meshes_host finishes them:
+ *   1. the slabs' normals concatenated with the merged numbering (a slab's foreign entries dropped, like its vertices);
  *   2. per seam, vcy_mesh_normals_seam_sum (or vcy_mesh_normals_host_seam) on the MERGED arrays with the face range
  *      [first face of the upper slab - layer_faces[1] of the lower slab, first face of the upper slab + layer_faces[0]
  *      of the upper slab) and the merged ids the upper slab's foreign vertices were mapped to by edge key.
@@ -307,9 +307,27 @@ int vcy_mesh_normals_host_seam(int64_t n_vertices, const float* vertices, const 
  * device results concatenated) instead of the positions.  For a mesh without NaN the two calls give the same bits.  A
  * mesh over NaN voxels has NaN face normals of either sign; this call takes the devices' own and adds them as the
  * vertex normals kernel does (of two NaNs the later term's), so that the seam vertices equal the whole-grid context's
- * to the bit there as well.  The mergers of the sharded carvers use this one.  Errors as above. */
+ * to the bit there as well.  vcy_merge_meshes_host uses this one.  Errors as above. */
 int vcy_mesh_normals_seam_sum(int64_t n_vertices, const int32_t* faces, const float* face_normals, int64_t face_begin,
                               int64_t face_end, int64_t n_seam, const int64_t* seam_vertex_ids, float* vertex_normals);
+/* The stitch of the meshes of a grid cut into z-slabs (host only, no GPU, no context): `slabs` = the n_slabs meshes in z
+ * order as vcy_extract_iso / vcy_extract_iso_normals_slab return them.  Own vertices keep their order and a slab's first
+ * n_foreign_vertices are dropped; a face corner that names one is re-pointed, by the vertex's edge key, to the own vertex
+ * with that key of the slab directly below.  The result is array for array the mesh of one context holding the grid.
+ * The arrays are the caller's, and their sizes follow from the structs alone:
+ *   merged vertices V = sum over the slabs of (n_vertices - n_foreign_vertices), merged faces F = sum of n_faces;
+ *   vertices 3 * V floats, faces 3 * F int32, edge_keys 2 * V int64 or NULL (not wanted).
+ * `normals` (one struct per slab, both arrays of every slab that has vertices / faces) and `layer_faces` (2 * n_slabs,
+ * the pair vcy_extract_iso_normals_slab returned per slab) are given together or both NULL.  Given, vertex_normals
+ * (3 * V) and face_normals (3 * F) receive steps 1 and 2 above: Mesh::CalcNormal of the merged mesh, to the bit what
+ * vcy_extract_iso_normals returns on the whole grid.  Not given, the two must be NULL.  An array of no elements may be NULL.
+ * VCY_ERR_INVALID_ARG, with the slab named in vcy_last_error(): a negative count or n_foreign_vertices > n_vertices, a
+ * null array, foreign vertices in slab 0 or without edge keys, normals missing for a slab, a layer_faces entry outside
+ * [0, n_faces], V > INT32_MAX, a foreign key without an owner in the slab below (the key is named) -- all found before
+ * the first write, the output arrays are untouched -- and a face that names a vertex outside its slab's, found while
+ * the faces are written: the output arrays are unspecified after that one. */
+int vcy_merge_meshes_host(int n_slabs, const vcy_mesh* slabs, const vcy_mesh_normals* normals, const int64_t* layer_faces,
+                          float* vertices, int32_t* faces, int64_t* edge_keys, float* vertex_normals, float* face_normals);
 
 /* ---- connected components of the hull ------------------------------------ */
 

@@ -80,6 +80,42 @@ def mesh_normals_seam_sum(n_vertices, faces, face_normals, face_begin, face_end,
     return vn
 
 
+def merge_meshes_host(vertices, faces, keys, n_foreign, normals=None, face_normals=None, layer_faces=None):
+    """vcy_merge_meshes_host: the meshes of z-slabs stitched by edge key into the mesh of the whole grid (rule and errors:
+    include/vacancy_hip.h).  Every argument is a list with one entry per slab, in z order; the last three are given
+    together (ExtractIsoSurfaceSlab's) or not at all.  Returns {"vertices" float32 [n, 3], "keys" int64 [n, 2], "faces"
+    int32 [m, 3]} plus, with normals, {"normals", "face_normals"}.  Serial, no GPU needed."""
+    n = len(vertices)
+    given = [x for x in (normals, face_normals, layer_faces) if x is not None]
+    with_normals = len(given) == 3
+    if len(given) not in (0, 3) or any(len(x) != n for x in [faces, keys, n_foreign] + given):
+        raise ValueError("one entry per slab in every list, and normals, face_normals and layer_faces together")
+    rows = lambda col, t, w: [np.ascontiguousarray(a, t).reshape(-1, w) for a in col]  # noqa: E731
+    ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if len(a) else None  # noqa: E731
+    v, f, k = rows(vertices, np.float32, 3), rows(faces, np.int32, 3), rows(keys, np.int64, 2)
+    vn, fn = (rows(normals, np.float32, 3), rows(face_normals, np.float32, 3)) if with_normals else (v, f)
+    slabs = (Mesh * max(n, 1))()
+    extra = (capi.MeshNormals * max(n, 1))()
+    for s in range(n):
+        if len(k[s]) not in (0, len(v[s])) or len(vn[s]) != len(v[s]) or len(fn[s]) != len(f[s]):
+            raise ValueError("slab %d: one edge key and one normal per vertex, one face normal per face" % s)
+        slabs[s] = Mesh(len(v[s]), len(f[s]), ptr(v[s], C.c_float), ptr(f[s], C.c_int32), ptr(k[s], C.c_int64), int(n_foreign[s]))
+        if with_normals:
+            extra[s] = capi.MeshNormals(ptr(vn[s], C.c_float), ptr(fn[s], C.c_float))
+    lf = (C.c_int64 * max(2 * n, 1))(*[int(x) for pair in layer_faces for x in pair]) if with_normals else None
+    nv = max(0, sum(len(a) - int(nfo) for a, nfo in zip(v, n_foreign)))
+    nf = sum(len(a) for a in f)
+    out = {"vertices": np.empty((nv, 3), np.float32), "keys": np.empty((nv, 2), np.int64), "faces": np.empty((nf, 3), np.int32)}
+    if with_normals:
+        out["normals"], out["face_normals"] = np.empty((nv, 3), np.float32), np.empty((nf, 3), np.float32)
+    rc = capi.load().vcy_merge_meshes_host(n, slabs, extra if with_normals else None, lf, _p(out["vertices"]), _p(out["faces"]),
+                                           _p(out["keys"]), _p(out["normals"]) if with_normals else None,
+                                           _p(out["face_normals"]) if with_normals else None)
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
 def _color_args(vertices, views, photos, normals, depth, mode, interp, depth_tolerance, min_cos, fallback):
     """The arrays and ctypes arguments vcy_color_vertices and vcy_color_vertices_host share; the first element keeps every
     array alive for the call."""

@@ -279,9 +279,9 @@ int device_make_sdf_batch(hipStream_t stream, int n, const uint8_t* const* masks
 // memory handed to callers (vcy_sdf_upload, vcy_device_alloc / _free, vcy_memcpy_*)
 // vcy_carve.hip: the carve entry points (vcy_carve*, vcy_make_sdf*, vcy_carve_batch_silhouettes, vcy_last_stream_ms),
 // the queue of pending views, the slab planner's wrappers and the two host SDF wrappers
-// vcy_mesh.hip: the vcy_extract_iso* wrappers, vcy_mesh_free / vcy_mesh_normals_free, the extraction's timers, the
-// normals and seam functions of the host (vcy_mesh_normals_host*, vcy_mesh_normals_seam_sum), and the
+// vcy_mesh.hip: the vcy_extract_iso* wrappers, vcy_mesh_free / vcy_mesh_normals_free, the extraction's timers, and the
 // host arrays of returned meshes (page-locked pool); released by vcy_mesh_free
+// mesh_host.hip (host code only): vcy_mesh_normals_host*, vcy_mesh_normals_seam_sum, vcy_merge_meshes_host
 void* mesh_host_alloc(size_t bytes, bool* pinned_out = nullptr);
 void mesh_host_free(void* p);
 void mesh_pool_trim();  // frees the pool's idle buffers (vcy_destroy, when the last context goes)

@@ -8,48 +8,34 @@
 #include <future>
 #include <limits>
 #include <string>
-#include <unordered_map>
 
-#include "vacancy_hip.h"
+#include "c_abi_structs.h"
 #include "mesh_copy.h"
 
 namespace vacancy {
 
 namespace {
 
-vcy_view MakeView(const Camera& camera, int width, int height, bool* ok) {
-  vcy_view v;
-  std::memset(&v, 0, sizeof(v));
-  const Eigen::Affine3f w2c = camera.w2c().cast<float>();
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) v.w2c[4 * i + j] = w2c.linear()(i, j);
-    v.w2c[4 * i + 3] = w2c.translation()[i];
+// fn(s) for every slab on a host thread of its own (a context is single-threaded, different contexts are independent;
+// vcy_last_error() is per thread, so a failure's text comes back with its status)
+template <typename Fn>
+bool ForEachSlab(size_t ns, const char* what, Fn fn) {
+  std::vector<std::future<std::pair<int, std::string>>> jobs;
+  for (size_t s = 0; s < ns; ++s)
+    jobs.push_back(std::async(std::launch::async, [s, &fn]() {
+      const int rc = fn(s);
+      return std::make_pair(rc, rc == VCY_OK ? std::string() : std::string(vcy_last_error()));
+    }));
+  bool ok = true;
+  for (auto& j : jobs) {
+    const std::pair<int, std::string> r = j.get();
+    if (r.first != VCY_OK) {
+      LOGE("sharded %s failed: %s\n", what, r.second.c_str());
+      ok = false;
+    }
   }
-  // Camera::Project is virtual in the reference (camera.h:39-40, called at voxel_carver.cc:460); the device knows the
-  // two projections the reference implements.  Anything else is refused, never projected with fx = fy = 0.
-  if (const PinholeCamera* p = dynamic_cast<const PinholeCamera*>(&camera)) {
-    v.fx = p->focal_length()[0];
-    v.fy = p->focal_length()[1];
-    v.cx = p->principal_point()[0];
-    v.cy = p->principal_point()[1];
-  } else if (dynamic_cast<const OrthoCamera*>(&camera)) {
-    v.is_ortho = 1;
-  } else {
-    *ok = false;
-    LOGE("VoxelCarver::Carve unsupported Camera subclass: the HIP path projects PinholeCamera and OrthoCamera only\n");
-  }
-  v.roi_max[0] = width - 1;
-  v.roi_max[1] = height - 1;
-  v.width = width;
-  v.height = height;
-  return v;
+  return ok;
 }
-
-struct KeyHash {
-  size_t operator()(const std::pair<int64_t, int64_t>& k) const {
-    return std::hash<int64_t>()(k.first * 1000003 + (k.second - k.first));
-  }
-};
 
 }  // namespace
 
@@ -87,34 +73,13 @@ void ShardedVoxelCarver::set_halo_transport(HaloTransport t) { impl_->peer_copy_
 
 int ShardedVoxelCarver::slab_count() const { return static_cast<int>(impl_->slabs.size()); }
 
-namespace {
-vcy_carver_option ToC(const VoxelCarverOption& o) {
-  vcy_carver_option c;
-  std::memset(&c, 0, sizeof(c));
-  for (int i = 0; i < 3; ++i) {
-    c.bb_max[i] = o.bb_max[i];
-    c.bb_min[i] = o.bb_min[i];
-  }
-  c.resolution = o.resolution;
-  c.sdf_minmax_normalize = o.sdf_minmax_normalize ? 1 : 0;
-  c.update_option.voxel_update = static_cast<int>(o.update_option.voxel_update);
-  c.update_option.sdf_interp = static_cast<int>(o.update_option.sdf_interp);
-  c.update_option.update_outside = static_cast<int>(o.update_option.update_outside);
-  c.update_option.voxel_max_update_num = o.update_option.voxel_max_update_num;
-  c.update_option.voxel_update_weight = o.update_option.voxel_update_weight;
-  c.update_option.use_truncation = o.update_option.use_truncation ? 1 : 0;
-  c.update_option.truncation_band = o.update_option.truncation_band;
-  return c;
-}
-}  // namespace
-
 void ShardedVoxelCarver::set_z_bounds(const std::vector<int>& z_bounds) { impl_->wanted_bounds = z_bounds; }
 const std::vector<int>& ShardedVoxelCarver::z_bounds() const { return impl_->bounds; }
 
 bool ShardedVoxelCarver::PlanPartition(const std::vector<const Camera*>& cameras,
                                        const std::vector<Image1b>& silhouettes) {
   if (cameras.empty() || cameras.size() != silhouettes.size()) return false;
-  const vcy_carver_option c = ToC(impl_->option);
+  const vcy_carver_option c = detail::ToC(impl_->option);
   const int count = static_cast<int>(impl_->devices.size()) * impl_->per_device;
   if (count < 2) return true;  // one slab: nothing to cut
   vcy_ctx* planner = nullptr;
@@ -127,7 +92,7 @@ bool ShardedVoxelCarver::PlanPartition(const std::vector<const Camera*>& cameras
   std::vector<float*> imgs(n, nullptr);
   bool ok = true;
   for (int i = 0; i < n && ok; ++i) {
-    views[i] = MakeView(*cameras[i], silhouettes[i].width(), silhouettes[i].height(), &ok);
+    views[i] = detail::ToView(*cameras[i], silhouettes[i].width(), silhouettes[i].height(), &ok);
     if (!ok) break;
     // MakeSignedDistanceField as Carve() will build it (voxel_carver.cc:405-408), on the device
     ok = vcy_make_sdf_device(planner, silhouettes[i].data().data(), views[i].width, views[i].height, views[i].roi_min,
@@ -149,7 +114,7 @@ bool ShardedVoxelCarver::Init() {
   for (vcy_ctx* c : impl_->slabs) vcy_destroy(c);
   impl_->slabs.clear();
   impl_->bounds.clear();
-  const vcy_carver_option c = ToC(impl_->option);
+  const vcy_carver_option c = detail::ToC(impl_->option);
   int32_t dims[3];
   if (vcy_compute_dims(c.bb_min, c.bb_max, c.resolution, dims) != VCY_OK) {
     LOGE("%s\n", vcy_last_error());
@@ -197,7 +162,7 @@ bool ShardedVoxelCarver::Carve(const std::vector<const Camera*>& cameras, const 
   std::vector<const uint8_t*> masks(n);
   for (int i = 0; i < n; ++i) {
     bool known = true;
-    views[i] = MakeView(*cameras[i], silhouettes[i].width(), silhouettes[i].height(), &known);
+    views[i] = detail::ToView(*cameras[i], silhouettes[i].width(), silhouettes[i].height(), &known);
     if (!known) return false;
     masks[i] = silhouettes[i].data().data();
   }
@@ -216,25 +181,11 @@ bool ShardedVoxelCarver::Carve(const std::vector<const Camera*>& cameras, const 
     }
     LOGW("ShardedVoxelCarver: %s; every slab builds its own SDF images\n", vcy_last_error());
   }
-  // one host thread per slab: a context is single-threaded, different contexts are independent.
-  // vcy_last_error() is per thread: the worker hands its message back with the status.
-  std::vector<std::future<std::pair<int, std::string>>> jobs;
-  for (vcy_ctx* ctx : impl_->slabs)
-    jobs.push_back(std::async(std::launch::async, [ctx, n, &views, &masks]() {
-      // one view: queued by the library, carved together with the following calls (vcy_set_param "defer")
-      const int rc = n == 1 ? vcy_carve_silhouette(ctx, &views[0], masks[0], nullptr)
-                            : vcy_carve_batch_silhouettes(ctx, n, views.data(), masks.data());
-      return std::make_pair(rc, rc == VCY_OK ? std::string() : std::string(vcy_last_error()));
-    }));
-  bool ok = true;
-  for (auto& j : jobs) {
-    const std::pair<int, std::string> r = j.get();
-    if (r.first != VCY_OK) {
-      LOGE("sharded carve failed: %s\n", r.second.c_str());
-      ok = false;
-    }
-  }
-  return ok;
+  return ForEachSlab(impl_->slabs.size(), "carve", [&](size_t s) {
+    // one view: queued by the library, carved together with the following calls (vcy_set_param "defer")
+    return n == 1 ? vcy_carve_silhouette(impl_->slabs[s], &views[0], masks[0], nullptr)
+                  : vcy_carve_batch_silhouettes(impl_->slabs[s], n, views.data(), masks.data());
+  });
 }
 
 // the two slices below every slab: ONE RCCL all-gather over the devices that hold slabs
@@ -253,26 +204,6 @@ bool ShardedVoxelCarver::ExchangeHalo() {
   }
   return true;
 }
-
-namespace {
-// fn(s) for every slab on a host thread of its own (a context is single-threaded, different contexts are independent;
-// vcy_last_error() is per thread, so a failure's text comes back with it)
-template <typename Fn>
-bool ForEachSlab(size_t ns, const char* what, Fn fn) {
-  std::vector<std::future<std::string>> jobs;
-  for (size_t s = 0; s < ns; ++s)
-    jobs.push_back(std::async(std::launch::async, [s, &fn]() { return fn(s) == VCY_OK ? std::string() : std::string(vcy_last_error()); }));
-  bool ok = true;
-  for (auto& j : jobs) {
-    const std::string e = j.get();
-    if (!e.empty()) {
-      LOGE("sharded %s failed: %s\n", what, e.c_str());
-      ok = false;
-    }
-  }
-  return ok;
-}
-}  // namespace
 
 // The order of calls of include/vacancy_hip.h ("connected components of a grid cut into z-slabs"): every slab labels its
 // own slices on its device; per seam the lower slab's top plane of labels (nx * ny int64) goes through host memory to the
@@ -348,10 +279,6 @@ bool ShardedVoxelCarver::LabelComponents(std::vector<VoxelComponent>* components
   return true;
 }
 
-// The rule of vcy_keep_components on the merged list, then every slab's own filter kernel over its pieces of the components
-// that go.  The two halo slices below every upper slab are stale afterwards, exactly as after a Carve(): ExtractIsoSurface
-// always, and ExtractVoxel whenever it reads the slice below a slab (inside_empty), call ExchangeHalo() before they
-// read them, so nothing has to be exchanged here.
 bool ShardedVoxelCarver::RenderHull(const Camera&, Image1f*, Image1b*) {
   LOGE("ShardedVoxelCarver::RenderHull: the ray-cast needs the whole grid in one context (VoxelCarver::RenderHull)\n");
   return false;
@@ -374,8 +301,8 @@ bool ShardedVoxelCarver::RenderHullSlabs(const Camera& camera, Image1f* depth, I
   }
   const int w = camera.width(), h = camera.height();
   bool known = true;
-  const vcy_view v = MakeView(camera, w, h, &known);
-  if (!known) return false;  // (MakeView has logged the camera type)
+  const vcy_view v = detail::ToView(camera, w, h, &known);
+  if (!known) return false;  // (ToView has logged the camera type)
   if (!depth || w <= 0 || h <= 0) {
     LOGE("ShardedVoxelCarver::RenderHullSlabs needs a depth image to fill and a camera with a size (%d x %d)\n", w, h);
     return false;
@@ -437,8 +364,8 @@ bool ShardedVoxelCarver::HullAgreementSlabs(const std::vector<const Camera*>& ca
       LOGE("ShardedVoxelCarver::HullAgreementSlabs: view %d has no camera or an empty silhouette\n", i);
       return false;
     }
-    views[static_cast<size_t>(i)] = MakeView(*cameras[static_cast<size_t>(i)], sil.width(), sil.height(), &known);
-    if (!known) return false;  // (MakeView has logged the camera type)
+    views[static_cast<size_t>(i)] = detail::ToView(*cameras[static_cast<size_t>(i)], sil.width(), sil.height(), &known);
+    if (!known) return false;  // (ToView has logged the camera type)
     words[static_cast<size_t>(i)] = (static_cast<size_t>(sil.width()) + 63) / 64 * static_cast<size_t>(sil.height());
   }
   std::vector<std::vector<std::vector<uint64_t>>> hits(ns);  // [slab][view]
@@ -467,6 +394,10 @@ bool ShardedVoxelCarver::HullAgreementSlabs(const std::vector<const Camera*>& ca
   return true;
 }
 
+// The rule of vcy_keep_components on the merged list, then every slab's own filter kernel over its pieces of the components
+// that go.  The two halo slices below every upper slab are stale afterwards, exactly as after a Carve(): ExtractIsoSurface
+// always, and ExtractVoxel whenever it reads the slice below a slab (inside_empty), call ExchangeHalo() before they
+// read them, so nothing has to be exchanged here.
 bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!std::isfinite(fill_sdf) || !(static_cast<double>(fill_sdf) >= iso_level)) {
     LOGE("KeepLargestComponents: fill_sdf %g must be finite and not below the iso level %g\n", static_cast<double>(fill_sdf),
@@ -509,23 +440,14 @@ void ShardedVoxelCarver::ExtractVoxel(Mesh* mesh, bool inside_empty) {
   if (inside_empty && !ExchangeHalo()) return;
   std::vector<int64_t*> ids(ns, nullptr);
   std::vector<int64_t> counts(ns, 0);
-  std::vector<std::string> errors(ns);
-  std::vector<std::future<int>> jobs;
-  for (size_t s = 0; s < ns; ++s)
-    jobs.push_back(std::async(std::launch::async, [this, s, inside_empty, &ids, &counts, &errors]() {
-      const int rc = vcy_extract_voxel_ids(impl_->slabs[s], inside_empty ? 1 : 0, &ids[s], &counts[s]);
-      if (rc != VCY_OK) errors[s] = vcy_last_error();
-      return rc;
-    }));
-  bool ok = true;
-  for (auto& j : jobs) ok = (j.get() == VCY_OK) && ok;
-  for (const std::string& e : errors)
-    if (!e.empty()) LOGE("sharded ExtractVoxel failed: %s\n", e.c_str());
+  const bool ok = ForEachSlab(ns, "ExtractVoxel", [&](size_t s) {
+    return vcy_extract_voxel_ids(impl_->slabs[s], inside_empty ? 1 : 0, &ids[s], &counts[s]);
+  });
   if (ok) {
     // the kept voxels of the whole grid in scan order = the slabs' lists in z order; ONE cube drifts through them
     std::vector<int64_t> all;
     for (size_t s = 0; s < ns; ++s) all.insert(all.end(), ids[s], ids[s] + counts[s]);
-    const vcy_carver_option c = ToC(impl_->option);
+    const vcy_carver_option c = detail::ToC(impl_->option);
     typedef detail::MeshArrays<Eigen::Vector3f, Eigen::Vector3i> Arrays;
     Arrays arrays{mesh->mutable_vertices(), mesh->mutable_vertex_indices()};
     if (vcy_voxel_cubes_into(&c, static_cast<int64_t>(all.size()), all.data(), &Arrays::Provide, &arrays) != VCY_OK) {
@@ -540,113 +462,38 @@ void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool li
   ExtractIsoSurface(mesh, iso_level, linear_interp, false);
 }
 
-// with_normals: every slab's normals come from its own device (vcy_extract_iso_normals_slab); the seam vertices -- those a
-// slab's foreign vertices are mapped to -- are finished on the host over the faces of the two cell layers that meet at
-// the seam (vcy_mesh_normals_seam_sum, from the slabs' own face normals).  The rule is the one of vacancy_amd.dist.merge_meshes.
+// Every slab extracts on its own device -- with_normals: its normals too (vcy_extract_iso_normals_slab) --, and
+// vcy_merge_meshes_host stitches the parts by edge key, and finishes the normals of the seam vertices, into the Mesh's
+// own vectors.
 void ShardedVoxelCarver::ExtractIsoSurface(Mesh* mesh, double iso_level, bool linear_interp, bool with_normals) {
   mesh->Clear();
   const size_t ns = impl_->slabs.size();
   if (ns == 0) return;
   if (!ExchangeHalo()) return;
-  std::vector<vcy_mesh> parts(ns);
+  std::vector<vcy_mesh> parts(ns);  // (all zero: nothing to free where a slab fails)
   std::vector<vcy_mesh_normals> normals(ns);
   std::vector<std::array<int64_t, 2>> layer_faces(ns);
-  std::vector<std::string> errors(ns);
-  std::vector<std::future<int>> jobs;
-  for (size_t s = 0; s < ns; ++s) {
-    std::memset(&parts[s], 0, sizeof(vcy_mesh));
-    std::memset(&normals[s], 0, sizeof(vcy_mesh_normals));
-    layer_faces[s] = {0, 0};
-    jobs.push_back(std::async(std::launch::async, [this, s, iso_level, linear_interp, with_normals, &parts, &normals,
-                                                    &layer_faces, &errors]() {
-      const int rc = with_normals ? vcy_extract_iso_normals_slab(impl_->slabs[s], iso_level, linear_interp ? 1 : 0,
-                                                                 VCY_NORMALS_VERTEX | VCY_NORMALS_FACE, &parts[s],
-                                                                 &normals[s], layer_faces[s].data())
-                                  : vcy_extract_iso(impl_->slabs[s], iso_level, linear_interp ? 1 : 0, &parts[s]);
-      if (rc != VCY_OK) errors[s] = vcy_last_error();
-      return rc;
-    }));
-  }
-  bool ok = true;
-  for (auto& j : jobs) ok = (j.get() == VCY_OK) && ok;
-  for (const std::string& e : errors)
-    if (!e.empty()) LOGE("sharded extraction failed: %s\n", e.c_str());
+  bool ok = ForEachSlab(ns, "extraction", [&](size_t s) {
+    return with_normals ? vcy_extract_iso_normals_slab(impl_->slabs[s], iso_level, linear_interp ? 1 : 0,
+                                                       VCY_NORMALS_VERTEX | VCY_NORMALS_FACE, &parts[s], &normals[s],
+                                                       layer_faces[s].data())
+                        : vcy_extract_iso(impl_->slabs[s], iso_level, linear_interp ? 1 : 0, &parts[s]);
+  });
   if (ok) {
-    // stitch: a slab's first n_foreign vertices are owned by the slab below -> look them up by edge key
-    std::vector<Eigen::Vector3f>* V = mesh->mutable_vertices();
-    std::vector<Eigen::Vector3i>* F = mesh->mutable_vertex_indices();
-    std::vector<Eigen::Vector3f>* N = mesh->mutable_normals();
-    std::vector<Eigen::Vector3f>* FN = mesh->mutable_face_normals();
-    std::unordered_map<std::pair<int64_t, int64_t>, int, KeyHash> prev;
-    struct Seam {
-      int64_t face_begin, face_end;
-      std::vector<int64_t> ids;
-    };
-    std::vector<Seam> seams;
-    int64_t offset = 0;
-    {
-      size_t total_v = 0, total_f = 0;
-      for (const vcy_mesh& m : parts) total_v += static_cast<size_t>(m.n_vertices - m.n_foreign_vertices), total_f += static_cast<size_t>(m.n_faces);
-      V->reserve(total_v);
-      F->reserve(total_f);
-      if (with_normals) N->reserve(total_v), FN->reserve(total_f);
-    }
-    for (size_t s = 0; s < ns && ok; ++s) {
-      const vcy_mesh& m = parts[s];
-      const int64_t nfo = m.n_foreign_vertices, nown = m.n_vertices - nfo;
-      std::vector<int> remap(static_cast<size_t>(m.n_vertices));
-      for (int64_t i = 0; i < nfo; ++i) {
-        auto it = prev.find({m.edge_keys[2 * i], m.edge_keys[2 * i + 1]});
-        if (it == prev.end()) {
-          LOGE("sharded merge: shared-plane vertex without an owner\n");
-          ok = false;
-          break;
-        }
-        remap[i] = it->second;
-      }
-      for (int64_t i = 0; i < nown; ++i) remap[nfo + i] = static_cast<int>(offset + i);
-      const size_t v0 = V->size(), f0 = F->size();
-      detail::CopyTriples(V, m.vertices + 3 * nfo, static_cast<size_t>(nown), v0);
-      F->resize(f0 + m.n_faces);
-      for (int64_t i = 0; i < m.n_faces; ++i)
-        (*F)[f0 + i] = Eigen::Vector3i(remap[m.faces[3 * i]], remap[m.faces[3 * i + 1]], remap[m.faces[3 * i + 2]]);
-      if (with_normals && ok) {
-        // the slab's normals with the merged numbering; its foreign entries go, like its foreign vertices
-        detail::CopyTriples(N, nown > 0 ? normals[s].vertex_normals + 3 * nfo : nullptr, static_cast<size_t>(nown), v0);
-        detail::CopyTriples(FN, normals[s].face_normals, static_cast<size_t>(m.n_faces), f0);
-        if (nfo > 0) {
-          Seam seam;
-          seam.face_begin = static_cast<int64_t>(f0) - layer_faces[s - 1][1];
-          seam.face_end = static_cast<int64_t>(f0) + layer_faces[s][0];
-          seam.ids.assign(remap.begin(), remap.begin() + nfo);
-          seams.push_back(std::move(seam));
-        }
-      }
-      prev.clear();
-      if (s + 1 < ns) {
-        // Only vertices on this slab's top plane can be referenced from above: edges with both voxels in the slice below
-        // the next slab (vcy_mesh::n_foreign_vertices; keys are (lower, higher) GLOBAL voxel ids).  Entering every vertex
-        // made the merge 35 ms for a 600 K-vertex mesh in 8 slabs, where the extraction itself takes 2.
-        const int64_t lo = static_cast<int64_t>(impl_->bounds[s + 1] - 1) * impl_->slice, hi = lo + impl_->slice;
-        for (int64_t i = 0; i < nown; ++i) {
-          const int64_t k0 = m.edge_keys[2 * (nfo + i)], k1 = m.edge_keys[2 * (nfo + i) + 1];
-          if (k0 >= lo && k1 < hi) prev[{k0, k1}] = static_cast<int>(offset + i);
-        }
-      }
-      offset += nown;
-    }
-    if (with_normals && ok) {
-      for (const Seam& seam : seams)
-        if (vcy_mesh_normals_seam_sum(static_cast<int64_t>(V->size()), reinterpret_cast<const int32_t*>(F->data()),
-                                      reinterpret_cast<const float*>(FN->data()), seam.face_begin, seam.face_end,
-                                      static_cast<int64_t>(seam.ids.size()), seam.ids.data(),
-                                      reinterpret_cast<float*>(N->data())) != VCY_OK) {
-          LOGE("sharded merge: %s\n", vcy_last_error());
-          ok = false;
-          break;
-        }
-      if (ok) mesh->set_normal_indices(mesh->vertex_indices());
-    }
+    static_assert(sizeof(Eigen::Vector3f) == 3 * sizeof(float) && sizeof(Eigen::Vector3i) == 3 * sizeof(int32_t), "packed vector layout");
+    size_t nv = 0, nf = 0;  // (the sizes of vcy_merge_meshes_host's arrays; resize() initialises nothing, see mesh_copy.h)
+    for (const vcy_mesh& m : parts) nv += static_cast<size_t>(m.n_vertices - m.n_foreign_vertices), nf += static_cast<size_t>(m.n_faces);
+    mesh->mutable_vertices()->resize(nv);
+    mesh->mutable_vertex_indices()->resize(nf);
+    if (with_normals) mesh->mutable_normals()->resize(nv), mesh->mutable_face_normals()->resize(nf);
+    ok = vcy_merge_meshes_host(static_cast<int>(ns), parts.data(), with_normals ? normals.data() : nullptr,
+                               with_normals ? layer_faces[0].data() : nullptr,
+                               reinterpret_cast<float*>(mesh->mutable_vertices()->data()),
+                               reinterpret_cast<int32_t*>(mesh->mutable_vertex_indices()->data()), nullptr,
+                               with_normals ? reinterpret_cast<float*>(mesh->mutable_normals()->data()) : nullptr,
+                               with_normals ? reinterpret_cast<float*>(mesh->mutable_face_normals()->data()) : nullptr) == VCY_OK;
+    if (!ok) LOGE("sharded merge: %s\n", vcy_last_error());
+    if (ok && with_normals) mesh->set_normal_indices(mesh->vertex_indices());
   }
   if (!ok) mesh->Clear();
   for (vcy_mesh& m : parts) vcy_mesh_free(&m);

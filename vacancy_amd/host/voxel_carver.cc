@@ -6,7 +6,7 @@
 #include <cstring>
 #include <limits>
 
-#include "vacancy_hip.h"
+#include "c_abi_structs.h"
 #include "mesh_copy.h"
 
 namespace vacancy {
@@ -18,36 +18,7 @@ double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-vcy_view ToView(const Camera& camera, const Eigen::Vector2i& roi_min, const Eigen::Vector2i& roi_max, int width,
-                int height, bool* ok) {
-  vcy_view v;
-  std::memset(&v, 0, sizeof(v));
-  const Eigen::Affine3f w2c = camera.w2c().cast<float>();  // reference voxel_carver.cc:438
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) v.w2c[4 * i + j] = w2c.linear()(i, j);
-    v.w2c[4 * i + 3] = w2c.translation()[i];
-  }
-  // Camera::Project is virtual in the reference (camera.h:39-40, called at voxel_carver.cc:460); the device knows the
-  // two projections the reference implements.  Anything else is refused, never projected with fx = fy = 0.
-  if (const PinholeCamera* p = dynamic_cast<const PinholeCamera*>(&camera)) {
-    v.fx = p->focal_length()[0];
-    v.fy = p->focal_length()[1];
-    v.cx = p->principal_point()[0];
-    v.cy = p->principal_point()[1];
-  } else if (dynamic_cast<const OrthoCamera*>(&camera)) {
-    v.is_ortho = 1;
-  } else {
-    *ok = false;
-    LOGE("VoxelCarver::Carve unsupported Camera subclass: the HIP path projects PinholeCamera and OrthoCamera only\n");
-  }
-  v.roi_min[0] = roi_min[0];
-  v.roi_min[1] = roi_min[1];
-  v.roi_max[0] = roi_max[0];
-  v.roi_max[1] = roi_max[1];
-  v.width = width;
-  v.height = height;
-  return v;
-}
+using detail::ToView;
 
 // Per-view Carve() calls only queue their view; the loop the reference times as "VoxelCarver::Carve main loop"
 // (voxel_carver.cc:435,492-493) runs when the queue is applied -- inside the next call that reads the state.  The
@@ -159,22 +130,7 @@ void VoxelCarver::set_device(int device_id) { impl_->device = device_id; }
 bool VoxelCarver::Init() {
   vcy_destroy(impl_->ctx);
   impl_->ctx = nullptr;
-  const VoxelCarverOption& o = impl_->option;
-  vcy_carver_option c;
-  std::memset(&c, 0, sizeof(c));
-  for (int i = 0; i < 3; ++i) {
-    c.bb_max[i] = o.bb_max[i];
-    c.bb_min[i] = o.bb_min[i];
-  }
-  c.resolution = o.resolution;
-  c.sdf_minmax_normalize = o.sdf_minmax_normalize ? 1 : 0;
-  c.update_option.voxel_update = static_cast<int>(o.update_option.voxel_update);
-  c.update_option.sdf_interp = static_cast<int>(o.update_option.sdf_interp);
-  c.update_option.update_outside = static_cast<int>(o.update_option.update_outside);
-  c.update_option.voxel_max_update_num = o.update_option.voxel_max_update_num;
-  c.update_option.voxel_update_weight = o.update_option.voxel_update_weight;
-  c.update_option.use_truncation = o.update_option.use_truncation ? 1 : 0;
-  c.update_option.truncation_band = o.update_option.truncation_band;
+  const vcy_carver_option c = detail::ToC(impl_->option);
   if (vcy_create(&c, impl_->device, 0, -1, &impl_->ctx) != VCY_OK) {
     LOGE("%s\n", vcy_last_error());
     return false;
@@ -258,8 +214,7 @@ bool VoxelCarver::Carve(const std::vector<const Camera*>& cameras, const std::ve
   for (int i = 0; i < n; ++i) {
     const Image1b& s = silhouettes[i];
     bool known = true;
-    views[i] = ToView(*cameras[i], Eigen::Vector2i(0, 0), Eigen::Vector2i(s.width() - 1, s.height() - 1), s.width(),
-                      s.height(), &known);
+    views[i] = ToView(*cameras[i], s.width(), s.height(), &known);
     if (!known) return false;
     masks[i] = s.data().data();
   }
@@ -353,7 +308,7 @@ bool VoxelCarver::RenderHull(const Camera& camera, Image1f* depth, Image1b* silh
   }
   const int w = camera.width(), h = camera.height();
   bool known = true;
-  const vcy_view v = ToView(camera, Eigen::Vector2i(0, 0), Eigen::Vector2i(w - 1, h - 1), w, h, &known);
+  const vcy_view v = ToView(camera, w, h, &known);
   if (!known) return false;  // (ToView has logged the camera type)
   if (!depth || w <= 0 || h <= 0) {
     LOGE("VoxelCarver::RenderHull needs a depth image to fill and a camera with a size (%d x %d)\n", w, h);
@@ -396,8 +351,7 @@ bool VoxelCarver::HullAgreement(const std::vector<const Camera*>& cameras, const
       LOGE("VoxelCarver::HullAgreement: view %d has no camera or an empty silhouette\n", i);
       return false;
     }
-    views[i] = ToView(*cameras[i], Eigen::Vector2i(0, 0), Eigen::Vector2i(s.width() - 1, s.height() - 1), s.width(),
-                      s.height(), &known);
+    views[i] = ToView(*cameras[i], s.width(), s.height(), &known);
     if (!known) return false;  // (ToView has logged the camera type)
     masks[i] = s.data().data();
   }
@@ -440,8 +394,7 @@ bool VoxelCarver::ColorMesh(Mesh* mesh, const std::vector<const Camera*>& camera
       LOGE("VoxelCarver::ColorMesh: view %d has no camera or an empty photograph\n", i);
       return false;
     }
-    views[i] = ToView(*cameras[i], Eigen::Vector2i(0, 0), Eigen::Vector2i(p.width() - 1, p.height() - 1), p.width(),
-                      p.height(), &known);
+    views[i] = ToView(*cameras[i], p.width(), p.height(), &known);
     if (!known) return false;  // (ToView has logged the camera type)
     data[i] = p.data().data();
   }
