@@ -1,6 +1,6 @@
 // C-ABI entry points of libvacancy_hip.so: the error string, version, lifetime of a context, its parameters, timers,
 // the carve log and the device-memory helpers.  State access and halos: vcy_state.hip; the carve entry points:
-// vcy_carve.hip; the mesh entry points and the host pool of their arrays: vcy_mesh.hip.
+// vcy_carve.hip and carve_stream.hip; the mesh entry points and the host pool of their arrays: vcy_mesh.hip.
 #include <algorithm>
 #include <cstdarg>
 #include <cstring>

@@ -242,6 +242,7 @@ int plan_z_slabs(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* 
 int selftest_fused(hipStream_t stream);
 int flush_pending(vcy_ctx* ctx, bool from_carve = false);   // applies vcy_ctx::pending (no-op when empty)
 int check_carve_views(vcy_ctx* ctx, int n_views, const vcy_view* views);  // argument checks of the carve entry points (vcy_carve.hip)
+int check_view_static(const vcy_view* v);  // ... the part of them that needs no context: image size and ROI (vcy_carve.hip)
 int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy_ctx::carve_log, or -1 (vcy_api.hip)
 // mc_extract.hip: the host driver of the marching-cubes extraction (its kernels and their launches: mc_kernels.hip,
 // mc_normals.hip; what the three share: mc_common.h)
@@ -277,8 +278,15 @@ int device_make_sdf_batch(hipStream_t stream, int n, const uint8_t* const* masks
 // vcy_api.hip: the error string (set_error above), vcy_version, vcy_create / vcy_destroy, dims and axis positions, the
 // stream, vcy_set_param / vcy_get_param, timers, the carve log and pair-count readers, the self test, and the device
 // memory handed to callers (vcy_sdf_upload, vcy_device_alloc / _free, vcy_memcpy_*)
-// vcy_carve.hip: the carve entry points (vcy_carve*, vcy_make_sdf*, vcy_carve_batch_silhouettes, vcy_last_stream_ms),
-// the queue of pending views, the slab planner's wrappers and the two host SDF wrappers
+// vcy_carve.hip: the per-view carve entry points (vcy_carve*, vcy_make_sdf_device), the queue of pending views, the slab
+// planner's wrappers and the two host SDF wrappers
+// carve_stream.hip: the streamed silhouette paths (vcy_make_sdf_batch_device, vcy_carve_batch_silhouettes,
+// vcy_carve_batch_silhouettes_sharded with its cached producer groups, vcy_last_stream_ms): one layout, one producer
+// step and one consume step for the three
+// rccl_api.h / rccl_api.hip: the dlopen'd RCCL table, the owner of a communicator, vcy_last_collective
+// halo_exchange.hip: vcy_halo_allgather with its cached communicator groups, vcy_comm_create / _destroy,
+// vcy_halo_allgather_ranks, vcy_halo_shutdown
+// rendezvous.hip (host code only): vcy_rendezvous_exchange, over a file or a TCP port
 // vcy_mesh.hip: the vcy_extract_iso* wrappers, vcy_mesh_free / vcy_mesh_normals_free, the extraction's timers, and the
 // host arrays of returned meshes (page-locked pool); released by vcy_mesh_free
 // mesh_host.hip (host code only): vcy_mesh_normals_host*, vcy_mesh_normals_seam_sum, vcy_merge_meshes_host
