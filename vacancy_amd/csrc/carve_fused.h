@@ -198,11 +198,15 @@ __device__ __forceinline__ FootprintRecord pack_footprint(const TileInfo& ti, co
   return r;
 }
 
-__device__ __forceinline__ TileInfo unpack_footprint(const FootprintRecord r) {
+// (bit casts that the host can make too: the unpack functions below are checked against each other on the CPU)
+__host__ __device__ __forceinline__ float bits_as_float(uint32_t b) { return __builtin_bit_cast(float, b); }
+__host__ __device__ __forceinline__ uint32_t float_as_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
+
+__host__ __device__ __forceinline__ TileInfo unpack_footprint(const FootprintRecord r) {
   TileInfo ti;
   const int tw = (int)((r.w1 >> 26) & 15u), th = (int)(r.w0 & 15u);
   const int tx0 = (int)(r.w1 & 8191u), ty0 = (int)((r.w1 >> 13) & 8191u);
-  ti.ub = __uint_as_float(r.w0 & ~63u);
+  ti.ub = bits_as_float(r.w0 & ~63u);
   ti.sure = (int)(r.w1 >> 30);
   ti.tx0 = tx0, ti.ty0 = ty0, ti.tw = tw, ti.th = (tw ? th : 0), ti.nq = tw * th;
   ti.pitchf = tw ? 16.0f : 0.0f;
@@ -212,8 +216,8 @@ __device__ __forceinline__ TileInfo unpack_footprint(const FootprintRecord r) {
     const int tx1 = tx0 + tw - 1, ty1 = ty0 + th - 1;
     ti.lo_x = (float)tx0, ti.lo_y = (float)ty0;
     // taps exist for floor(u) in [tx0, tx1]; at the ROI edge u == roi_max (== tx1) is still inside
-    ti.hi_x = (r.w0 & 16u) ? (float)tx1 : __uint_as_float(__float_as_uint((float)(tx1 + 1)) - 1u);
-    ti.hi_y = (r.w0 & 32u) ? (float)ty1 : __uint_as_float(__float_as_uint((float)(ty1 + 1)) - 1u);
+    ti.hi_x = (r.w0 & 16u) ? (float)tx1 : bits_as_float(float_as_bits((float)(tx1 + 1)) - 1u);
+    ti.hi_y = (r.w0 & 32u) ? (float)ty1 : bits_as_float(float_as_bits((float)(ty1 + 1)) - 1u);
   } else {
     ti.lo_x = ti.lo_y = INFINITY;  // nothing passes the tile test
     ti.hi_x = ti.hi_y = -INFINITY;
@@ -221,6 +225,53 @@ __device__ __forceinline__ TileInfo unpack_footprint(const FootprintRecord r) {
     ti.sure = 0;
   }
   return ti;
+}
+
+// The same record for a wave that keeps it packed (carve_fused_kernel with raw tiles, records from the pre-pass and a
+// brick per wave: lane v holds the two words of view v).  Unpacked into a TileInfo by every lane and parked in LDS, each
+// field a processed view needs came back through a ds_read and a v_readfirstlane; here the words of the view in hand are
+// fetched with two v_readlane and taken apart as integers, which for uniform words is work of the scalar unit.
+//   footprint_ub_word   what the lane keeps of word 0: the word itself, or +inf where the record has no tile
+//   footprint_ub        the bound in it (TileInfo::ub)
+//   unpack_footprint_scalar   the integer fields of (that word, word 1)
+//   footprint_base / footprint_bounds   TileInfo::base and lo / hi, formed where they are needed
+// Each equals the field of unpack_footprint bit for bit, for every record (tests/test_footprint_unpack_host.py).  The
+// pitch of a raw tile is kTileRaw, which is TileInfo::pitchf of every record that has a tile.
+struct FootprintFields {
+  int tx0, ty0, tw, th, nq;  // (th: 0 without a tile)
+  int sure;                  // TileInfo::sure
+  int edge;                  // bit 0 / 1: the tile ends at the ROI's last column / row
+};
+struct FootprintBounds {
+  float lo_x, hi_x, lo_y, hi_y;
+};
+__host__ __device__ __forceinline__ uint32_t footprint_ub_word(uint32_t w0, uint32_t w1) {
+  return ((w1 >> 26) & 15u) ? w0 : 0x7f800000u;
+}
+__host__ __device__ __forceinline__ float footprint_ub(uint32_t ub_word) { return bits_as_float(ub_word & ~63u); }
+__host__ __device__ __forceinline__ FootprintFields unpack_footprint_scalar(uint32_t ub_word, uint32_t w1) {
+  FootprintFields f;
+  const int th = (int)(ub_word & 15u);
+  f.tw = (int)((w1 >> 26) & 15u);
+  f.tx0 = (int)(w1 & 8191u), f.ty0 = (int)((w1 >> 13) & 8191u);
+  f.th = f.tw ? th : 0, f.nq = f.tw * th;
+  f.sure = f.tw ? (int)(w1 >> 30) : 0;
+  f.edge = (int)((ub_word >> 4) & 3u);
+  return f;
+}
+__host__ __device__ __forceinline__ int footprint_base(const FootprintFields& f) { return f.tw ? -(f.ty0 * 16 + f.tx0) : 0; }
+__host__ __device__ __forceinline__ FootprintBounds footprint_bounds(const FootprintFields& f) {
+  FootprintBounds b;
+  if (f.tw) {
+    const int tx1 = f.tx0 + f.tw - 1, ty1 = f.ty0 + f.th - 1;
+    b.lo_x = (float)f.tx0, b.lo_y = (float)f.ty0;
+    b.hi_x = (f.edge & 1) ? (float)tx1 : bits_as_float(float_as_bits((float)(tx1 + 1)) - 1u);
+    b.hi_y = (f.edge & 2) ? (float)ty1 : bits_as_float(float_as_bits((float)(ty1 + 1)) - 1u);
+  } else {
+    b.lo_x = b.lo_y = INFINITY;  // nothing passes the tile test
+    b.hi_x = b.hi_y = -INFINITY;
+  }
+  return b;
 }
 
 // Exact n / d for 32-bit unsigned n (Granlund-Montgomery, as in mc_kernels.hip): three integer instructions where the

@@ -226,18 +226,8 @@ typedef uint32_t __attribute__((address_space(3))) lds_u32;
 // Raw tile of view `v` into the wave-private LDS buffer `buf` (256 floats): pixel (i, j) of the tile =
 // image pixel (min(tx0 + i, roi_max.x), min(ty0 + j, roi_max.y)), for the th + 1 <= 16 rows the taps reach.
 // Asynchronous: the data is in LDS once the wave's vmcnt has drained (raw_tile_wait).
-__device__ __forceinline__ void raw_prefetch(const ViewParams& v, const TileInfo& ti, int lane, float* buf) {
-#ifdef VCY_FLOOR_NO_TILE_LOADS  // development build (issue floor, profiles/tools/issue_floor.sh): the taps read whatever LDS holds
-  return;
-#endif
-  // (opaque: lane >> 4 and lane & 15 are formed here, every time -- hoisted out of the view loop they were two more
-  // registers live through every view, and the weighted-average kernels spilled exactly those to scratch)
-  asm volatile("" : "+v"(lane));
-  const int nq = __builtin_amdgcn_readfirstlane(ti.nq);
-  if (nq == 0) return;
-  const int th = __builtin_amdgcn_readfirstlane(ti.th);
-  const int tx0 = __builtin_amdgcn_readfirstlane(ti.tx0);
-  const int ty0 = __builtin_amdgcn_readfirstlane(ti.ty0);
+// raw_prefetch_rows: the requests, given the tile's uniform origin and height.
+__device__ __forceinline__ void raw_prefetch_rows(const ViewParams& v, int th, int tx0, int ty0, int lane, float* buf) {
   gfloat_ptr img = (gfloat_ptr)v.sdf;
   const unsigned width = (unsigned)v.width;
   lds_float* dst = (lds_float*)buf;
@@ -262,6 +252,58 @@ __device__ __forceinline__ void raw_prefetch(const ViewParams& v, const TileInfo
       const unsigned yy = (unsigned)min(yl + 4 * r, v.roi_max_yi);
       __builtin_amdgcn_global_load_lds(img + (__umul24(width, yy) + xx), dst + 64 * r, 4, 0, 0);
     }
+  }
+}
+__device__ __forceinline__ void raw_prefetch(const ViewParams& v, const TileInfo& ti, int lane, float* buf) {
+#ifdef VCY_FLOOR_NO_TILE_LOADS  // development build (issue floor, profiles/tools/issue_floor.sh): the taps read whatever LDS holds
+  return;
+#endif
+  // (opaque: lane >> 4 and lane & 15 are formed here, every time -- hoisted out of the view loop they were two more
+  // registers live through every view, and the weighted-average kernels spilled exactly those to scratch)
+  asm volatile("" : "+v"(lane));
+  const int nq = __builtin_amdgcn_readfirstlane(ti.nq);
+  if (nq == 0) return;
+  const int th = __builtin_amdgcn_readfirstlane(ti.th);
+  const int tx0 = __builtin_amdgcn_readfirstlane(ti.tx0);
+  const int ty0 = __builtin_amdgcn_readfirstlane(ti.ty0);
+  raw_prefetch_rows(v, th, tx0, ty0, lane, buf);
+}
+// ... for a wave that holds the record's fields as scalars (unpack_footprint_scalar): nothing to make uniform
+__device__ __forceinline__ void raw_prefetch(const ViewParams& v, const FootprintFields& f, int lane, float* buf) {
+#ifdef VCY_FLOOR_NO_TILE_LOADS
+  return;
+#endif
+  asm volatile("" : "+v"(lane));  // (as above)
+  if (f.nq == 0) return;
+  // The same requests as raw_prefetch_rows makes -- one per group of four rows that holds a tap row (taps reach rows
+  // 0 .. th) -- entered at the last group and falling through to the first: one forward branch on the uniform group
+  // count instead of a test in front of every request.  (Requests complete in order whichever is issued first.)
+  gfloat_ptr img = (gfloat_ptr)v.sdf;
+  const unsigned width = (unsigned)v.width;
+  lds_float* dst = (lds_float*)buf;
+  const int groups = (f.th >> 2) + 1;
+  if (f.tx0 + 15 <= v.roi_max_xi && f.ty0 + 15 <= v.roi_max_yi) {  // (uniform) nothing is clamped
+    const unsigned lane_off = __umul24(width, (unsigned)lane >> 4) + ((unsigned)lane & 15u);
+    gfloat_ptr base = img + (__umul24(width, (unsigned)f.ty0) + (unsigned)f.tx0);
+    switch (groups) {
+      default: __builtin_amdgcn_global_load_lds(base + (size_t)12 * width + lane_off, dst + 192, 4, 0, 0); [[fallthrough]];
+      case 3: __builtin_amdgcn_global_load_lds(base + (size_t)8 * width + lane_off, dst + 128, 4, 0, 0); [[fallthrough]];
+      case 2: __builtin_amdgcn_global_load_lds(base + (size_t)4 * width + lane_off, dst + 64, 4, 0, 0); [[fallthrough]];
+      case 1: __builtin_amdgcn_global_load_lds(base + lane_off, dst, 4, 0, 0);
+    }
+    return;
+  }
+  const unsigned xx = (unsigned)min(f.tx0 + (lane & 15), v.roi_max_xi);
+  const int yl = f.ty0 + (lane >> 4);
+  auto row = [&](int r) {
+    const unsigned yy = (unsigned)min(yl + 4 * r, v.roi_max_yi);
+    __builtin_amdgcn_global_load_lds(img + (__umul24(width, yy) + xx), dst + 64 * r, 4, 0, 0);
+  };
+  switch (groups) {
+    default: row(3); [[fallthrough]];
+    case 3: row(2); [[fallthrough]];
+    case 2: row(1); [[fallthrough]];
+    case 1: row(0);
   }
 }
 
@@ -573,6 +615,25 @@ __device__ __attribute__((noinline)) float brick_footprints(const FusedView* __r
     ub_lane = ti.ub;
   }
   return ub_lane;
+}
+
+// The same for the raw-tile kernels that keep their footprints as packed records in registers: lane vi returns the record
+// the pre-pass would have written for view vi (footprint_records_kernel), a lane without a view "no tile, no bound".
+template <bool SAMEF, bool GEN>
+__device__ __attribute__((noinline)) FootprintRecord brick_footprint_records(const FusedView* __restrict__ views, int nviews,
+                                                                             int lane, float xl, float xh, float yl, float yh,
+                                                                             float zl_, float zh, bool is_ortho,
+                                                                             bool outside_max, bool want_bound,
+                                                                             bool want_lower) {
+  FootprintRecord rec;
+  rec.w0 = 0x7f800000u, rec.w1 = 0u;
+  if (lane < nviews) {
+    const FusedView fv = load_fused_view(views, lane);
+    const TileInfo ti = footprint_of<SAMEF, kTileRaw, GEN>(fv, xl, xh, yl, yh, zl_, zh, is_ortho, outside_max, want_bound,
+                                                            want_lower);
+    rec = pack_footprint(ti, fv.v);
+  }
+  return rec;
 }
 
 }  // namespace

@@ -44,6 +44,15 @@ constexpr int carve_waves_per_simd() {
   if (UPDATE == kUpdateWaUnitWeight) return NB == 0 ? VCY_WAVES_WA_ONE : VCY_WAVES_WA;
   return NB == 0 ? VCY_WAVES_ONE : VCY_WAVES;
 }
+// The instances that keep a wave's footprint records packed in registers instead of a TileInfo per view in LDS
+// (unpack_footprint_scalar, carve_fused.h): kMax with raw tiles and a brick per wave.  The weighted-average instances sit
+// at their register limit -- with the second record word the unit-weight truncating one spills 80 bytes per lane where it
+// spilled 64 (profiles/record_regs) -- and keep the TileInfo; so do the big tile (its pitch and bounds are not in a
+// record) and the few-view flavour (a lane per PAIR, LDS to spare).
+template <int UPDATE, int TQ, int NB>
+constexpr bool carve_keeps_records() {
+  return UPDATE == VCY_UPDATE_MAX && TQ == kTileRaw && NB == 1;
+}
 template <typename CountT, int UPDATE, bool TRUNC, bool SAMEF, bool CHECKMAX, int TQ, bool GEN, int DIV, int NB = 1>
 __global__ __launch_bounds__(64 * (NB > 1 ? kRowWaves : kWgWaves))
 __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHECKMAX, TQ, GEN, NB>(),
@@ -76,10 +85,13 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   const bool nt_store = (state_flags & kStateStreamStore) != 0;  // cooperative write-back with streaming stores
   constexpr bool kRows = NB > 1;  // the few-view flavour: this WAVE walks NB bricks of a row (kRowBricks)
   static_assert(!kRows || (TQ == kTileRaw && !CHECKMAX), "the few-view flavour: raw tiles, no update limit in reach");
-  // dynamic LDS: [4 waves][TQ] quads, then [4 waves][nviews] TileInfo (sized by the launch), then the staging of the
-  // cooperative write-back
+  // dynamic LDS: [4 waves][TQ] quads, then [4 waves][nviews] TileInfo (sized by the launch; none where the records stay
+  // in registers: NB == 0, kRecRegs), then the staging of the cooperative write-back
   extern __shared__ float4 fused_lds[];
   constexpr bool kRaw = TQ == kTileRaw;                  // raw-pixel tiles, loaded straight into LDS
+  // kMax with raw tiles and a brick per wave: the footprint records stay PACKED, two registers per lane (lane v: view v),
+  // and no TileInfo goes to LDS -- see unpack_footprint_scalar and carve_keeps_records.
+  constexpr bool kRecRegs = carve_keeps_records<UPDATE, TQ, NB>();
   // (NB == 0: ONE tile buffer -- there is no next view to fetch ahead -- and no TileInfo: 18.4 KB per workgroup with the
   // cooperative write-back's staging instead of 22.5, i.e. eight workgroups per CU where seven fit)
   constexpr int kTileF4 = NB == 0 ? 64 : tile_f4_per_wave<TQ>();
@@ -119,8 +131,8 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   typedef CountT CountVec8 __attribute__((ext_vector_type(WX)));
   typedef CountVec8 __attribute__((address_space(3))) lds_countvec;
   typedef unsigned long long __attribute__((address_space(3))) lds_u64;
-  float* coop_s = NB == 0 ? (float*)(fused_lds + kWgWaves * kTileF4)
-                          : (float*)((TileInfo*)(fused_lds + kWgWaves * kTileF4) + kWgWaves * nviews);
+  float* coop_s = (NB == 0 || kRecRegs) ? (float*)(fused_lds + kWgWaves * kTileF4)
+                                        : (float*)((TileInfo*)(fused_lds + kWgWaves * kTileF4) + kWgWaves * nviews);
   CountT* coop_n = (CountT*)(coop_s + 64 * kCoopSdfPitch);
   lds_u64* coop_mask = (lds_u64*)(unsigned long long*)(coop_n + 64 * coop_cnt_pitch<CountT>());
   // A wave that leaves early tells the others that none of its rows is to be stored and that it will not be there to
@@ -137,8 +149,26 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     if constexpr (kOneRegs) return ti_one;
     else return tinfo[p];
   };
+  // kRecRegs: this lane's record -- word 0 (footprint_ub_word: the bound, th, the edge bits) and word 1; a lane without
+  // a view holds "no tile, no bound"
+  uint32_t rec_w0 = 0x7f800000u, rec_w1 = 0u;
+  auto rec_of = [&](int p) -> FootprintFields {  // the fields of view p's record, as scalars
+    return unpack_footprint_scalar((uint32_t)__builtin_amdgcn_readlane((int)rec_w0, p),
+                                   (uint32_t)__builtin_amdgcn_readlane((int)rec_w1, p));
+  };
   int cur = 0;  // raw tiles: which of the wave's buffers holds the view being carved
   auto raw_buf = [&](int b) -> float* { return (float*)tile + 256 * b; };
+  // requests the raw tile of view / pair p into `buf`
+  auto prefetch_tile = [&](int p, float* buf) {
+    const ViewParams& v = views[kRows ? (p & 7) : p].v;
+    if constexpr (kRecRegs) raw_prefetch(v, rec_of(p), lane, buf);
+    else raw_prefetch(v, tile_of(p), lane, buf);
+  };
+  // TileInfo::sure of view / pair p, uniform
+  auto sure_of = [&](int p) -> int {
+    if constexpr (kRecRegs) return rec_of(p).sure;
+    else return __builtin_amdgcn_readfirstlane(tile_of(p).sure);
+  };
   const int ly = lane & (BY - 1), lz = lane >> 3;
   // XCD-aware order: the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, so
   // workgroup b runs on XCD b % 8.  Give every XCD one contiguous eighth of the brick list: bricks
@@ -284,18 +314,33 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     ti_one = unpack_footprint(rec);
     ub_lane = ti_one.ub;
   } else if (kRaw && records != nullptr) {
-    // raw tiles: the footprints come from the pre-pass (footprint_records_kernel), 8 bytes per view
+    // raw tiles: the footprints come from the pre-pass (footprint_records_kernel), 8 bytes per view (kRecRegs: and stay
+    // as they are in the lane that loaded them)
     ub_lane = INFINITY;
     if (lane < nviews) {
       typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
       typedef const u32x2 __attribute__((address_space(1))) * grec_ptr;
       const u32x2 raw = ((grec_ptr)records)[(int64_t)lane * nbricks + brick_lin];
-      FootprintRecord rec;
-      rec.w0 = raw.x, rec.w1 = raw.y;
-      const TileInfo ti = unpack_footprint(rec);
-      store_tile_info((lds_u32*)tinfo, lane, ti);
-      ub_lane = ti.ub;
+      if constexpr (kRecRegs) {
+        rec_w0 = footprint_ub_word(raw.x, raw.y), rec_w1 = raw.y;
+      } else {
+        FootprintRecord rec;
+        rec.w0 = raw.x, rec.w1 = raw.y;
+        const TileInfo ti = unpack_footprint(rec);
+        store_tile_info((lds_u32*)tinfo, lane, ti);
+        ub_lane = ti.ub;
+      }
     }
+  } else if constexpr (kRecRegs) {
+    // "prologue" 1: the record the pre-pass would have left for this lane's view, made here (brick_footprint_records)
+    const int x_lo = min(x_first, g.nx - 1), x_hi = min(x_first + WX - 1, g.nx - 1);
+    const int y_hi = min(by * BY + BY - 1, g.ny - 1);
+    const int z_hi = min(zl0 + BZ - 1, g.nz_local - 1);
+    const FootprintRecord rec = brick_footprint_records<SAMEF, GEN>(
+        views, nviews, lane, g.px[x_lo], g.px[x_hi], g.py[by * BY], g.py[y_hi], g.pz[g.z0 + zl0], g.pz[g.z0 + z_hi],
+        mode.ortho != 0, mode.outside == VCY_OUTSIDE_MAX, want_bound, want_bound && TRUNC && UPDATE != VCY_UPDATE_MAX);
+    rec_w0 = footprint_ub_word(rec.w0, rec.w1), rec_w1 = rec.w1;
+    ub_lane = INFINITY;
   } else {
     // the big tile -- and raw tiles of a launch whose records would not fit (`records` null: 2048^3 x 64 views would
     // write and read back 8.6 GB of them in nine chunks; with 64 views every lane of this prologue has a view)
@@ -307,6 +352,11 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
                                                mode.outside == VCY_OUTSIDE_MAX, want_bound,
                                                want_bound && TRUNC && UPDATE != VCY_UPDATE_MAX, (lds_u32*)tinfo);
   }
+  // this lane's bound (TileInfo::ub of its view)
+  auto lane_ub = [&]() -> float {
+    if constexpr (kRecRegs) return footprint_ub(rec_w0);
+    else return ub_lane;
+  };
   wave_lds_fence();
 #if defined(VCY_DEV_EXIT_AT) && VCY_DEV_EXIT_AT == 2  // development build: where a wave's scalar instructions go (profiles/tools/salu_attribution.sh)
   {
@@ -322,12 +372,12 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   if (want_bound && !fresh && !(kOne && list_entry != nullptr)) {
     const bool have_min = UPDATE == VCY_UPDATE_MAX && (state_flags & kStateBrickMinValid) != 0 && brick_min != nullptr;
     if (TRUNC || have_min) {
-      bool drop0 = TRUNC && ub_lane < -1.0f;
+      bool drop0 = TRUNC && lane_ub() < -1.0f;
       if (have_min) {
         float smin0;
         if constexpr (kRows) smin0 = pair_valid ? brick_min[brick_seg + pair_j] : 0.0f;  // (this lane's brick)
         else smin0 = ((cfloat_ptr)brick_min)[brick_lin];  // (uniform: a scalar load)
-        drop0 = drop0 || ub_lane <= smin0;  // (a brick with an untouched voxel holds lowest(): never true)
+        drop0 = drop0 || lane_ub() <= smin0;  // (a brick with an untouched voxel holds lowest(): never true)
       }
       live = __ballot(!drop0) & view_mask;
       if (live == 0ull) {
@@ -338,7 +388,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   }
 #ifdef VCY_PHASE_TIMING
   {
-    asm volatile("" ::"v"(ub_lane));
+    asm volatile("" ::"v"(lane_ub()));
     const unsigned long long t_ = __builtin_amdgcn_s_memtime();
     pt_acc[13] += t_ - pt_last;  // (includes slot 12)
   }
@@ -357,6 +407,22 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   typedef typename std::conditional<kFloatCount, float, int>::type NT;
   float s[WX];
   NT n[WX];
+  // kMax on a fresh slab: the first live view of nearly every brick is `sure`, and its run (FIRST) overwrites all sixteen
+  // registers -- the untouched state is only written out where something reads it: the checked paths, the write-back
+  constexpr bool kLazyFresh = UPDATE == VCY_UPDATE_MAX && !TRUNC && !CHECKMAX && NB == 1;
+  bool state_set = true;  // (uniform) false: fresh slab, s[] / n[] not yet formed
+  auto set_fresh_state = [&]() {
+    if constexpr (kLazyFresh) {
+      if (!state_set) {
+#pragma unroll
+        for (int k = 0; k < WX; ++k) {
+          s[k] = kInvalidSdf;
+          n[k] = (NT)0;
+        }
+        state_set = true;
+      }
+    }
+  };
   const int64_t row0 = ((int64_t)zl * g.ny + y) * g.nx;  // this lane's row; voxel k is at row0 + min(x_first + k, nx - 1)
   // The first view this brick will process is usually known BEFORE its state is: it is the first view the bounds do not
   // drop, and what the bounds are compared with -- the truncation limit, the brick minimum the previous launch left --
@@ -372,16 +438,16 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       if (!(fresh || UPDATE != VCY_UPDATE_MAX || !want_bound || have_min || listed_live)) return;
       bool drop = false;
       if (want_bound && !listed_live) {
-        if (TRUNC) drop = ub_lane < -1.0f;
+        if (TRUNC) drop = lane_ub() < -1.0f;
         if (have_min) {
           const float smin0 = ((cfloat_ptr)brick_min)[brick_lin];
           // (lowest(): a voxel of the brick is untouched -- all_touched will be false and nothing is dropped by this rule)
-          if (smin0 != kInvalidSdf) drop = drop || ub_lane <= smin0;
+          if (smin0 != kInvalidSdf) drop = drop || lane_ub() <= smin0;
         }
       }
       const unsigned long long lp = __ballot(!drop) & view_mask;
       vi_pre = lp ? (__ffsll((long long)lp) - 1) : nviews;
-      if (vi_pre < nviews) raw_prefetch(views[vi_pre].v, tile_of(vi_pre), lane, raw_buf(0));
+      if (vi_pre < nviews) prefetch_tile(vi_pre, raw_buf(0));
     }
   };
   // rows are whole bricks when nx % 8 == 0: the run is one 32-byte (sdf) and one 8/16-byte (update_num) vector
@@ -429,10 +495,14 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       }
     }
   } else if (fresh) {  // a fresh slab is known to be untouched everywhere: nothing to read
+    if constexpr (kLazyFresh) {
+      state_set = false;
+    } else {
 #pragma unroll
-    for (int k = 0; k < WX; ++k) {
-      s[k] = kInvalidSdf;
-      n[k] = (NT)0;
+      for (int k = 0; k < WX; ++k) {
+        s[k] = kInvalidSdf;
+        n[k] = (NT)0;
+      }
     }
   } else if (vec_io) {
     // (streaming LOADS of the state were measured too: 2.7 -> 5.3 ms per view, profiles/r06/nontemporal.txt)
@@ -513,13 +583,13 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   auto live_views = [&]() -> unsigned long long {
     bool drop = false;
     if (want_bound) {
-      if (TRUNC) drop = ub_lane < -1.0f;
+      if (TRUNC) drop = lane_ub() < -1.0f;
       if (UPDATE == VCY_UPDATE_MAX && all_touched) {
         float m = s[0];
 #pragma unroll
         for (int k = 1; k < WX; ++k) m = fminf(m, s[k]);
         const float smin = wave_min(m);
-        drop = drop || ub_lane <= smin;
+        drop = drop || lane_ub() <= smin;
       }
     }
     if constexpr (kRows) {  // (the bounds of the other bricks' pairs stand as they are)
@@ -540,7 +610,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   unsigned long long changed_lanes = 0ull;
   if (!kRows) live = live_views();
   int vi = live ? (__ffsll((long long)live) - 1) : vi_end;
-  if (kRaw && vi < vi_end && vi != vi_pre) raw_prefetch(views[kRows ? (vi & 7) : vi].v, tile_of(vi), lane, raw_buf(0));
+  if (kRaw && vi < vi_end && vi != vi_pre) prefetch_tile(vi, raw_buf(0));
   // NB > 1: the brick whose turn it is takes its state from the staging area (the LDS-direct requests above have
   // landed once the wave has waited for its first tile) and leaves it there again when the next brick begins
   typedef CountT CountVecR __attribute__((ext_vector_type(WX)));
@@ -636,10 +706,13 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     wave_lds_fence();
     // the next live view's tile is fetched while this one is computed
     vnext = next_view(live, vi);
-    if (kRaw && vnext < vi_end) raw_prefetch(views[kRows ? (vnext & 7) : vnext].v, tile_of(vnext), lane, raw_buf(cur ^ 1));
+    if (kRaw && vnext < vi_end) prefetch_tile(vnext, raw_buf(cur ^ 1));
     ++n_processed;
-    pitchf = tile_of(vi).pitchf;
-    base = tile_of(vi).base;
+    if constexpr (kRecRegs) {  // (a raw tile's pitch is 16; a record without a tile is never sampled from)
+      pitchf = (float)kTileRaw, base = footprint_base(rec_of(vi));
+    } else {
+      pitchf = tile_of(vi).pitchf, base = tile_of(vi).base;
+    }
     big_pitch = kRaw ? 16 : (int)pitchf;  // pixels per row of the big tile
     rawcur = (const lds_float*)raw_buf(cur);
     // c1 + c2 of this lane's (y, z): the inner sum of pc = t + (c0 + (c1 + c2)) (voxel_carver.cc:453)
@@ -663,7 +736,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       if (v2 != vnext) {
         vnext = v2;
         // (the dropped view's pixels may still be arriving in that buffer: loads complete in order)
-        if (kRaw && vnext < vi_end) raw_prefetch(views[kRows ? (vnext & 7) : vnext].v, tile_of(vnext), lane, raw_buf(cur ^ 1));
+        if (kRaw && vnext < vi_end) prefetch_tile(vnext, raw_buf(cur ^ 1));
       }
     }
     vi = vnext;
@@ -675,7 +748,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   auto next_fast_bits = [&]() -> int {
     if (kOne || vi >= vi_end) return 0;
     if (kRows && (vi >> 3) != jc) return 0;  // (the pair belongs to another brick of the segment)
-    const int bits = __builtin_amdgcn_readfirstlane(tile_of(vi).sure);
+    const int bits = sure_of(vi);
     return (bits & 1) != 0 ? bits : 0;
   };
   while (vi < vi_end) {
@@ -690,7 +763,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
         if (((live >> vi) & 1ull) == 0ull) {
           vi = next_view(live, vi);
           // (the dropped pair's pixels may still be arriving in that buffer: loads complete in order)
-          if (vi < vi_end) raw_prefetch(views[vi & 7].v, tile_of(vi), lane, raw_buf(cur));
+          if (vi < vi_end) prefetch_tile(vi, raw_buf(cur));
           continue;
         }
       }
@@ -715,8 +788,15 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     auto carve_view = [&](auto sure_tag) {
       constexpr bool SURE = decltype(sure_tag)::value;
       cview& v = *vp;
-      const float lo_x = tile_of(vi).lo_x, hi_x = tile_of(vi).hi_x;
-      const float lo_y = tile_of(vi).lo_y, hi_y = tile_of(vi).hi_y;
+      // the closed range of (u, w) whose taps are in the tile (kRecRegs: formed here, only the checked loop asks)
+      float lo_x, hi_x, lo_y, hi_y;
+      if constexpr (kRecRegs) {
+        const FootprintBounds fb = footprint_bounds(rec_of(vi));
+        lo_x = fb.lo_x, hi_x = fb.hi_x, lo_y = fb.lo_y, hi_y = fb.hi_y;
+      } else {
+        lo_x = tile_of(vi).lo_x, hi_x = tile_of(vi).hi_x;
+        lo_y = tile_of(vi).lo_y, hi_y = tile_of(vi).hi_y;
+      }
       bool slow[WX];
       bool any_slow = false;
       bool moved = false;  // some voxel of this lane changed
@@ -897,7 +977,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       return (kFastMax && !FIRST) ? took != 0ull : true;
     };
     bool brick_moved;
-    const int sure_bits = __builtin_amdgcn_readfirstlane(tile_of(vi).sure);
+    const int sure_bits = sure_of(vi);
     const bool sure = (sure_bits & 1) != 0, never_truncated = (sure_bits & 2) != 0;
     // (Branch weights: the checked loops below are the rare ones in the kernels that have a select-free loop;
     // the register allocator then spills there, if anywhere, and not in the loops that do the work.)
@@ -906,6 +986,8 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     // general weights: every voxel updated by this view and all counts equal -- a first touch stores the sample
     // (voxel_carver.cc:482-486), later views average with the brick's weights
     const bool fast_general = kFastWaGeneral && sure && uniform_cnt && (!TRUNC || never_truncated);
+    if (kLazyFresh && fast_first) state_set = true;  // (FIRST writes every s[k], n[k])
+    else set_fresh_state();
     if (kFastWaGeneral && __builtin_expect_with_probability(fast_general, 1, 0.9)) {
       if (fnu < 1.0f) {
         brick_moved = carve_view_fast(std::true_type{}, std::false_type{}, std::false_type{});
@@ -1002,6 +1084,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     return;
   }
   leave_uniform();
+  set_fresh_state();  // (no view was processed)
   // Where this lane's run lies is worked out again from the thread id (opaque to the compiler): kept from the prologue
   // it occupies three registers through every view, and the weighted-average kernels are short of exactly those --
   // their loop pre-header spilled to scratch, which every wave executes.
@@ -1126,12 +1209,14 @@ template <typename CountT, int UPDATE, bool TRUNC, bool SAMEF, bool CHECKMAX, in
 void launch_instance(const CarveLaunch& l) {
   constexpr bool kRows = NB > 1;
   // dynamic LDS.  kRows: every wave its own region.  Otherwise: the waves' tiles (NB == 0: ONE raw tile each), the
-  // TileInfo of every (wave, view) (NB == 0: in registers), the staging of the cooperative write-back.
+  // TileInfo of every (wave, view) (NB == 0 and carve_keeps_records: none, the records are in registers), the staging
+  // of the cooperative write-back.
   const size_t coop = (l.state_flags & kStateCoopStore) ? coop_lds_bytes<CountT>() : 0;
+  constexpr bool rec_regs = carve_keeps_records<UPDATE, TQ, NB>();
   const size_t lds = kRows    ? (size_t)kRowWaves * row_lds_bytes_per_wave<CountT, NB>()
                      : NB == 0 ? (size_t)kWgWaves * 64 * sizeof(float4) + coop
                                : (size_t)kWgWaves * tile_f4_per_wave<TQ>() * sizeof(float4) +
-                                     (size_t)kWgWaves * l.n_views * sizeof(TileInfo) + coop;
+                                     (rec_regs ? 0 : (size_t)kWgWaves * l.n_views * sizeof(TileInfo)) + coop;
   // (kRows: `grid_x` workgroups of kRowWaves waves, a segment per wave; the decode deals the launch's segments to the XCDs)
   const BlockDecode bd = make_block_decode(kRows ? (unsigned)l.row_units : l.grid_x, l.nbx, l.nby);
   hipLaunchKernelGGL((carve_fused_kernel<CountT, UPDATE, TRUNC, SAMEF, CHECKMAX, TQ, GEN, DIV, NB>), dim3(l.grid_x),
