@@ -274,6 +274,58 @@ __host__ __device__ __forceinline__ FootprintBounds footprint_bounds(const Footp
   return b;
 }
 
+// ---- the step between two views' runs (carve_fused_kernel, the instances of carve_keeps_records) -------------------
+// Between two runs the wave works on ONE view's record at a time, on the scalar unit, of which a CU has one for its four
+// SIMDs: what the step asks of a record is therefore phrased as integer operations on the two words, one or two
+// instructions each, and every uniform test as ONE integer comparison (a `||` of two uniform bools is carried as two
+// 64-bit lane masks and costs five instructions).  The words are the lane's: footprint_ub_word and footprint_tile_word,
+// which a lane forms ONCE for its view -- one vector instruction there does it for all views of the launch.
+//   footprint_tile_word    word 1, or 0 where the record has nothing to fetch (tw == 0 or th == 0): "no tile" is `== 0`,
+//                          and every field of a record without a tile reads 0 -- not `sure`, origin 0, base 0
+//   footprint_has_tile / footprint_sure / footprint_tx0 / footprint_ty0 / footprint_step_base   of a tile word
+//   footprint_row_groups   of the lane's word 0: the groups of four tile rows that hold a tap row, (th >> 2) + 1
+//   footprint_window_unclamped   the whole 16 x 16 window lies inside the ROI: nothing to clamp (one comparison)
+// Each equals the field of unpack_footprint for every record that has a tile and for every record without one
+// (tests/test_view_step_host.py); a word 1 with tw != 0 and th == 0, which pack_footprint never writes and whose quad count
+// is 0, reads "no tile" like tw == 0.
+__host__ __device__ __forceinline__ uint32_t footprint_tile_word(uint32_t w0, uint32_t w1) {
+  return (((w1 >> 26) & 15u) != 0u && (w0 & 15u) != 0u) ? w1 : 0u;
+}
+__host__ __device__ __forceinline__ bool footprint_has_tile(uint32_t tile_word) { return tile_word != 0u; }
+__host__ __device__ __forceinline__ int footprint_sure(uint32_t tile_word) { return (int)(tile_word >> 30); }
+__host__ __device__ __forceinline__ int footprint_tx0(uint32_t tile_word) { return (int)(tile_word & 8191u); }
+__host__ __device__ __forceinline__ int footprint_ty0(uint32_t tile_word) { return (int)((tile_word >> 13) & 8191u); }
+__host__ __device__ __forceinline__ int footprint_step_base(uint32_t tile_word) {  // TileInfo::base of a raw tile
+  return -(footprint_ty0(tile_word) * 16 + footprint_tx0(tile_word));
+}
+__host__ __device__ __forceinline__ int footprint_row_groups(uint32_t ub_word) { return (int)((ub_word >> 2) & 3u) + 1; }
+__host__ __device__ __forceinline__ bool footprint_window_unclamped(int tx0, int ty0, int roi_max_xi, int roi_max_yi) {
+  // tx0 + 15 <= roi_max_xi && ty0 + 15 <= roi_max_yi (|operands| < 2^14: no overflow)
+  const int rx = roi_max_xi - tx0, ry = roi_max_yi - ty0;
+  return (rx < ry ? rx : ry) >= 15;
+}
+// The step addresses the launch's tables with 32-bit BYTE offsets from their three bases: the view records, the c0
+// records, a view's image.  An image is at most 8192 x 8192 floats (fused_eligible), 2^28 bytes; the other two are bounded
+// by carve_offsets_fit_32, which fused_eligible asks.
+__host__ __device__ __forceinline__ uint32_t view_byte_offset(int view) { return (uint32_t)view * (uint32_t)sizeof(FusedView); }
+__host__ __device__ __forceinline__ uint32_t c0_view_bytes(int nbw) { return (uint32_t)nbw * (uint32_t)(kC0Stride * sizeof(float)); }
+__host__ __device__ __forceinline__ uint32_t c0_byte_offset(int view, uint32_t view_bytes, int brick_x) {
+  return (uint32_t)view * view_bytes + (uint32_t)brick_x * (uint32_t)(kC0Stride * sizeof(float));
+}
+__host__ __device__ __forceinline__ uint32_t tile_origin_bytes(uint32_t width, int tx0, int ty0) {
+  return (width * (uint32_t)ty0 + (uint32_t)tx0) * (uint32_t)sizeof(float);
+}
+// Do the view records and the c0 records of a launch of `n_views` views over `nbw` wave bricks along x end below 2^31
+// bytes?  (With at most 64 views per launch the view records always do; the c0 records do up to 2^18 bricks, x
+// resolutions beyond two million voxels.  A launch that does not is not a fused launch: fused_eligible.)
+__host__ __device__ __forceinline__ bool carve_offsets_fit_32(int64_t n_views, int64_t nbw) {
+  if (n_views < 0 || nbw < 0) return false;
+  const uint64_t lim = 1ull << 31;
+  if ((uint64_t)n_views >= lim || (uint64_t)nbw >= lim) return false;  // (the products below stay inside 64 bits)
+  return (uint64_t)n_views * sizeof(FusedView) < lim &&
+         (uint64_t)n_views * (uint64_t)nbw < lim / (uint64_t)(kC0Stride * sizeof(float));
+}
+
 // Exact n / d for 32-bit unsigned n (Granlund-Montgomery, as in mc_kernels.hip): three integer instructions where the
 // compiler's division by a run-time value takes about twenty.
 struct FastDivU32 {

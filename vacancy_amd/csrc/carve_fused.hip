@@ -290,6 +290,9 @@ bool fused_eligible(const vcy_ctx* c, int n_views, const vcy_view* views) {
   const vcy_update_option& u = c->opt.update_option;
   if (count_width_for(c, c->views_carved + n_views) > 2) return false;  // (32-bit counters: the per-view kernel)
   if (u.voxel_update == VCY_UPDATE_WEIGHTED_AVERAGE && !sane(u.voxel_update_weight)) return false;
+  // (the view step addresses the view and c0 records of a LAUNCH with 32-bit byte offsets, and a launch holds at most
+  // kMaxFusedViews views: with them it cannot happen below 2^18 bricks along x, but the kernel relies on it)
+  if (!carve_offsets_fit_32(std::min(n_views, kMaxFusedViews), (c->nx + WX - 1) / WX)) return false;
   for (int i = 0; i < n_views; ++i) {
     const vcy_view& v = views[i];
     if (v.is_ortho != views[0].is_ortho) return false;  // one projection model per launch

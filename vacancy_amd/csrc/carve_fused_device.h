@@ -307,6 +307,63 @@ __device__ __forceinline__ void raw_prefetch(const ViewParams& v, const Footprin
   }
 }
 
+// ... for the view step of the instances that keep their records (carve_fused_kernel, kRecRegs): the two words of the
+// record as scalars, a record that HAS a tile (footprint_has_tile), and the view through the constant address space.
+// What differs from the form above is what it costs the scalar unit, not what it requests:
+//  - the view's four fields are read into locals before the first test, so they are ONE batch of scalar loads behind one
+//    wait (behind the `&&` of the clamp test the second bound was a scalar-cache round trip of its own);
+//  - the clamp test is one comparison (footprint_window_unclamped);
+//  - every request takes ONE scalar base, the tile's origin in the image, and a 32-bit vector offset in bytes: the
+//    lane's own, plus four image rows per row group (one vector add where the scalar unit widened a product and added
+//    a 64-bit pair per group; an image is at most 2^28 bytes: fused_eligible).
+typedef const ViewParams __attribute__((address_space(4))) * cview_ptr;
+__device__ __forceinline__ void raw_prefetch_step(cview_ptr v, uint32_t ub_word, uint32_t tile_word, int lane, float* buf) {
+#ifdef VCY_FLOOR_NO_TILE_LOADS
+  return;
+#endif
+  asm volatile("" : "+v"(lane));  // (as above)
+  typedef const char __attribute__((address_space(1))) * gchar_ptr;
+  const int roi_max_xi = v->roi_max_xi, roi_max_yi = v->roi_max_yi;
+  const unsigned width = (unsigned)v->width;
+  gchar_ptr img = (gchar_ptr)v->sdf;
+  const int tx0 = footprint_tx0(tile_word), ty0 = footprint_ty0(tile_word);
+  const int groups = footprint_row_groups(ub_word);
+  lds_float* dst = (lds_float*)buf;
+  if (footprint_window_unclamped(tx0, ty0, roi_max_xi, roi_max_yi)) {  // (uniform) nothing is clamped
+    gchar_ptr origin = img + tile_origin_bytes(width, tx0, ty0);
+    const unsigned four_rows = width * 16u;  // (bytes)
+    unsigned off = (__umul24(width, (unsigned)lane >> 4) + ((unsigned)lane & 15u)) << 2;  // this lane's pixel of group 0
+    auto request = [&](unsigned r) {
+      if (r > 0) off += four_rows;
+      __builtin_amdgcn_global_load_lds((gfloat_ptr)(origin + off), dst + 64 * r, 4, 0, 0);
+    };
+    // (nested tests instead of a switch that falls through, which came out of the compiler as lane-mask flags tested in
+    // front of every request; first group first, so that no request is shared with the clamped form below -- merged,
+    // the shared one took a 64-bit vector address)
+    request(0);
+    if (groups > 1) {
+      request(1);
+      if (groups > 2) {
+        request(2);
+        if (groups > 3) request(3);
+      }
+    }
+    return;
+  }
+  const unsigned xx = (unsigned)min(tx0 + (lane & 15), roi_max_xi);
+  const int yl = ty0 + (lane >> 4);
+  auto row = [&](int r) {
+    const unsigned yy = (unsigned)min(yl + 4 * r, roi_max_yi);
+    __builtin_amdgcn_global_load_lds((gfloat_ptr)img + (__umul24(width, yy) + xx), dst + 64 * r, 4, 0, 0);
+  };
+  switch (groups) {
+    default: row(3); [[fallthrough]];
+    case 3: row(2); [[fallthrough]];
+    case 2: row(1); [[fallthrough]];
+    case 1: row(0);
+  }
+}
+
 __device__ __forceinline__ void raw_tile_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // min over the wave (NaN operands are ignored, like the `dist > s` test ignores them): six DPP

@@ -23,6 +23,7 @@
 // emits for IEEE division minus the exponent pre-scaling, which is a no-op for operands in
 // [2^-60, 2^60]; anything outside that range takes the generic path.
 #pragma once
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -149,8 +150,8 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     if constexpr (kOneRegs) return ti_one;
     else return tinfo[p];
   };
-  // kRecRegs: this lane's record -- word 0 (footprint_ub_word: the bound, th, the edge bits) and word 1; a lane without
-  // a view holds "no tile, no bound"
+  // kRecRegs: this lane's record -- word 0 (footprint_ub_word: the bound, th, the edge bits) and word 1
+  // (footprint_tile_word: 0 where there is nothing to fetch); a lane without a view holds "no tile, no bound"
   uint32_t rec_w0 = 0x7f800000u, rec_w1 = 0u;
   auto rec_of = [&](int p) -> FootprintFields {  // the fields of view p's record, as scalars
     return unpack_footprint_scalar((uint32_t)__builtin_amdgcn_readlane((int)rec_w0, p),
@@ -169,6 +170,26 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     if constexpr (kRecRegs) return rec_of(p).sure;
     else return __builtin_amdgcn_readfirstlane(tile_of(p).sure);
   };
+  // kRecRegs: the scalar state of the step between two runs (carve_fused.h, "the step between two views' runs").
+  //   ahead        the live views BEHIND the one in hand, as a mask: the next view is its lowest bit, taking a view
+  //                clears that bit, and a re-bound is an AND with the ballot of the lanes whose bound still stands
+  //   cur_*        the view in hand: its tile word and the byte offset of its view record
+  //   nxt_*        the same of the next view, whose tile is in flight (and its word 0, for the request); nxt_w1 == 0
+  //                when there is none.  Taken apart ONCE, when the view is chosen, and handed over when it becomes the
+  //                view in hand.
+  //   moved_mask   the lanes whose voxels the last select-free run changed (what carve_view_fast returns as a bool)
+  //   rebound_mask all ones when a run that moved the brick is followed by a re-bound (kMax with "cull" on), else zero:
+  //                `moved_mask & rebound_mask` is ONE scalar instruction that sets the condition code, where the `&&` of
+  //                the two uniform bools was five.  Formed from the launch's 0 / 1 by arithmetic -- from
+  //                `cull_enabled != 0` the compiler sees a bool in it again.  (Another non-zero value would leave bits out
+  //                of the mask and so skip a re-bound, which only ever drops views that change nothing; never add one.)
+  // (c0_per_view and the mask are set in these instances only: the others compile as before)
+  unsigned long long ahead = 0ull, moved_mask = 0ull;
+  uint32_t cur_w1 = 0u, cur_voff = 0u, nxt_w0 = 0u, nxt_w1 = 0u, nxt_voff = 0u;
+  uint32_t c0_per_view = 0u, rebound_half = 0u;
+  if constexpr (kRecRegs) c0_per_view = c0_view_bytes(((g.nx + WX - 1) & ~(WX - 1)) / WX);
+  if constexpr (kRecRegs && kNeedBound) rebound_half = 0u - (uint32_t)cull_enabled;
+  const unsigned long long rebound_mask = ((unsigned long long)rebound_half << 32) | rebound_half;
   const int ly = lane & (BY - 1), lz = lane >> 3;
   // XCD-aware order: the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, so
   // workgroup b runs on XCD b % 8.  Give every XCD one contiguous eighth of the brick list: bricks
@@ -322,7 +343,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       typedef const u32x2 __attribute__((address_space(1))) * grec_ptr;
       const u32x2 raw = ((grec_ptr)records)[(int64_t)lane * nbricks + brick_lin];
       if constexpr (kRecRegs) {
-        rec_w0 = footprint_ub_word(raw.x, raw.y), rec_w1 = raw.y;
+        rec_w0 = footprint_ub_word(raw.x, raw.y), rec_w1 = footprint_tile_word(raw.x, raw.y);
       } else {
         FootprintRecord rec;
         rec.w0 = raw.x, rec.w1 = raw.y;
@@ -339,7 +360,7 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     const FootprintRecord rec = brick_footprint_records<SAMEF, GEN>(
         views, nviews, lane, g.px[x_lo], g.px[x_hi], g.py[by * BY], g.py[y_hi], g.pz[g.z0 + zl0], g.pz[g.z0 + z_hi],
         mode.ortho != 0, mode.outside == VCY_OUTSIDE_MAX, want_bound, want_bound && TRUNC && UPDATE != VCY_UPDATE_MAX);
-    rec_w0 = footprint_ub_word(rec.w0, rec.w1), rec_w1 = rec.w1;
+    rec_w0 = footprint_ub_word(rec.w0, rec.w1), rec_w1 = footprint_tile_word(rec.w0, rec.w1);
     ub_lane = INFINITY;
   } else {
     // the big tile -- and raw tiles of a launch whose records would not fit (`records` null: 2048^3 x 64 views would
@@ -580,9 +601,10 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   };
   // views that may still change something, as a wave-uniform bit mask
   int jc = -1;  // NB > 1: the brick of the segment whose state is in registers
-  auto live_views = [&]() -> unsigned long long {
+  // does this lane's view (pair) change nothing, as the state stands?  (`known`: the caller has established want_bound)
+  auto dropped_now = [&](auto known) -> bool {
     bool drop = false;
-    if (want_bound) {
+    if (decltype(known)::value || want_bound) {
       if (TRUNC) drop = lane_ub() < -1.0f;
       if (UPDATE == VCY_UPDATE_MAX && all_touched) {
         float m = s[0];
@@ -592,13 +614,30 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
         drop = drop || lane_ub() <= smin;
       }
     }
+    return drop;
+  };
+  auto live_views = [&]() -> unsigned long long {
+    const bool drop = dropped_now(std::false_type{});
     if constexpr (kRows) {  // (the bounds of the other bricks' pairs stand as they are)
       const unsigned long long cur_bits = 0xffull << (8 * jc);
       return (live & ~cur_bits) | (__ballot(!drop) & view_mask & cur_bits);
     }
     return __ballot(!drop) & view_mask;
   };
-  const int vi_end = kRows ? 64 : nviews;  // "no further view / pair"
+  // kRecRegs, behind a run that moved the brick: the lanes whose bound still stands (the compare's own mask -- __ballot
+  // takes an int, and the mask came back through v_cndmask + v_cmp_ne)
+  auto standing_bounds = [&]() -> unsigned long long {
+    return __builtin_amdgcn_ballot_w64(!dropped_now(std::true_type{}));
+  };
+  // "no further view / pair" (kRecRegs: -1, what the lowest bit of an empty mask reads as)
+  const int vi_end = kRecRegs ? -1 : (kRows ? 64 : nviews);
+  // the lowest set bit of a uniform mask, -1 when it is empty: what s_ff1_i32_b64 returns (through __ffsll the empty
+  // case is a compare and a select of its own)
+  auto first_of = [&](unsigned long long mask) -> int {
+    int r;
+    asm("s_ff1_i32_b64 %0, %1" : "=s"(r) : "s"(mask));
+    return r;
+  };
   auto next_view = [&](unsigned long long live, int after) -> int {
     const unsigned long long rest = (after >= 63) ? 0ull : (live & ~((2ull << after) - 1ull));
     return rest ? (__ffsll((long long)rest) - 1) : vi_end;
@@ -610,7 +649,11 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   unsigned long long changed_lanes = 0ull;
   if (!kRows) live = live_views();
   int vi = live ? (__ffsll((long long)live) - 1) : vi_end;
-  if (kRaw && vi < vi_end && vi != vi_pre) prefetch_tile(vi, raw_buf(0));
+  if (kRaw && (kRecRegs ? vi >= 0 : vi < vi_end) && vi != vi_pre) prefetch_tile(vi, raw_buf(0));
+  if constexpr (kRecRegs) {  // the first view's scalar state (the prologue's request has taken its record apart itself)
+    ahead = live & (live - 1ull);
+    if (vi >= 0) cur_w1 = (uint32_t)__builtin_amdgcn_readlane((int)rec_w1, vi), cur_voff = view_byte_offset(vi);
+  }
   // NB > 1: the brick whose turn it is takes its state from the staging area (the LDS-direct requests above have
   // landed once the wave has waited for its first tile) and leaves it there again when the next brick begins
   typedef CountT CountVecR __attribute__((ext_vector_type(WX)));
@@ -689,12 +732,31 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   int base = 0, big_pitch = 0;
   const lds_float* rawcur = nullptr;
   float h12x = 0.0f, h12y = 0.0f, h12z = 0.0f;
+  typedef const char __attribute__((address_space(4))) cbyte;
+  auto view_at = [&](uint32_t voff) -> cview* { return (cview*)((cbyte*)views + voff); };  // (FusedView::v comes first)
+  static_assert(offsetof(FusedView, v) == 0, "view_at");
+  // kRecRegs: the next live view from `vnext` on -- its record, taken apart once, and the request of its tile
+  auto request_next = [&]() {
+    if (vnext < 0) {
+      nxt_w1 = 0u;  // (not `sure`: the run loop ends)
+      return;
+    }
+    nxt_w0 = (uint32_t)__builtin_amdgcn_readlane((int)rec_w0, vnext);
+    nxt_w1 = (uint32_t)__builtin_amdgcn_readlane((int)rec_w1, vnext);
+    nxt_voff = view_byte_offset(vnext);
+    if (footprint_has_tile(nxt_w1)) raw_prefetch_step(view_at(nxt_voff), nxt_w0, nxt_w1, lane, raw_buf(cur ^ 1));
+  };
   auto begin_view = [&]() {
     const int vv = kRows ? (vi & 7) : vi;  // the view of pair vi
     const ViewParams& v = views[vv].v;
-    vp = (cview*)&v;
-    // this view's record of the wave brick's x products: (x, y) pairs at [2 k], z at [16 + k]
-    c0 = (cfloat_ptr)(c0_all + ((size_t)vv * (nxp / WX) + (x_first / WX)) * kC0Stride);
+    if constexpr (kRecRegs) {  // (both from 32-bit offsets: carve_offsets_fit_32)
+      vp = view_at(cur_voff);
+      c0 = (cfloat_ptr)((cbyte*)c0_all + c0_byte_offset(vi, c0_per_view, x_first / WX));
+    } else {
+      vp = (cview*)&v;
+      // this view's record of the wave brick's x products: (x, y) pairs at [2 k], z at [16 + k]
+      c0 = (cfloat_ptr)(c0_all + ((size_t)vv * (nxp / WX) + (x_first / WX)) * kC0Stride);
+    }
     // stage this view's tile (wave-private: program order is enough)
     VCY_SETPRIO(3);
     wave_lds_fence();
@@ -705,11 +767,16 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     }
     wave_lds_fence();
     // the next live view's tile is fetched while this one is computed
-    vnext = next_view(live, vi);
-    if (kRaw && vnext < vi_end) prefetch_tile(vnext, raw_buf(cur ^ 1));
+    if constexpr (kRecRegs) {
+      vnext = first_of(ahead);
+      request_next();
+    } else {
+      vnext = next_view(live, vi);
+      if (kRaw && vnext < vi_end) prefetch_tile(vnext, raw_buf(cur ^ 1));
+    }
     ++n_processed;
     if constexpr (kRecRegs) {  // (a raw tile's pitch is 16; a record without a tile is never sampled from)
-      pitchf = (float)kTileRaw, base = footprint_base(rec_of(vi));
+      pitchf = (float)kTileRaw, base = footprint_step_base(cur_w1);
     } else {
       pitchf = tile_of(vi).pitchf, base = tile_of(vi).base;
     }
@@ -722,6 +789,23 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     VCY_PT(1);
   };
   // Behind a view's run: what the views that follow ask of the state, and the step to the next live view.
+  // kRecRegs: the step to the next live view, behind a re-bound if the run calls for one
+  auto step_rec = [&](bool rebound) {
+    if (rebound) {
+      ahead &= standing_bounds();  // (min(sdf) only grows: a bound that fell stays fallen)
+      const int v2 = first_of(ahead);
+      if (v2 != vnext) {
+        vnext = v2;
+        // (the dropped view's pixels may still be arriving in that buffer: loads complete in order)
+        request_next();
+      }
+    }
+    // the next view becomes the view in hand, with what was taken out of its record when its tile was requested
+    vi = vnext, cur_w1 = nxt_w1, cur_voff = nxt_voff;
+    ahead &= ahead - 1ull;  // (its bit is the lowest one; an empty mask stays empty)
+    cur ^= 1;
+    VCY_PT(5);
+  };
   auto end_view = [&](bool brick_moved) {
     VCY_SETPRIO(3);
     if (brick_moved) VCY_PT_COUNT(11);
@@ -730,6 +814,10 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
 
     // state moved: some of the remaining views may have become droppable (min(sdf) only grows)
     // (an unchanged brick leaves every bound comparison as it was)
+    if constexpr (kRecRegs) {
+      step_rec(want_bound && brick_moved);
+      return;
+    }
     if (!kOne && want_bound && UPDATE == VCY_UPDATE_MAX && brick_moved) {
       live = live_views();
       const int v2 = next_view(live, vi);
@@ -746,12 +834,13 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   // TileInfo::sure of the view end_view() stepped to when it is another select-free run of the brick in registers
   // (bit 0 set), else 0.
   auto next_fast_bits = [&]() -> int {
+    if constexpr (kRecRegs) return footprint_sure(cur_w1);  // (0 when there is no further view)
     if (kOne || vi >= vi_end) return 0;
     if (kRows && (vi >> 3) != jc) return 0;  // (the pair belongs to another brick of the segment)
     const int bits = sure_of(vi);
     return (bits & 1) != 0 ? bits : 0;
   };
-  while (vi < vi_end) {
+  while (kRecRegs ? vi >= 0 : vi < vi_end) {
     if constexpr (kRows) {
       if ((vi >> 3) != jc) {  // (uniform) the next pair belongs to another brick of the segment
         raw_tile_wait();      // everything requested so far has landed: the state of every brick, this pair's tile
@@ -974,10 +1063,13 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
       // every lane took every sample, unless the update was conditional (kMax on a touched brick, the truncating average)
       constexpr bool kConditional = !FIRST && !UNIFORM && (kFastMax || (kFastWa && TRUNC && !NOTRUNC));
       changed_lanes |= kConditional ? took : ~0ull;
+      if constexpr (kRecRegs) moved_mask = (kFastMax && !FIRST) ? took : ~0ull;
       return (kFastMax && !FIRST) ? took != 0ull : true;
     };
     bool brick_moved;
-    const int sure_bits = sure_of(vi);
+    int sure_bits;
+    if constexpr (kRecRegs) sure_bits = footprint_sure(cur_w1);
+    else sure_bits = sure_of(vi);
     const bool sure = (sure_bits & 1) != 0, never_truncated = (sure_bits & 2) != 0;
     // (Branch weights: the checked loops below are the rare ones in the kernels that have a select-free loop;
     // the register allocator then spills there, if anywhere, and not in the loops that do the work.)
@@ -1014,6 +1106,32 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
         begin_view();
         return true;
       };
+      if constexpr (kRecRegs) {
+        // (the same loop; what says whether it goes on is the next view's `sure` bit itself, an integer tested where
+        // it is needed -- as run()'s bool it was carried to the latch as a lane mask and tested there a second time)
+        auto run_rec = [&](auto first_tag) -> uint32_t {
+          brick_moved = carve_view_fast(first_tag, std::false_type{}, std::false_type{});
+          VCY_PT(2);
+          VCY_PT_COUNT(7);
+          // end_view() for a run of this loop.  The brick is touched everywhere -- FIRST stores every voxel, the others
+          // are only entered on such a brick; said here, the tests of it fold away instead of living on as lane masks
+          // -- and "moved, and a re-bound is wanted" is one AND of two masks.
+          VCY_SETPRIO(3);
+          if (brick_moved) VCY_PT_COUNT(11);
+          none_touched = false, all_touched = true;
+          step_rec((moved_mask & rebound_mask) != 0ull);
+          uint32_t go_on = cur_w1 & (1u << 30);
+          if (go_on != 0u) begin_view();
+          // (opaque BEHIND the join: the loop keeps one exit, at its latch, tested with one compare.  Threaded through
+          // the `if`, the two exits were merged again with a lane-mask flag.)
+          asm volatile("" : "+s"(go_on));
+          return go_on;
+        };
+        uint32_t more_rec = 1u;
+        if (fast_first) more_rec = run_rec(std::true_type{});
+        while (more_rec != 0u) more_rec = run_rec(std::false_type{});
+        continue;
+      }
       bool more = true;
       if (fast_first) more = run(std::true_type{});
       while (more) more = run(std::false_type{});
