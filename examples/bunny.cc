@@ -1,10 +1,15 @@
 // The reference's demo (examples.cc:75-152) on the MI355X path: 6 masks + TUM poses of data/
 // bunny, 10 mm voxels; per view carve -> marching cubes (interpolated and not), PLY out.
 // Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs] [planned] [--keep-largest] [--render DIR]
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] --tolerate M [--blank-view I]
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
 //   --render DIR (DIR must exist) writes DIR/hull_<view>.png, the silhouette of the carved hull as every input camera
 //   sees it, and prints per view how it agrees with the input silhouette: the three pixel counts and the IoU.
+//   --tolerate M carves the six views with the robust hull instead (VoxelCarver::CarveRobust: a voxel is carved only when
+//   more than M views say outside), prints per view how many solid voxels it was overruled on, writes
+//   surface_robust.ply and ends; n_slabs does not apply (the sharded carver has the call in Python only).
+//   --blank-view I replaces the silhouette of view I by an all-background image first: the wrong mask the call is for.
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -50,6 +55,8 @@ int main(int argc, char* argv[]) {
   // of the hull but the largest (VoxelCarver::KeepLargestComponents) -- the floaters six views leave; with slabs, the
   // sharded run is filtered too (ShardedVoxelCarver::KeepLargestComponents) and its kept mesh compared
   bool keep_largest = false;
+  int tolerate = -1;       // --tolerate M: the robust hull instead of the per-view demo
+  int blank_view = -1;     // --blank-view I: that view's silhouette becomes all background
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
@@ -61,6 +68,13 @@ int main(int argc, char* argv[]) {
           return 10;
         }
         render_dir = argv[++i];
+      } else if (std::string(argv[i]) == "--tolerate" || std::string(argv[i]) == "--blank-view") {
+        if (i + 1 >= argc) {
+          std::fprintf(stderr, "%s needs a number\n", argv[i]);
+          return 10;
+        }
+        (std::string(argv[i]) == "--tolerate" ? tolerate : blank_view) = std::atoi(argv[i + 1]);
+        ++i;
       } else argv[n++] = argv[i];
     }
     argc = n;
@@ -84,6 +98,29 @@ int main(int argc, char* argv[]) {
   option.resolution = resolution;
   vacancy::VoxelCarver carver(option);
   if (!carver.Init()) return 2;
+
+  if (tolerate >= 0) {  // the robust hull of the six views in one call, and who was overruled where
+    std::vector<std::shared_ptr<vacancy::Camera>> cams;
+    std::vector<vacancy::Image1b> sils(poses.size() < 6 ? poses.size() : 6);
+    for (size_t i = 0; i < sils.size(); ++i) {
+      cams.push_back(std::make_shared<vacancy::PinholeCamera>(320, 240, poses[i], Eigen::Vector2f(159.3f, 127.65f),
+                                                              Eigen::Vector2f(258.65f, 258.25f)));
+      if (!sils[i].Load(data_dir + "/mask_" + vacancy::zfill(i) + ".png")) return 3;
+      if (static_cast<int>(i) == blank_view) {
+        const int w = sils[i].width(), h = sils[i].height();
+        sils[i].Init(w, h, static_cast<unsigned char>(0));
+      }
+    }
+    std::vector<std::int64_t> overruled;
+    if (!carver.CarveRobust(cams, sils, tolerate, &overruled)) return 13;
+    for (size_t i = 0; i < overruled.size(); ++i)
+      std::printf("ROBUST view %zu overruled %lld\n", i, static_cast<long long>(overruled[i]));
+    vacancy::Mesh mesh;
+    carver.ExtractIsoSurface(&mesh, 0.0);
+    mesh.WritePly(out_dir + "/surface_robust.ply");
+    std::printf("ROBUST tolerate %d verts %zu faces %zu\n", tolerate, mesh.vertices().size(), mesh.vertex_indices().size());
+    return 0;
+  }
 
   std::unique_ptr<vacancy::ShardedVoxelCarver> sharded;
   if (n_slabs > 0) {

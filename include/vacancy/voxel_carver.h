@@ -148,6 +148,17 @@ class VoxelCarver {
   bool HullAgreement(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
                      std::vector<std::array<std::int64_t, 3>>* counts);
 
+  // The robust visual hull (vcy_carve_robust_silhouettes; the definition is in vacancy_hip.h): REPLACES the state by, per
+  // voxel, the (tolerate + 1)-th largest sample over all cameras instead of the largest, so that a voxel is carved only
+  // when more than `tolerate` (0 .. 3) views say outside -- up to `tolerate` wrong masks no longer remove a part of the
+  // object.  overruled (optional) gets one count per view: the voxels kept solid at iso_level although that view says
+  // outside; a bad mask shows as a count far above the others'.  kMax options only, up to 1024 views.  false + LOGE on an
+  // error, the state then stays as it was.
+  bool CarveRobust(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes, int tolerate,
+                   std::vector<std::int64_t>* overruled = nullptr, double iso_level = 0.0);
+  bool CarveRobust(const std::vector<std::shared_ptr<Camera>>& cameras, const std::vector<Image1b>& silhouettes, int tolerate,
+                   std::vector<std::int64_t>* overruled = nullptr, double iso_level = 0.0);
+
   // Fills mesh->vertex_colors() (float RGB in 0 .. 255, what WritePly emits) from the photographs, on the device
   // (vcy_color_vertices): a view colours a vertex it sees -- whose camera depth is at most the hull's depth at its pixel,
   // ray-cast here at iso_level, + depth_tolerance.  photos[i] belongs to cameras[i] and gives the view its size; the ROI

@@ -202,6 +202,57 @@ int vcy_make_sdf_device(vcy_ctx* ctx, const uint8_t* mask_host, int width, int h
                         const int32_t roi_min[2], const int32_t roi_max[2], int minmax_normalize,
                         int use_truncation, float truncation_band, float** sdf_device_out);
 
+/* ---- robust carve: keep a voxel unless more than m views carve it ---------- */
+/* No counterpart in the reference, whose arithmetic it reuses.  A visual hull is the intersection of the silhouettes: ONE
+ * wrong mask (a blown segmentation, a blank frame, an object cut off at the image border) removes a real part of the
+ * object.  The robust hull takes, per voxel, the (m + 1)-th largest sample over the views instead of the largest
+ * (UpdateVoxelMax, voxel_carver.cc:78-86; positive = outside the silhouette): a voxel is carved only when MORE than m
+ * views say outside.  An order statistic needs all views at once (the state keeps one number per voxel), so this is one
+ * call over all of them, with a kernel of its own (carve_robust.hip).
+ *
+ * Inputs.  A context whose option has voxel_update == kMax (weighted average: VCY_ERR_INVALID_ARG); n_views in 1 .. 1024;
+ * tolerate = m in 0 .. 3; n_views views with one SDF image each in device memory; an iso_level.  The call REPLACES the
+ * context's state, as vcy_reset followed by a carve would: it does not combine with what was carved before.
+ *
+ * Samples.  For every owned voxel the views are visited in the order given.  View i contributes a sample d_i exactly when
+ * the reference's loop (voxel_carver.cc:453-480) would reach its update: the voxel is not behind the camera; it is inside
+ * the ROI, or update_outside == kMax gives max_sdf; and the truncation test does not drop it.  Projection, ROI test,
+ * sampler and float operation order are those of every other carve entry point.  voxel_max_update_num is NOT applied:
+ * its effect depends on the order of the views and has no meaning for an order statistic.  Every view's own is_ortho is
+ * honoured: a call may mix the two camera models.
+ *
+ * Top list.  K = m + 1.  The list t[0 .. K-1] starts empty.  For each sample d, in view order:
+ *   1. if the list holds fewer than K entries, append d; otherwise, if d > t[K-1], replace the last entry; if not, drop d;
+ *   2. while the new entry has a predecessor t[j-1] and d > t[j-1], swap it upwards.
+ * Only the comparison `>` is used, so NaN samples behave as in UpdateVoxelMax (a NaN never moves up and is never
+ * displaced by the test); for K = 1 the procedure is exactly first touch followed by UpdateVoxelMax.  The view index of
+ * every entry is carried beside its value.
+ *
+ * Result, with n samples:  n == 0: sdf = lowest(), update_num = 0 (the fill state).  n >= 1: sdf = t[min(K, n) - 1] --
+ * the (m + 1)-th largest, or the smallest when fewer than m + 1 views see the voxel, which can therefore never be carved
+ * -- and update_num = n.  update_num == 0 still implies sdf == lowest().  n can reach n_views: a context whose
+ * voxel_max_update_num keeps its counters at one byte (<= 254) refuses more than 255 views.
+ *
+ * Blame.  overruled[i] (int64 per view; may be NULL) counts the owned voxels whose result satisfies (double)sdf < iso_level
+ * and for which view i holds a discarded entry t[j], j < min(K, n) - 1, with (double)t[j] >= iso_level: the voxels kept
+ * solid although view i says outside -- a bad mask shows as a count far above the others'.  Integer sums: exact and
+ * independent of the schedule.  A z-slab context counts its own slices; the counts of slabs that cover a grid add up.
+ *
+ * Views queued by earlier per-view calls are applied first (their failure is returned); then the state is the call's:
+ * halos, brick minima and component labels are stale, vcy_render_hull builds its bit planes again.  Refusals
+ * (VCY_ERR_INVALID_ARG: tolerate outside 0 .. 3, n_views outside 1 .. 1024, weighted-average mode, null images, and what
+ * vcy_carve_batch_device refuses in a view) leave the state and `overruled` untouched and set vcy_last_error().  The
+ * images are read while the launch runs; the call returns when it has finished. */
+int vcy_carve_robust_device(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* sdf_device, int tolerate,
+                            double iso_level, int64_t* overruled);
+/* The same from silhouettes in host memory: MakeSignedDistanceField of all n_views on the device, with the context's
+ * options (vcy_make_sdf_batch_device into images the call owns: width * height * 4 bytes per view at once), then
+ * vcy_carve_robust_device. */
+int vcy_carve_robust_silhouettes(vcy_ctx* ctx, int n_views, const vcy_view* views, const uint8_t* const* masks_host,
+                                 int tolerate, double iso_level, int64_t* overruled);
+/* Device milliseconds of the last robust carve's launch (events around the kernel; the SDF build is not in it). */
+int vcy_last_robust_ms(const vcy_ctx* ctx, float* device_ms);
+
 /* ---- surface extraction ------------------------------------------------- */
 
 /* Replaces void VoxelCarver::ExtractIsoSurface(Mesh*, double iso_level,

@@ -245,6 +245,40 @@ class VoxelCarver:
         assert self._lib.vcy_last_stream_ms(self._ctx, C.byref(a), C.byref(b), C.byref(w)) == 0, last_error()
         return a.value, b.value, w.value
 
+    # -- the robust visual hull (no reference counterpart; definition: include/vacancy_hip.h, "robust carve")
+    def _carve_robust(self, entry, views, pointers, keep, tolerate, iso_level):
+        n = len(views)
+        arr = (View * max(n, 1))(*views)
+        ptrs = (C.c_void_p * max(n, 1))(*pointers)
+        overruled = np.zeros(n, np.int64)
+        rc = entry(self._ctx, n, arr, ptrs, int(tolerate), float(iso_level), _p(overruled))
+        del keep
+        if rc != 0:
+            e = RuntimeError(last_error())
+            e.rc = rc
+            raise e
+        ms = C.c_float()
+        self._lib.vcy_last_robust_ms(self._ctx, C.byref(ms))
+        return {"overruled": overruled, "device_ms": ms.value}
+
+    def CarveRobustDevice(self, views, sdf_devs, tolerate, iso_level=0.0):
+        """vcy_carve_robust_device: REPLACES the state by the robust hull of `views` (SDF images resident on the device):
+        per voxel the (tolerate + 1)-th largest sample instead of the largest, so a voxel is carved only when more than
+        `tolerate` views say outside.  {"overruled": int64 [n], the voxels kept solid although view i says outside;
+        "device_ms"}.  RuntimeError (with .rc) on a refusal; the state is then untouched."""
+        ptrs = [p.value if isinstance(p, C.c_void_p) else p for p in sdf_devs]
+        if len(ptrs) != len(views):
+            raise ValueError("one SDF image per view")
+        return self._carve_robust(self._lib.vcy_carve_robust_device, views, ptrs, None, tolerate, iso_level)
+
+    def CarveRobustSilhouettes(self, views, silhouettes, tolerate, iso_level=0.0):
+        """vcy_carve_robust_silhouettes: the same from silhouettes in host memory; every SDF is built on the device."""
+        masks = [np.ascontiguousarray(m, np.uint8) for m in silhouettes]
+        if len(masks) != len(views):
+            raise ValueError("one silhouette per view")
+        return self._carve_robust(self._lib.vcy_carve_robust_silhouettes, views, [m.ctypes.data for m in masks], masks,
+                                  tolerate, iso_level)
+
     def download_voxels(self, ids):
         ids = np.ascontiguousarray(ids, np.int64)
         s = np.empty(len(ids), np.float32)

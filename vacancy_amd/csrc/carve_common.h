@@ -3,6 +3,8 @@
 // at each step; float operation order is the reference's (no FMA contraction).
 #pragma once
 
+#include <vector>
+
 #include "vcy_internal.h"
 
 namespace vcy {
@@ -35,6 +37,11 @@ struct ModeParams {
   int update, interp, outside, trunc, ortho;
   int div_level;  // host side only: which division sequence the fused kernel is instantiated with
 };
+
+// The views as the kernels read them, max_sdf resolved on the device where update_outside = kMax reads it
+// (carve_kernels.hip; shared with carve_robust.hip).
+int resolve_views(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* sdf_dev,
+                  std::vector<ViewParams>* out);
 
 // ---- sampling, shared by every carve kernel --------------------------------------------
 

@@ -116,7 +116,7 @@ static void launch_view(vcy_ctx* c, const GridParams& g, const ViewParams& v, co
 
 // The views as the kernels read them: max over the whole SDF buffer resolved (voxel_carver.cc:436; only
 // update_outside = kMax reads it).
-static int resolve_views(vcy_ctx* c, int n_views, const vcy_view* views, const float* const* sdf_dev,
+int resolve_views(vcy_ctx* c, int n_views, const vcy_view* views, const float* const* sdf_dev,
                          std::vector<ViewParams>* out) {
   const vcy_update_option& u = c->opt.update_option;
   // max over the whole SDF buffer (voxel_carver.cc:436); only update_outside = kMax reads it

@@ -215,6 +215,10 @@ struct vcy_ctx {
   vcy::Event ev_cl_begin, ev_cl_end;
   float last_color_device_ms = 0.0f;
 
+  // robust carve (carve_robust.hip)
+  vcy::Event ev_rb_begin, ev_rb_end;  // around its launch (vcy_last_robust_ms)
+  float last_robust_device_ms = 0.0f;
+
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
 
@@ -261,6 +265,7 @@ int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
 // vcy_ctx::d_rn_out and holds until the context next renders; waits for the launch; vcy_last_render_ms as for the render
 int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who);
 // color.hip: vcy_color_vertices, vcy_color_vertices_host, vcy_last_color_ms
+// carve_robust.hip: vcy_carve_robust_device, vcy_carve_robust_silhouettes, vcy_last_robust_ms
 // render_merge.hip (host code only): vcy_render_merge_host, vcy_hull_agreement_host, and the view checks of the ray-cast
 int check_render_view(const vcy_view* v, int i);
 // sdf2d.hip

@@ -373,6 +373,50 @@ bool VoxelCarver::HullAgreement(const std::vector<Camera>& cameras, const std::v
   return HullAgreement(ptrs, silhouettes, counts);
 }
 
+bool VoxelCarver::CarveRobust(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes, int tolerate,
+                              std::vector<std::int64_t>* overruled, double iso_level) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (cameras.size() != silhouettes.size() || cameras.empty()) {
+    LOGE("VoxelCarver::CarveRobust needs one silhouette per camera, at least one (%zu cameras, %zu silhouettes)\n",
+         cameras.size(), silhouettes.size());
+    return false;
+  }
+  const int n = static_cast<int>(cameras.size());
+  std::vector<vcy_view> views(n);
+  std::vector<const uint8_t*> masks(n);
+  for (int i = 0; i < n; ++i) {
+    const Image1b& s = silhouettes[i];
+    bool known = true;
+    if (!cameras[i] || s.empty()) {
+      LOGE("VoxelCarver::CarveRobust: view %d has no camera or an empty silhouette\n", i);
+      return false;
+    }
+    views[i] = ToView(*cameras[i], s.width(), s.height(), &known);
+    if (!known) return false;  // (ToView has logged the camera type)
+    masks[i] = s.data().data();
+  }
+  std::vector<std::int64_t> counts(static_cast<size_t>(n), 0);
+  const int rc = vcy_carve_robust_silhouettes(impl_->ctx, n, views.data(), masks.data(), tolerate, iso_level,
+                                              overruled ? counts.data() : nullptr);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  if (overruled) overruled->swap(counts);
+  return true;
+}
+
+bool VoxelCarver::CarveRobust(const std::vector<std::shared_ptr<Camera>>& cameras, const std::vector<Image1b>& silhouettes,
+                              int tolerate, std::vector<std::int64_t>* overruled, double iso_level) {
+  std::vector<const Camera*> ptrs(cameras.size());
+  for (size_t i = 0; i < cameras.size(); ++i) ptrs[i] = cameras[i].get();
+  return CarveRobust(ptrs, silhouettes, tolerate, overruled, iso_level);
+}
+
 bool VoxelCarver::ColorMesh(Mesh* mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
                             const ColorOption& option, double iso_level) {
   if (!impl_->ctx) {

@@ -199,6 +199,14 @@ class ShardedVoxelCarver:
         ok = self._per_device(lambda i, cs: all(c.CarveBatchSilhouettes(views, silhouettes) for c in cs))
         return all(ok)
 
+    # -- the robust visual hull over the slabs (include/vacancy_hip.h, "robust carve"): the result of a voxel depends on
+    # that voxel alone, so every slab carves its own slices (and builds the SDF images on its device); overruled[i] of the
+    # grid is the sum over the slabs
+    def CarveRobustSilhouettes(self, views, silhouettes, tolerate, iso_level=0.0):
+        """VoxelCarver.CarveRobustSilhouettes of the whole grid: the same dict; "device_ms" is the sum over the slabs."""
+        parts = self._each_slab(self.slabs, lambda i, c: c.CarveRobustSilhouettes(views, silhouettes, tolerate, iso_level))
+        return {"overruled": sum(p["overruled"] for p in parts), "device_ms": float(sum(p["device_ms"] for p in parts))}
+
     def last_stream_ms(self):
         """[(producer ms, carve ms, wall ms)] per slab of the last CarveBatchSilhouettes."""
         return [c.last_stream_ms() for c in self.slabs]
