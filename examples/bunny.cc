@@ -1,6 +1,6 @@
 // The reference's demo (examples.cc:75-152) on the MI355X path: 6 masks + TUM poses of data/
 // bunny, 10 mm voxels; per view carve -> marching cubes (interpolated and not), PLY out.
-// Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs] [planned] [--keep-largest] [--render DIR]
+// Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs] [planned] [--keep-largest] [--render DIR] [--fuse-depth]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --tolerate M [--blank-view I]
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
@@ -10,6 +10,9 @@
 //   more than M views say outside), prints per view how many solid voxels it was overruled on, writes
 //   surface_robust.ply and ends; n_slabs does not apply (the sharded carver has the call in Python only).
 //   --blank-view I replaces the silhouette of view I by an all-background image first: the wrong mask the call is for.
+//   --fuse-depth (after the ordinary carve) renders the hull's depth from every input camera, fuses those images into a second
+//   carver of the same box and resolution (weighted average, band = 3 voxels: VoxelCarver::CarveDepth), writes the
+//   iso-surface as <out_dir>/depth_fused.ply and prints its size and the device time of the fusion.
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -55,6 +58,7 @@ int main(int argc, char* argv[]) {
   // of the hull but the largest (VoxelCarver::KeepLargestComponents) -- the floaters six views leave; with slabs, the
   // sharded run is filtered too (ShardedVoxelCarver::KeepLargestComponents) and its kept mesh compared
   bool keep_largest = false;
+  bool fuse_depth = false;  // --fuse-depth: the hull's rendered depth images fused into a second carver
   int tolerate = -1;       // --tolerate M: the robust hull instead of the per-view demo
   int blank_view = -1;     // --blank-view I: that view's silhouette becomes all background
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
@@ -62,6 +66,7 @@ int main(int argc, char* argv[]) {
     int n = 1;
     for (int i = 1; i < argc; ++i) {
       if (std::string(argv[i]) == "--keep-largest") keep_largest = true;
+      else if (std::string(argv[i]) == "--fuse-depth") fuse_depth = true;
       else if (std::string(argv[i]) == "--render") {
         if (i + 1 >= argc) {
           std::fprintf(stderr, "--render needs a directory\n");
@@ -201,6 +206,25 @@ int main(int argc, char* argv[]) {
     std::printf("RESULT view %zu verts %zu faces %zu nointerp_verts %zu nointerp_faces %zu vsum %.6f %.6f %.6f "
                 "voxel_verts %zu\n",
                 i, nv, nf, mesh.vertices().size(), mesh.vertex_indices().size(), sum[0], sum[1], sum[2], voxel_verts);
+  }
+
+  if (fuse_depth) {  // the hull's own depth images, fused as a sensor's would be (vcy_render_hull -> vcy_carve_depth)
+    std::vector<std::shared_ptr<vacancy::Camera>> cams;
+    std::vector<vacancy::Image1f> depths(poses.size() < 6 ? poses.size() : 6);
+    for (size_t i = 0; i < depths.size(); ++i) {
+      cams.push_back(std::make_shared<vacancy::PinholeCamera>(width, height, poses[i], Eigen::Vector2f(159.3f, 127.65f),
+                                                              Eigen::Vector2f(258.65f, 258.25f)));
+      if (!carver.RenderHull(*cams.back(), &depths[i])) return 14;
+    }
+    vacancy::VoxelCarverOption fused_option = option;
+    fused_option.update_option.voxel_update = vacancy::VoxelUpdate::kWeightedAverage;
+    vacancy::VoxelCarver fused(fused_option);
+    if (!fused.Init() || !fused.CarveDepth(cams, depths, 3.0f * resolution)) return 14;
+    vacancy::Mesh mesh;
+    fused.ExtractIsoSurface(&mesh, 0.0);
+    mesh.WritePly(out_dir + "/depth_fused.ply");
+    std::printf("DEPTH fused verts %zu faces %zu device_ms %.4f\n", mesh.vertices().size(), mesh.vertex_indices().size(),
+                fused.last_depth_ms());
   }
 
   if (!render_dir.empty()) {  // what the hull looks like from every input camera (vcy_render_hull / vcy_hull_agreement)

@@ -159,6 +159,18 @@ class VoxelCarver {
   bool CarveRobust(const std::vector<std::shared_ptr<Camera>>& cameras, const std::vector<Image1b>& silhouettes, int tolerate,
                    std::vector<std::int64_t>* overruled = nullptr, double iso_level = 0.0);
 
+  // Carve from depth images (vcy_carve_depth; the definition is in vacancy_hip.h): per voxel and view the sample
+  // (depth(pixel) - z_c) / band, clamped to 1 and dropped below -1, through the option's update rule -- the projective
+  // TSDF, which recovers the concavities a visual hull cannot.  depth has RenderHull's meaning (camera depth, +inf where
+  // the ray meets nothing; NaN, 0 and negative values are "no measurement") and gives the view its size; the ROI is the
+  // whole image; band is in world units, finite and > 0.  Depth and silhouette views may be applied to the same state.
+  // false + LOGE on an error, the state then stays as it was.  last_depth_ms(): device milliseconds of the last call's
+  // launches.
+  bool CarveDepth(const Camera& camera, const Image1f& depth, float band);
+  bool CarveDepth(const std::vector<const Camera*>& cameras, const std::vector<Image1f>& depths, float band);
+  bool CarveDepth(const std::vector<std::shared_ptr<Camera>>& cameras, const std::vector<Image1f>& depths, float band);
+  float last_depth_ms() const;
+
   // Fills mesh->vertex_colors() (float RGB in 0 .. 255, what WritePly emits) from the photographs, on the device
   // (vcy_color_vertices): a view colours a vertex it sees -- whose camera depth is at most the hull's depth at its pixel,
   // ray-cast here at iso_level, + depth_tolerance.  photos[i] belongs to cameras[i] and gives the view its size; the ROI

@@ -253,6 +253,55 @@ int vcy_carve_robust_silhouettes(vcy_ctx* ctx, int n_views, const vcy_view* view
 /* Device milliseconds of the last robust carve's launch (events around the kernel; the SDF build is not in it). */
 int vcy_last_robust_ms(const vcy_ctx* ctx, float* device_ms);
 
+/* ---- carve from depth images: projective TSDF fusion ----------------------- */
+/* No counterpart in the reference, whose projection, ROI test, nearest-neighbour pixel and update rules it reuses.  A
+ * visual hull never recovers a concavity; a depth image does.  The sample of a voxel for a depth view is NOT a pixel of
+ * a 2-D SDF: it depends on the voxel's own camera depth, depth(pixel) - z_c, truncated to a band -- the projective TSDF of
+ * KinectFusion, which voxel_update = kWeightedAverage averages and kMax carves with.
+ *
+ * Inputs.  A context of either update mode; n_views >= 1 views with any mix of is_ortho; per view a depth image
+ * float[height][width], row-major, with vcy_render_hull's meaning (camera depth z_c, +inf = the ray meets nothing); band
+ * in world units, finite and > 0 with a finite 1.0f / band.  inv_band = 1.0f / band is computed once on the host, in float.
+ *
+ * Per owned voxel at (px, py, pz) the views are visited in the order given, and the running (sdf, update_num) is updated
+ * exactly as by n_views calls of one view.  For view i:
+ *   1. Gate.  Skip if update_num > voxel_max_update_num (voxel_carver.cc:447-450), tested on the running count.
+ *   2. Projection.  pc[r] = t[r] + (R[r][0]*px + (R[r][1]*py + R[r][2]*pz)); skip if pc[2] < 0.  Pinhole:
+ *      u = fx / pc[2] * pc[0] + cx, w = fy / pc[2] * pc[1] + cy; ortho: u = pc[0], w = pc[1].  The float operations of
+ *      every carve kernel, so a voxel lands on the pixel it lands on in vcy_carve.
+ *   3. ROI test.  inside = u >= roi_min.x && w >= roi_min.y && u <= roi_max.x && w <= roi_max.y (the ROI as float; a NaN
+ *      coordinate is outside).  Skip when outside: update_outside is NOT read -- outside the image there is no measurement.
+ *   4. Pixel.  xi = (int)roundf(u), yi = (int)roundf(w), each clamped into the ROI; Z = depth[yi][xi].  sdf_interp is NOT
+ *      read: depth is never interpolated across a discontinuity.
+ *   5. Validity.  The view contributes only if Z > 0.0f: NaN, 0 and negative values mean "no measurement"; +inf passes.
+ *   6. Sample.  e = Z - pc[2]; d = e * inv_band (the product rounded on its own, no FMA); if d > 1.0f then d = 1.0f; the
+ *      view contributes only if d >= -1.0f (a NaN is dropped, and so is a voxel more than one band behind the surface:
+ *      occluded).  Positive = free space in front of the surface = "outside", the sign convention of the silhouette SDF,
+ *      so depth views and silhouette views may be applied to the same state.  The truncation is always on; use_truncation
+ *      and truncation_band of the option belong to the silhouette builder and are not read.
+ *   7. Update.  First touch (update_num < 1: sdf = d, update_num = 1, voxel_carver.cc:482-486), else UpdateVoxelMax
+ *      (:78-86) or UpdateVoxelWeightedAverage (:88-95) with the context's voxel_update_weight.
+ *
+ * Bookkeeping, as a per-view (non-fused) carve: views queued by earlier per-view calls are applied first (their failure is
+ * returned); update counters widen as for any carve of n_views views; brick minima, halos and component labels become
+ * stale, vcy_render_hull builds its bit planes again.  More than 64 views run as further launches of 64.  Refusals
+ * (VCY_ERR_INVALID_ARG: a bad band, n_views < 1, a NULL image, and what vcy_carve_batch_device refuses in a view) leave
+ * the state untouched and set vcy_last_error().
+ *
+ * The images are in the memory of the context's device and are read while the launches run; the call returns when they
+ * have finished. */
+int vcy_carve_depth_device(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* depth_device, float band);
+/* The same from images in host memory: uploads them (width * height * 4 bytes per view, all at once), then runs the
+ * device path. */
+int vcy_carve_depth(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* depth_host, float band);
+/* The definition, serial, on the host: no GPU, no context.  Works in place on sdf / update_num in vcy_download's layout
+ * for the slices [z_begin, z_end) of the grid of `option` (x fastest, then y, then z - z_begin); the voxel positions are
+ * vcy_axis_positions'.  The device path equals it bit for bit.  The same refusals; the arrays are then untouched. */
+int vcy_carve_depth_host(const vcy_carver_option* option, int z_begin, int z_end, int n_views, const vcy_view* views,
+                         const float* const* depth, float band, float* sdf, int32_t* update_num);
+/* Device milliseconds of the last depth carve's launches (events around every kernel, summed; uploads are not in it). */
+int vcy_last_depth_ms(const vcy_ctx* ctx, float* device_ms);
+
 /* ---- surface extraction ------------------------------------------------- */
 
 /* Replaces void VoxelCarver::ExtractIsoSurface(Mesh*, double iso_level,

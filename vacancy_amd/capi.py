@@ -169,6 +169,10 @@ def load():
         "vcy_carve_robust_device": (C.c_int, [vp, C.c_int, P(View), P(vp), C.c_int, C.c_double, vp]),
         "vcy_carve_robust_silhouettes": (C.c_int, [vp, C.c_int, P(View), P(vp), C.c_int, C.c_double, vp]),
         "vcy_last_robust_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_carve_depth_device": (C.c_int, [vp, C.c_int, P(View), P(vp), C.c_float]),
+        "vcy_carve_depth": (C.c_int, [vp, C.c_int, P(View), P(vp), C.c_float]),
+        "vcy_carve_depth_host": (C.c_int, [P(CarverOption), C.c_int, C.c_int, C.c_int, P(View), P(vp), C.c_float, vp, vp]),
+        "vcy_last_depth_ms": (C.c_int, [vp, P(C.c_float)]),
         "vcy_download_voxels": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
         "vcy_distance_transform_l1": (C.c_int, [vp, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), vp]),
         "vcy_make_sdf": (C.c_int, [vp, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32),

@@ -157,6 +157,35 @@ def color_vertices_host(vertices, views, photos, depth, normals=None, mode=capi.
     return out
 
 
+def carve_depth_host(option, views, depths, band, sdf, update_num, z_range=None):
+    """vcy_carve_depth_host: the depth carve (definition: include/vacancy_hip.h, "carve from depth images") serially on the
+    host, no GPU needed, IN PLACE on `sdf` (float32) and `update_num` (int32), C-contiguous arrays in download()'s layout
+    for the slices z_range = (z_begin, z_end) of the grid of `option` (default: the whole grid).  `depths`: one float32
+    height x width image per view.  RuntimeError (with .rc) on a refusal; the arrays are then untouched."""
+    lib = capi.load()
+    n = len(views)
+    dp = [np.ascontiguousarray(d, np.float32) for d in depths]
+    if len(dp) != n or any(d.shape != (v.height, v.width) for d, v in zip(dp, views)):
+        raise ValueError("one height x width float32 depth image per view")
+    for a, t in ((sdf, np.float32), (update_num, np.int32)):
+        if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("sdf and update_num must be writeable C-contiguous float32 / int32 arrays")
+    dims = (C.c_int32 * 3)()
+    if lib.vcy_compute_dims(option.bb_min, option.bb_max, option.resolution, dims) != 0:
+        raise RuntimeError(last_error())
+    z0, z1 = z_range if z_range is not None else (0, int(dims[2]))
+    if sdf.size != update_num.size or sdf.size != int(dims[0]) * int(dims[1]) * max(z1 - z0, 0):
+        raise ValueError("sdf and update_num hold one entry per voxel of the slices [%d, %d)" % (z0, z1))
+    arr = (View * max(n, 1))(*views)
+    ptrs = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in dp])
+    rc = lib.vcy_carve_depth_host(C.byref(option), int(z0), int(z1), n, arr, ptrs, float(band), _p(sdf), _p(update_num))
+    if rc != 0:
+        e = RuntimeError(last_error())
+        e.rc = rc
+        raise e
+    return sdf, update_num
+
+
 class VoxelCarver:
     def __init__(self, option=None, device_id=0, z_range=None):
         self._lib = capi.load()
@@ -278,6 +307,38 @@ class VoxelCarver:
             raise ValueError("one silhouette per view")
         return self._carve_robust(self._lib.vcy_carve_robust_silhouettes, views, [m.ctypes.data for m in masks], masks,
                                   tolerate, iso_level)
+
+    # -- carve from depth images (no reference counterpart; definition: include/vacancy_hip.h, "carve from depth images")
+    def _carve_depth(self, entry, views, pointers, keep, band):
+        n = len(views)
+        arr = (View * max(n, 1))(*views)
+        ptrs = (C.c_void_p * max(n, 1))(*pointers)
+        rc = entry(self._ctx, n, arr, ptrs, float(band))
+        del keep
+        if rc != 0:
+            e = RuntimeError(last_error())
+            e.rc = rc
+            raise e
+        ms = C.c_float()
+        self._lib.vcy_last_depth_ms(self._ctx, C.byref(ms))
+        return {"device_ms": ms.value}
+
+    def CarveDepthDevice(self, views, depth_devs, band):
+        """vcy_carve_depth_device: fuses the depth images of `views` (resident on the device; RenderHull's meaning: camera
+        depth, +inf on a miss) into the state -- per voxel and view the sample (depth(pixel) - z_c) / band, clamped to 1
+        and dropped below -1, through the context's update rule.  {"device_ms"}.  RuntimeError (with .rc) on a refusal;
+        the state is then untouched."""
+        ptrs = [p.value if isinstance(p, C.c_void_p) else p for p in depth_devs]
+        if len(ptrs) != len(views):
+            raise ValueError("one depth image per view")
+        return self._carve_depth(self._lib.vcy_carve_depth_device, views, ptrs, None, band)
+
+    def CarveDepth(self, views, depths, band):
+        """vcy_carve_depth: the same from numpy images (float32 height x width per view), uploaded by the call."""
+        dp = [np.ascontiguousarray(d, np.float32) for d in depths]
+        if len(dp) != len(views) or any(d.shape != (v.height, v.width) for d, v in zip(dp, views)):
+            raise ValueError("one height x width float32 depth image per view")
+        return self._carve_depth(self._lib.vcy_carve_depth, views, [d.ctypes.data for d in dp], dp, band)
 
     def download_voxels(self, ids):
         ids = np.ascontiguousarray(ids, np.int64)

@@ -10,22 +10,6 @@
 using namespace vcy;
 
 namespace vcy {
-int check_view_static(const vcy_view* v) {
-  if (!v || v->width <= 0 || v->height <= 0) {
-    set_error("invalid view");
-    return VCY_ERR_INVALID_ARG;
-  }
-  // The reference indexes sdf.at() unchecked (assert only); a ROI outside the image is
-  // undefined there and rejected here.
-  if (v->roi_min[0] < 0 || v->roi_min[1] < 0 || v->roi_max[0] >= v->width ||
-      v->roi_max[1] >= v->height || v->roi_min[0] > v->roi_max[0] || v->roi_min[1] > v->roi_max[1]) {
-    set_error("ROI [%d,%d]-[%d,%d] outside the %dx%d SDF image", v->roi_min[0], v->roi_min[1],
-              v->roi_max[0], v->roi_max[1], v->width, v->height);
-    return VCY_ERR_INVALID_ARG;
-  }
-  return VCY_OK;
-}
-
 static int check_view(const vcy_ctx* c, const vcy_view* v) {
   if (!c) {
     set_error("VoxelCarver::Carve voxel grid has not been initialized");

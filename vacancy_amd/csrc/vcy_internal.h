@@ -13,9 +13,9 @@
 
 #include "vacancy_hip.h"
 
-namespace vcy {
+#include "host_shared.h"  // set_error, axis_positions, dims_from_option, check_view_static
 
-void set_error(const char* fmt, ...);
+namespace vcy {
 
 #define VCY_HIP_CHECK(expr)                                                        \
   do {                                                                             \
@@ -219,6 +219,10 @@ struct vcy_ctx {
   vcy::Event ev_rb_begin, ev_rb_end;  // around its launch (vcy_last_robust_ms)
   float last_robust_device_ms = 0.0f;
 
+  // depth carve (carve_depth.hip)
+  std::vector<vcy::Event> ev_dp;      // a pair around every launch of the last call (vcy_last_depth_ms), created on demand
+  float last_depth_device_ms = 0.0f;
+
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
 
@@ -246,7 +250,7 @@ int plan_z_slabs(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* 
 int selftest_fused(hipStream_t stream);
 int flush_pending(vcy_ctx* ctx, bool from_carve = false);   // applies vcy_ctx::pending (no-op when empty)
 int check_carve_views(vcy_ctx* ctx, int n_views, const vcy_view* views);  // argument checks of the carve entry points (vcy_carve.hip)
-int check_view_static(const vcy_view* v);  // ... the part of them that needs no context: image size and ROI (vcy_carve.hip)
+// ... the part of them that needs no context, image size and ROI: check_view_static (host_shared.h)
 int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy_ctx::carve_log, or -1 (vcy_api.hip)
 // mc_extract.hip: the host driver of the marching-cubes extraction (its kernels and their launches: mc_kernels.hip,
 // mc_normals.hip; what the three share: mc_common.h)
@@ -266,6 +270,8 @@ int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
 int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who);
 // color.hip: vcy_color_vertices, vcy_color_vertices_host, vcy_last_color_ms
 // carve_robust.hip: vcy_carve_robust_device, vcy_carve_robust_silhouettes, vcy_last_robust_ms
+// carve_depth.hip: vcy_carve_depth_device, vcy_carve_depth, vcy_last_depth_ms; carve_depth_host.hip (host code only):
+// vcy_carve_depth_host; what the two share: depth_sample.h
 // render_merge.hip (host code only): vcy_render_merge_host, vcy_hull_agreement_host, and the view checks of the ray-cast
 int check_render_view(const vcy_view* v, int i);
 // sdf2d.hip

@@ -205,6 +205,9 @@ int vcy_upload(vcy_ctx* c, const float* sdf, const int32_t* update_num) {
       mx = v > mx ? v : mx;
     }
     { const int rcw = ensure_count_width(c, std::max<int64_t>(mx, c->views_carved)); if (rcw != VCY_OK) return rcw; }
+    // (a widening converts the old counters on the context's stream; the copy below is not ordered behind that stream and
+    // must not be overtaken by it)
+    VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
     std::vector<uint8_t> raw((size_t)n * c->cnt_bytes);
     for (int64_t i = 0; i < n; ++i) {
       const int32_t v = update_num[i];

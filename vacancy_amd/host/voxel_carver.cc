@@ -417,6 +417,56 @@ bool VoxelCarver::CarveRobust(const std::vector<std::shared_ptr<Camera>>& camera
   return CarveRobust(ptrs, silhouettes, tolerate, overruled, iso_level);
 }
 
+bool VoxelCarver::CarveDepth(const std::vector<const Camera*>& cameras, const std::vector<Image1f>& depths, float band) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (cameras.size() != depths.size() || cameras.empty()) {
+    LOGE("VoxelCarver::CarveDepth needs one depth image per camera, at least one (%zu cameras, %zu images)\n", cameras.size(),
+         depths.size());
+    return false;
+  }
+  const int n = static_cast<int>(cameras.size());
+  std::vector<vcy_view> views(n);
+  std::vector<const float*> images(n);
+  for (int i = 0; i < n; ++i) {
+    const Image1f& d = depths[i];
+    bool known = true;
+    if (!cameras[i] || d.empty()) {
+      LOGE("VoxelCarver::CarveDepth: view %d has no camera or an empty depth image\n", i);
+      return false;
+    }
+    views[i] = ToView(*cameras[i], d.width(), d.height(), &known);
+    if (!known) return false;  // (ToView has logged the camera type)
+    images[i] = d.data().data();
+  }
+  const int rc = vcy_carve_depth(impl_->ctx, n, views.data(), images.data(), band);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  return true;
+}
+
+bool VoxelCarver::CarveDepth(const std::vector<std::shared_ptr<Camera>>& cameras, const std::vector<Image1f>& depths, float band) {
+  std::vector<const Camera*> ptrs(cameras.size());
+  for (size_t i = 0; i < cameras.size(); ++i) ptrs[i] = cameras[i].get();
+  return CarveDepth(ptrs, depths, band);
+}
+
+bool VoxelCarver::CarveDepth(const Camera& camera, const Image1f& depth, float band) {
+  // (one image: copied once into the vector the batch overload reads)
+  return CarveDepth(std::vector<const Camera*>{&camera}, std::vector<Image1f>{depth}, band);
+}
+
+float VoxelCarver::last_depth_ms() const {
+  float ms = 0.0f;
+  if (impl_->ctx) vcy_last_depth_ms(impl_->ctx, &ms);
+  return ms;
+}
+
 bool VoxelCarver::ColorMesh(Mesh* mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
                             const ColorOption& option, double iso_level) {
   if (!impl_->ctx) {

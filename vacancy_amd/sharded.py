@@ -207,6 +207,13 @@ class ShardedVoxelCarver:
         parts = self._each_slab(self.slabs, lambda i, c: c.CarveRobustSilhouettes(views, silhouettes, tolerate, iso_level))
         return {"overruled": sum(p["overruled"] for p in parts), "device_ms": float(sum(p["device_ms"] for p in parts))}
 
+    # -- carve from depth images over the slabs (include/vacancy_hip.h, "carve from depth images"): the kernel only touches
+    # owned slices, so every slab makes the same call and nothing is exchanged
+    def CarveDepth(self, views, depths, band):
+        """VoxelCarver.CarveDepth of the whole grid: {"device_ms"}, the sum over the slabs."""
+        parts = self._each_slab(self.slabs, lambda i, c: c.CarveDepth(views, depths, band))
+        return {"device_ms": float(sum(p["device_ms"] for p in parts))}
+
     def last_stream_ms(self):
         """[(producer ms, carve ms, wall ms)] per slab of the last CarveBatchSilhouettes."""
         return [c.last_stream_ms() for c in self.slabs]
