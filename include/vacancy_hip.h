@@ -494,8 +494,11 @@ int  vcy_last_components_ms(const vcy_ctx* ctx, float* device_ms);
  *   5. for the filter, vcy_keep_components_slab on every slab with the pieces that go.
  * Steps 2, 4 and 5 speak about the state step 1 labelled: after a carve, vcy_upload or vcy_reset they return
  * VCY_ERR_INVALID_ARG until the slab is labelled again.  A slab's halo below an upper slab is stale after step 5, as
- * after a carve: exchange the halos (vcy_halo_allgather, ...) before the next extraction, which every sharded
- * extractor does anyway. */
+ * after a carve, and the library enforces it in the same way: every successful vcy_keep_components_slab on an upper
+ * slab marks its halo as not installed -- also when this slab itself removed nothing, because the slab below may have
+ * --, and vcy_extract_iso* and the on-surface vcy_extract_voxel_ids then refuse ("halo slices not installed", the
+ * error they return after a carve) until the halos are exchanged again (vcy_halo_allgather, ...), which every sharded extractor does
+ * anyway. */
 
 /* vcy_label_components on the slices this context owns (any context: on a whole grid the list is exactly
  * vcy_label_components').  Applies queued views; the state is not changed; a context nothing has been carved into

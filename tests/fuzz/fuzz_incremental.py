@@ -3,7 +3,9 @@ carved in GROUPS of 1..5 per call on a state that is already carved (footprint r
 minima before any state is read, live-workgroup list on / off, several chunks of brick layers), with extractions
 in between (bricks outside the surface skipped: "mcskip" 1, against 0 and against the oracle at random iso
 levels) and writes that bypass the fused kernel (vcy_upload, the per-view kernel).  State against the oracle bit
-for bit after every group, as one context and as two z-slab contexts.
+for bit after every group, as one context and as two z-slab contexts.  The writers this script does not know -- the streamed
+batch, queued views, the depth and the robust carve, the component filter, vcy_reset -- and the readers other than marching
+cubes are in the sequences of tests/state_model.py (tests/fuzz/fuzz_state_sequences.py FIRST_SEED LAST_SEED).
 usage: python tests/fuzz/fuzz_incremental.py FIRST_SEED LAST_SEED [modes]   (round 3: seeds 0..520, 1 560 contexts, chunked launches mixed in from 400 on, and 1000..1150 with the extra modes: 0 mismatches)"""
 import sys, os, time
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

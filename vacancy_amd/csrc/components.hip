@@ -908,6 +908,9 @@ int vcy_keep_components_slab(vcy_ctx* c, float fill_sdf, int64_t n_remove, const
     // the labels stay those from before the removal (vcy_download_labels), but no second filter may lean on them
     c->cc_slab_labelled = false;
   }
+  // step 5 of the slab flow: the slab below has run its own filter as well, so the two slices kept from it are stale
+  // whether or not anything went HERE -- as after a carve, extraction refuses until the halos are exchanged again
+  if (c->halo_lo > 0) c->halo_valid = false;
   if (removed_voxels) *removed_voxels = rv_n;
   return VCY_OK;
 }
