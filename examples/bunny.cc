@@ -2,6 +2,7 @@
 // bunny, 10 mm voxels; per view carve -> marching cubes (interpolated and not), PLY out.
 // Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs] [planned] [--keep-largest] [--render DIR] [--fuse-depth]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --tolerate M [--blank-view I]
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] --smooth N [--lambda L --mu M]
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
 //   --render DIR (DIR must exist) writes DIR/hull_<view>.png, the silhouette of the carved hull as every input camera
@@ -13,6 +14,10 @@
 //   --fuse-depth (after the ordinary carve) renders the hull's depth from every input camera, fuses those images into a second
 //   carver of the same box and resolution (weighted average, band = 3 voxels: VoxelCarver::CarveDepth), writes the
 //   iso-surface as <out_dir>/depth_fused.ply and prints its size and the device time of the fusion.
+//   --smooth N (after the ordinary carve) smooths the final iso-surface with N Taubin iterations on the device
+//   (VoxelCarver::SmoothMesh, factors --lambda / --mu, by default the usual pair 0.5 / -0.53) and recomputes its normals
+//   before it writes it as <out_dir>/surface_smooth.ply (binary, with normals); with slabs the merged mesh is smoothed
+//   through ShardedVoxelCarver::SmoothMesh as well and compared.
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -61,6 +66,8 @@ int main(int argc, char* argv[]) {
   bool fuse_depth = false;  // --fuse-depth: the hull's rendered depth images fused into a second carver
   int tolerate = -1;       // --tolerate M: the robust hull instead of the per-view demo
   int blank_view = -1;     // --blank-view I: that view's silhouette becomes all background
+  int smooth = -1;         // --smooth N: Taubin iterations over the final iso-surface before it is written
+  float smooth_lambda = 0.5f, smooth_mu = -0.53f;  // --lambda L, --mu M
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
@@ -79,6 +86,14 @@ int main(int argc, char* argv[]) {
           return 10;
         }
         (std::string(argv[i]) == "--tolerate" ? tolerate : blank_view) = std::atoi(argv[i + 1]);
+        ++i;
+      } else if (std::string(argv[i]) == "--smooth" || std::string(argv[i]) == "--lambda" || std::string(argv[i]) == "--mu") {
+        if (i + 1 >= argc) {
+          std::fprintf(stderr, "%s needs a number\n", argv[i]);
+          return 10;
+        }
+        if (std::string(argv[i]) == "--smooth") smooth = std::atoi(argv[i + 1]);
+        else (std::string(argv[i]) == "--lambda" ? smooth_lambda : smooth_mu) = (float)std::atof(argv[i + 1]);
         ++i;
       } else argv[n++] = argv[i];
     }
@@ -225,6 +240,28 @@ int main(int argc, char* argv[]) {
     mesh.WritePly(out_dir + "/depth_fused.ply");
     std::printf("DEPTH fused verts %zu faces %zu device_ms %.4f\n", mesh.vertices().size(), mesh.vertex_indices().size(),
                 fused.last_depth_ms());
+  }
+
+  if (smooth >= 0) {  // the final surface, smoothed on the device, with the normals of the smoothed positions
+    vacancy::Mesh mesh;
+    carver.ExtractIsoSurface(&mesh, 0.0);
+    const vacancy::Mesh raw = mesh;
+    if (!carver.SmoothMesh(&mesh, smooth, smooth_lambda, smooth_mu, false, true)) return 15;
+    mesh.WritePlyBinary(out_dir + "/surface_smooth.ply");
+    const std::array<float, 3> ms = carver.last_smooth_ms();
+    std::printf("SMOOTH iterations %d lambda %g mu %g verts %zu faces %zu build_ms %.4f passes_ms %.4f normals_ms %.4f\n", smooth,
+                smooth_lambda, smooth_mu, mesh.vertices().size(), mesh.vertex_indices().size(), ms[0], ms[1], ms[2]);
+    if (sharded) {  // the merged mesh through the first slab's context, and Mesh::Smooth on the host: the same bits
+      vacancy::Mesh sm, hm = raw;
+      sharded->ExtractIsoSurface(&sm, 0.0);
+      if (!sharded->SmoothMesh(&sm, smooth, smooth_lambda, smooth_mu, false, true) || !hm.Smooth(smooth, smooth_lambda, smooth_mu)) return 15;
+      bool same = sm.vertices().size() == mesh.vertices().size() && sm.normals().size() == mesh.normals().size() &&
+                  hm.vertices().size() == mesh.vertices().size();
+      for (size_t k = 0; same && k < sm.vertices().size(); ++k)
+        same = std::memcmp(&sm.vertices()[k], &mesh.vertices()[k], 12) == 0 && std::memcmp(&hm.vertices()[k], &mesh.vertices()[k], 12) == 0 &&
+               std::memcmp(&sm.normals()[k], &mesh.normals()[k], 12) == 0;
+      std::printf("SMOOTHSHARDED slabs %d verts %zu identical %d\n", sharded->slab_count(), sm.vertices().size(), same ? 1 : 0);
+    }
   }
 
   if (!render_dir.empty()) {  // what the hull looks like from every input camera (vcy_render_hull / vcy_hull_agreement)

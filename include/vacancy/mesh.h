@@ -22,6 +22,12 @@ class Mesh {
   // fills the same three vectors from the device, bit for bit.
   void CalcNormal();
   void CalcFaceNormal();
+  // `iterations` Taubin iterations over the vertices, serial on the host (vcy_smooth_mesh_host; the rule is in
+  // vacancy_hip.h, "mesh smoothing"): a pass with factor lambda, then one with mu (0: plain Laplacian smoothing);
+  // pin_boundary keeps the vertices of an edge that one face uses.  normals(), face_normals() and normal_indices() are
+  // recomputed if they were filled.  VoxelCarver::SmoothMesh runs the same on the device, bit for bit.  false + LOGE on
+  // an error (a face index out of range, a non-finite factor ...), the mesh then stays as it was.
+  bool Smooth(int iterations, float lambda = 0.5f, float mu = -0.53f, bool pin_boundary = false);
   const std::vector<Eigen::Vector3f>& normals() const { return normals_; }
   const std::vector<Eigen::Vector3f>& face_normals() const { return face_normals_; }
   const std::vector<Eigen::Vector3i>& normal_indices() const { return normal_indices_; }

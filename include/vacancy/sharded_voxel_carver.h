@@ -59,6 +59,10 @@ class ShardedVoxelCarver {
   // stale after the filter as after a Carve(); the extractions exchange them before they read them.
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
+  // VoxelCarver::SmoothMesh for the merged mesh: the call needs a device and a stream, not the voxels, so the first slab's
+  // context runs it (vcy_smooth_mesh).  The same bits as VoxelCarver::SmoothMesh and Mesh::Smooth.
+  bool SmoothMesh(Mesh* mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool pin_boundary = false,
+                  bool with_normals = false);
   // VoxelCarver::RenderHull / HullAgreement over the slabs: RenderHullSlabs / HullAgreementSlabs below.  These two older
   // names keep logging an error and returning false.
   bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);

@@ -179,6 +179,14 @@ class VoxelCarver {
   bool ColorMesh(Mesh* mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
                  const ColorOption& option = ColorOption(), double iso_level = 0.0);
 
+  // Mesh::Smooth on this carver's device (vcy_smooth_mesh), the same bits: the mesh goes up, the incidence table is built
+  // there, the passes and -- with_normals -- Mesh::CalcNormal() of the result run there, the vertices (and normals) come
+  // back.  Any mesh will do, not only one this carver extracted; the voxel state is not touched.  false + LOGE on an
+  // error, the mesh then stays as it was.  last_smooth_ms(): device milliseconds of the table, the passes, the normals.
+  bool SmoothMesh(Mesh* mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool pin_boundary = false,
+                  bool with_normals = false);
+  std::array<float, 3> last_smooth_ms() const;
+
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;
   bool Download(std::vector<float>* sdf, std::vector<int>* update_num) const;

@@ -714,6 +714,59 @@ int vcy_color_vertices(vcy_ctx* ctx, double iso_level, int64_t n_vertices, const
  * not included; the ray-cast of a call without depth images is in vcy_last_render_ms. */
 int vcy_last_color_ms(const vcy_ctx* ctx, float* device_ms);
 
+/* ---- mesh smoothing: Taubin passes over an indexed mesh, fresh normals ----- */
+/* No reference counterpart: this section is the definition.  vcy_smooth_mesh_host is it in serial host code,
+ * tests/smooth_ref.py restates it in numpy, vcy_smooth_mesh runs it on the device; the three agree bit for bit.
+ *
+ * All arithmetic is float; every product, sum and division is rounded on its own (no FMA), division and square root
+ * are correctly rounded -- the flags the library is built with.
+ *
+ * Rows.  The row of vertex v lists every corner (f, j) with faces[3f + j] == v in ascending f, then ascending j; a face
+ * that names v twice has two corners in the row.  cnt(v) is twice the row's length.
+ *
+ * One pass with factor s, from positions p to positions q (a Jacobi pass: every q is computed from the same p).
+ *   cnt(v) == 0 or v pinned:  q[v] = p[v], an exact copy of the bits.
+ *   otherwise, per coordinate c:  S_c = +0; through the row in order, for each corner (f, j), with
+ *     a = p[faces[3f + (j+1)%3]],  b = p[faces[3f + (j+2)%3]]:   S_c = S_c + a_c;  S_c = S_c + b_c.
+ *   Then  m_c = S_c / (float)cnt,  d_c = m_c - p_c,  q_c = p_c + s * d_c.
+ * On a closed manifold this is the uniform umbrella operator with every neighbour counted twice; the order of the sum is
+ * Mesh::CalcNormal's.  The passes of a call: lambda, mu, lambda, mu, ... -- 2 * iterations of them; iterations == 0
+ * returns the input bits.  (A pass with s == 0 is still a pass: p_c + 0 * d_c.)
+ *
+ * Pinned vertices.  With pin_boundary, v is pinned iff some vertex u != v occurs exactly once among the cnt(v) ids the
+ * pass would gather for v: an edge that one face uses.
+ *
+ * Normals.  If either normals output is non-NULL, the result is vcy_mesh_normals_host of (vertices_out, faces), to the bit.
+ * A vertex that no face names gets NaN, as there; the sign of that NaN is not part of the contract.
+ *
+ * Non-finite input positions go through the same arithmetic; which NaN comes out (sign, payload) is not part of the
+ * contract.  vertices_out may alias vertices.
+ *
+ * VCY_ERR_INVALID_ARG, nothing written, for a NULL required pointer, negative counts, a face index outside
+ * [0, n_vertices), iterations outside 0 .. 10000, a non-finite lambda or mu, pin_boundary not 0 or 1.
+ * VCY_ERR_UNSUPPORTED when 3 * n_faces >= 2^31 or n_vertices >= 2^31 (corner ids are int32 on the device).
+ * n_vertices == 0 is VCY_OK and writes nothing. */
+typedef struct vcy_smooth_option {
+  int32_t iterations;    /* >= 0; one iteration = a lambda pass, then a mu pass; at most 10000 */
+  float   lambda;        /* finite */
+  float   mu;            /* finite; 0 makes it plain Laplacian smoothing */
+  int32_t pin_boundary;  /* 0 / 1 */
+} vcy_smooth_option;
+
+int vcy_smooth_mesh_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                         const vcy_smooth_option* option, float* vertices_out,
+                         float* vertex_normals_out /* may be NULL */, float* face_normals_out /* may be NULL */);
+/* The same on the device of `ctx`, on its stream, from and into HOST arrays (as vcy_color_vertices).  The context only
+ * names the device and the stream: any context will do, a z-slab included -- a sharded caller smooths the merged mesh on
+ * one of its slabs.  The voxel state, queued views and every cache stay untouched.  Device memory: about 175 bytes per
+ * vertex of a triangle mesh, kept by the context (grow-only). */
+int vcy_smooth_mesh(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                    const vcy_smooth_option* option, float* vertices_out,
+                    float* vertex_normals_out /* may be NULL */, float* face_normals_out /* may be NULL */);
+/* Device time of the last vcy_smooth_mesh: the incidence table (count, scan, fill, row sort, gather rows), all passes, the
+ * normals (0 when none were asked for).  Any output may be NULL. */
+int vcy_last_smooth_ms(const vcy_ctx* ctx, float* build_ms, float* passes_ms, float* normals_ms);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and
@@ -867,6 +920,9 @@ int vcy_reset(vcy_ctx* ctx);
  * "rayskip" (default 1): the rays of vcy_render_hull / vcy_hull_agreement step over 8 x 8 x 8 bricks without a solid voxel
  * and jump to the plane through which they enter the grid; 0: every ray walks crossing by crossing.  Results identical
  * (readable through vcy_get_param).
+ * "smoothpad" (default 0): 1 keeps the positions of vcy_smooth_mesh's passes at 16 bytes per vertex (one 16-byte gather)
+ * instead of 12 (three 4-byte gathers); measured slower at every size (profiles/smooth/measure_smooth.txt).  Results
+ * identical (readable through vcy_get_param).
  * "inject_carve_failure" (test hook, default 0): the next `value` applications of views fail with
  * VCY_ERR_INTERNAL before anything is launched -- how the tests exercise the error contract of vcy_carve. */
 int vcy_set_param(vcy_ctx* ctx, const char* name, int value);

@@ -107,6 +107,16 @@ class ColorOption(C.Structure):
         super().__init__(mode, interp, depth_tolerance, min_cos, (C.c_float * 3)(*fallback))
 
 
+class SmoothOption(C.Structure):
+    """vcy_smooth_option: the passes of vcy_smooth_mesh (one iteration = a lambda pass, then a mu pass)."""
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("lam", C.c_float),
+        ("mu", C.c_float),
+        ("pin_boundary", C.c_int32),
+    ]
+
+
 class Component(C.Structure):
     """vcy_component: one 6-connected component of the solid voxels (vcy_label_components)."""
     _fields_ = [
@@ -208,6 +218,9 @@ def load():
         "vcy_color_vertices": (C.c_int, [vp, C.c_double, C.c_int64, vp, vp, C.c_int, P(View), P(vp), P(vp), P(ColorOption),
                                          vp, vp, vp]),
         "vcy_last_color_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_smooth_mesh_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
+        "vcy_smooth_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
+        "vcy_last_smooth_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float), P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_mesh_normals_seam_sum": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import CarverOption, ColorOption, Mesh, UpdateOption, View, make_view  # noqa: F401
+from .capi import CarverOption, ColorOption, Mesh, SmoothOption, UpdateOption, View, make_view  # noqa: F401
 
 
 def _p(a):
@@ -154,6 +154,35 @@ def color_vertices_host(vertices, views, photos, depth, normals=None, mode=capi.
     keep, args, out = _color_args(vertices, views, photos, normals, depth, mode, interp, depth_tolerance, min_cos, fallback)
     if capi.load().vcy_color_vertices_host(*args) != 0:
         raise RuntimeError(last_error())
+    return out
+
+
+def _smooth_args(vertices, faces, iterations, lam, mu, pin_boundary, normals):
+    """The arrays and ctypes arguments vcy_smooth_mesh and vcy_smooth_mesh_host share; the first element keeps every array
+    alive for the call."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    opt = SmoothOption(int(iterations), float(lam), float(mu), int(pin_boundary))
+    out = {"vertices": np.zeros((len(v), 3), np.float32)}
+    if normals:
+        out["normals"] = np.zeros((len(v), 3), np.float32)
+        out["face_normals"] = np.zeros((len(f), 3), np.float32)
+    args = (len(v), len(f), _p(v), _p(f), C.byref(opt), _p(out["vertices"]),
+            _p(out["normals"]) if normals else None, _p(out["face_normals"]) if normals else None)
+    return (v, f, opt), args, out
+
+
+def smooth_mesh_host(vertices, faces, iterations, lam, mu, pin_boundary=False, normals=False):
+    """vcy_smooth_mesh_host: `iterations` Taubin iterations (a pass with factor `lam`, then one with `mu`; mu = 0: plain
+    Laplacian smoothing) over an indexed mesh, serial, no GPU needed (definition: include/vacancy_hip.h, "mesh
+    smoothing").  pin_boundary: vertices of an edge that one face uses stay.  Returns {"vertices": float32 [n, 3]} and, with
+    normals=True, "normals" / "face_normals" = mesh_normals_host of the result.  RuntimeError (with .rc) on a refusal."""
+    keep, args, out = _smooth_args(vertices, faces, iterations, lam, mu, pin_boundary, normals)
+    rc = capi.load().vcy_smooth_mesh_host(*args)
+    if rc != 0:
+        e = RuntimeError(last_error())
+        e.rc = rc
+        raise e
     return out
 
 
@@ -699,6 +728,23 @@ class VoxelCarver:
         ms = C.c_float()
         self._lib.vcy_last_color_ms(self._ctx, C.byref(ms))
         out["device_ms"] = ms.value
+        return out
+
+    # -- Taubin smoothing of an indexed mesh (no reference counterpart; definition: include/vacancy_hip.h)
+    def SmoothMesh(self, vertices, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=False, normals=False):
+        """vcy_smooth_mesh: smooth_mesh_host on this context's device and stream, the same bits.  The context only names the
+        device: its voxel state is not touched, and a z-slab will do.  Returns {"vertices"}, with normals=True "normals" and
+        "face_normals" (Mesh::CalcNormal of the result), and the device times "build_ms" (incidence table), "passes_ms",
+        "normals_ms".  RuntimeError (with .rc) on a refusal."""
+        keep, args, out = _smooth_args(vertices, faces, iterations, lam, mu, pin_boundary, normals)
+        rc = self._lib.vcy_smooth_mesh(self._ctx, *args)
+        if rc != 0:
+            e = RuntimeError(last_error())
+            e.rc = rc
+            raise e
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        self._lib.vcy_last_smooth_ms(self._ctx, *[C.byref(m) for m in ms])
+        out["build_ms"], out["passes_ms"], out["normals_ms"] = (m.value for m in ms)
         return out
 
     # -- state access

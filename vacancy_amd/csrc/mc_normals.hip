@@ -17,6 +17,7 @@
 //
 // Arithmetic: include/vacancy/linalg.h's, i.e. squaredNorm = x*x + (y*y + z*z), normalized() = n2 > 0 ? v / sqrt(n2) : v,
 // true division per component; no contraction, correctly rounded sqrt and division, denormals kept (Makefile).
+#include "face_normal.h"
 #include "mc_common.h"
 #include "vcy_internal.h"
 
@@ -94,28 +95,7 @@ __device__ __forceinline__ void edge_position(const McParams& p, const u64* __re
   vertex_interp(p.iso, pa, pb, corner_value(p, s, ca), corner_value(p, s, cb), p.linear != 0, out);
 }
 
-// Eigen::Vector3f::normalize() as include/vacancy/linalg.h evaluates it
-__device__ __forceinline__ void normalize3(float v[3]) {
-  const float n2 = v[0] * v[0] + (v[1] * v[1] + v[2] * v[2]);
-  if (n2 > 0.0f) {
-    const float n = sqrtf(n2);
-    v[0] = v[0] / n;
-    v[1] = v[1] / n;
-    v[2] = v[2] / n;
-  }
-}
-
-// Mesh::CalcFaceNormal for one face (mesh.cc:231-240)
-__device__ __forceinline__ void face_normal(const float p0[3], const float p1[3], const float p2[3], float fn[3]) {
-  float v1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-  float v2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-  normalize3(v1);
-  normalize3(v2);
-  fn[0] = v1[1] * v2[2] - v1[2] * v2[1];
-  fn[1] = v1[2] * v2[0] - v1[0] * v2[2];
-  fn[2] = v1[0] * v2[1] - v1[1] * v2[0];
-  normalize3(fn);
-}
+// normalize3, face_normal: face_normal.h
 
 // the counts of the chain, and whether mc_emit has written a mesh at all (it has not when a capacity was too small:
 // the host then runs the chain again with room, and these kernels with it)

@@ -223,6 +223,12 @@ struct vcy_ctx {
   std::vector<vcy::Event> ev_dp;      // a pair around every launch of the last call (vcy_last_depth_ms), created on demand
   float last_depth_device_ms = 0.0f;
 
+  // mesh smoothing (mesh_smooth.hip); grow-only
+  vcy::DeviceBuf<> d_sm_buf;          // the mesh, its incidence table and gather rows, both position arrays, the normals
+  vcy::Event ev_sm[4];                // around the table's launches, the passes and the normals (vcy_last_smooth_ms)
+  float last_smooth_ms[3] = {0.0f, 0.0f, 0.0f};
+  int smooth_pad = 0;                 // "smoothpad": positions of the passes padded to 16 bytes (one dwordx4 gather) instead of 12 (three dword gathers)
+
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
 
@@ -269,6 +275,14 @@ int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
 // vcy_ctx::d_rn_out and holds until the context next renders; waits for the launch; vcy_last_render_ms as for the render
 int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who);
 // color.hip: vcy_color_vertices, vcy_color_vertices_host, vcy_last_color_ms
+// mesh_smooth.hip: vcy_smooth_mesh, vcy_last_smooth_ms; mesh_smooth_host.hip (host code only): vcy_smooth_mesh_host and
+// the argument checks of the two
+int smooth_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                      const vcy_smooth_option* option, const float* vertices_out);
+// the in-place exclusive scan of mc_kernels.hip for the other compactions of the library; `scratch`: the chunk sums of
+// every level
+int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long long* d_total, unsigned long long* scratch,
+                              hipStream_t stream);
 // carve_robust.hip: vcy_carve_robust_device, vcy_carve_robust_silhouettes, vcy_last_robust_ms
 // carve_depth.hip: vcy_carve_depth_device, vcy_carve_depth, vcy_last_depth_ms; carve_depth_host.hip (host code only):
 // vcy_carve_depth_host; what the two share: depth_sample.h

@@ -11,6 +11,7 @@
 
 #include "c_abi_structs.h"
 #include "mesh_copy.h"
+#include "mesh_smooth.h"
 
 namespace vacancy {
 
@@ -398,6 +399,17 @@ bool ShardedVoxelCarver::HullAgreementSlabs(const std::vector<const Camera*>& ca
 // that go.  The two halo slices below every upper slab are stale afterwards, exactly as after a Carve(): ExtractIsoSurface
 // always, and ExtractVoxel whenever it reads the slice below a slab (inside_empty), call ExchangeHalo() before they
 // read them, so nothing has to be exchanged here.
+bool ShardedVoxelCarver::SmoothMesh(Mesh* mesh, int iterations, float lambda, float mu, bool pin_boundary, bool with_normals) {
+  if (impl_->slabs.empty() || !mesh) {
+    LOGE("ShardedVoxelCarver::SmoothMesh needs a mesh and an initialized carver\n");
+    return false;
+  }
+  vcy_ctx* ctx = impl_->slabs[0];
+  return detail::SmoothMeshWith(mesh, iterations, lambda, mu, pin_boundary, with_normals,
+                                [ctx](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_smooth_option* o,
+                                      float* out, float* vn, float* fn) { return vcy_smooth_mesh(ctx, nv, nf, v, f, o, out, vn, fn); });
+}
+
 bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!std::isfinite(fill_sdf) || !(static_cast<double>(fill_sdf) >= iso_level)) {
     LOGE("KeepLargestComponents: fill_sdf %g must be finite and not below the iso level %g\n", static_cast<double>(fill_sdf),

@@ -13,6 +13,8 @@
 #include "vacancy/mesh.h"
 #include "vacancy_hip.h"
 
+#include "mesh_smooth.h"
+
 namespace vacancy {
 
 // ---- logger ---------------------------------------------------------------------------------
@@ -68,6 +70,10 @@ void Mesh::CalcNormal() {
     face_normals_.clear();
     normal_indices_.clear();
   }
+}
+
+bool Mesh::Smooth(int iterations, float lambda, float mu, bool pin_boundary) {
+  return detail::SmoothMeshWith(this, iterations, lambda, mu, pin_boundary, false, &vcy_smooth_mesh_host);
 }
 
 // ---- PLY --------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 
 #include "c_abi_structs.h"
 #include "mesh_copy.h"
+#include "mesh_smooth.h"
 
 namespace vacancy {
 
@@ -513,6 +514,27 @@ bool VoxelCarver::ColorMesh(Mesh* mesh, const std::vector<const Camera*>& camera
   }
   mesh->set_vertex_colors(colors);
   return true;
+}
+
+bool VoxelCarver::SmoothMesh(Mesh* mesh, int iterations, float lambda, float mu, bool pin_boundary, bool with_normals) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (!mesh) {
+    LOGE("VoxelCarver::SmoothMesh needs a mesh\n");
+    return false;
+  }
+  vcy_ctx* ctx = impl_->ctx;
+  return detail::SmoothMeshWith(mesh, iterations, lambda, mu, pin_boundary, with_normals,
+                                [ctx](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_smooth_option* o,
+                                      float* out, float* vn, float* fn) { return vcy_smooth_mesh(ctx, nv, nf, v, f, o, out, vn, fn); });
+}
+
+std::array<float, 3> VoxelCarver::last_smooth_ms() const {
+  std::array<float, 3> ms = {{0.0f, 0.0f, 0.0f}};
+  if (impl_->ctx) vcy_last_smooth_ms(impl_->ctx, &ms[0], &ms[1], &ms[2]);
+  return ms;
 }
 
 bool VoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {

@@ -214,6 +214,12 @@ class ShardedVoxelCarver:
         parts = self._each_slab(self.slabs, lambda i, c: c.CarveDepth(views, depths, band))
         return {"device_ms": float(sum(p["device_ms"] for p in parts))}
 
+    # -- Taubin smoothing of the MERGED mesh (include/vacancy_hip.h, "mesh smoothing"): the call needs a device and a
+    # stream, not the voxels, so the first slab's context runs it
+    def SmoothMesh(self, vertices, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=False, normals=False):
+        """VoxelCarver.SmoothMesh on the first slab's context: the same dict."""
+        return self.slabs[0].SmoothMesh(vertices, faces, iterations, lam, mu, pin_boundary, normals)
+
     def last_stream_ms(self):
         """[(producer ms, carve ms, wall ms)] per slab of the last CarveBatchSilhouettes."""
         return [c.last_stream_ms() for c in self.slabs]
