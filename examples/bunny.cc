@@ -3,6 +3,7 @@
 // Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs] [planned] [--keep-largest] [--render DIR] [--fuse-depth]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --tolerate M [--blank-view I]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --smooth N [--lambda L --mu M]
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] --decimate CELLS [--decimate-mode mean|nearest|first]
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
 //   --render DIR (DIR must exist) writes DIR/hull_<view>.png, the silhouette of the carved hull as every input camera
@@ -18,6 +19,10 @@
 //   (VoxelCarver::SmoothMesh, factors --lambda / --mu, by default the usual pair 0.5 / -0.53) and recomputes its normals
 //   before it writes it as <out_dir>/surface_smooth.ply (binary, with normals); with slabs the merged mesh is smoothed
 //   through ShardedVoxelCarver::SmoothMesh as well and compared.
+//   --decimate CELLS (after the ordinary carve, and after --smooth if both are given) decimates the final iso-surface by
+//   vertex clustering on the device (VoxelCarver::DecimateMesh: cells of CELLS * resolution from the box's corner, the
+//   cluster's mean, its member nearest to the mean or its first member) and writes it as <out_dir>/surface_decimated.ply
+//   (binary, with normals); with slabs the merged mesh goes through ShardedVoxelCarver::DecimateMesh as well and is compared.
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -68,6 +73,8 @@ int main(int argc, char* argv[]) {
   int blank_view = -1;     // --blank-view I: that view's silhouette becomes all background
   int smooth = -1;         // --smooth N: Taubin iterations over the final iso-surface before it is written
   float smooth_lambda = 0.5f, smooth_mu = -0.53f;  // --lambda L, --mu M
+  float decimate = 0.0f;   // --decimate CELLS: vertex clustering over cells of CELLS voxels before the surface is written
+  int decimate_mode = 0;   // --decimate-mode mean|nearest|first
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
@@ -94,6 +101,25 @@ int main(int argc, char* argv[]) {
         }
         if (std::string(argv[i]) == "--smooth") smooth = std::atoi(argv[i + 1]);
         else (std::string(argv[i]) == "--lambda" ? smooth_lambda : smooth_mu) = (float)std::atof(argv[i + 1]);
+        ++i;
+      } else if (std::string(argv[i]) == "--decimate") {
+        if (i + 1 >= argc) {
+          std::fprintf(stderr, "%s needs a number\n", argv[i]);
+          return 10;
+        }
+        decimate = (float)std::atof(argv[i + 1]);
+        if (!(decimate > 0.0f)) {
+          std::fprintf(stderr, "%s needs a positive number\n", argv[i]);
+          return 10;
+        }
+        ++i;
+      } else if (std::string(argv[i]) == "--decimate-mode") {
+        const std::string m = i + 1 < argc ? argv[i + 1] : "";
+        if (m != "mean" && m != "nearest" && m != "first") {
+          std::fprintf(stderr, "%s needs mean, nearest or first\n", argv[i]);
+          return 10;
+        }
+        decimate_mode = m == "mean" ? 0 : m == "nearest" ? 1 : 2;
         ++i;
       } else argv[n++] = argv[i];
     }
@@ -261,6 +287,34 @@ int main(int argc, char* argv[]) {
         same = std::memcmp(&sm.vertices()[k], &mesh.vertices()[k], 12) == 0 && std::memcmp(&hm.vertices()[k], &mesh.vertices()[k], 12) == 0 &&
                std::memcmp(&sm.normals()[k], &mesh.normals()[k], 12) == 0;
       std::printf("SMOOTHSHARDED slabs %d verts %zu identical %d\n", sharded->slab_count(), sm.vertices().size(), same ? 1 : 0);
+    }
+  }
+
+  if (decimate > 0.0f) {  // the final surface (smoothed first if asked for), clustered on the device, with fresh normals
+    const char* mode_names[3] = {"mean", "nearest", "first"};
+    const float cell = decimate * resolution;
+    vacancy::Mesh mesh;
+    carver.ExtractIsoSurface(&mesh, 0.0);
+    if (smooth >= 0 && !carver.SmoothMesh(&mesh, smooth, smooth_lambda, smooth_mu, false, false)) return 16;
+    const vacancy::Mesh before = mesh;
+    if (!carver.DecimateMesh(&mesh, cell, decimate_mode, true)) return 16;
+    mesh.WritePlyBinary(out_dir + "/surface_decimated.ply");
+    const std::array<float, 4> ms = carver.last_decimate_ms();
+    std::printf("DECIMATE cell %g mode %s vertices %zu -> %zu faces %zu -> %zu cluster_ms %.4f faces_ms %.4f emit_ms %.4f normals_ms %.4f\n",
+                cell, mode_names[decimate_mode], before.vertices().size(), mesh.vertices().size(), before.vertex_indices().size(),
+                mesh.vertex_indices().size(), ms[0], ms[1], ms[2], ms[3]);
+    if (sharded) {  // the merged mesh through the first slab's context: the same bits
+      vacancy::Mesh sm;
+      sharded->ExtractIsoSurface(&sm, 0.0);
+      if (smooth >= 0 && !sharded->SmoothMesh(&sm, smooth, smooth_lambda, smooth_mu, false, false)) return 16;
+      if (!sharded->DecimateMesh(&sm, cell, decimate_mode, true)) return 16;
+      bool same = sm.vertices().size() == mesh.vertices().size() && sm.normals().size() == mesh.normals().size() &&
+                  sm.vertex_indices().size() == mesh.vertex_indices().size();
+      for (size_t k = 0; same && k < sm.vertices().size(); ++k)
+        same = std::memcmp(&sm.vertices()[k], &mesh.vertices()[k], 12) == 0 && std::memcmp(&sm.normals()[k], &mesh.normals()[k], 12) == 0;
+      for (size_t k = 0; same && k < sm.vertex_indices().size(); ++k)
+        same = std::memcmp(&sm.vertex_indices()[k], &mesh.vertex_indices()[k], 12) == 0;
+      std::printf("DECIMATESHARDED slabs %d verts %zu identical %d\n", sharded->slab_count(), sm.vertices().size(), same ? 1 : 0);
     }
   }
 

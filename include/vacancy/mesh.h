@@ -28,6 +28,14 @@ class Mesh {
   // recomputed if they were filled.  VoxelCarver::SmoothMesh runs the same on the device, bit for bit.  false + LOGE on
   // an error (a face index out of range, a non-finite factor ...), the mesh then stays as it was.
   bool Smooth(int iterations, float lambda = 0.5f, float mu = -0.53f, bool pin_boundary = false);
+  // Vertex-clustering decimation, serial on the host (vcy_decimate_mesh_host; the rule is in vacancy_hip.h, "mesh
+  // decimation"): the vertices of one cube of edge `cell` of a lattice with a corner at the origin become one vertex --
+  // mode 0 their mean, 1 the member nearest to the mean, 2 the first member --, faces that collapse or repeat go, vertices
+  // no face names go.  normals(), face_normals() and normal_indices() are recomputed if they were filled; vertex_colors()
+  // are cleared.  VoxelCarver::DecimateMesh runs the same on the device, bit for bit, with the lattice at the carver's
+  // bb_min.  false + LOGE on an error (a face index out of range, cell <= 0, a non-finite vertex ...), the mesh then stays
+  // as it was.
+  bool Decimate(float cell, int mode = 0);
   const std::vector<Eigen::Vector3f>& normals() const { return normals_; }
   const std::vector<Eigen::Vector3f>& face_normals() const { return face_normals_; }
   const std::vector<Eigen::Vector3i>& normal_indices() const { return normal_indices_; }

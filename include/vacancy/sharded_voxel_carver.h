@@ -63,6 +63,9 @@ class ShardedVoxelCarver {
   // context runs it (vcy_smooth_mesh).  The same bits as VoxelCarver::SmoothMesh and Mesh::Smooth.
   bool SmoothMesh(Mesh* mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool pin_boundary = false,
                   bool with_normals = false);
+  // VoxelCarver::DecimateMesh for the merged mesh, on the first slab's context (vcy_decimate_mesh), the lattice at the
+  // grid's bb_min.  The same bits as VoxelCarver::DecimateMesh.
+  bool DecimateMesh(Mesh* mesh, float cell, int mode = 0, bool with_normals = false);
   // VoxelCarver::RenderHull / HullAgreement over the slabs: RenderHullSlabs / HullAgreementSlabs below.  These two older
   // names keep logging an error and returning false.
   bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);

@@ -187,6 +187,14 @@ class VoxelCarver {
                   bool with_normals = false);
   std::array<float, 3> last_smooth_ms() const;
 
+  // Mesh::Decimate on this carver's device (vcy_decimate_mesh), the same bits, with the cell lattice at this carver's
+  // bb_min, so that cells of `cell` = k * resolution hold k x k x k voxels: the mesh goes up, clusters, surviving faces
+  // and -- with_normals -- Mesh::CalcNormal() of the result are computed there, the decimated mesh comes back.  Any mesh
+  // will do, not only one this carver extracted; the voxel state is not touched.  false + LOGE on an error, the mesh
+  // then stays as it was.  last_decimate_ms(): device milliseconds of the clusters, the faces, the emit, the normals.
+  bool DecimateMesh(Mesh* mesh, float cell, int mode = 0, bool with_normals = false);
+  std::array<float, 4> last_decimate_ms() const;
+
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;
   bool Download(std::vector<float>* sdf, std::vector<int>* update_num) const;

@@ -767,6 +767,80 @@ int vcy_smooth_mesh(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const flo
  * normals (0 when none were asked for).  Any output may be NULL. */
 int vcy_last_smooth_ms(const vcy_ctx* ctx, float* build_ms, float* passes_ms, float* normals_ms);
 
+/* ---- mesh decimation: vertex clustering over an indexed mesh, fresh normals ----- */
+/* No reference counterpart: this section is the definition (vertex clustering after Rossignac and Borrel).
+ * vcy_decimate_mesh_host is it in serial host code, tests/decimate_ref.py restates it in numpy, vcy_decimate_mesh runs it on
+ * the device; the three agree bit for bit.
+ *
+ * All arithmetic is float; every difference, product, sum and division is rounded on its own (no FMA), division is
+ * correctly rounded -- the flags the library is built with.
+ *
+ * Cell of a vertex.  Per coordinate c:  t_c = (p_c - origin_c) / cell,  k_c = floor(t_c) as int32 (-0.0 gives 0).  A
+ * non-finite p_c, or |t_c| >= 2^30, makes the call fail.
+ *
+ * Clusters.  Two vertices are in one cluster iff their three k are equal.  Every input vertex is a member, whether or not
+ * a face names it.  Clusters are numbered 0, 1, ... by ascending lowest member index.
+ *
+ * Faces, in ascending input index: every corner is replaced by its cluster number, (a, b, c).  The face is dropped if two
+ * of the three are equal.  Otherwise its canonical form is the rotation of (a, b, c) that puts the smallest number first,
+ * cyclic order kept: (a, b, c), (b, c, a) and (c, a, b) are the same, (a, c, b) is not.  Of the faces with one canonical
+ * form only the lowest input index survives.  Surviving faces keep their input order and their own corner order (they are
+ * not rotated).
+ *
+ * Output vertices: the clusters that at least one surviving face names, in cluster order.  vertex_map[v] is the output
+ * index of v's cluster, or -1; face_source[g] is the input index of output face g; faces_out names output vertices.
+ *
+ * Position of a cluster with members i_0 < i_1 < ... < i_{n-1}:
+ *   FIRST    the bits of p[i_0].
+ *   MEAN     per coordinate S = +0, then S = S + p[i_j]_c for j = 0 .. n-1, then m_c = S / (float)n.
+ *   NEAREST  m as in MEAN;  d(i) = (dx*dx + dy*dy) + dz*dz  with dx = p[i]_x - m_x, likewise dy, dz;  best = i_0; for
+ *            j = 1 .. n-1, i_j replaces best iff d(i_j) < d(best) (strict: a NaN never wins, ties go to the lower index);
+ *            the output is the bits of p[best].
+ *
+ * Normals.  If either normals output is non-NULL, the result is vcy_mesh_normals_host of the output mesh, to the bit.
+ *
+ * Checks, in this order.  VCY_ERR_INVALID_ARG: negative counts; option, n_vertices_out or n_faces_out NULL; with both
+ * counts > 0 any of vertices, faces, vertices_out, faces_out NULL; cell not finite or <= 0; a non-finite origin; mode
+ * outside 0 .. 2.  VCY_ERR_UNSUPPORTED: n_vertices >= 2^31 or 3 * n_faces >= 2^31.  Then n_vertices == 0 or n_faces == 0 is
+ * VCY_OK with both counts 0, no array read and no array written.  Then VCY_ERR_INVALID_ARG for a face index outside
+ * [0, n_vertices) and for a vertex that fails the cell rule.  Whatever is refused, nothing is written, not even the
+ * counts.  Outputs must not overlap inputs or each other; this is not checked. */
+#define VCY_DECIMATE_MEAN 0
+#define VCY_DECIMATE_NEAREST 1
+#define VCY_DECIMATE_FIRST 2
+typedef struct vcy_decimate_option {
+  float   cell;       /* finite, > 0: edge of the clustering cells          */
+  float   origin[3];  /* finite: a corner of the cell lattice               */
+  int32_t mode;       /* 0 MEAN, 1 NEAREST, 2 FIRST                         */
+} vcy_decimate_option;   /* 20 bytes */
+
+int vcy_decimate_mesh_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                           const vcy_decimate_option* option,
+                           float* vertices_out   /* room for 3 * n_vertices */,
+                           int32_t* faces_out    /* room for 3 * n_faces    */,
+                           int64_t* n_vertices_out, int64_t* n_faces_out,
+                           int32_t* vertex_map   /* [n_vertices], may be NULL */,
+                           int32_t* face_source  /* room for n_faces, may be NULL */,
+                           float* vertex_normals_out /* room for 3 * n_vertices, may be NULL */,
+                           float* face_normals_out   /* room for 3 * n_faces, may be NULL */);
+/* The same on the device of `ctx`, on its stream, from and into HOST arrays (as vcy_smooth_mesh).  The context only names
+ * the device and the stream: any context will do, a z-slab included -- a sharded caller decimates the merged mesh on one of
+ * its slabs.  The voxel state, queued views and every cache stay untouched.  Face indices and the cell rule are checked on
+ * the device (flags read at the call's one wait for its launches; the results are copied out behind it, sized by the
+ * counts).  A cluster's sum is serial by definition: a cell that holds more than 256 vertices is summed by one lane of a
+ * workgroup of its own, so cells far larger than the mesh's spacing are correct but slow.  Device memory: 108 bytes per
+ * input vertex and 52 per input face plus the two tables, 8 to 16 bytes per vertex and per face (a closed triangle mesh:
+ * about 250 bytes per vertex), kept by the context (grow-only); the normals of the result use vcy_smooth_mesh's pool. */
+int vcy_decimate_mesh(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                      const vcy_decimate_option* option, float* vertices_out, int32_t* faces_out,
+                      int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map /* may be NULL */,
+                      int32_t* face_source /* may be NULL */, float* vertex_normals_out /* may be NULL */,
+                      float* face_normals_out /* may be NULL */);
+/* Device time of the last vcy_decimate_mesh: clusters (keys, table, numbering, member rows), faces (mapping, duplicate
+ * table, numbering of survivors and of output vertices), emit (positions, faces, maps), normals (0 when none were asked
+ * for).  Any output may be NULL. */
+int vcy_last_decimate_ms(const vcy_ctx* ctx, float* cluster_ms, float* faces_ms, float* emit_ms, float* normals_ms);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and

@@ -117,6 +117,21 @@ class SmoothOption(C.Structure):
     ]
 
 
+VCY_DECIMATE_MEAN, VCY_DECIMATE_NEAREST, VCY_DECIMATE_FIRST = 0, 1, 2
+
+
+class DecimateOption(C.Structure):
+    """vcy_decimate_option: the cell lattice and the representative of vcy_decimate_mesh."""
+    _fields_ = [
+        ("cell", C.c_float),
+        ("origin", C.c_float * 3),
+        ("mode", C.c_int32),
+    ]
+
+    def __init__(self, cell=1.0, origin=(0.0, 0.0, 0.0), mode=0):
+        super().__init__(cell, (C.c_float * 3)(*origin), mode)
+
+
 class Component(C.Structure):
     """vcy_component: one 6-connected component of the solid voxels (vcy_label_components)."""
     _fields_ = [
@@ -221,6 +236,11 @@ def load():
         "vcy_smooth_mesh_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
         "vcy_smooth_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
         "vcy_last_smooth_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float), P(C.c_float)]),
+        "vcy_decimate_mesh_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, P(DecimateOption), vp, vp, P(C.c_int64), P(C.c_int64),
+                                             vp, vp, vp, vp]),
+        "vcy_decimate_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(DecimateOption), vp, vp, P(C.c_int64), P(C.c_int64),
+                                        vp, vp, vp, vp]),
+        "vcy_last_decimate_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_mesh_normals_seam_sum": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import CarverOption, ColorOption, Mesh, SmoothOption, UpdateOption, View, make_view  # noqa: F401
+from .capi import CarverOption, ColorOption, DecimateOption, Mesh, SmoothOption, UpdateOption, View, make_view  # noqa: F401
 
 
 def _p(a):
@@ -184,6 +184,52 @@ def smooth_mesh_host(vertices, faces, iterations, lam, mu, pin_boundary=False, n
         e.rc = rc
         raise e
     return out
+
+
+def _decimate_args(vertices, faces, cell, origin, mode, normals):
+    """The arrays and ctypes arguments vcy_decimate_mesh and vcy_decimate_mesh_host share; the first element keeps every array
+    alive for the call."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    opt = DecimateOption(float(cell), [float(x) for x in origin], int(mode))
+    out = {"vertices": np.zeros((len(v), 3), np.float32), "faces": np.zeros((len(f), 3), np.int32),
+           "vertex_map": np.zeros(len(v), np.int32), "face_source": np.zeros(len(f), np.int32)}
+    if normals:
+        out["normals"] = np.zeros((len(v), 3), np.float32)
+        out["face_normals"] = np.zeros((len(f), 3), np.float32)
+    counts = (C.c_int64(-1), C.c_int64(-1))
+    args = (len(v), len(f), _p(v), _p(f), C.byref(opt), _p(out["vertices"]), _p(out["faces"]), C.byref(counts[0]),
+            C.byref(counts[1]), _p(out["vertex_map"]), _p(out["face_source"]),
+            _p(out["normals"]) if normals else None, _p(out["face_normals"]) if normals else None)
+    return (v, f, opt, counts), args, out
+
+
+def _decimate_result(rc, keep, out):
+    """The outputs cut to the counts the call returned."""
+    if rc != 0:
+        e = RuntimeError(last_error())
+        e.rc = rc
+        raise e
+    nv, nf = keep[3][0].value, keep[3][1].value
+    if len(keep[0]) == 0 or len(keep[1]) == 0:
+        out["vertex_map"][...] = -1      # (an empty call writes no array: no vertex has an output)
+    for key in ("vertices", "normals"):
+        if key in out:
+            out[key] = out[key][:nv]
+    for key in ("faces", "face_source", "face_normals"):
+        if key in out:
+            out[key] = out[key][:nf]
+    return out
+
+
+def decimate_mesh_host(vertices, faces, cell, origin=(0.0, 0.0, 0.0), mode=capi.VCY_DECIMATE_MEAN, normals=False):
+    """vcy_decimate_mesh_host: vertex clustering of an indexed mesh over a lattice of cubes of edge `cell` with a corner at
+    `origin`, serial, no GPU needed (definition: include/vacancy_hip.h, "mesh decimation").  mode: the representative of a
+    cluster, VCY_DECIMATE_MEAN / _NEAREST / _FIRST.  Returns {"vertices", "faces", "vertex_map" (output index of every input
+    vertex, or -1), "face_source" (input index of every output face)} and, with normals=True, "normals" / "face_normals" =
+    mesh_normals_host of the result.  RuntimeError (with .rc) on a refusal."""
+    keep, args, out = _decimate_args(vertices, faces, cell, origin, mode, normals)
+    return _decimate_result(capi.load().vcy_decimate_mesh_host(*args), keep, out)
 
 
 def carve_depth_host(option, views, depths, band, sdf, update_num, z_range=None):
@@ -745,6 +791,21 @@ class VoxelCarver:
         ms = [C.c_float(), C.c_float(), C.c_float()]
         self._lib.vcy_last_smooth_ms(self._ctx, *[C.byref(m) for m in ms])
         out["build_ms"], out["passes_ms"], out["normals_ms"] = (m.value for m in ms)
+        return out
+
+    # -- vertex-clustering decimation of an indexed mesh (no reference counterpart; definition: include/vacancy_hip.h)
+    def DecimateMesh(self, vertices, faces, cell, origin=None, mode=capi.VCY_DECIMATE_MEAN, normals=False):
+        """vcy_decimate_mesh: decimate_mesh_host on this context's device and stream, the same bits.  `origin` defaults to
+        the carver's bb_min, so the cells line up with the voxels.  The context only names the device: its voxel state is
+        not touched, and a z-slab will do.  Returns decimate_mesh_host's dict plus the device times "cluster_ms",
+        "faces_ms", "emit_ms", "normals_ms".  RuntimeError (with .rc) on a refusal."""
+        if origin is None:
+            origin = tuple(self.option.bb_min)
+        keep, args, out = _decimate_args(vertices, faces, cell, origin, mode, normals)
+        out = _decimate_result(self._lib.vcy_decimate_mesh(self._ctx, *args), keep, out)
+        ms = [C.c_float() for _ in range(4)]
+        self._lib.vcy_last_decimate_ms(self._ctx, *[C.byref(m) for m in ms])
+        out["cluster_ms"], out["faces_ms"], out["emit_ms"], out["normals_ms"] = (m.value for m in ms)
         return out
 
     # -- state access

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "face_normal.h"
+#include "mesh_rows.h"
 #include "vcy_internal.h"
 
 namespace vcy {
@@ -60,30 +61,6 @@ __global__ __launch_bounds__(256) void sm_fill_kernel(Table t) {
   if (c >= t.nc) return;
   const int slot = atomicAdd(&t.cursor[t.faces[c]], 1);  // (< off[v + 1]: the row has a slot per corner counted)
   t.corners[slot] = (int)c;
-}
-
-// in place, ascending; one thread, any length
-__device__ void heap_sift(int* a, int i, int n) {
-  for (;;) {
-    const int l = 2 * i + 1;
-    if (l >= n) return;
-    const int r = l + 1;
-    const int m = (r < n && a[r] > a[l]) ? r : l;
-    const int ai = a[i], am = a[m];
-    if (ai >= am) return;
-    a[i] = am;
-    a[m] = ai;
-    i = m;
-  }
-}
-__device__ void heap_sort(int* a, int n) {
-  for (int i = n / 2 - 1; i >= 0; --i) heap_sift(a, i, n);
-  for (int end = n - 1; end > 0; --end) {
-    const int t = a[0];
-    a[0] = a[end];
-    a[end] = t;
-    heap_sift(a, 0, end);
-  }
 }
 
 // the two ids a pass gathers for corner c = 3f + j: faces[3f + (j+1)%3], faces[3f + (j+2)%3]
@@ -274,6 +251,33 @@ namespace {
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// The vertex -> incident-corner table of t.faces: counts, row offsets, rows sorted ascending, gather rows, pinned flags.
+// `total`: one word, `scratch`: the scan's chunk sums, ((n + 1) / 1024 + 64) * 2 words.
+int build_table(hipStream_t s, const sm::Table& t, sm::u64* total, sm::u64* scratch, bool pin) {
+  const size_t n = (size_t)t.n, nc = (size_t)t.nc;
+  const dim3 blk(256), grid_v((unsigned)((n + 255) / 256)), grid_v1((unsigned)((n + 256) / 256)), grid_c((unsigned)((nc + 255) / 256));
+  VCY_HIP_CHECK(hipMemsetAsync(t.deg, 0, 8 * (n + 1), s));
+  if (nc > 0) hipLaunchKernelGGL(sm::sm_count_kernel, grid_c, blk, 0, s, t);
+  VCY_HIP_CHECK(hipGetLastError());
+  { const int rc = device_exclusive_scan_u64(t.deg, (int64_t)n + 1, total, scratch, s); if (rc != VCY_OK) return rc; }
+  hipLaunchKernelGGL(sm::sm_offsets_kernel, grid_v1, blk, 0, s, t);
+  if (nc > 0) hipLaunchKernelGGL(sm::sm_fill_kernel, grid_c, blk, 0, s, t);
+  if (pin) hipLaunchKernelGGL(sm::sm_rows_kernel<true>, grid_v, blk, 0, s, t);
+  else hipLaunchKernelGGL(sm::sm_rows_kernel<false>, grid_v, blk, 0, s, t);
+  VCY_HIP_CHECK(hipGetLastError());
+  return VCY_OK;
+}
+
+// Mesh::CalcNormal of (verts, t.faces) through the table: face normals into fn, vertex normals into vn unless it is null.
+int launch_normals(hipStream_t s, const sm::Table& t, const float* verts, float* fn, float* vn) {
+  const size_t n = (size_t)t.n, nf = (size_t)t.nc / 3;
+  const dim3 blk(256), grid_v((unsigned)((n + 255) / 256)), grid_f((unsigned)((nf + 255) / 256));
+  if (nf > 0) hipLaunchKernelGGL(sm::sm_face_normals_kernel, grid_f, blk, 0, s, (int)nf, t.faces, verts, fn);
+  if (vn) hipLaunchKernelGGL(sm::sm_vertex_normals_kernel, grid_v, blk, 0, s, (int)n, t.off, t.corners, fn, vn);
+  VCY_HIP_CHECK(hipGetLastError());
+  return VCY_OK;
+}
+
 int smooth_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
                   const vcy_smooth_option& o, float* vertices_out, float* vertex_normals_out, float* face_normals_out) {
   VCY_HIP_CHECK(hipSetDevice(c->device));
@@ -325,15 +329,7 @@ int smooth_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, 
 
   // ---- build
   VCY_HIP_CHECK(hipEventRecord(c->ev_sm[0], s));
-  VCY_HIP_CHECK(hipMemsetAsync(t.deg, 0, 8 * (n + 1), s));
-  if (nc > 0) hipLaunchKernelGGL(sm::sm_count_kernel, grid_c, blk, 0, s, t);
-  VCY_HIP_CHECK(hipGetLastError());
-  { const int rc = device_exclusive_scan_u64(t.deg, (int64_t)n + 1, (sm::u64*)(base + at_total), (sm::u64*)(base + at_scan), s); if (rc != VCY_OK) return rc; }
-  hipLaunchKernelGGL(sm::sm_offsets_kernel, grid_v1, blk, 0, s, t);
-  if (nc > 0) hipLaunchKernelGGL(sm::sm_fill_kernel, grid_c, blk, 0, s, t);
-  if (o.pin_boundary) hipLaunchKernelGGL(sm::sm_rows_kernel<true>, grid_v, blk, 0, s, t);
-  else hipLaunchKernelGGL(sm::sm_rows_kernel<false>, grid_v, blk, 0, s, t);
-  VCY_HIP_CHECK(hipGetLastError());
+  { const int rc = build_table(s, t, (sm::u64*)(base + at_total), (sm::u64*)(base + at_scan), o.pin_boundary != 0); if (rc != VCY_OK) return rc; }
 
   // ---- passes: lambda, mu, lambda, mu ... from `src` to `dst` and back; an even number of them ends where it began
   VCY_HIP_CHECK(hipEventRecord(c->ev_sm[1], s));
@@ -355,11 +351,7 @@ int smooth_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, 
   VCY_HIP_CHECK(hipEventRecord(c->ev_sm[2], s));
   float* fn = (float*)(base + at_fn);
   float* vn = (float*)(base + at_vn);
-  if (normals) {
-    if (nf > 0) hipLaunchKernelGGL(sm::sm_face_normals_kernel, grid_f, blk, 0, s, (int)nf, t.faces, p3, fn);
-    if (vertex_normals_out) hipLaunchKernelGGL(sm::sm_vertex_normals_kernel, grid_v, blk, 0, s, (int)n, t.off, t.corners, fn, vn);
-    VCY_HIP_CHECK(hipGetLastError());
-  }
+  if (normals) { const int rc = launch_normals(s, t, p3, fn, vertex_normals_out ? vn : nullptr); if (rc != VCY_OK) return rc; }
   VCY_HIP_CHECK(hipEventRecord(c->ev_sm[3], s));
 
   VCY_HIP_CHECK(hipMemcpyAsync(vertices_out, p3, 12 * n, hipMemcpyDeviceToHost, s));
@@ -372,6 +364,40 @@ int smooth_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, 
 }
 
 }  // namespace
+
+// Mesh::CalcNormal of a mesh that lies in device memory, for the other mesh operators (mesh_decimate.hip): the table and
+// the normals in the smoothing's pool (vcy_ctx::d_sm_buf), launched on the context's stream, not waited for.
+int mesh_normals_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* d_vertices, const int32_t* d_faces, bool vertex_normals,
+                        float** d_face_normals, float** d_vertex_normals) {
+  const size_t n = (size_t)n64, nf = (size_t)nf64, nc = 3 * nf;
+  const size_t scan_words = ((n + 1) / 1024 + 64) * 2;
+  const size_t at_deg = 0;
+  const size_t at_scan = at_deg + align256(8 * (n + 1));
+  const size_t at_total = at_scan + align256(8 * scan_words);
+  const size_t at_off = at_total + 256;
+  const size_t at_cursor = at_off + align256(4 * (n + 1));
+  const size_t at_corners = at_cursor + align256(4 * n);
+  const size_t at_gather = at_corners + align256(4 * nc);
+  const size_t at_pinned = at_gather + align256(8 * nc);
+  const size_t at_fn = at_pinned + align256(n);
+  const size_t at_vn = at_fn + align256(12 * nf);
+  const size_t total = at_vn + align256(12 * n);
+  VCY_HIP_CHECK(c->d_sm_buf.grow(total, c->stream));
+  char* base = (char*)c->d_sm_buf;
+  sm::Table t{};
+  t.n = (int)n, t.nc = (int)nc;
+  t.faces = d_faces;
+  t.deg = (sm::u64*)(base + at_deg);
+  t.off = (int*)(base + at_off);
+  t.cursor = (int*)(base + at_cursor);
+  t.corners = (int*)(base + at_corners);
+  t.gather = (int*)(base + at_gather);
+  t.pinned = (uint8_t*)(base + at_pinned);
+  *d_face_normals = (float*)(base + at_fn);
+  *d_vertex_normals = (float*)(base + at_vn);
+  if (vertex_normals) { const int rc = build_table(c->stream, t, (sm::u64*)(base + at_total), (sm::u64*)(base + at_scan), false); if (rc != VCY_OK) return rc; }
+  return launch_normals(c->stream, t, d_vertices, *d_face_normals, vertex_normals ? *d_vertex_normals : nullptr);
+}
 
 }  // namespace vcy
 

@@ -229,6 +229,11 @@ struct vcy_ctx {
   float last_smooth_ms[3] = {0.0f, 0.0f, 0.0f};
   int smooth_pad = 0;                 // "smoothpad": positions of the passes padded to 16 bytes (one dwordx4 gather) instead of 12 (three dword gathers)
 
+  // mesh decimation (mesh_decimate.hip); grow-only.  The normals of its result use the smoothing's pool (mesh_normals_device).
+  vcy::DeviceBuf<> d_dc_buf;          // the mesh, keys, both tables, flags and their scans, member rows, the outputs
+  vcy::Event ev_dc[6];                // around the cluster, faces, emit launches, and around the normals (vcy_last_decimate_ms)
+  float last_decimate_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
 
@@ -279,6 +284,15 @@ int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* v
 // the argument checks of the two
 int smooth_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
                       const vcy_smooth_option* option, const float* vertices_out);
+// ... and Mesh::CalcNormal of a mesh in device memory through the smoothing's table and normals kernels, in its pool
+// (vcy_ctx::d_sm_buf): launched on the context's stream, not waited for; the two results are device pointers
+int mesh_normals_device(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* d_vertices, const int32_t* d_faces,
+                        bool vertex_normals, float** d_face_normals, float** d_vertex_normals);
+// mesh_decimate.hip: vcy_decimate_mesh, vcy_last_decimate_ms; mesh_decimate_host.hip (host code only):
+// vcy_decimate_mesh_host and the argument checks of the two; what the two share: mesh_decimate.h
+int decimate_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                        const vcy_decimate_option* option, const float* vertices_out, const int32_t* faces_out,
+                        const int64_t* n_vertices_out, const int64_t* n_faces_out);
 // the in-place exclusive scan of mc_kernels.hip for the other compactions of the library; `scratch`: the chunk sums of
 // every level
 int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long long* d_total, unsigned long long* scratch,

@@ -11,6 +11,7 @@
 
 #include "c_abi_structs.h"
 #include "mesh_copy.h"
+#include "mesh_decimate.h"
 #include "mesh_smooth.h"
 
 namespace vacancy {
@@ -408,6 +409,18 @@ bool ShardedVoxelCarver::SmoothMesh(Mesh* mesh, int iterations, float lambda, fl
   return detail::SmoothMeshWith(mesh, iterations, lambda, mu, pin_boundary, with_normals,
                                 [ctx](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_smooth_option* o,
                                       float* out, float* vn, float* fn) { return vcy_smooth_mesh(ctx, nv, nf, v, f, o, out, vn, fn); });
+}
+
+bool ShardedVoxelCarver::DecimateMesh(Mesh* mesh, float cell, int mode, bool with_normals) {
+  if (impl_->slabs.empty() || !mesh) {
+    LOGE("ShardedVoxelCarver::DecimateMesh needs a mesh and an initialized carver\n");
+    return false;
+  }
+  vcy_ctx* ctx = impl_->slabs[0];
+  return detail::DecimateMeshWith(mesh, cell, impl_->option.bb_min, mode, with_normals,
+                                  [ctx](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_decimate_option* o,
+                                        float* vo, int32_t* fo, int64_t* nvo, int64_t* nfo, int32_t* map, int32_t* src, float* vn,
+                                        float* fn) { return vcy_decimate_mesh(ctx, nv, nf, v, f, o, vo, fo, nvo, nfo, map, src, vn, fn); });
 }
 
 bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {

@@ -13,6 +13,7 @@
 #include "vacancy/mesh.h"
 #include "vacancy_hip.h"
 
+#include "mesh_decimate.h"
 #include "mesh_smooth.h"
 
 namespace vacancy {
@@ -74,6 +75,10 @@ void Mesh::CalcNormal() {
 
 bool Mesh::Smooth(int iterations, float lambda, float mu, bool pin_boundary) {
   return detail::SmoothMeshWith(this, iterations, lambda, mu, pin_boundary, false, &vcy_smooth_mesh_host);
+}
+
+bool Mesh::Decimate(float cell, int mode) {
+  return detail::DecimateMeshWith(this, cell, Eigen::Vector3f(0.0f, 0.0f, 0.0f), mode, false, &vcy_decimate_mesh_host);
 }
 
 // ---- PLY --------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 
 #include "c_abi_structs.h"
 #include "mesh_copy.h"
+#include "mesh_decimate.h"
 #include "mesh_smooth.h"
 
 namespace vacancy {
@@ -534,6 +535,28 @@ bool VoxelCarver::SmoothMesh(Mesh* mesh, int iterations, float lambda, float mu,
 std::array<float, 3> VoxelCarver::last_smooth_ms() const {
   std::array<float, 3> ms = {{0.0f, 0.0f, 0.0f}};
   if (impl_->ctx) vcy_last_smooth_ms(impl_->ctx, &ms[0], &ms[1], &ms[2]);
+  return ms;
+}
+
+bool VoxelCarver::DecimateMesh(Mesh* mesh, float cell, int mode, bool with_normals) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (!mesh) {
+    LOGE("VoxelCarver::DecimateMesh needs a mesh\n");
+    return false;
+  }
+  vcy_ctx* ctx = impl_->ctx;
+  return detail::DecimateMeshWith(mesh, cell, impl_->option.bb_min, mode, with_normals,
+                                  [ctx](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_decimate_option* o,
+                                        float* vo, int32_t* fo, int64_t* nvo, int64_t* nfo, int32_t* map, int32_t* src, float* vn,
+                                        float* fn) { return vcy_decimate_mesh(ctx, nv, nf, v, f, o, vo, fo, nvo, nfo, map, src, vn, fn); });
+}
+
+std::array<float, 4> VoxelCarver::last_decimate_ms() const {
+  std::array<float, 4> ms = {{0.0f, 0.0f, 0.0f, 0.0f}};
+  if (impl_->ctx) vcy_last_decimate_ms(impl_->ctx, &ms[0], &ms[1], &ms[2], &ms[3]);
   return ms;
 }
 

@@ -220,6 +220,14 @@ class ShardedVoxelCarver:
         """VoxelCarver.SmoothMesh on the first slab's context: the same dict."""
         return self.slabs[0].SmoothMesh(vertices, faces, iterations, lam, mu, pin_boundary, normals)
 
+    # -- vertex-clustering decimation of the MERGED mesh (include/vacancy_hip.h, "mesh decimation"): as SmoothMesh, on the
+    # first slab's context
+    def DecimateMesh(self, vertices, faces, cell, origin=None, mode=0, normals=False):
+        """VoxelCarver.DecimateMesh on the first slab's context: the same dict.  `origin` defaults to the grid's bb_min."""
+        if origin is None:
+            origin = tuple(self.option.bb_min)
+        return self.slabs[0].DecimateMesh(vertices, faces, cell, origin, mode, normals)
+
     def last_stream_ms(self):
         """[(producer ms, carve ms, wall ms)] per slab of the last CarveBatchSilhouettes."""
         return [c.last_stream_ms() for c in self.slabs]
