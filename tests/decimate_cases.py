@@ -16,7 +16,7 @@ SMOOTH_NAMES = ("octahedron", "mc_sphere", "two_components", "open_patch", "fan3
                 "257_vertices")
 # no vertex without a face, no repeated or degenerate face: cell 0.001 returns these unchanged
 CLEAN = ("octahedron", "mc_sphere", "two_components", "open_patch", "fan300", "257_vertices", "mc_sphere_40", "crowd",
-         "two_sheets_opposite")
+         "two_sheets_opposite", "row_tiers")
 
 memo = SC.memo
 bits = SC.bits
@@ -33,6 +33,27 @@ def crowd():
     ring = np.stack([2.05 + 6.0 * np.cos(a), 2.05 + 6.0 * np.sin(a), 2.05 + 0.0 * a], axis=-1).astype(F)
     f = np.array([[i, 700 + i % 16, 700 + (i + 1) % 16] for i in range(700)], np.int32)
     return np.concatenate([inner, ring]), f[rng.permutation(700)]
+
+
+TIER_SIZES = (1, 16, 17, 48, 49, 256, 257)
+
+
+def row_tiers():
+    """Clusters of exactly 1, 16, 17, 48, 49, 256 and 257 members at cell 2.0, one cell each, stacked along z below a ring
+    whose vertices have a cell each; every point in a face with two ring vertices: member rows at both edges of the
+    two in-register sorts and of the row that gets a workgroup of its own."""
+    rng = np.random.RandomState(12)
+    groups = [np.array([1.8, 1.8, -12.2 + 2.0 * k], F) + (0.5 * rng.rand(m, 3)).astype(F) for k, m in enumerate(TIER_SIZES)]
+    inner = np.concatenate(groups).astype(F)
+    n = len(inner)
+    a = 2.0 * np.pi * np.arange(16) / 16.0
+    ring = np.stack([2.05 + 6.0 * np.cos(a), 2.05 + 6.0 * np.sin(a), 2.05 + 0.0 * a], axis=-1).astype(F)
+    order = rng.permutation(n)                   # (a cell's members are not neighbours in the vertex array either)
+    f = np.array([[i, n + i % 16, n + (i + 1) % 16] for i in range(n)], np.int32)
+    rank = np.empty(n, np.int32)
+    rank[order] = np.arange(n, dtype=np.int32)
+    f[:, 0] = rank[f[:, 0]]
+    return np.concatenate([inner[order], ring]), f[rng.permutation(n)]
 
 
 def two_sheets(opposite):
@@ -75,7 +96,7 @@ def mc_sphere_40():
     return m["vertices"].astype(F), m["faces"].astype(np.int32)
 
 
-OWN = {"crowd": crowd, "two_sheets_same": lambda: two_sheets(False), "two_sheets_opposite": lambda: two_sheets(True),
+OWN = {"crowd": crowd, "row_tiers": row_tiers, "two_sheets_same": lambda: two_sheets(False), "two_sheets_opposite": lambda: two_sheets(True),
        "rotations": rotations, "boundary": boundary, "mc_sphere_40": mc_sphere_40}
 CASE_NAMES = SMOOTH_NAMES + tuple(OWN)
 
@@ -124,6 +145,9 @@ def check_case(name, v, f):
         for cell in CELLS[1:]:
             r = ref(cell)
             assert r["members"].max() >= 700 and (len(r["faces"]) >= 1 or cell == 1000.0), cell
+    elif name == "row_tiers":
+        sizes = sorted(ref(2.0)["members"])
+        assert sizes == sorted(TIER_SIZES + (1,) * 16), sizes              # (the ring: sixteen cells of one vertex)
     elif name == "two_sheets_same":
         r = ref(2.0)
         assert 0 < len(r["faces"]) < r["n_noncollapsed"]

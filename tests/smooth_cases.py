@@ -75,6 +75,29 @@ def fan300():
     return v, f[rng.permutation(300)]            # (the hub's row is not in rim order)
 
 
+FAN_SIZES = (11, 12, 13, 14)
+
+
+def fans_11_14():
+    """Four closed fans whose hubs have 11, 12, 13 and 14 faces: rows on both sides of the 12 corners a row is sorted with
+    in registers, and the lengths next to them."""
+    rng = np.random.RandomState(10)
+    verts, faces, hubs = [], [], []
+    for i, k in enumerate(FAN_SIZES):
+        hub = len(verts)
+        hubs.append(hub)
+        a = 2.0 * np.pi * np.arange(k) / k
+        verts += [[4.0 * i + 0.03, -0.02, 1.0]] + [[4.0 * i + np.cos(t), np.sin(t), 0.2 * rng.rand()] for t in a]
+        faces += [[hub, hub + 1 + j, hub + 1 + (j + 1) % k] for j in range(k)]
+    f = np.array(faces, np.int32)[rng.permutation(len(faces))]
+    off, corners = SR.rows(len(verts), f)
+    assert tuple(off[h + 1] - off[h] for h in hubs) == FAN_SIZES       # corner counts of 12 and 13 occur
+    for h in hubs:                                                     # no hub's faces walk its rim in order
+        rim = f[(f == h).any(axis=1), 1]
+        assert not np.array_equal(np.sort(rim), rim), h
+    return np.array(verts, F), f
+
+
 def degenerate():
     """Faces that name a vertex twice and three times, one face present twice, a non-manifold edge with three faces."""
     rng = np.random.RandomState(7)
@@ -111,7 +134,7 @@ def strip_257():
 
 MAKERS = {"octahedron": octahedron, "mc_sphere": mc_sphere, "two_components": two_components, "open_patch": open_patch,
           "fan300": fan300, "degenerate": degenerate, "isolated": isolated, "one_vertex": one_vertex,
-          "257_vertices": strip_257}
+          "257_vertices": strip_257, "fans_11_14": fans_11_14}
 CASE_NAMES = tuple(MAKERS)
 
 

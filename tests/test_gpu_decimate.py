@@ -193,7 +193,7 @@ def test_smooth_then_decimate_equals_the_host_functions_composed():
     dev = TR.make_dev(opt)
     sm = dev.SmoothMesh(mesh["vertices"], mesh["faces"], 3)
     got = dev.DecimateMesh(sm["vertices"], mesh["faces"], 2.5, mode=DR.MEAN, normals=True)
-    again = dev.SmoothMesh(mesh["vertices"], mesh["faces"], 3)             # the two operators share the normals' pool
+    again = dev.SmoothMesh(mesh["vertices"], mesh["faces"], 3)             # a decimation between two smoothings disturbs neither
     hs = vc.smooth_mesh_host(mesh["vertices"], mesh["faces"], 3, 0.5, -0.53)
     want = vc.decimate_mesh_host(hs["vertices"], mesh["faces"], 2.5, tuple(opt.bb_min), DR.MEAN, normals=True)
     assert_same(got, want, "smooth then decimate")

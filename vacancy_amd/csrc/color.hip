@@ -259,7 +259,12 @@ void fill_view(const vcy_view& v, View* r) {
 
 namespace {
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+// where the images of one view lie among those of its chunk: the photograph as given, RGBX, the depth image when the
+// caller uploads one (the sizing of the pool and the chunk's copies both walk the views through this)
+struct ImageSlots { size_t raw, rgbx, depth; };
+ImageSlots take_images(PoolLayout& at, size_t px, bool with_depth) {
+  return ImageSlots{at.take(3 * px), at.take(4 * px), with_depth ? at.take(4 * px) : 0};
+}
 
 // the checks the two entry points share; depth_required: the host function's
 int check_args(const char* who, int64_t n_vertices, const float* vertices, const float* normals, int n_views,
@@ -343,23 +348,18 @@ int color_device(vcy_ctx* c, double iso, int64_t n, const float* vertices, const
 
   // [view records | pack jobs | vertices | normals | rgb | n_used | best_view | carry | per view of the largest chunk:
   //  photograph as given, RGBX, depth (when uploaded)]: sized once, so that what the first part holds outlives the chunks
-  const size_t at_views = 0;
-  const size_t at_jobs = at_views + align256(sizeof(cl::View) * cl::kMaxViewsPerLaunch);
-  const size_t at_vtx = at_jobs + align256(sizeof(cl::PackJob) * cl::kMaxViewsPerLaunch);
-  const size_t at_nrm = at_vtx + align256(sizeof(float) * 3 * (size_t)n);
-  const size_t at_rgb = at_nrm + (with_normals ? align256(sizeof(float) * 3 * (size_t)n) : 0);
-  const size_t at_used = at_rgb + align256(sizeof(float) * 3 * (size_t)n);
-  const size_t at_best = at_used + align256(sizeof(int32_t) * (size_t)n);
-  const size_t at_carry = at_best + align256(sizeof(int32_t) * (size_t)n);
-  const size_t at_images = at_carry + (n_chunks > 1 ? align256(sizeof(float) * cl::kCarryWords * (size_t)n) : 0);
+  PoolLayout at;
+  const size_t at_views = at.take(sizeof(cl::View) * cl::kMaxViewsPerLaunch),
+               at_jobs = at.take(sizeof(cl::PackJob) * cl::kMaxViewsPerLaunch), at_vtx = at.take(sizeof(float) * 3 * (size_t)n),
+               at_nrm = at.take(with_normals ? sizeof(float) * 3 * (size_t)n : 0), at_rgb = at.take(sizeof(float) * 3 * (size_t)n),
+               at_used = at.take(sizeof(int32_t) * (size_t)n), at_best = at.take(sizeof(int32_t) * (size_t)n),
+               at_carry = at.take(n_chunks > 1 ? sizeof(float) * cl::kCarryWords * (size_t)n : 0), at_images = at.total();
   size_t image_bytes = 0;
   for (int first = 0; first < n_views; first += cl::kMaxViewsPerLaunch) {
-    size_t b = 0;
-    for (int i = first; i < std::min(n_views, first + cl::kMaxViewsPerLaunch); ++i) {
-      const size_t px = (size_t)views[i].width * (size_t)views[i].height;
-      b += align256(3 * px) + align256(4 * px) + (depth ? align256(4 * px) : 0);
-    }
-    image_bytes = std::max(image_bytes, b);
+    PoolLayout images;
+    for (int i = first; i < std::min(n_views, first + cl::kMaxViewsPerLaunch); ++i)
+      (void)take_images(images, (size_t)views[i].width * (size_t)views[i].height, depth != nullptr);
+    image_bytes = std::max(image_bytes, images.total());
   }
   VCY_HIP_CHECK(c->d_cl_buf.grow(at_images + image_bytes, c->stream, false));
   char* base = (char*)c->d_cl_buf;
@@ -397,20 +397,19 @@ int color_device(vcy_ctx* c, double iso, int64_t n, const float* vertices, const
       if (rc != VCY_OK) return rc;
       render_ms += c->last_render_device_ms;
     }
-    size_t at = at_images;
+    PoolLayout images;
+    char* image_base = base + at_images;
     int64_t px_max = 0;
     for (int i = 0; i < m; ++i) {
       const vcy_view& v = views[first + i];
       const size_t px = (size_t)v.width * (size_t)v.height;
       cl::fill_view(v, &rec[(size_t)i]);
-      uint8_t* raw = (uint8_t*)(base + at);
-      at += align256(3 * px);
-      uint32_t* rgbx = (uint32_t*)(base + at);
-      at += align256(4 * px);
+      const ImageSlots slots = take_images(images, px, depth != nullptr);
+      uint8_t* raw = (uint8_t*)(image_base + slots.raw);
+      uint32_t* rgbx = (uint32_t*)(image_base + slots.rgbx);
       VCY_HIP_CHECK(hipMemcpyAsync(raw, photos[first + i], 3 * px, hipMemcpyHostToDevice, c->stream));
       if (depth) {
-        float* d = (float*)(base + at);
-        at += align256(4 * px);
+        float* d = (float*)(image_base + slots.depth);
         VCY_HIP_CHECK(hipMemcpyAsync(d, depth[first + i], 4 * px, hipMemcpyHostToDevice, c->stream));
         depth_dev[(size_t)i] = d;
       }

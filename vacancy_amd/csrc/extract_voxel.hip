@@ -91,9 +91,6 @@ __global__ __launch_bounds__(256) void xv_compact_kernel(const u64* __restrict__
 
 }  // namespace
 
-int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long long* d_total,
-                              unsigned long long* scratch, hipStream_t stream);  // mc_kernels.hip
-
 }  // namespace vcy
 
 // Kept voxel ids on the host: page-locked memory from the mesh pool (mesh_host_alloc) -- the copy from the device runs at
@@ -134,10 +131,9 @@ static int kept_voxel_ids(vcy_ctx* c, int inside_empty, HostIds* out_ids) {
   // ---- device: keep bits -> block counts -> scan -> kept voxel ids ---------------------------------
   if (!c->fresh) {  // a fresh grid is untouched everywhere: nothing is kept under either predicate
     const int64_t nblocks = (n + 255) / 256;
-    auto align = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t sz_bits = align(sizeof(u64) * (size_t)nblocks * 4);
-    const size_t sz_counts = align(sizeof(u64) * ((size_t)nblocks + 1));
-    const size_t sz_scan = align(sizeof(u64) * ((size_t)nblocks / 1024 + 64) * 2);
+    const size_t sz_bits = align256(sizeof(u64) * (size_t)nblocks * 4);
+    const size_t sz_counts = align256(sizeof(u64) * ((size_t)nblocks + 1));
+    const size_t sz_scan = align256(sizeof(u64) * scan_scratch_words((size_t)nblocks));
     // (grow-only device scratch kept by the context, an eighth of headroom whenever it has to grow: an extraction per
     // view allocated and freed twice per call)
     {

@@ -1,5 +1,5 @@
 // Mesh::CalcFaceNormal on the device, shared by the normals of the extraction chain (mc_normals.hip) and the normals of a
-// general indexed mesh (mesh_smooth.hip).  Arithmetic: include/vacancy/linalg.h's, i.e. squaredNorm = x*x + (y*y + z*z),
+// general indexed mesh (mesh_normals.hip).  Arithmetic: include/vacancy/linalg.h's, i.e. squaredNorm = x*x + (y*y + z*z),
 // normalized() = n2 > 0 ? v / sqrt(n2) : v, true division per component; no contraction, correctly rounded sqrt and
 // division, denormals kept (Makefile).  The host's statement of the same is mesh_host.hip's.
 #pragma once
@@ -30,6 +30,18 @@ __device__ __forceinline__ void face_normal(const float p0[3], const float p1[3]
   fn[1] = v1[2] * v2[0] - v1[0] * v2[2];
   fn[2] = v1[0] * v2[1] - v1[1] * v2[0];
   normalize3(fn);
+}
+
+// ... of the face (i0, i1, i2) of an indexed mesh: nine position loads, then the above
+__device__ __forceinline__ void face_normal_of(const float* verts, int i0, int i1, int i2, float fn[3]) {
+  float q[3][3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    q[0][k] = verts[3 * (int64_t)i0 + k];
+    q[1][k] = verts[3 * (int64_t)i1 + k];
+    q[2][k] = verts[3 * (int64_t)i2 + k];
+  }
+  face_normal(q[0], q[1], q[2], fn);
 }
 
 }  // namespace mc

@@ -18,7 +18,6 @@ using namespace mc;
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 int64_t with_headroom(int64_t v) { return v + v / 4 + 4096; }  // the next view's mesh is a little different
 double now_us() {
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -170,7 +169,7 @@ struct Extraction {
     const size_t sz_act = align256(sizeof(u64) * (size_t)p.nwords);
     const size_t sz_woff = align256(sizeof(uint32_t) * (size_t)p.nwords);
     const size_t sz_counts = align256(sizeof(u64) * ((size_t)nblocks + 1));
-    const size_t sz_scan = align256(sizeof(u64) * ((size_t)nblocks / 1024 + 64) * 2);
+    const size_t sz_scan = align256(sizeof(u64) * scan_scratch_words((size_t)nblocks));
     const size_t sz_ghost = sweep ? align256(sizeof(u64) * 3 * (size_t)c->ny * p.Wr) : 0;  // IN / OK / TC of one slice
     const size_t need = (sweep ? 1 : 3) * sz_plane + sz_ghost + sz_act + sz_woff + sz_counts + sz_scan + 256;
     VCY_HIP_CHECK(c->d_mc_scratch.grow(need, s));
@@ -219,7 +218,7 @@ struct Extraction {
     const size_t sz_info = align256(sizeof(uint32_t) * (size_t)cap_cells);
     const size_t sz_nact = align256(sizeof(uint16_t) * (size_t)cap_cells);
     const size_t sz_cc = align256(sizeof(u64) * ((size_t)chain.cell_blocks + 1));
-    const size_t sz_cs = align256(sizeof(u64) * ((size_t)chain.cell_blocks / 1024 + 64) * 2);
+    const size_t sz_cs = align256(sizeof(u64) * scan_scratch_words((size_t)chain.cell_blocks));
     const size_t need = sz_list + sz_info + sz_nact + sz_cc + sz_cs + 256;
     VCY_HIP_CHECK(c->d_mc_cells.grow(need, s));
     char* b = (char*)c->d_mc_cells;

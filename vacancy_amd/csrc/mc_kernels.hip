@@ -1218,11 +1218,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VCY_EMIT_WA
 
 }  // namespace
 
-// the same scan for the other compactions of the library (extract_voxel.hip)
+// the same scan for the other compactions of the library (extract_voxel.hip, the mesh operators)
 int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long long* d_total,
                               unsigned long long* scratch, hipStream_t stream) {
   return exclusive_scan_u64(d, n, d_total, scratch, stream);
 }
+size_t scan_scratch_words(size_t n) { return (n / 1024 + 64) * 2; }  // (the chunk sums of every level, generously)
 
 // ---- launches (declared in mc_common.h; the host driver: mc_extract.hip) ---------------------------------
 

@@ -95,7 +95,7 @@ __device__ __forceinline__ void edge_position(const McParams& p, const u64* __re
   vertex_interp(p.iso, pa, pb, corner_value(p, s, ca), corner_value(p, s, cb), p.linear != 0, out);
 }
 
-// normalize3, face_normal: face_normal.h
+// normalize3, face_normal, face_normal_of: face_normal.h
 
 // the counts of the chain, and whether mc_emit has written a mesh at all (it has not when a capacity was too small:
 // the host then runs the chain again with room, and these kernels with it)
@@ -115,16 +115,8 @@ __global__ __launch_bounds__(256) void mc_face_normals_kernel(NormalsLaunch a) {
   if (f >= nf) return;
   const int i0 = a.faces[3 * f + 0], i1 = a.faces[3 * f + 1], i2 = a.faces[3 * f + 2];
   float fn[3] = {0.0f, 0.0f, 0.0f};
-  float q[3][3];
-  if ((int64_t)(unsigned)i0 < nv && (int64_t)(unsigned)i1 < nv && (int64_t)(unsigned)i2 < nv) {  // (always, for a mesh of mc_emit)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      q[0][k] = a.verts[3 * (int64_t)i0 + k];
-      q[1][k] = a.verts[3 * (int64_t)i1 + k];
-      q[2][k] = a.verts[3 * (int64_t)i2 + k];
-    }
-    face_normal(q[0], q[1], q[2], fn);
-  }
+  if ((int64_t)(unsigned)i0 < nv && (int64_t)(unsigned)i1 < nv && (int64_t)(unsigned)i2 < nv)  // (always, for a mesh of mc_emit)
+    face_normal_of(a.verts, i0, i1, i2, fn);
   a.face_normals[3 * f + 0] = fn[0];
   a.face_normals[3 * f + 1] = fn[1];
   a.face_normals[3 * f + 2] = fn[2];

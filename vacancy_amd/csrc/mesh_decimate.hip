@@ -9,11 +9,11 @@
 //            the answer does not depend on who is there at the moment --; a match ends in atomicMin of the lane's index, a
 //            mismatch moves to the next slot), dc_vflag (a vertex is a representative iff its slot holds its own index),
 //            the exclusive scan of mc_kernels.hip over the flags (cluster numbers by ascending lowest member),
-//            dc_vcluster (cluster of every vertex; for MEAN and NEAREST an integer atomicAdd counts the members), scan,
-//            dc_fill (slots of the member rows through an atomic cursor, in arbitrary order), dc_rows (one lane per
-//            cluster sorts its row ascending -- the order of the definition's sum whatever order the atomics ran in --,
-//            in registers up to 48 members, in global memory up to 256 --, then the sum in registers, the mean, the nearest
-//            member; a row of more than 256 members goes on a list),
+//            dc_vcluster (cluster of every vertex; for MEAN and NEAREST an integer atomicAdd counts the members: the
+//            count of mesh_rows.h's row table of the vertices by cluster, whose scan, offsets and fill follow), dc_rows
+//            (one lane per cluster sorts its row ascending -- the order of the definition's sum whatever order the
+//            atomics ran in --, in registers up to 48 members, in global memory up to 256 --, then the sum in registers,
+//            the mean, the nearest member; a row of more than 256 members goes on a list),
 //            dc_long_rows (one workgroup per listed row: see there).  FIRST needs no rows.
 //   faces    dc_fmap (one lane per face: index check, corners -> clusters, collapsed faces flagged, the canonical triple),
 //            dc_finsert (the same table trick, a slot holds a face index, canonical triples compared), dc_fflag (a face
@@ -21,13 +21,11 @@
 //            (output faces, output vertices).
 //   emit     dc_emit_v (vertex_map, positions), dc_emit_f (faces, face_source).
 // Then the one wait for these launches: the host reads the three flags and the three counts.  Behind it the normals of the
-// output mesh, still in device memory, through the smoothing's table and normals kernels (mesh_normals_device), and the
+// output mesh, still in device memory (mesh_normals.hip's mesh_normals_device), and the
 // copies into the caller's arrays, sized by the counts; a refused call copies nothing.
 // Integer atomics only; no float atomics anywhere.  Every probe loop is bounded by the table size and raises a flag if it
 // runs out.  Both tables are cleared on the stream at the start of every call.
 #include <algorithm>
-#include <climits>
-#include <cstring>
 
 #include "mesh_decimate.h"
 #include "mesh_rows.h"
@@ -136,41 +134,6 @@ __global__ __launch_bounds__(256) void dc_vcluster_kernel(Dec d) {
   if (ROWS) atomicAdd(&d.deg[cl], 1ull);
 }
 
-__global__ __launch_bounds__(256) void dc_offsets_kernel(Dec d) {
-  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (v > d.n) return;
-  const int o = (int)d.deg[v];
-  d.off[v] = o;
-  if (v < d.n) d.cursor[v] = o;
-}
-
-__global__ __launch_bounds__(256) void dc_fill_kernel(Dec d) {
-  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (v >= d.n) return;
-  const int slot = atomicAdd(&d.cursor[d.cluster[v]], 1);  // (< off[cluster + 1]: the row has a slot per member counted)
-  d.member[slot] = (int)v;
-}
-
-// a row of up to K ids, ascending, in registers: odd-even transposition sort, K rounds, every index static
-template <int K>
-__device__ __forceinline__ void sort_in_registers(int* row, int len) {
-  int r[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) r[k] = k < len ? row[k] : INT_MAX;
-#pragma unroll
-  for (int round = 0; round < K; ++round) {
-#pragma unroll
-    for (int i = round & 1; i + 1 < K; i += 2) {
-      const int lo = min(r[i], r[i + 1]), hi = max(r[i], r[i + 1]);
-      r[i] = lo;
-      r[i + 1] = hi;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-    if (k < len) row[k] = r[k];
-}
-
 template <bool NEAREST>
 __global__ __launch_bounds__(256) void dc_rows_kernel(Dec d) {
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -183,9 +146,7 @@ __global__ __launch_bounds__(256) void dc_rows_kernel(Dec d) {
     if (w < d.long_cap) d.longlist[w] = (int)c;
     return;
   }
-  if (len <= kShortRow) sort_in_registers<kShortRow>(row, len);
-  else if (len <= kMidRow) sort_in_registers<kMidRow>(row, len);
-  else sm::heap_sort(row, len);  // up to kLongRow members: sorted in place in global memory by this thread
+  rows::sort_row<kShortRow, kMidRow>(row, len);  // (beyond kMidRow, up to kLongRow members: in place in global memory)
   float m[3];
   row_mean(d.pos, row, len, m);
   if (NEAREST) {
@@ -342,8 +303,6 @@ __global__ __launch_bounds__(256) void dc_emit_f_kernel(Dec d) {
 
 namespace {
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // slots of an open-addressing table for n entries: a power of two >= 2 n, so a load of at most 1/2
 size_t table_slots(size_t n) {
   size_t s = 1024;
@@ -370,20 +329,15 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
   // [report | faces | positions | keys | vslot | vtable | vflag | cluster | rep | deg | off | cursor | member | cpos | fcanon |
   //  fslot | ftable | fflag | used | scan scratch | the four outputs]: 108 bytes and 8 to 16 of table per vertex, 52 and 8 to
   //  16 per face
-  size_t at = 0;
-  const auto take = [&at](size_t bytes) {
-    const size_t here = at;
-    at += align256(bytes);
-    return here;
-  };
-  const size_t at_report = take(sizeof(Report)), at_faces = take(4 * nc), at_pos = take(12 * n), at_key = take(12 * n),
-               at_vslot = take(4 * n), at_vtable = take(4 * vslots), at_vflag = take(8 * (n + 1)), at_cluster = take(4 * n),
-               at_rep = take(4 * n), at_deg = take(8 * (n + 1)), at_off = take(4 * (n + 1)), at_cursor = take(4 * n),
-               at_member = take(4 * n), at_cpos = take(12 * n), at_long = take(4 * (n / dc::kLongRow + 1)), at_fcanon = take(4 * nc), at_fslot = take(4 * nf),
-               at_ftable = take(4 * fslots), at_fflag = take(8 * (nf + 1)), at_used = take(8 * (n + 1)),
-               at_scan = take(8 * ((std::max(n, nf) + 1) / 1024 + 64) * 2), at_pos_out = take(12 * n),
-               at_faces_out = take(4 * nc), at_vmap = take(4 * n), at_fsrc = take(4 * nf);
-  VCY_HIP_CHECK(c->d_dc_buf.grow(at, c->stream));
+  PoolLayout at;
+  const size_t at_report = at.take(sizeof(Report)), at_faces = at.take(4 * nc), at_pos = at.take(12 * n), at_key = at.take(12 * n),
+               at_vslot = at.take(4 * n), at_vtable = at.take(4 * vslots), at_vflag = at.take(8 * (n + 1)), at_cluster = at.take(4 * n),
+               at_rep = at.take(4 * n), at_deg = at.take(8 * (n + 1)), at_off = at.take(4 * (n + 1)), at_cursor = at.take(4 * n),
+               at_member = at.take(4 * n), at_cpos = at.take(12 * n), at_long = at.take(4 * (n / dc::kLongRow + 1)), at_fcanon = at.take(4 * nc), at_fslot = at.take(4 * nf),
+               at_ftable = at.take(4 * fslots), at_fflag = at.take(8 * (nf + 1)), at_used = at.take(8 * (n + 1)),
+               at_scan = at.take(8 * scan_scratch_words(std::max(n, nf) + 1)), at_pos_out = at.take(12 * n),
+               at_faces_out = at.take(4 * nc), at_vmap = at.take(4 * n), at_fsrc = at.take(4 * nf);
+  VCY_HIP_CHECK(c->d_dc_buf.grow(at.total(), c->stream));
   char* base = (char*)c->d_dc_buf;
   hipStream_t s = c->stream;
   Report* d_report = (Report*)(base + at_report);
@@ -427,9 +381,8 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
   if (rows) {
     hipLaunchKernelGGL(dc::dc_vcluster_kernel<true>, grid_v, blk, 0, s, d);
     VCY_HIP_CHECK(hipGetLastError());
-    { const int rc = device_exclusive_scan_u64(d.deg, (int64_t)n + 1, d_report->totals + 3, scan, s); if (rc != VCY_OK) return rc; }
-    hipLaunchKernelGGL(dc::dc_offsets_kernel, grid_v1, blk, 0, s, d);
-    hipLaunchKernelGGL(dc::dc_fill_kernel, grid_v, blk, 0, s, d);
+    const rows::Table members{d.n, d.n, d.cluster, d.deg, d.off, d.cursor, d.member};  // (counted by dc_vcluster)
+    { const int rc = rows::fill(s, members, d_report->totals + 3, scan, true); if (rc != VCY_OK) return rc; }
     const dim3 grid_long((unsigned)std::min<size_t>(n / dc::kLongRow + 1, 1024));  // (workgroups loop over the list)
     if (o.mode == VCY_DECIMATE_NEAREST) {
       hipLaunchKernelGGL(dc::dc_rows_kernel<true>, grid_v, blk, 0, s, d);

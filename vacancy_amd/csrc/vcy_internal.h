@@ -229,7 +229,10 @@ struct vcy_ctx {
   float last_smooth_ms[3] = {0.0f, 0.0f, 0.0f};
   int smooth_pad = 0;                 // "smoothpad": positions of the passes padded to 16 bytes (one dwordx4 gather) instead of 12 (three dword gathers)
 
-  // mesh decimation (mesh_decimate.hip); grow-only.  The normals of its result use the smoothing's pool (mesh_normals_device).
+  // normals of an indexed mesh in device memory (mesh_normals.hip): its incidence table and the normals; grow-only
+  vcy::DeviceBuf<> d_mn_buf;
+
+  // mesh decimation (mesh_decimate.hip); grow-only
   vcy::DeviceBuf<> d_dc_buf;          // the mesh, keys, both tables, flags and their scans, member rows, the outputs
   vcy::Event ev_dc[6];                // around the cluster, faces, emit launches, and around the normals (vcy_last_decimate_ms)
   float last_decimate_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -284,8 +287,12 @@ int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* v
 // the argument checks of the two
 int smooth_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
                       const vcy_smooth_option* option, const float* vertices_out);
-// ... and Mesh::CalcNormal of a mesh in device memory through the smoothing's table and normals kernels, in its pool
-// (vcy_ctx::d_sm_buf): launched on the context's stream, not waited for; the two results are device pointers
+// mesh_normals.hip: Mesh::CalcNormal of a mesh in device memory for the mesh operators, launched, not waited for: the two
+// kernels through a vertex -> incident-corner table the caller has built (mesh_rows.h; rows sorted ascending) ...
+int launch_mesh_normals(hipStream_t stream, int64_t n_vertices, int64_t n_faces, const float* d_vertices, const int32_t* d_faces,
+                        const int* d_row_offsets, const int* d_rows, float* d_face_normals, float* d_vertex_normals);
+// ... and with a table built for the purpose in a pool of its own (vcy_ctx::d_mn_buf), on the context's stream; the two
+// results are device pointers into that pool
 int mesh_normals_device(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* d_vertices, const int32_t* d_faces,
                         bool vertex_normals, float** d_face_normals, float** d_vertex_normals);
 // mesh_decimate.hip: vcy_decimate_mesh, vcy_last_decimate_ms; mesh_decimate_host.hip (host code only):
@@ -294,9 +301,10 @@ int decimate_check_args(const char* who, int64_t n_vertices, int64_t n_faces, co
                         const vcy_decimate_option* option, const float* vertices_out, const int32_t* faces_out,
                         const int64_t* n_vertices_out, const int64_t* n_faces_out);
 // the in-place exclusive scan of mc_kernels.hip for the other compactions of the library; `scratch`: the chunk sums of
-// every level
+// every level, scan_scratch_words(n) words
 int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long long* d_total, unsigned long long* scratch,
                               hipStream_t stream);
+size_t scan_scratch_words(size_t n);
 // carve_robust.hip: vcy_carve_robust_device, vcy_carve_robust_silhouettes, vcy_last_robust_ms
 // carve_depth.hip: vcy_carve_depth_device, vcy_carve_depth, vcy_last_depth_ms; carve_depth_host.hip (host code only):
 // vcy_carve_depth_host; what the two share: depth_sample.h

@@ -2,6 +2,7 @@
 // streams.  All are move-only, empty when default-constructed, and release what they hold in their destructor -- a
 // resource of the context (vcy_ctx) is a member of one of these types, a temporary of a function a local of one, and
 // nothing is freed by name.  Every operation answers with the runtime's own error code; callers check it.
+// Next to them PoolLayout, which places the arrays of one pooled buffer.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -77,6 +78,19 @@ template <class T = void>
 using DeviceBuf = Buffer<T, DeviceMemory>;
 template <class T = void, unsigned Flags = hipHostMallocDefault>
 using PinnedBuf = Buffer<T, PinnedMemory<Flags>>;
+
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The arrays of one pooled buffer (a grow-only DeviceBuf of the context), one behind the other in the order they are
+// taken, each at a multiple of 256 bytes: `take` answers an array's offset, `total` the bytes the buffer must hold.
+class PoolLayout {
+ public:
+  size_t take(size_t bytes) { return std::exchange(at_, at_ + align256(bytes)); }
+  size_t total() const { return at_; }
+
+ private:
+  size_t at_ = 0;
+};
 
 // An event, created on first use.
 class Event {
