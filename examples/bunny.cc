@@ -3,7 +3,7 @@
 // Usage: bunny <data_dir> <out_dir> [resolution] [n_slabs] [planned] [--keep-largest] [--render DIR] [--fuse-depth]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --tolerate M [--blank-view I]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --smooth N [--lambda L --mu M]
-//        bunny <data_dir> <out_dir> [resolution] [n_slabs] --decimate CELLS [--decimate-mode mean|nearest|first]
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] --decimate CELLS [--decimate-mode mean|nearest|first|quadric [--quadric-reg R]]
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
 //   --render DIR (DIR must exist) writes DIR/hull_<view>.png, the silhouette of the carved hull as every input camera
@@ -23,6 +23,8 @@
 //   vertex clustering on the device (VoxelCarver::DecimateMesh: cells of CELLS * resolution from the box's corner, the
 //   cluster's mean, its member nearest to the mean or its first member) and writes it as <out_dir>/surface_decimated.ply
 //   (binary, with normals); with slabs the merged mesh goes through ShardedVoxelCarver::DecimateMesh as well and is compared.
+//   --decimate-mode quadric puts every cluster at its quadric-error representative instead (VoxelCarver::DecimateMeshQuadric,
+//   regularisation --quadric-reg R in [0, 1], by default 0.001) and prints how many output vertices kept the mean.
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -74,7 +76,9 @@ int main(int argc, char* argv[]) {
   int smooth = -1;         // --smooth N: Taubin iterations over the final iso-surface before it is written
   float smooth_lambda = 0.5f, smooth_mu = -0.53f;  // --lambda L, --mu M
   float decimate = 0.0f;   // --decimate CELLS: vertex clustering over cells of CELLS voxels before the surface is written
-  int decimate_mode = 0;   // --decimate-mode mean|nearest|first
+  int decimate_mode = 0;   // --decimate-mode mean|nearest|first|quadric (3: VoxelCarver::DecimateMeshQuadric)
+  float quadric_reg = 1e-3f;  // --quadric-reg R
+  bool quadric_reg_given = false;
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
@@ -115,15 +119,27 @@ int main(int argc, char* argv[]) {
         ++i;
       } else if (std::string(argv[i]) == "--decimate-mode") {
         const std::string m = i + 1 < argc ? argv[i + 1] : "";
-        if (m != "mean" && m != "nearest" && m != "first") {
-          std::fprintf(stderr, "%s needs mean, nearest or first\n", argv[i]);
+        if (m != "mean" && m != "nearest" && m != "first" && m != "quadric") {
+          std::fprintf(stderr, "%s needs mean, nearest, first or quadric\n", argv[i]);
           return 10;
         }
-        decimate_mode = m == "mean" ? 0 : m == "nearest" ? 1 : 2;
+        decimate_mode = m == "mean" ? 0 : m == "nearest" ? 1 : m == "first" ? 2 : 3;
+        ++i;
+      } else if (std::string(argv[i]) == "--quadric-reg") {
+        quadric_reg = i + 1 < argc ? (float)std::atof(argv[i + 1]) : -1.0f;
+        if (!(quadric_reg >= 0.0f && quadric_reg <= 1.0f)) {
+          std::fprintf(stderr, "%s needs a number in [0, 1]\n", argv[i]);
+          return 10;
+        }
+        quadric_reg_given = true;
         ++i;
       } else argv[n++] = argv[i];
     }
     argc = n;
+    if (quadric_reg_given && decimate_mode != 3) {
+      std::fprintf(stderr, "--quadric-reg goes with --decimate-mode quadric\n");
+      return 10;
+    }
   }
   const std::string data_dir = argc > 1 ? argv[1] : "../data/";
   const std::string out_dir = argc > 2 ? argv[2] : data_dir;
@@ -291,23 +307,28 @@ int main(int argc, char* argv[]) {
   }
 
   if (decimate > 0.0f) {  // the final surface (smoothed first if asked for), clustered on the device, with fresh normals
-    const char* mode_names[3] = {"mean", "nearest", "first"};
+    const char* mode_names[4] = {"mean", "nearest", "first", "quadric"};
+    const bool quadric = decimate_mode == 3;
+    std::int64_t n_fallback = 0;
     const float cell = decimate * resolution;
     vacancy::Mesh mesh;
     carver.ExtractIsoSurface(&mesh, 0.0);
     if (smooth >= 0 && !carver.SmoothMesh(&mesh, smooth, smooth_lambda, smooth_mu, false, false)) return 16;
     const vacancy::Mesh before = mesh;
-    if (!carver.DecimateMesh(&mesh, cell, decimate_mode, true)) return 16;
+    if (!(quadric ? carver.DecimateMeshQuadric(&mesh, cell, quadric_reg, true, &n_fallback) : carver.DecimateMesh(&mesh, cell, decimate_mode, true)))
+      return 16;
     mesh.WritePlyBinary(out_dir + "/surface_decimated.ply");
     const std::array<float, 4> ms = carver.last_decimate_ms();
-    std::printf("DECIMATE cell %g mode %s vertices %zu -> %zu faces %zu -> %zu cluster_ms %.4f faces_ms %.4f emit_ms %.4f normals_ms %.4f\n",
-                cell, mode_names[decimate_mode], before.vertices().size(), mesh.vertices().size(), before.vertex_indices().size(),
-                mesh.vertex_indices().size(), ms[0], ms[1], ms[2], ms[3]);
+    std::printf("DECIMATE cell %g mode %s vertices %zu -> %zu faces %zu -> %zu", cell, mode_names[decimate_mode], before.vertices().size(),
+                mesh.vertices().size(), before.vertex_indices().size(), mesh.vertex_indices().size());
+    if (quadric) std::printf(" fallback %lld regularize %g quadric_ms %.4f", (long long)n_fallback, quadric_reg, carver.last_quadric_ms());
+    std::printf(" cluster_ms %.4f faces_ms %.4f emit_ms %.4f normals_ms %.4f\n", ms[0], ms[1], ms[2], ms[3]);
     if (sharded) {  // the merged mesh through the first slab's context: the same bits
       vacancy::Mesh sm;
       sharded->ExtractIsoSurface(&sm, 0.0);
       if (smooth >= 0 && !sharded->SmoothMesh(&sm, smooth, smooth_lambda, smooth_mu, false, false)) return 16;
-      if (!sharded->DecimateMesh(&sm, cell, decimate_mode, true)) return 16;
+      if (!(quadric ? sharded->DecimateMeshQuadric(&sm, cell, quadric_reg, true) : sharded->DecimateMesh(&sm, cell, decimate_mode, true)))
+        return 16;
       bool same = sm.vertices().size() == mesh.vertices().size() && sm.normals().size() == mesh.normals().size() &&
                   sm.vertex_indices().size() == mesh.vertex_indices().size();
       for (size_t k = 0; same && k < sm.vertices().size(); ++k)

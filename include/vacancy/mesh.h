@@ -36,6 +36,11 @@ class Mesh {
   // bb_min.  false + LOGE on an error (a face index out of range, cell <= 0, a non-finite vertex ...), the mesh then stays
   // as it was.
   bool Decimate(float cell, int mode = 0);
+  // The same clusters, faces and maps as Decimate(cell, 0), every cluster at its quadric-error representative instead of
+  // its mean (vcy_decimate_mesh_quadric_host; vacancy_hip.h, "mesh decimation, quadric representatives"): edges and corners
+  // keep their place.  regularize in [0, 1] pulls towards the mean; a cluster whose optimum is undefined or leaves its cell
+  // keeps the mean.  VoxelCarver::DecimateMeshQuadric runs the same on the device, bit for bit.
+  bool DecimateQuadric(float cell, float regularize = 1e-3f);
   const std::vector<Eigen::Vector3f>& normals() const { return normals_; }
   const std::vector<Eigen::Vector3f>& face_normals() const { return face_normals_; }
   const std::vector<Eigen::Vector3i>& normal_indices() const { return normal_indices_; }

@@ -66,6 +66,9 @@ class ShardedVoxelCarver {
   // VoxelCarver::DecimateMesh for the merged mesh, on the first slab's context (vcy_decimate_mesh), the lattice at the
   // grid's bb_min.  The same bits as VoxelCarver::DecimateMesh.
   bool DecimateMesh(Mesh* mesh, float cell, int mode = 0, bool with_normals = false);
+  // VoxelCarver::DecimateMeshQuadric for the merged mesh, on the first slab's context (vcy_decimate_mesh_quadric): the same bits.
+  bool DecimateMeshQuadric(Mesh* mesh, float cell, float regularize = 1e-3f, bool with_normals = false,
+                           std::int64_t* n_fallback = nullptr);
   // VoxelCarver::RenderHull / HullAgreement over the slabs: RenderHullSlabs / HullAgreementSlabs below.  These two older
   // names keep logging an error and returning false.
   bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);

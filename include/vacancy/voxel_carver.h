@@ -194,6 +194,12 @@ class VoxelCarver {
   // then stays as it was.  last_decimate_ms(): device milliseconds of the clusters, the faces, the emit, the normals.
   bool DecimateMesh(Mesh* mesh, float cell, int mode = 0, bool with_normals = false);
   std::array<float, 4> last_decimate_ms() const;
+  // Mesh::DecimateQuadric on this carver's device (vcy_decimate_mesh_quadric), the same bits, under DecimateMesh's terms.
+  // *n_fallback: the output vertices that kept their cluster's mean.  last_decimate_ms() reports this call's four groups,
+  // last_quadric_ms() the quadric stage alone (it is part of the clusters).
+  bool DecimateMeshQuadric(Mesh* mesh, float cell, float regularize = 1e-3f, bool with_normals = false,
+                           std::int64_t* n_fallback = nullptr);
+  float last_quadric_ms() const;
 
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;

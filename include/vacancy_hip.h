@@ -841,6 +841,72 @@ int vcy_decimate_mesh(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const f
  * for).  Any output may be NULL. */
 int vcy_last_decimate_ms(const vcy_ctx* ctx, float* cluster_ms, float* faces_ms, float* emit_ms, float* normals_ms);
 
+/* ---- mesh decimation, quadric representatives: the cluster's least-squares point ----- */
+/* No reference counterpart: this section is the definition (quadric error after Garland and Heckbert, per cluster after
+ * Lindstrom).  The host function below is it in serial host code, tests/quadric_ref.py restates it in numpy, the device
+ * function runs it on the device; the three agree bit for bit.
+ *
+ * Cells, clusters, cluster numbering, face rules, output vertices, vertex_map, face_source, normals and the order of the
+ * checks are those of "mesh decimation", word for word.  Only the position of a cluster differs: MEAN pulls the surface
+ * inward at every edge and corner; this position minimises the sum of squared (area-weighted) distances to the planes of
+ * the input faces around the cluster's members.
+ *
+ * All arithmetic below is double; every product, sum, difference and division is rounded on its own (no FMA), division
+ * is correctly rounded; (double) of a float is exact.
+ *
+ * Mean.  m is the cluster's MEAN, in float as defined above.
+ *
+ * Quadric of a face f = (i0, i1, i2), seen from cluster C:  a = (double)p[i0] - (double)m per coordinate, likewise b, c;
+ * e = b - a, g = c - a;  nx = e_y*g_z - e_z*g_y,  ny = e_z*g_x - e_x*g_z,  nz = e_x*g_y - e_y*g_x;
+ * d = -((nx*a_x + ny*a_y) + nz*a_z);  q(f) = (nx*nx, nx*ny, nx*nz, ny*ny, ny*nz, nz*nz, nx*d, ny*d, nz*d).
+ *
+ * Quadric of a vertex v in cluster C.  Qv = nine zeros; then through v's corner row -- every corner (f, j) with
+ * faces[3f+j] == v, in ascending f, then ascending j -- Qv = Qv + q(f) componentwise.  A face that names v twice is added
+ * twice.
+ *
+ * Quadric of a cluster.  Q = nine zeros; through the members in ascending index, Q = Q + Qv.  Two levels of sums, in this
+ * order.
+ *
+ * Solve.  t = (Q0 + Q3) + Q5;  w = (double)regularize * t;  A00 = Q0 + w, A11 = Q3 + w, A22 = Q5 + w, A01 = Q1, A02 = Q2,
+ * A12 = Q4;  r = (-Q6, -Q7, -Q8);  d0 = A00;  l10 = A01/d0, l20 = A02/d0;  d1 = A11 - l10*A01;  u = A12 - l20*A01,
+ * l21 = u/d1;  d2 = (A22 - l20*A02) - l21*u;  y0 = r0, y1 = r1 - l10*y0, y2 = (r2 - l20*y0) - l21*y1;  z_i = y_i/d_i;
+ * x2 = z2, x1 = z1 - l21*x2, x0 = (z0 - l10*x1) - l20*x2;  P_c = (float)((double)m_c + x_c), rounded to nearest even.
+ *
+ * Fallback.  The cluster's position is the bits of m instead of P whenever t is not finite or not > 0 (a cluster without
+ * faces, or with zero-area faces only); one of d0, d1, d2 is not > 0; a coordinate of P is not finite; the cell rule of
+ * "mesh decimation" fails for P; or the cell of P is not the cluster's: a representative never leaves its cell.
+ *
+ * regularize pulls the optimum towards the mean by a share of the quadric's trace: on a flat part the tangential position
+ * stays at the mean.  With regularize == 0 a flat or edge-like cluster falls back.
+ *
+ * Checks: those of "mesh decimation" in their order; where the mode check stands there, here: option->mode must be
+ * VCY_DECIMATE_MEAN, regularize finite and in [0, 1], else VCY_ERR_INVALID_ARG.  *n_fallback (may be NULL) is the number
+ * of OUTPUT vertices that carry the mean.  Whatever is refused, nothing is written, not the counts and not *n_fallback;
+ * n_vertices == 0 or n_faces == 0 sets all three to 0. */
+int vcy_decimate_mesh_quadric_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                                   const vcy_decimate_option* option, float regularize,
+                                   float* vertices_out   /* room for 3 * n_vertices */,
+                                   int32_t* faces_out    /* room for 3 * n_faces    */,
+                                   int64_t* n_vertices_out, int64_t* n_faces_out,
+                                   int32_t* vertex_map   /* [n_vertices], may be NULL */,
+                                   int32_t* face_source  /* room for n_faces, may be NULL */,
+                                   float* vertex_normals_out /* room for 3 * n_vertices, may be NULL */,
+                                   float* face_normals_out   /* room for 3 * n_faces, may be NULL */,
+                                   int64_t* n_fallback       /* may be NULL */);
+/* The same on the device of `ctx`, under the terms of the device function of "mesh decimation".  The quadric stage runs
+ * behind the member rows and means: the vertex -> corner table of the input mesh (a corner with a bad index is left out and
+ * refuses the call like any bad face index), nine doubles per vertex, one lane per cluster for the sum and the solve; a
+ * cell that holds more than 256 vertices is correct but slow here too.  Device memory on top of the MEAN call's: 77 bytes
+ * per input vertex (72 of them the vertex quadrics) and 12 per input face (the corner table). */
+int vcy_decimate_mesh_quadric(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                              const vcy_decimate_option* option, float regularize, float* vertices_out, int32_t* faces_out,
+                              int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map /* may be NULL */,
+                              int32_t* face_source /* may be NULL */, float* vertex_normals_out /* may be NULL */,
+                              float* face_normals_out /* may be NULL */, int64_t* n_fallback /* may be NULL */);
+/* Device time of the quadric stage (corner table, vertex quadrics, sums and solves) of the last device call of this section;
+ * 0 after one that had nothing to do.  vcy_last_decimate_ms reports that call's four groups, this stage inside "clusters". */
+int vcy_last_quadric_ms(const vcy_ctx* ctx, float* device_ms);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and

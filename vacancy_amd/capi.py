@@ -241,6 +241,11 @@ def load():
         "vcy_decimate_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(DecimateOption), vp, vp, P(C.c_int64), P(C.c_int64),
                                         vp, vp, vp, vp]),
         "vcy_last_decimate_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]),
+        "vcy_decimate_mesh_quadric_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, P(DecimateOption), C.c_float, vp, vp,
+                                                     P(C.c_int64), P(C.c_int64), vp, vp, vp, vp, P(C.c_int64)]),
+        "vcy_decimate_mesh_quadric": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(DecimateOption), C.c_float, vp, vp,
+                                                P(C.c_int64), P(C.c_int64), vp, vp, vp, vp, P(C.c_int64)]),
+        "vcy_last_quadric_ms": (C.c_int, [vp, P(C.c_float)]),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_mesh_normals_seam_sum": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),

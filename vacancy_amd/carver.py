@@ -232,6 +232,29 @@ def decimate_mesh_host(vertices, faces, cell, origin=(0.0, 0.0, 0.0), mode=capi.
     return _decimate_result(capi.load().vcy_decimate_mesh_host(*args), keep, out)
 
 
+def _quadric_args(vertices, faces, cell, origin, regularize, normals):
+    """_decimate_args for vcy_decimate_mesh_quadric and its host function: MEAN, `regularize` behind the option, the fallback
+    count (keep[4]) at the end."""
+    keep, args, out = _decimate_args(vertices, faces, cell, origin, capi.VCY_DECIMATE_MEAN, normals)
+    n_fallback = C.c_int64(-1)
+    return keep + (n_fallback,), args[:5] + (C.c_float(regularize),) + args[5:] + (C.byref(n_fallback),), out
+
+
+def _quadric_result(rc, keep, out):
+    out = _decimate_result(rc, keep, out)
+    out["n_fallback"] = keep[4].value
+    return out
+
+
+def decimate_mesh_quadric_host(vertices, faces, cell, origin=(0.0, 0.0, 0.0), regularize=1e-3, normals=False):
+    """vcy_decimate_mesh_quadric_host: decimate_mesh_host with MEAN clusters whose representative is the quadric-error
+    optimum of the input faces around the cluster (definition: include/vacancy_hip.h, "mesh decimation, quadric
+    representatives"), serial, no GPU needed.  Returns decimate_mesh_host's dict plus "n_fallback", the output vertices that
+    kept the mean.  RuntimeError (with .rc) on a refusal."""
+    keep, args, out = _quadric_args(vertices, faces, cell, origin, regularize, normals)
+    return _quadric_result(capi.load().vcy_decimate_mesh_quadric_host(*args), keep, out)
+
+
 def carve_depth_host(option, views, depths, band, sdf, update_num, z_range=None):
     """vcy_carve_depth_host: the depth carve (definition: include/vacancy_hip.h, "carve from depth images") serially on the
     host, no GPU needed, IN PLACE on `sdf` (float32) and `update_num` (int32), C-contiguous arrays in download()'s layout
@@ -806,6 +829,20 @@ class VoxelCarver:
         ms = [C.c_float() for _ in range(4)]
         self._lib.vcy_last_decimate_ms(self._ctx, *[C.byref(m) for m in ms])
         out["cluster_ms"], out["faces_ms"], out["emit_ms"], out["normals_ms"] = (m.value for m in ms)
+        return out
+
+    def DecimateMeshQuadric(self, vertices, faces, cell, origin=None, regularize=1e-3, normals=False):
+        """vcy_decimate_mesh_quadric: decimate_mesh_quadric_host on this context's device and stream, the same bits, under
+        DecimateMesh's terms.  Returns its dict (with "n_fallback") plus DecimateMesh's four device times and "quadric_ms",
+        the quadric stage alone (it is part of "cluster_ms")."""
+        if origin is None:
+            origin = tuple(self.option.bb_min)
+        keep, args, out = _quadric_args(vertices, faces, cell, origin, regularize, normals)
+        out = _quadric_result(self._lib.vcy_decimate_mesh_quadric(self._ctx, *args), keep, out)
+        ms = [C.c_float() for _ in range(5)]
+        self._lib.vcy_last_decimate_ms(self._ctx, *[C.byref(m) for m in ms[:4]])
+        self._lib.vcy_last_quadric_ms(self._ctx, C.byref(ms[4]))
+        out["cluster_ms"], out["faces_ms"], out["emit_ms"], out["normals_ms"], out["quadric_ms"] = (m.value for m in ms)
         return out
 
     # -- state access

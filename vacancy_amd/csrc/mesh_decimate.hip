@@ -15,6 +15,14 @@
 //            atomics ran in --, in registers up to 48 members, in global memory up to 256 --, then the sum in registers,
 //            the mean, the nearest member; a row of more than 256 members goes on a list),
 //            dc_long_rows (one workgroup per listed row: see there).  FIRST needs no rows.
+//            Quadric representatives (vcy_decimate_mesh_quadric; "mesh decimation, quadric representatives", the
+//            arithmetic: mesh_quadric.h) are MEAN plus one stage behind the rows: mesh_rows.h's table of the input mesh's
+//            corners by vertex, built with its checked kernels -- the verdict on the face indices is not read yet, so a
+//            corner with a bad index is left out and raises the face flag --, dc_qv (one lane per vertex sorts its corner
+//            row and adds the quadrics of its faces, seen from its cluster's mean, in registers: nine doubles per vertex),
+//            dc_qsolve (one lane per cluster adds its members' nine doubles in row order -- every row is sorted by now,
+//            the long ones too --, solves, and overwrites the mean unless the fallback rule holds; a byte per cluster
+//            says which, and dc_emit_v counts the bytes of the clusters it emits: a ballot and one integer add per wave).
 //   faces    dc_fmap (one lane per face: index check, corners -> clusters, collapsed faces flagged, the canonical triple),
 //            dc_finsert (the same table trick, a slot holds a face index, canonical triples compared), dc_fflag (a face
 //            survives iff its slot holds its own index; survivors mark their clusters with a plain store of 1), two scans
@@ -28,6 +36,7 @@
 #include <algorithm>
 
 #include "mesh_decimate.h"
+#include "mesh_quadric.h"
 #include "mesh_rows.h"
 #include "vcy_internal.h"
 
@@ -39,6 +48,7 @@ typedef unsigned long long u64;
 constexpr int kShortRow = 16;   // members a row is sorted with in registers ...
 constexpr int kMidRow = 48;     // ... and by a second, wider network (cells of 4 voxels hold about 18 vertices, at most a few dozen)
 constexpr int kLongRow = 256;   // members from which on a row goes to a workgroup of its own (dc_long_rows_kernel)
+constexpr int kShortCorners = 12;  // corners a vertex's row is sorted with in registers (a marching-cubes row holds 4 - 12)
 enum { kErrVertex = 0, kErrTable = 1, kErrFace = 2, kLongCount = 3 };  // words of Dec::err
 
 struct Dec {
@@ -72,6 +82,13 @@ struct Dec {
   int* fsrc;            // [nf]
   int* err;             // [4]
   const u64* totals;    // clusters, output faces, output vertices
+  // quadric representatives
+  float regularize;
+  int* coff;            // [n + 1] offsets of the corner rows
+  int* corner;          // [3 nf] rows of corners 3 f + j by vertex
+  double* qv;           // [9 n] Qv of every vertex
+  unsigned char* fell;  // [n] per cluster: it keeps the mean
+  u64* fallbacks;       // the output vertices that keep the mean
 };
 
 __global__ __launch_bounds__(256) void dc_keys_kernel(Dec d) {
@@ -236,6 +253,51 @@ __global__ __launch_bounds__(256) void dc_long_rows_kernel(Dec d) {
   }
 }
 
+// Qv of every vertex: the quadrics of the faces around it in corner order, seen from the mean of its cluster.  Nine double
+// accumulators and one face's temporaries per lane.  A face in the row may still name a bad index at another corner (the
+// face flag is up then and the call refused): it is left out, never read through.  As compiled for gfx950: 54 VGPRs, no
+// scratch, 8 waves per SIMD (dc_qsolve_kernel: 52, none, 8) -- launch bounds beyond the block size would buy nothing.
+__global__ __launch_bounds__(256) void dc_qv_kernel(Dec d) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= d.n) return;
+  const int b = d.coff[v], len = d.coff[v + 1] - b;
+  double Q[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (len > 0) {
+    int* row = d.corner + b;
+    rows::sort_row<kShortCorners>(row, len);
+    const float* mp = d.cpos + 3 * (int64_t)d.cluster[v];
+    const float m[3] = {mp[0], mp[1], mp[2]};
+    for (int k = 0; k < len; ++k) {
+      const int64_t f = row[k] / 3;
+      const int i0 = d.faces[3 * f], i1 = d.faces[3 * f + 1], i2 = d.faces[3 * f + 2];
+      if (i0 < 0 || i0 >= d.n || i1 < 0 || i1 >= d.n || i2 < 0 || i2 >= d.n) continue;
+      double q[9];
+      face_quadric(d.pos + 3 * (int64_t)i0, d.pos + 3 * (int64_t)i1, d.pos + 3 * (int64_t)i2, m, q);
+      quadric_add(Q, q);
+    }
+  }
+  double* out = d.qv + 9 * v;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) out[k] = Q[k];
+}
+
+// The position of every cluster: its members' Qv added in row order, the solve, the fallback rule.
+__global__ __launch_bounds__(256) void dc_qsolve_kernel(Dec d) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= (int64_t)min(d.totals[0], (u64)d.n)) return;
+  const int b = d.off[c], len = d.off[c + 1] - b;
+  const int lowest = d.rep[c];
+  if (len <= 0 || lowest < 0 || lowest >= d.n) return;  // (only where the table failed)
+  const int* row = d.member + b;
+  double Q[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = 0; j < len; ++j) quadric_add(Q, d.qv + 9 * (int64_t)row[j]);  // (a long row: serial, as its mean is)
+  const float m[3] = {d.cpos[3 * c], d.cpos[3 * c + 1], d.cpos[3 * c + 2]};
+  float P[3];
+  const bool fell = solve_or_mean(Q, m, d.regularize, d.origin, d.cell, d.key + 3 * (int64_t)lowest, P);
+  d.fell[c] = fell ? 1 : 0;
+  if (!fell) d.cpos[3 * c] = P[0], d.cpos[3 * c + 1] = P[1], d.cpos[3 * c + 2] = P[2];
+}
+
 __global__ __launch_bounds__(256) void dc_fmap_kernel(Dec d) {
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= d.nf) return;
@@ -274,7 +336,7 @@ __global__ __launch_bounds__(256) void dc_fflag_kernel(Dec d) {
   }
 }
 
-template <bool FIRST>
+template <bool FIRST, bool QUADRIC>
 __global__ __launch_bounds__(256) void dc_emit_v_kernel(Dec d) {
   const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (v >= d.n) return;
@@ -282,11 +344,20 @@ __global__ __launch_bounds__(256) void dc_emit_v_kernel(Dec d) {
   const u64 o = d.used[cl];
   d.vmap[v] = d.used[cl + 1] != o ? (int)o : -1;
   // the same lane as cluster v
-  if (v >= (int64_t)min(d.totals[0], (u64)d.n)) return;
-  const u64 g = d.used[v];
-  if (d.used[v + 1] == g) return;
-  const float* src = FIRST ? d.pos + 3 * (int64_t)d.rep[v] : d.cpos + 3 * v;
-  d.pos_out[3 * g] = src[0], d.pos_out[3 * g + 1] = src[1], d.pos_out[3 * g + 2] = src[2];
+  bool emits = v < (int64_t)min(d.totals[0], (u64)d.n);
+  u64 g = 0;
+  if (emits) {
+    g = d.used[v];
+    emits = d.used[v + 1] != g;
+  }
+  if (emits) {
+    const float* src = FIRST ? d.pos + 3 * (int64_t)d.rep[v] : d.cpos + 3 * v;
+    d.pos_out[3 * g] = src[0], d.pos_out[3 * g + 1] = src[1], d.pos_out[3 * g + 2] = src[2];
+  }
+  if (QUADRIC) {  // (every lane with v < n is here: one integer add per wave)
+    const u64 kept = __ballot(emits && d.fell[v] != 0);
+    if (kept != 0 && (int)(threadIdx.x & 63) == __ffsll((long long)kept) - 1) atomicAdd(d.fallbacks, (u64)__popcll(kept));
+  }
 }
 
 __global__ __launch_bounds__(256) void dc_emit_f_kernel(Dec d) {
@@ -313,14 +384,20 @@ size_t table_slots(size_t n) {
 struct Report {
   int err[4];
   dc::u64 totals[4];  // clusters, output faces, output vertices
+  dc::u64 corners;    // quadric representatives: the corner table's total,
+  dc::u64 fallbacks;  // the output vertices that keep the mean
 };
 
-int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
-                    const vcy_decimate_option& o, float* vertices_out, int32_t* faces_out, int64_t* n_vertices_out,
-                    int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source, float* vertex_normals_out,
-                    float* face_normals_out) {
+// `regularize` non-NULL: quadric representatives (MEAN, then the quadric stage), their fallbacks into `n_fallback`
+int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
+                    const vcy_decimate_option& o, const float* regularize, float* vertices_out, int32_t* faces_out,
+                    int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
+                    float* vertex_normals_out, float* face_normals_out, int64_t* n_fallback) {
   VCY_HIP_CHECK(hipSetDevice(c->device));
   for (vcy::Event& e : c->ev_dc) VCY_HIP_CHECK(e.ensure());
+  const bool quadric = regularize != nullptr;
+  if (quadric)
+    for (vcy::Event& e : c->ev_dq) VCY_HIP_CHECK(e.ensure());
   const size_t n = (size_t)n64, nf = (size_t)nf64, nc = 3 * nf;
   const bool normals = vertex_normals_out || face_normals_out;
   const bool rows = o.mode != VCY_DECIMATE_FIRST;
@@ -328,7 +405,8 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
 
   // [report | faces | positions | keys | vslot | vtable | vflag | cluster | rep | deg | off | cursor | member | cpos | fcanon |
   //  fslot | ftable | fflag | used | scan scratch | the four outputs]: 108 bytes and 8 to 16 of table per vertex, 52 and 8 to
-  //  16 per face
+  //  16 per face; quadric representatives add [coff | corners | Qv | fell]: 77 bytes per vertex and 12 per face (the corner
+  //  table's counts and cursors are the member table's, free again by then)
   PoolLayout at;
   const size_t at_report = at.take(sizeof(Report)), at_faces = at.take(4 * nc), at_pos = at.take(12 * n), at_key = at.take(12 * n),
                at_vslot = at.take(4 * n), at_vtable = at.take(4 * vslots), at_vflag = at.take(8 * (n + 1)), at_cluster = at.take(4 * n),
@@ -337,6 +415,8 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
                at_ftable = at.take(4 * fslots), at_fflag = at.take(8 * (nf + 1)), at_used = at.take(8 * (n + 1)),
                at_scan = at.take(8 * scan_scratch_words(std::max(n, nf) + 1)), at_pos_out = at.take(12 * n),
                at_faces_out = at.take(4 * nc), at_vmap = at.take(4 * n), at_fsrc = at.take(4 * nf);
+  const size_t at_coff = at.take(quadric ? 4 * (n + 1) : 0), at_corner = at.take(quadric ? 4 * nc : 0),
+               at_qv = at.take(quadric ? 72 * n : 0), at_fell = at.take(quadric ? n : 0);
   VCY_HIP_CHECK(c->d_dc_buf.grow(at.total(), c->stream));
   char* base = (char*)c->d_dc_buf;
   hipStream_t s = c->stream;
@@ -359,6 +439,9 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
   d.pos_out = (float*)(base + at_pos_out), d.faces_out = (int*)(base + at_faces_out);
   d.vmap = (int*)(base + at_vmap), d.fsrc = (int*)(base + at_fsrc);
   d.err = d_report->err, d.totals = d_report->totals;
+  d.regularize = quadric ? *regularize : 0.0f;
+  d.coff = (int*)(base + at_coff), d.corner = (int*)(base + at_corner), d.qv = (double*)(base + at_qv);
+  d.fell = (unsigned char*)(base + at_fell), d.fallbacks = &d_report->fallbacks;
 
   VCY_HIP_CHECK(hipMemcpyAsync(base + at_pos, vertices, 12 * n, hipMemcpyHostToDevice, s));
   VCY_HIP_CHECK(hipMemcpyAsync(base + at_faces, faces, 4 * nc, hipMemcpyHostToDevice, s));
@@ -391,6 +474,15 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
       hipLaunchKernelGGL(dc::dc_rows_kernel<false>, grid_v, blk, 0, s, d);
       hipLaunchKernelGGL(dc::dc_long_rows_kernel<false>, grid_long, blk, 0, s, d);
     }
+    if (quadric) {
+      VCY_HIP_CHECK(hipGetLastError());
+      VCY_HIP_CHECK(hipEventRecord(c->ev_dq[0], s));
+      const rows::Table corners{d.n, (int)nc, d.faces, d.deg, d.coff, d.cursor, d.corner, d.err + dc::kErrFace};
+      { const int rc = rows::fill<true>(s, corners, &d_report->corners, scan); if (rc != VCY_OK) return rc; }
+      hipLaunchKernelGGL(dc::dc_qv_kernel, grid_v, blk, 0, s, d);
+      hipLaunchKernelGGL(dc::dc_qsolve_kernel, grid_v, blk, 0, s, d);
+      VCY_HIP_CHECK(hipEventRecord(c->ev_dq[1], s));
+    }
   } else {
     hipLaunchKernelGGL(dc::dc_vcluster_kernel<false>, grid_v, blk, 0, s, d);
   }
@@ -407,8 +499,9 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
 
   // ---- emit
   VCY_HIP_CHECK(hipEventRecord(c->ev_dc[2], s));
-  if (rows) hipLaunchKernelGGL(dc::dc_emit_v_kernel<false>, grid_v, blk, 0, s, d);
-  else hipLaunchKernelGGL(dc::dc_emit_v_kernel<true>, grid_v, blk, 0, s, d);
+  if (quadric) hipLaunchKernelGGL((dc::dc_emit_v_kernel<false, true>), grid_v, blk, 0, s, d);
+  else if (rows) hipLaunchKernelGGL((dc::dc_emit_v_kernel<false, false>), grid_v, blk, 0, s, d);
+  else hipLaunchKernelGGL((dc::dc_emit_v_kernel<true, false>), grid_v, blk, 0, s, d);
   hipLaunchKernelGGL(dc::dc_emit_f_kernel, grid_f, blk, 0, s, d);
   VCY_HIP_CHECK(hipGetLastError());
   VCY_HIP_CHECK(hipEventRecord(c->ev_dc[3], s));
@@ -418,15 +511,15 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
   VCY_HIP_CHECK(hipMemcpyAsync(&r, d_report, sizeof(Report), hipMemcpyDeviceToHost, s));
   VCY_HIP_CHECK(hipStreamSynchronize(s));
   if (r.err[dc::kErrFace]) {
-    set_error("vcy_decimate_mesh: a face names a vertex outside 0 .. %lld", (long long)n64 - 1);
+    set_error("%s: a face names a vertex outside 0 .. %lld", who, (long long)n64 - 1);
     return VCY_ERR_INVALID_ARG;
   }
   if (r.err[dc::kErrVertex]) {
-    set_error("vcy_decimate_mesh: a vertex is not finite or lies 2^30 cells or more from the origin");
+    set_error("%s: a vertex is not finite or lies 2^30 cells or more from the origin", who);
     return VCY_ERR_INVALID_ARG;
   }
   if (r.err[dc::kErrTable] || (size_t)r.err[dc::kLongCount] > n / dc::kLongRow + 1 || r.totals[0] > n || r.totals[1] > nf || r.totals[2] > r.totals[0]) {
-    set_error("vcy_decimate_mesh: a table ran out of slots (%llu clusters, %llu faces, %llu vertices)", r.totals[0], r.totals[1], r.totals[2]);
+    set_error("%s: a table ran out of slots (%llu clusters, %llu faces, %llu vertices)", who, r.totals[0], r.totals[1], r.totals[2]);
     return VCY_ERR_INTERNAL;
   }
   const size_t nvo = (size_t)r.totals[2], nfo = (size_t)r.totals[1];
@@ -451,8 +544,10 @@ int decimate_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices
   for (int k = 0; k < 3; ++k) VCY_HIP_CHECK(hipEventElapsedTime(&c->last_decimate_ms[k], c->ev_dc[k], c->ev_dc[k + 1]));
   c->last_decimate_ms[3] = 0.0f;
   if (normals) VCY_HIP_CHECK(hipEventElapsedTime(&c->last_decimate_ms[3], c->ev_dc[4], c->ev_dc[5]));
+  if (quadric) VCY_HIP_CHECK(hipEventElapsedTime(&c->last_quadric_ms, c->ev_dq[0], c->ev_dq[1]));
   *n_vertices_out = (int64_t)nvo;
   *n_faces_out = (int64_t)nfo;
+  if (n_fallback) *n_fallback = (int64_t)r.fallbacks;
   return VCY_OK;
 }
 
@@ -478,10 +573,41 @@ int vcy_decimate_mesh(vcy_ctx* c, int64_t n_vertices, int64_t n_faces, const flo
     *n_vertices_out = *n_faces_out = 0;
     return VCY_OK;
   }
-  const int rc = decimate_device(c, n_vertices, n_faces, vertices, faces, *option, vertices_out, faces_out, n_vertices_out,
-                                 n_faces_out, vertex_map, face_source, vertex_normals_out, face_normals_out);
+  const int rc = decimate_device("vcy_decimate_mesh", c, n_vertices, n_faces, vertices, faces, *option, nullptr, vertices_out,
+                                 faces_out, n_vertices_out, n_faces_out, vertex_map, face_source, vertex_normals_out,
+                                 face_normals_out, nullptr);
   if (rc != VCY_OK) (void)hipStreamSynchronize(c->stream);  // (queued copies still name the caller's arrays)
   return rc;
+}
+
+int vcy_decimate_mesh_quadric(vcy_ctx* c, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                              const vcy_decimate_option* option, float regularize, float* vertices_out, int32_t* faces_out,
+                              int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
+                              float* vertex_normals_out, float* face_normals_out, int64_t* n_fallback) {
+  const char* who = "vcy_decimate_mesh_quadric";
+  { const int rc = decimate_check_args(who, n_vertices, n_faces, vertices, faces, option, vertices_out, faces_out, n_vertices_out, n_faces_out, &regularize); if (rc != VCY_OK) return rc; }
+  if (!c) {
+    set_error("voxel grid has not been initialized");
+    return VCY_ERR_NOT_INITIALIZED;
+  }
+  for (float& ms : c->last_decimate_ms) ms = 0.0f;
+  c->last_quadric_ms = 0.0f;
+  if (n_vertices == 0 || n_faces == 0) {
+    *n_vertices_out = *n_faces_out = 0;
+    if (n_fallback) *n_fallback = 0;
+    return VCY_OK;
+  }
+  const int rc = decimate_device(who, c, n_vertices, n_faces, vertices, faces, *option, &regularize, vertices_out, faces_out,
+                                 n_vertices_out, n_faces_out, vertex_map, face_source, vertex_normals_out, face_normals_out,
+                                 n_fallback);
+  if (rc != VCY_OK) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+int vcy_last_quadric_ms(const vcy_ctx* c, float* device_ms) {
+  if (!c) return VCY_ERR_INVALID_ARG;
+  if (device_ms) *device_ms = c->last_quadric_ms;
+  return VCY_OK;
 }
 
 int vcy_last_decimate_ms(const vcy_ctx* c, float* cluster_ms, float* faces_ms, float* emit_ms, float* normals_ms) {

@@ -1,23 +1,27 @@
 // Vertex-clustering decimation of an indexed mesh, serially on the host (vcy_decimate_mesh_host; the definition is the
 // section "mesh decimation" of vacancy_hip.h, restated in numpy in tests/decimate_ref.py).  Host code only -- no GPU, no
 // context, nothing of the HIP runtime --, like mesh_smooth_host.hip; vcy_mesh_normals_host (mesh_host.hip) gives the
-// normals of the result.  Also the argument checks the device entry point (mesh_decimate.hip) shares.
+// normals of the result.  Also the argument checks the device entry point (mesh_decimate.hip) shares, and the same with
+// quadric-error representatives (vcy_decimate_mesh_quadric_host; "mesh decimation, quadric representatives", restated in
+// tests/quadric_ref.py; the arithmetic: mesh_quadric.h).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "mesh_decimate.h"
+#include "mesh_quadric.h"
 #include "vacancy_hip.h"
 
 namespace vcy {
 
 void set_error(const char* fmt, ...);
 
-// Everything the definition refuses without looking into the arrays, before anything is written.
+// Everything the definition refuses without looking into the arrays, before anything is written.  `regularize`: non-NULL
+// for the quadric entry points, whose rule (MEAN, a regularisation in [0, 1]) stands where the mode check does.
 int decimate_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
                         const vcy_decimate_option* o, const float* vertices_out, const int32_t* faces_out,
-                        const int64_t* n_vertices_out, const int64_t* n_faces_out) {
+                        const int64_t* n_vertices_out, const int64_t* n_faces_out, const float* regularize) {
   if (n_vertices < 0 || n_faces < 0 || !o || !n_vertices_out || !n_faces_out ||
       (n_vertices > 0 && n_faces > 0 && (!vertices || !faces || !vertices_out || !faces_out))) {
     set_error("%s: invalid argument", who);
@@ -31,7 +35,16 @@ int decimate_check_args(const char* who, int64_t n_vertices, int64_t n_faces, co
     set_error("%s: the origin must be finite (%g, %g, %g)", who, (double)o->origin[0], (double)o->origin[1], (double)o->origin[2]);
     return VCY_ERR_INVALID_ARG;
   }
-  if (o->mode < VCY_DECIMATE_MEAN || o->mode > VCY_DECIMATE_FIRST) {
+  if (regularize) {
+    if (o->mode != VCY_DECIMATE_MEAN) {
+      set_error("%s: mode %d: quadric representatives start from MEAN (0)", who, o->mode);
+      return VCY_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(*regularize) || !(*regularize >= 0.0f) || !(*regularize <= 1.0f)) {
+      set_error("%s: regularize %g must be finite and in [0, 1]", who, (double)*regularize);
+      return VCY_ERR_INVALID_ARG;
+    }
+  } else if (o->mode < VCY_DECIMATE_MEAN || o->mode > VCY_DECIMATE_FIRST) {
     set_error("%s: mode %d outside 0 .. 2", who, o->mode);
     return VCY_ERR_INVALID_ARG;
   }
@@ -55,18 +68,15 @@ size_t table_slots(size_t n) {
   return s;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vcy_decimate_mesh_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
-                           const vcy_decimate_option* option, float* vertices_out, int32_t* faces_out,
-                           int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
-                           float* vertex_normals_out, float* face_normals_out) {
-  const char* who = "vcy_decimate_mesh_host";
-  { const int rc = decimate_check_args(who, n_vertices, n_faces, vertices, faces, option, vertices_out, faces_out, n_vertices_out, n_faces_out); if (rc != VCY_OK) return rc; }
+// The definition, serially.  `regularize` non-NULL: MEAN with quadric representatives, and their fallbacks counted.
+int decimate_host(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                  const vcy_decimate_option* option, const float* regularize, float* vertices_out, int32_t* faces_out,
+                  int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
+                  float* vertex_normals_out, float* face_normals_out, int64_t* n_fallback) {
+  { const int rc = decimate_check_args(who, n_vertices, n_faces, vertices, faces, option, vertices_out, faces_out, n_vertices_out, n_faces_out, regularize); if (rc != VCY_OK) return rc; }
   if (n_vertices == 0 || n_faces == 0) {
     *n_vertices_out = *n_faces_out = 0;
+    if (n_fallback) *n_fallback = 0;
     return VCY_OK;
   }
   const size_t nv = (size_t)n_vertices, nf = (size_t)n_faces;
@@ -154,6 +164,19 @@ int vcy_decimate_mesh_host(int64_t n_vertices, int64_t n_faces, const float* ver
     for (size_t v = 0; v < nv; ++v) member[(size_t)cursor[(size_t)cluster[v]]++] = (int32_t)v;
   }
 
+  // quadric representatives: corner rows 3 f + j in ascending order behind coff[v] (the same counting sort)
+  std::vector<int64_t> coff;
+  std::vector<int32_t> corner;
+  if (regularize) {
+    coff.assign(nv + 1, 0);
+    for (size_t i = 0; i < 3 * nf; ++i) ++coff[(size_t)faces[i] + 1];
+    for (size_t v = 0; v < nv; ++v) coff[v + 1] += coff[v];
+    corner.resize(3 * nf);
+    std::vector<int64_t> cursor(coff.begin(), coff.end() - 1);
+    for (size_t i = 0; i < 3 * nf; ++i) corner[(size_t)cursor[(size_t)faces[i]]++] = (int32_t)i;
+  }
+  int64_t fallbacks = 0;
+
   // ---- nothing is refused past this point: the outputs
   for (size_t c = 0; c < ncl; ++c) {
     if (out_id[c] < 0) continue;
@@ -163,6 +186,23 @@ int vcy_decimate_mesh_host(int64_t n_vertices, int64_t n_faces, const float* ver
       const int64_t len = off[c + 1] - off[c];
       float m[3];
       dc::row_mean(vertices, row, len, m);
+      if (regularize) {
+        double Q[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int64_t j = 0; j < len; ++j) {  // (a vertex has one cluster: its Qv is needed here and nowhere else)
+          const size_t v = (size_t)row[j];
+          double Qv[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, q[9];
+          for (int64_t k = coff[v]; k < coff[v + 1]; ++k) {
+            const int32_t* tri = faces + 3 * (size_t)(corner[(size_t)k] / 3);
+            dc::face_quadric(vertices + 3 * (size_t)tri[0], vertices + 3 * (size_t)tri[1], vertices + 3 * (size_t)tri[2], m, q);
+            dc::quadric_add(Qv, q);
+          }
+          dc::quadric_add(Q, Qv);
+        }
+        float P[3];
+        if (dc::solve_or_mean(Q, m, *regularize, option->origin, option->cell, &key[3 * (size_t)rep[c]], P)) ++fallbacks;
+        std::memcpy(vertices_out + 3 * (size_t)out_id[c], P, 3 * sizeof(float));
+        continue;
+      }
       if (option->mode == VCY_DECIMATE_MEAN) {
         std::memcpy(vertices_out + 3 * (size_t)out_id[c], m, 3 * sizeof(float));
         continue;
@@ -180,9 +220,31 @@ int vcy_decimate_mesh_host(int64_t n_vertices, int64_t n_faces, const float* ver
     for (size_t v = 0; v < nv; ++v) vertex_map[v] = out_id[(size_t)cluster[v]];
   *n_vertices_out = (int64_t)nvo;
   *n_faces_out = (int64_t)nfo;
+  if (n_fallback) *n_fallback = fallbacks;
   if (vertex_normals_out || face_normals_out)
     return vcy_mesh_normals_host((int64_t)nvo, (int64_t)nfo, vertices_out, faces_out, vertex_normals_out, face_normals_out);
   return VCY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vcy_decimate_mesh_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                           const vcy_decimate_option* option, float* vertices_out, int32_t* faces_out,
+                           int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
+                           float* vertex_normals_out, float* face_normals_out) {
+  return decimate_host("vcy_decimate_mesh_host", n_vertices, n_faces, vertices, faces, option, nullptr, vertices_out, faces_out,
+                       n_vertices_out, n_faces_out, vertex_map, face_source, vertex_normals_out, face_normals_out, nullptr);
+}
+
+int vcy_decimate_mesh_quadric_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                                   const vcy_decimate_option* option, float regularize, float* vertices_out, int32_t* faces_out,
+                                   int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
+                                   float* vertex_normals_out, float* face_normals_out, int64_t* n_fallback) {
+  return decimate_host("vcy_decimate_mesh_quadric_host", n_vertices, n_faces, vertices, faces, option, &regularize, vertices_out,
+                       faces_out, n_vertices_out, n_faces_out, vertex_map, face_source, vertex_normals_out, face_normals_out,
+                       n_fallback);
 }
 
 }  // extern "C"

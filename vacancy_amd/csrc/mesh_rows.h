@@ -23,12 +23,20 @@ struct Table {
   int* off;             // [n_rows + 1] row offsets
   int* cursor;          // [n_rows]
   int* items;           // [n_items] rows of item ids
+  int* bad;             // CHECKED builds only: one word, set to 1 where a key lies outside [0, n_rows); that item has no row
 };
 
+// CHECKED: the keys come from the caller unverified (a mesh's face indices before the verdict on them is read)
+template <bool CHECKED>
 static __global__ __launch_bounds__(256) void rows_count_kernel(Table t) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= t.n_items) return;
-  atomicAdd(&t.deg[t.key[i]], 1ull);
+  const int k = t.key[i];
+  if (CHECKED && (k < 0 || k >= t.n_rows)) {
+    *t.bad = 1;
+    return;
+  }
+  atomicAdd(&t.deg[k], 1ull);
 }
 
 static __global__ __launch_bounds__(256) void rows_offsets_kernel(Table t) {
@@ -39,25 +47,29 @@ static __global__ __launch_bounds__(256) void rows_offsets_kernel(Table t) {
   if (r < t.n_rows) t.cursor[r] = o;
 }
 
+template <bool CHECKED>
 static __global__ __launch_bounds__(256) void rows_fill_kernel(Table t) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= t.n_items) return;
-  const int slot = atomicAdd(&t.cursor[t.key[i]], 1);  // (< off[key + 1]: the row has a slot per item counted)
+  const int k = t.key[i];
+  if (CHECKED && (k < 0 || k >= t.n_rows)) return;  // (counted nowhere: the rows hold the other items, off[n_rows] of them)
+  const int slot = atomicAdd(&t.cursor[k], 1);  // (< off[key + 1]: the row has a slot per item counted)
   t.items[slot] = (int)i;
 }
 
 // Counts, row offsets, and the items in their rows in arbitrary order.  `total`: one word, `scratch`: the scan's,
 // scan_scratch_words(n_rows + 1) words.  `counted`: the caller has cleared t.deg and counted into it already.
+template <bool CHECKED = false>
 inline int fill(hipStream_t s, const Table& t, u64* total, u64* scratch, bool counted = false) {
   const size_t n = (size_t)t.n_rows, m = (size_t)t.n_items;
   const dim3 blk(256), grid_r1((unsigned)((n + 256) / 256)), grid_i((unsigned)((m + 255) / 256));
   if (!counted) {
     VCY_HIP_CHECK(hipMemsetAsync(t.deg, 0, 8 * (n + 1), s));
-    if (m > 0) hipLaunchKernelGGL(rows_count_kernel, grid_i, blk, 0, s, t);
+    if (m > 0) hipLaunchKernelGGL(rows_count_kernel<CHECKED>, grid_i, blk, 0, s, t);
   }
   { const int rc = device_exclusive_scan_u64(t.deg, (int64_t)n + 1, total, scratch, s); if (rc != VCY_OK) return rc; }
   hipLaunchKernelGGL(rows_offsets_kernel, grid_r1, blk, 0, s, t);
-  if (m > 0) hipLaunchKernelGGL(rows_fill_kernel, grid_i, blk, 0, s, t);
+  if (m > 0) hipLaunchKernelGGL(rows_fill_kernel<CHECKED>, grid_i, blk, 0, s, t);
   VCY_HIP_CHECK(hipGetLastError());
   return VCY_OK;
 }

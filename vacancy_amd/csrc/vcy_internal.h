@@ -236,6 +236,8 @@ struct vcy_ctx {
   vcy::DeviceBuf<> d_dc_buf;          // the mesh, keys, both tables, flags and their scans, member rows, the outputs
   vcy::Event ev_dc[6];                // around the cluster, faces, emit launches, and around the normals (vcy_last_decimate_ms)
   float last_decimate_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  vcy::Event ev_dq[2];                // around the quadric stage of vcy_decimate_mesh_quadric (vcy_last_quadric_ms)
+  float last_quadric_ms = 0.0f;
 
   // upper bound on any voxel's update_num (each carved view adds at most one)
   int64_t views_carved = 0;
@@ -295,11 +297,13 @@ int launch_mesh_normals(hipStream_t stream, int64_t n_vertices, int64_t n_faces,
 // results are device pointers into that pool
 int mesh_normals_device(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* d_vertices, const int32_t* d_faces,
                         bool vertex_normals, float** d_face_normals, float** d_vertex_normals);
-// mesh_decimate.hip: vcy_decimate_mesh, vcy_last_decimate_ms; mesh_decimate_host.hip (host code only):
-// vcy_decimate_mesh_host and the argument checks of the two; what the two share: mesh_decimate.h
+// mesh_decimate.hip: vcy_decimate_mesh, vcy_last_decimate_ms, vcy_decimate_mesh_quadric, vcy_last_quadric_ms;
+// mesh_decimate_host.hip (host code only): vcy_decimate_mesh_host, vcy_decimate_mesh_quadric_host and the argument checks
+// of the four (`regularize` non-NULL: those of the quadric entry points); what device and host share: mesh_decimate.h,
+// mesh_quadric.h
 int decimate_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
                         const vcy_decimate_option* option, const float* vertices_out, const int32_t* faces_out,
-                        const int64_t* n_vertices_out, const int64_t* n_faces_out);
+                        const int64_t* n_vertices_out, const int64_t* n_faces_out, const float* regularize = nullptr);
 // the in-place exclusive scan of mc_kernels.hip for the other compactions of the library; `scratch`: the chunk sums of
 // every level, scan_scratch_words(n) words
 int device_exclusive_scan_u64(unsigned long long* d, int64_t n, unsigned long long* d_total, unsigned long long* scratch,

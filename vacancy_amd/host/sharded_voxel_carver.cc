@@ -423,6 +423,23 @@ bool ShardedVoxelCarver::DecimateMesh(Mesh* mesh, float cell, int mode, bool wit
                                         float* fn) { return vcy_decimate_mesh(ctx, nv, nf, v, f, o, vo, fo, nvo, nfo, map, src, vn, fn); });
 }
 
+bool ShardedVoxelCarver::DecimateMeshQuadric(Mesh* mesh, float cell, float regularize, bool with_normals, std::int64_t* n_fallback) {
+  if (impl_->slabs.empty() || !mesh) {
+    LOGE("ShardedVoxelCarver::DecimateMeshQuadric needs a mesh and an initialized carver\n");
+    return false;
+  }
+  vcy_ctx* ctx = impl_->slabs[0];
+  int64_t fallbacks = 0;
+  const bool ok = detail::DecimateMeshWith(
+      mesh, cell, impl_->option.bb_min, VCY_DECIMATE_MEAN, with_normals,
+      [ctx, regularize, &fallbacks](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_decimate_option* o, float* vo,
+                                    int32_t* fo, int64_t* nvo, int64_t* nfo, int32_t* map, int32_t* src, float* vn, float* fn) {
+        return vcy_decimate_mesh_quadric(ctx, nv, nf, v, f, o, regularize, vo, fo, nvo, nfo, map, src, vn, fn, &fallbacks);
+      });
+  if (ok && n_fallback) *n_fallback = fallbacks;
+  return ok;
+}
+
 bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!std::isfinite(fill_sdf) || !(static_cast<double>(fill_sdf) >= iso_level)) {
     LOGE("KeepLargestComponents: fill_sdf %g must be finite and not below the iso level %g\n", static_cast<double>(fill_sdf),

@@ -81,6 +81,15 @@ bool Mesh::Decimate(float cell, int mode) {
   return detail::DecimateMeshWith(this, cell, Eigen::Vector3f(0.0f, 0.0f, 0.0f), mode, false, &vcy_decimate_mesh_host);
 }
 
+bool Mesh::DecimateQuadric(float cell, float regularize) {
+  return detail::DecimateMeshWith(this, cell, Eigen::Vector3f(0.0f, 0.0f, 0.0f), VCY_DECIMATE_MEAN, false,
+                                  [regularize](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_decimate_option* o,
+                                               float* vo, int32_t* fo, int64_t* nvo, int64_t* nfo, int32_t* map, int32_t* src, float* vn,
+                                               float* fn) {
+                                    return vcy_decimate_mesh_quadric_host(nv, nf, v, f, o, regularize, vo, fo, nvo, nfo, map, src, vn, fn, nullptr);
+                                  });
+}
+
 // ---- PLY --------------------------------------------------------------------------------------
 // ASCII layout of the reference writer (mesh.cc:583-631): "x y z \n" with ostream default
 // formatting (== %g) and "3 a b c \n".

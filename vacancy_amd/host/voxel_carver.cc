@@ -554,9 +554,36 @@ bool VoxelCarver::DecimateMesh(Mesh* mesh, float cell, int mode, bool with_norma
                                         float* fn) { return vcy_decimate_mesh(ctx, nv, nf, v, f, o, vo, fo, nvo, nfo, map, src, vn, fn); });
 }
 
+bool VoxelCarver::DecimateMeshQuadric(Mesh* mesh, float cell, float regularize, bool with_normals, std::int64_t* n_fallback) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (!mesh) {
+    LOGE("VoxelCarver::DecimateMeshQuadric needs a mesh\n");
+    return false;
+  }
+  vcy_ctx* ctx = impl_->ctx;
+  int64_t fallbacks = 0;
+  const bool ok = detail::DecimateMeshWith(
+      mesh, cell, impl_->option.bb_min, VCY_DECIMATE_MEAN, with_normals,
+      [ctx, regularize, &fallbacks](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_decimate_option* o, float* vo,
+                                    int32_t* fo, int64_t* nvo, int64_t* nfo, int32_t* map, int32_t* src, float* vn, float* fn) {
+        return vcy_decimate_mesh_quadric(ctx, nv, nf, v, f, o, regularize, vo, fo, nvo, nfo, map, src, vn, fn, &fallbacks);
+      });
+  if (ok && n_fallback) *n_fallback = fallbacks;
+  return ok;
+}
+
 std::array<float, 4> VoxelCarver::last_decimate_ms() const {
   std::array<float, 4> ms = {{0.0f, 0.0f, 0.0f, 0.0f}};
   if (impl_->ctx) vcy_last_decimate_ms(impl_->ctx, &ms[0], &ms[1], &ms[2], &ms[3]);
+  return ms;
+}
+
+float VoxelCarver::last_quadric_ms() const {
+  float ms = 0.0f;
+  if (impl_->ctx) vcy_last_quadric_ms(impl_->ctx, &ms);
   return ms;
 }
 

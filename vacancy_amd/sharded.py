@@ -228,6 +228,12 @@ class ShardedVoxelCarver:
             origin = tuple(self.option.bb_min)
         return self.slabs[0].DecimateMesh(vertices, faces, cell, origin, mode, normals)
 
+    def DecimateMeshQuadric(self, vertices, faces, cell, origin=None, regularize=1e-3, normals=False):
+        """VoxelCarver.DecimateMeshQuadric on the first slab's context: the same dict."""
+        if origin is None:
+            origin = tuple(self.option.bb_min)
+        return self.slabs[0].DecimateMeshQuadric(vertices, faces, cell, origin, regularize, normals)
+
     def last_stream_ms(self):
         """[(producer ms, carve ms, wall ms)] per slab of the last CarveBatchSilhouettes."""
         return [c.last_stream_ms() for c in self.slabs]
