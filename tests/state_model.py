@@ -1,7 +1,7 @@
 """Every writer of the voxel state against every reader that keeps something derived from it, in sequences.
 
 A vcy_ctx holds flags and counters beside the state (fresh, cnt_implied, the brick minima, halo_valid, the queue of deferred
-views, state_epoch and the ray-cast's bit planes, the marching-cubes size hints, the component labels); every reader is right
+views, the epoch of the state and the ray-cast's bit planes, the marching-cubes size hints, the component labels); every reader is right
 only if every writer cleared exactly the right ones.  This module has
 
   Model   (sdf, update_num) of the WHOLE grid on the CPU, every writer applied with the restatement the suite already trusts
@@ -63,7 +63,7 @@ ROBUST_TOLERATE = 1
 DEPTH_BAND = 2.0
 # The ray-casts of a case -- RenderHull and the internal one of ColorVertices -- walk through this pattern, so that the iso
 # level of the kept bit planes moves between some casts and stays between others: with two casts per round of readers every
-# FIRST cast after a writer asks for the level the planes were last built for, where only state_epoch makes them stale.  (At
+# FIRST cast after a writer asks for the level the planes were last built for, where only the epoch of the state makes them stale.  (At
 # -0.3 the hull is smaller with truncation and EMPTY without: test_state_model_cpu.py says why; kept planes show either way.)
 RENDER_ISOS = (0.0, -0.3)
 ISO_PATTERN = (0.0, -0.3, -0.3, 0.0)

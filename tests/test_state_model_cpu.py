@@ -1,6 +1,8 @@
 """The conditions that keep tests/test_gpu_state_pairs.py and tests/test_gpu_state_sequences.py from passing vacuously, checked on
 the model alone (tests/state_model.py; no GPU): every writer changes the base state, the states have something to extract, to
 render and to label, the collected seeds cover what they are meant to cover, and the model agrees with itself."""
+import os
+import subprocess
 import time
 
 import numpy as np
@@ -159,3 +161,14 @@ def test_model_time_per_pair_case():
     per_case = (time.perf_counter() - t0) / len(pairs)
     print("model time per pair case at %s: %.2f s" % (dims, per_case))
     assert per_case < 3.0
+
+
+def test_state_flags_follow_the_transition_table_under_host_sanitizers():
+    """The stand-alone program of tests/state_flags_host_check.cpp: every writer's declaration from every reachable combination
+    of what a context keeps beside its state (vacancy_amd/csrc/state_flags.h), against the table written out there as data,
+    under AddressSanitizer and UBSan, on the CPU."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run(["make", "-C", os.path.join(root, "vacancy_amd", "csrc"), "-s", "state_flags_host_check"],
+                         capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "state_flags_host_check: ok" in run.stdout

@@ -43,6 +43,17 @@ struct ModeParams {
 int resolve_views(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* sdf_dev,
                   std::vector<ViewParams>* out);
 
+// What the per-view, the robust and the depth carve share beside the kernels' arithmetic (carve_kernels.hip):
+// the owned slab as the kernels see it, `cnt` at the width the counters have NOW (ensure_count_width may change it)
+GridParams slab_grid_params(const vcy_ctx* ctx);
+// one lane per voxel of the owned slab: blockIdx.x over (y, 256-voxel segment of the row), z = blockIdx.y + 65535 *
+// blockIdx.z (a 1-D grid of a 2048^3 slab would exceed the 2^32 threads of a launch dimension); the kernel checks x and z
+int voxel_lane_grid(const vcy_ctx* ctx, int* segs_per_row, dim3* grid);
+// device memory for the images a call takes from the host: one allocation, every image 256-byte aligned (`who`, `what`:
+// for the out-of-memory message)
+int alloc_view_images(const char* who, const char* what, int n_views, const vcy_view* views, DeviceBuf<char>* owner,
+                      std::vector<float*>* images);
+
 // ---- sampling, shared by every carve kernel --------------------------------------------
 
 __device__ __forceinline__ float tap(const float* __restrict__ s, int width, int x, int y) {
@@ -140,6 +151,5 @@ __device__ __forceinline__ bool fuse(const ModeParams& m, float weight, float di
   n = n + 1;
   return true;
 }
-
 
 }  // namespace vcy

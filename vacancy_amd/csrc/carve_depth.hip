@@ -86,19 +86,15 @@ int depth_check(vcy_ctx* c, int n_views, const vcy_view* views, const void* cons
   return check_carve_views(c, n_views, views);
 }
 
-// The launches and the bookkeeping of the state (the non-fused branch of launch_carve); the arguments have passed
-// depth_check and the images are on the context's device.
+// The launches and the bookkeeping of the state; the arguments have passed depth_check and the images are on the context's
+// device.
 int depth_run(vcy_ctx* c, int n_views, const vcy_view* views, const float* const* depth_dev, float band) {
   VCY_HIP_CHECK(hipSetDevice(c->device));
-  {
-    const int rcf = flush_pending(c, true);  // views queued by earlier calls are applied (and their failure reported) first
-    if (rcf != VCY_OK) return rcf;
-  }
-  const int segs = (c->nx + 255) / 256;
-  if ((int64_t)c->ny * segs > 0xffffffLL) {
-    set_error("slab too large for one launch");
-    return VCY_ERR_TOO_MANY_VOXELS;
-  }
+  // views queued by earlier calls are applied (and their failure reported) first
+  { const int rcf = flush_pending(c, true); if (rcf != VCY_OK) return rcf; }
+  DepthLaunch L;
+  dim3 grid;
+  { const int rcg = voxel_lane_grid(c, &L.segs_per_row, &grid); if (rcg != VCY_OK) return rcg; }
   const vcy_update_option& u = c->opt.update_option;
   std::vector<dp::View> rec((size_t)n_views);
   for (int i = 0; i < n_views; ++i) dp::fill_view(views[i], depth_dev[i], &rec[(size_t)i]);
@@ -109,39 +105,18 @@ int depth_run(vcy_ctx* c, int n_views, const vcy_view* views, const float* const
   if (c->ev_dp.size() < 2 * (size_t)n_chunks) c->ev_dp.resize(2 * (size_t)n_chunks);
   for (int k = 0; k < 2 * n_chunks; ++k) VCY_HIP_CHECK(c->ev_dp[(size_t)k].ensure());
 
-  ++c->state_epoch;  // (vcy_render_hull builds its bit planes again)
-  {
-    const int rcm = materialize(c);
-    if (rcm != VCY_OK) return rcm;
-  }
-  c->brick_min_valid = false;  // (this kernel does not keep the brick minima)
-  c->cc_slab_labelled = false;
-  c->halo_valid = false;
-
-  DepthLaunch L;
-  L.g.sdf = c->owned_slab_sdf();
-  L.g.cnt = nullptr;  // set per launch: the counter array may be widened between two chunks (ensure_count_width)
-  L.g.px = c->d_px;
-  L.g.py = c->d_py;
-  L.g.pz = c->d_pz;
-  L.g.nx = c->nx;
-  L.g.ny = c->ny;
-  L.g.z0 = c->z0;
-  L.g.nz_local = c->nz_local();
-  L.g.max_update_num = u.voxel_max_update_num;
-  L.g.weight = u.voxel_update_weight;
-  L.segs_per_row = segs;
+  // from here on the state is the call's (this kernel does not keep the brick minima)
+  const int64_t before = c->st.views_carved;
+  c->st.written(StateWrite::depth(n_views));
+  { const int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
+  L.g = slab_grid_params(c);  // (L.g.cnt again per launch below: ensure_count_width may widen between two)
   L.inv_band = 1.0f / band;
-  const int nzl = c->nz_local();
-  const dim3 grid((unsigned)(c->ny * segs), (unsigned)std::min(nzl, 65535), (unsigned)((nzl + 65534) / 65535));
 
   int chunks_run = 0;
   for (int first = 0; first < n_views; first += dp::kMaxViewsPerLaunch, ++chunks_run) {
     const int m = std::min(dp::kMaxViewsPerLaunch, n_views - first);
-    {
-      const int rcw = ensure_count_width(c, c->views_carved + m);  // (update_num <= views applied)
-      if (rcw != VCY_OK) return rcw;
-    }
+    // (update_num <= views applied)
+    { const int rcw = ensure_count_width(c, before + first + m); if (rcw != VCY_OK) return rcw; }
     L.g.cnt = c->owned_slab_cnt();
     L.views = d_rec + first;
     L.n_views = m;
@@ -151,7 +126,6 @@ int depth_run(vcy_ctx* c, int n_views, const vcy_view* views, const float* const
     else launch_depth<uint32_t>(L, u.voxel_update, grid, c->stream);
     VCY_HIP_CHECK(hipGetLastError());
     VCY_HIP_CHECK(hipEventRecord(c->ev_dp[2 * (size_t)chunks_run + 1], c->stream));
-    c->views_carved += m;
   }
   VCY_HIP_CHECK(hipStreamSynchronize(c->stream));  // (the view records and the caller's images go with this call)
   float total = 0.0f;
@@ -181,20 +155,12 @@ int vcy_carve_depth(vcy_ctx* c, int n_views, const vcy_view* views, const float*
   const int rc = depth_check(c, n_views, views, (const void* const*)depth_host, band);
   if (rc != VCY_OK) return rc;
   VCY_HIP_CHECK(hipSetDevice(c->device));
-  std::vector<size_t> off((size_t)n_views + 1, 0);
-  for (int i = 0; i < n_views; ++i)
-    off[(size_t)i + 1] = off[(size_t)i] + (sizeof(float) * (size_t)views[i].width * views[i].height + 255) / 256 * 256;
   DeviceBuf<char> d_images;
-  if (d_images.alloc(off[(size_t)n_views]) != hipSuccess) {
-    set_error("depth carve: out of device memory for %d depth images (%zu bytes)", n_views, off[(size_t)n_views]);
-    return VCY_ERR_HIP;
-  }
-  std::vector<const float*> images((size_t)n_views);
-  for (int i = 0; i < n_views; ++i) {
-    images[(size_t)i] = (const float*)(d_images + off[(size_t)i]);
-    VCY_HIP_CHECK(hipMemcpyAsync(d_images + off[(size_t)i], depth_host[i], sizeof(float) * (size_t)views[i].width * views[i].height,
+  std::vector<float*> images;
+  { const int rca = alloc_view_images("depth carve", "depth", n_views, views, &d_images, &images); if (rca != VCY_OK) return rca; }
+  for (int i = 0; i < n_views; ++i)
+    VCY_HIP_CHECK(hipMemcpyAsync(images[(size_t)i], depth_host[i], sizeof(float) * (size_t)views[i].width * views[i].height,
                                  hipMemcpyHostToDevice, c->stream));
-  }
   return depth_run(c, n_views, views, images.data(), band);
 }
 

@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void c0_records_kernel(const FusedView* __rest
 // True when the fused kernel can take these views (otherwise the per-view kernel does).
 bool fused_eligible(const vcy_ctx* c, int n_views, const vcy_view* views) {
   const vcy_update_option& u = c->opt.update_option;
-  if (count_width_for(c, c->views_carved + n_views) > 2) return false;  // (32-bit counters: the per-view kernel)
+  if (count_width_for(c, c->st.views_carved + n_views) > 2) return false;  // (32-bit counters: the per-view kernel)
   if (u.voxel_update == VCY_UPDATE_WEIGHTED_AVERAGE && !sane(u.voxel_update_weight)) return false;
   // (the view step addresses the view and c0 records of a LAUNCH with 32-bit byte offsets, and a launch holds at most
   // kMaxFusedViews views: with them it cannot happen below 2^18 bricks along x, but the kernel relies on it)
@@ -461,8 +461,9 @@ void build_window_planes(vcy_ctx* c, const PreparedViews& pv, int n_views, bool 
   }
 }
 
-// Carves views[0..n_views) (n_views <= 32, max_sdf already resolved) in one launch.
-int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewParams* vp) {
+// Carves views[0..n_views) (n_views <= 32, max_sdf already resolved) in one launch.  The caller has declared the write
+// (StateFlags::written, once for all its launches); `views_before`: views applied since the fill when this one starts.
+int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewParams* vp, int64_t views_before) {
   const vcy_update_option& u = c->opt.update_option;
   const int nzl = c->nz_local();
   const int nxp = (c->nx + WX - 1) / WX * WX, nbw = nxp / WX;
@@ -513,7 +514,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
   }
   c->last_div_level = m.div_level;
   // update_num can only exceed voxel_max_update_num after more than that many views
-  const bool checkmax = c->views_carved + n_views > (int64_t)u.voxel_max_update_num;
+  const bool checkmax = views_before + n_views > (int64_t)u.voxel_max_update_num;
   // Tile kind: footprint of an 8x8x8 wave brick in pixels ~ (8*sqrt(3)*pixels_per_voxel + 3)^2.  The raw
   // 16 x 16 pixel tile covers voxels up to ~0.85 px; the 2048-pixel tile filled in place up to ~3 px; wider
   // footprints take the generic path inside the kernel either way.
@@ -541,16 +542,15 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
   if (!c->d_brick_min) {
     const size_t bytes = sizeof(float) * (size_t)nbw * nby * nbz;
     if (c->d_brick_min.alloc(bytes) != hipSuccess) (void)hipGetLastError();
-    c->brick_min_valid = false;
   }
-  if (!c->cnt_implied) c->brick_min_valid = false;
+  // (st.brick_min_valid is only ever true with the array allocated and cnt_implied: StateFlags)
   // Not every wave of the launches below rewrites its entry: a wave whose every view lies below the truncation limit
   // returns before it has read anything, a workgroup left off the live list never starts.  That is harmless while the
   // entry was valid on entry (it still is).  When it was not -- the per-view kernel or a vcy_upload has written to the
   // state since, or the array has just been allocated over a slab that is not fresh -- every entry starts from
   // lowest(): "a voxel of this brick may be untouched", which never drops a view and never lets marching cubes skip
   // the brick.  (A fresh slab needs nothing: there every wave runs and stores its minimum.)
-  if (c->d_brick_min && !c->fresh && !c->brick_min_valid && c->cnt_implied) {
+  if (c->d_brick_min && !c->st.fresh && !c->st.brick_min_valid && c->st.cnt_implied) {
     const int64_t nb = (int64_t)nbw * nby * nbz;
     hipLaunchKernelGGL(fill_lowest_kernel, dim3((unsigned)std::min<int64_t>((nb + 255) / 256, 4096)), dim3(256), 0,
                        c->stream, c->d_brick_min, nb);
@@ -574,14 +574,14 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
   // a launch of ONE view through the kernel instance that knows it ("oneview" 0: the general instance)
   const bool one_view = c->one_view && n_views == 1 && !rows && !big && !checkmax && c->prologue_mode != 1;
   const bool coop_ok = (kWgWaves == 4 || kWgWaves == 8) && (c->nx & (WX - 1)) == 0 && !big && !rows;
-  const int coop_views = c->fresh ? 1 : (u.voxel_update == VCY_UPDATE_MAX ? 1 : kLiveListMaxViews);
+  const int coop_views = c->st.fresh ? 1 : (u.voxel_update == VCY_UPDATE_MAX ? 1 : kLiveListMaxViews);
   const bool coop = coop_ok && (c->coop_store > 0 || (c->coop_store < 0 && n_views <= coop_views));
   // "ntstore": streaming stores whenever the cooperative write-back runs (0: never) -- whole 128-byte segments that this
   // launch does not read again: 0.5 - 1.5 % on single-view launches (profiles/r06/nontemporal.txt)
   const bool nt = coop && c->nt_store != 0;
   // (kStateEager and kStateListRecords are decided per chunk below: they depend on whether the launch is a listed one)
-  const int state_flags_base = (c->fresh ? kStateFresh : 0) | (c->cnt_implied ? kStateCountImplied : 0) |
-                               (c->brick_min_valid && !c->fresh ? kStateBrickMinValid : 0) |
+  const int state_flags_base = (c->st.fresh ? kStateFresh : 0) | (c->st.cnt_implied ? kStateCountImplied : 0) |
+                               (c->st.brick_min_valid && !c->st.fresh ? kStateBrickMinValid : 0) |
                                (coop ? kStateCoopStore : 0) | (nt ? kStateStreamStore : 0);
   // Raw tiles: the footprint records of every (wave brick, view) pair come from a pre-pass (footprint_records_kernel),
   // 8 bytes per pair.  The slab is carved in chunks of whole brick layers so that the records of a chunk stay
@@ -658,7 +658,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
     const bool list_pays = c->h_live_hint == nullptr || c->h_live_hint[1] <= 0 ||
                            (double)c->h_live_hint[0] < 0.6 * (double)c->h_live_hint[1];
     ++c->live_list_age;
-    if (!big && recs != nullptr && c->use_live_list && need_bound && !c->fresh && n_views <= kLiveListMaxViews && (m.trunc != 0 || have_min) &&
+    if (!big && recs != nullptr && c->use_live_list && need_bound && !c->st.fresh && n_views <= kLiveListMaxViews && (m.trunc != 0 || have_min) &&
         (list_pays || c->live_list_age % 16 == 0)) {  // (every 16th launch looks again)
       const int nwg = (int)grid.x;
       // (a launch of ONE view: entries {id, live waves, the four records} -- "listrecords" 0: ids only)
@@ -694,7 +694,7 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
     // that skipped its list because the last one held most workgroups (-1 that rule, 0 never, 1 every one-view launch).
     // 1024^3, one view per launch: weighted average 2.51 -> 2.46 ms, kMax 0.521 -> 0.487 (profiles/r06/eager_state.txt).
     const bool nearly_all_live = wgl != nullptr ? launch_grid.x < grid.x || !list_pays : !list_pays;
-    const bool eager_state = !c->fresh && one_view &&
+    const bool eager_state = !c->st.fresh && one_view &&
                              (c->eager_state > 0 || (c->eager_state < 0 && nearly_all_live));
     CarveLaunch launch;
     launch.update = u.voxel_update == VCY_UPDATE_MAX ? VCY_UPDATE_MAX
@@ -720,9 +720,9 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
     if (stamp >= 0) VCY_HIP_CHECK(hipEventRecord(c->carve_log[stamp].ev[2], c->stream));
   }
   log_guard.done = true;
-  c->fresh = false;  // the launches store every voxel of a fresh slab
+  c->st.stored();  // the launches store every voxel of a fresh slab
   // (every wave that ran to its end wrote its entry; the others' entries were valid on entry or hold lowest(), see above)
-  c->brick_min_valid = c->d_brick_min != nullptr && c->cnt_implied;
+  c->st.minima_rebuilt(c->d_brick_min != nullptr);
   return VCY_OK;
 }
 

@@ -91,11 +91,41 @@ static void fill_view(const vcy_view& in, const float* sdf_dev, float max_sdf, V
   v->sdf = sdf_dev;
 }
 
-template <typename CountT>
-static void launch_view(vcy_ctx* c, const GridParams& g, const ViewParams& v, const ModeParams& m) {
+GridParams slab_grid_params(const vcy_ctx* c) {
+  const vcy_update_option& u = c->opt.update_option;
+  return GridParams{c->owned_slab_sdf(), c->owned_slab_cnt(), c->d_px, c->d_py, c->d_pz, c->nx, c->ny, c->z0, c->nz_local(),
+                    u.voxel_max_update_num, u.voxel_update_weight};
+}
+
+int voxel_lane_grid(const vcy_ctx* c, int* segs_per_row, dim3* grid) {
   const int segs = (c->nx + 255) / 256;
+  if ((int64_t)c->ny * segs > 0xffffffLL) {
+    set_error("slab too large for one launch");
+    return VCY_ERR_TOO_MANY_VOXELS;
+  }
   const int nzl = c->nz_local();
-  const dim3 grid((unsigned)(c->ny * segs), (unsigned)std::min(nzl, 65535), (unsigned)((nzl + 65534) / 65535)), block(256);
+  *segs_per_row = segs;
+  *grid = dim3((unsigned)(c->ny * segs), (unsigned)std::min(nzl, 65535), (unsigned)((nzl + 65534) / 65535));
+  return VCY_OK;
+}
+
+int alloc_view_images(const char* who, const char* what, int n_views, const vcy_view* views, DeviceBuf<char>* owner,
+                      std::vector<float*>* images) {
+  std::vector<size_t> off((size_t)n_views + 1, 0);
+  for (int i = 0; i < n_views; ++i)
+    off[(size_t)i + 1] = off[(size_t)i] + (sizeof(float) * (size_t)views[i].width * views[i].height + 255) / 256 * 256;
+  if (owner->alloc(off[(size_t)n_views]) != hipSuccess) {
+    set_error("%s: out of device memory for %d %s images (%zu bytes)", who, n_views, what, off[(size_t)n_views]);
+    return VCY_ERR_HIP;
+  }
+  images->resize((size_t)n_views);
+  for (int i = 0; i < n_views; ++i) (*images)[(size_t)i] = (float*)(*owner + off[(size_t)i]);
+  return VCY_OK;
+}
+
+template <typename CountT>
+static void launch_view(vcy_ctx* c, const GridParams& g, const ViewParams& v, const ModeParams& m, dim3 grid, int segs) {
+  const dim3 block(256);
   const bool is_default = m.update == VCY_UPDATE_MAX && m.interp == VCY_INTERP_BILINEAR &&
                           m.outside == VCY_OUTSIDE_NONE && !m.trunc && !m.ortho;
   const bool is_tsdf = m.update == VCY_UPDATE_WEIGHTED_AVERAGE && m.interp == VCY_INTERP_BILINEAR &&
@@ -145,7 +175,6 @@ int resolve_views(vcy_ctx* c, int n_views, const vcy_view* views, const float* c
   return VCY_OK;
 }
 
-
 // Applies the views queued by the per-view entry points, in order, as one batch.  `from_carve`: the caller is
 // a carve entry point, whose own return value carries a failure to the `if (!Carve())` of the host loop; any
 // other caller (an extraction, a download ...) cannot, so the failure is kept for the next carve call.
@@ -160,15 +189,13 @@ int flush_pending(vcy_ctx* c, bool from_carve) {
     ptrs[i] = todo[i].d_sdf;
   }
   VCY_HIP_CHECK(hipSetDevice(c->device));
-  // the halo slices were invalidated when the views were queued; halos installed since then were taken
-  // from a neighbour that has applied the same views and stay valid
-  const bool halo_valid = c->halo_valid;
-  const int rc = launch_carve(c, (int)todo.size(), views.data(), ptrs.data());
+  // `queued`: the one write that leaves the halo slices as they are.  They were invalidated when the views were queued
+  // (enqueue_view); a halo installed since then was taken from a neighbour that has applied the same views.
+  const int rc = launch_carve(c, (int)todo.size(), views.data(), ptrs.data(), /*queued=*/true);
   if (rc != VCY_OK && !from_carve) {  // also reported by the next carve call (vacancy_hip.h, vcy_carve)
     c->deferred_rc = rc;
     c->deferred_msg = vcy_last_error();
   }
-  c->halo_valid = halo_valid;
   // stream order: a buffer handed out again is only written after this launch
   for (auto& t : todo) c->sdf_pool.push_back(std::move(t.d_sdf));
   // image sizes that keep changing would let idle buffers pile up: keep at most two queues' worth
@@ -177,73 +204,50 @@ int flush_pending(vcy_ctx* c, bool from_carve) {
   return rc;
 }
 
-int launch_carve(vcy_ctx* c, int n_views, const vcy_view* views, const float* const* sdf_dev) {
-  {
-    const int rcf = flush_pending(c, true);  // earlier per-view calls come first
-    if (rcf != VCY_OK) return rcf;
-  }
+int launch_carve(vcy_ctx* c, int n_views, const vcy_view* views, const float* const* sdf_dev, bool queued) {
+  { const int rcf = flush_pending(c, true); if (rcf != VCY_OK) return rcf; }  // earlier per-view calls come first
   if (c->inject_fail > 0) {  // test hook (vcy_set_param "inject_carve_failure"): this application of views fails
     --c->inject_fail;
     set_error("injected failure (vcy_set_param inject_carve_failure)");
     return VCY_ERR_INTERNAL;
   }
   const vcy_update_option& u = c->opt.update_option;
-  GridParams g;
-  g.sdf = c->owned_slab_sdf();
-  g.cnt = nullptr;  // set per launch below: the counter array may be widened between two chunks (ensure_count_width)
-  g.px = c->d_px;
-  g.py = c->d_py;
-  g.pz = c->d_pz;
-  g.nx = c->nx;
-  g.ny = c->ny;
-  g.z0 = c->z0;
-  g.nz_local = c->nz_local();
-  g.max_update_num = u.voxel_max_update_num;
-  g.weight = u.voxel_update_weight;
-  if ((int64_t)c->ny * ((c->nx + 255) / 256) > 0xffffffLL) {
-    set_error("slab too large for one launch");
-    return VCY_ERR_TOO_MANY_VOXELS;
-  }
-
+  int segs = 0;
+  dim3 grid;
+  { const int rcg = voxel_lane_grid(c, &segs, &grid); if (rcg != VCY_OK) return rcg; }
+  GridParams g = slab_grid_params(c);  // (g.cnt again per launch below: ensure_count_width may widen between two)
   std::vector<ViewParams> vp;
-  {
-    const int rcv = resolve_views(c, n_views, views, sdf_dev, &vp);
-    if (rcv != VCY_OK) return rcv;
-  }
+  { const int rcv = resolve_views(c, n_views, views, sdf_dev, &vp); if (rcv != VCY_OK) return rcv; }
 
-  ++c->state_epoch;  // (whatever is launched below changes the state: vcy_render_hull builds its bit planes again)
+  // From here on the state is the call's, whatever becomes of its launches.  The fused kernel keeps the brick minima, the
+  // per-view kernel does not.
   const bool fused = c->use_fused && fused_eligible(c, n_views, views);
-  if (!fused) {
-    int rcm = materialize(c);
-    if (rcm != VCY_OK) return rcm;
-  }
+  const int64_t before = c->st.views_carved;
+  c->st.written(StateWrite::silhouettes(n_views, fused, queued));
   if (fused) {
     c->fused_ortho = views[0].is_ortho != 0;
     const int chunk = fused_max_views();
     for (int i = 0; i < n_views; i += chunk) {
       const int m = std::min(chunk, n_views - i);
-      int rc = ensure_count_width(c, c->views_carved + m);  // (update_num <= views applied: u8 up to the 255th view)
+      int rc = ensure_count_width(c, before + i + m);  // (update_num <= views applied: u8 up to the 255th view)
       if (rc != VCY_OK) return rc;
       g.cnt = c->owned_slab_cnt();
-      rc = launch_carve_fused(c, g, m, &vp[i]);
+      rc = launch_carve_fused(c, g, m, &vp[i], before + i);
       if (rc != VCY_OK) return rc;
-      c->views_carved += m;
     }
   } else {
-    c->brick_min_valid = false;  // (the per-view kernel does not keep the brick minima)
+    { const int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
     for (int i = 0; i < n_views; ++i) {
       ModeParams m{u.voxel_update, u.sdf_interp, u.update_outside, u.use_truncation ? 1 : 0,
                    views[i].is_ortho ? 1 : 0, 0};
-      { const int rcw = ensure_count_width(c, c->views_carved + 1); if (rcw != VCY_OK) return rcw; }
+      { const int rcw = ensure_count_width(c, before + i + 1); if (rcw != VCY_OK) return rcw; }
       g.cnt = c->owned_slab_cnt();
-      if (c->cnt_bytes == 1) launch_view<uint8_t>(c, g, vp[i], m);
-      else if (c->cnt_bytes == 2) launch_view<uint16_t>(c, g, vp[i], m);
-      else launch_view<uint32_t>(c, g, vp[i], m);
+      if (c->cnt_bytes == 1) launch_view<uint8_t>(c, g, vp[i], m, grid, segs);
+      else if (c->cnt_bytes == 2) launch_view<uint16_t>(c, g, vp[i], m, grid, segs);
+      else launch_view<uint32_t>(c, g, vp[i], m, grid, segs);
       VCY_HIP_CHECK(hipGetLastError());
-      c->views_carved += 1;
     }
   }
-  c->halo_valid = false;
   return VCY_OK;
 }
 

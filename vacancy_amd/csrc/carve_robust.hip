@@ -187,21 +187,14 @@ int robust_check(vcy_ctx* c, int n_views, const vcy_view* views, const void* con
 int robust_run(vcy_ctx* c, int n_views, const vcy_view* views, const float* const* sdf_dev, int tolerate, double iso,
                int64_t* overruled) {
   VCY_HIP_CHECK(hipSetDevice(c->device));
-  {
-    const int rcf = flush_pending(c, true);  // views queued by earlier calls are applied (and their failure reported) first
-    if (rcf != VCY_OK) return rcf;
-  }
-  const int segs = (c->nx + 255) / 256;
-  if ((int64_t)c->ny * segs > 0xffffffLL) {
-    set_error("slab too large for one launch");
-    return VCY_ERR_TOO_MANY_VOXELS;
-  }
+  // views queued by earlier calls are applied (and their failure reported) first
+  { const int rcf = flush_pending(c, true); if (rcf != VCY_OK) return rcf; }
+  int segs = 0;
+  dim3 grid;
+  { const int rcg = voxel_lane_grid(c, &segs, &grid); if (rcg != VCY_OK) return rcg; }
   const vcy_update_option& u = c->opt.update_option;
   std::vector<ViewParams> vp;
-  {
-    const int rcv = resolve_views(c, n_views, views, sdf_dev, &vp);
-    if (rcv != VCY_OK) return rcv;
-  }
+  { const int rcv = resolve_views(c, n_views, views, sdf_dev, &vp); if (rcv != VCY_OK) return rcv; }
   std::vector<RobustView> rv((size_t)n_views);
   for (int i = 0; i < n_views; ++i) rv[(size_t)i] = RobustView{vp[(size_t)i], views[i].is_ortho ? 1 : 0};
 
@@ -216,32 +209,12 @@ int robust_run(vcy_ctx* c, int n_views, const vcy_view* views, const float* cons
   VCY_HIP_CHECK(c->ev_rb_end.ensure());
 
   // The counters as a reset followed by a carve of n_views would leave them: the width that holds n_views.  What the
-  // arrays hold is about to be overwritten, so nothing is converted (set_count_width on a fresh slab).
+  // arrays hold is about to be overwritten, so nothing is converted.
   const int width = !c->lazy_count ? c->cnt_bytes_wire : (n_views <= 255 ? 1 : (n_views <= 65535 ? 2 : 4));
-  if (width != c->cnt_bytes) {
-    const bool was_fresh = c->fresh, was_halo = c->halo_valid;
-    c->fresh = true;
-    c->halo_valid = false;
-    const int rcw = set_count_width(c, width);
-    if (rcw != VCY_OK) {
-      c->fresh = was_fresh;
-      c->halo_valid = was_halo;
-      return rcw;
-    }
-  }
+  { const int rcw = set_count_width(c, width, /*keep_contents=*/false); if (rcw != VCY_OK) return rcw; }
 
   RobustLaunch L;
-  L.g.sdf = c->owned_slab_sdf();
-  L.g.cnt = c->owned_slab_cnt();
-  L.g.px = c->d_px;
-  L.g.py = c->d_py;
-  L.g.pz = c->d_pz;
-  L.g.nx = c->nx;
-  L.g.ny = c->ny;
-  L.g.z0 = c->z0;
-  L.g.nz_local = c->nz_local();
-  L.g.max_update_num = u.voxel_max_update_num;  // (not read: see the definition)
-  L.g.weight = u.voxel_update_weight;
+  L.g = slab_grid_params(c);  // (max_update_num is not read: see the definition)
   L.m = ModeParams{u.voxel_update, u.sdf_interp, u.update_outside, u.use_truncation ? 1 : 0, 0, 0};
   L.views = (const RobustView*)(char*)d_buf;
   L.n_views = n_views;
@@ -249,17 +222,11 @@ int robust_run(vcy_ctx* c, int n_views, const vcy_view* views, const float* cons
   L.iso = iso;
   L.overruled = overruled ? d_blame : nullptr;
   const bool is_default = u.sdf_interp == VCY_INTERP_BILINEAR && u.update_outside == VCY_OUTSIDE_NONE && !u.use_truncation;
-  const int nzl = c->nz_local();
-  const dim3 grid((unsigned)(c->ny * segs), (unsigned)std::min(nzl, 65535), (unsigned)((nzl + 65534) / 65535));
 
-  // from here on the state is the call's
-  c->fresh = false;
-  c->brick_min_valid = false;
-  ++c->state_epoch;
-  c->halo_valid = false;
-  c->cc_slab_labelled = false;
-  c->views_carved = n_views;
-  c->cnt_implied = true;  // (update_num = 0 only where no view gave a sample: sdf = lowest() there)
+  // From here on the state is the call's, and starts over: the launch stores every voxel, fresh or not, and leaves
+  // update_num = 0 only where no view gave a sample -- sdf = lowest() there.
+  c->st.written(StateWrite::robust(n_views));
+  c->st.stored();
 
   VCY_HIP_CHECK(hipEventRecord(c->ev_rb_begin, c->stream));
   if (c->cnt_bytes == 1) launch_robust_k<uint8_t>(L, tolerate + 1, is_default, grid, c->stream);
@@ -301,16 +268,10 @@ int vcy_carve_robust_silhouettes(vcy_ctx* c, int n_views, const vcy_view* views,
   VCY_HIP_CHECK(hipSetDevice(c->device));
   // every SDF image of the call on the device at once (the order statistic needs all views in one launch), built by the
   // batch builder of the streamed paths
-  std::vector<size_t> off((size_t)n_views + 1, 0);
-  for (int i = 0; i < n_views; ++i)
-    off[(size_t)i + 1] = off[(size_t)i] + (sizeof(float) * (size_t)views[i].width * views[i].height + 255) / 256 * 256;
   DeviceBuf<char> d_images;
-  if (d_images.alloc(off[(size_t)n_views]) != hipSuccess) {
-    set_error("robust carve: out of device memory for %d SDF images (%zu bytes)", n_views, off[(size_t)n_views]);
-    return VCY_ERR_HIP;
-  }
-  std::vector<float*> images((size_t)n_views);
-  for (int i = 0; i < n_views; ++i) images[(size_t)i] = (float*)(d_images + off[(size_t)i]);
+  std::vector<float*> images;
+  rc = alloc_view_images("robust carve", "SDF", n_views, views, &d_images, &images);
+  if (rc != VCY_OK) return rc;
   rc = vcy_make_sdf_batch_device(c, n_views, views, masks_host, images.data());
   if (rc != VCY_OK) return rc;
   return robust_run(c, n_views, views, images.data(), tolerate, iso_level, overruled);

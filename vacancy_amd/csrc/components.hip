@@ -378,7 +378,7 @@ int launch_solid_bits(vcy_ctx* c, double iso, unsigned long long* bits) {
   const dim3 grid((unsigned)((nwords + 4 * cc::kBitsWordsPerWave - 1) / (4 * cc::kBitsWordsPerWave)));
 #define VCY_CC_BITS(T, IMPL) \
   hipLaunchKernelGGL((cc::cc_bits_kernel<T, IMPL>), grid, dim3(256), 0, c->stream, sdf, (const T*)cnt, nx, Wr, nwords, iso, bits)
-  if (c->cnt_implied) VCY_CC_BITS(uint8_t, true);
+  if (c->st.cnt_implied) VCY_CC_BITS(uint8_t, true);
   else if (c->cnt_bytes == 1) VCY_CC_BITS(uint8_t, false);
   else if (c->cnt_bytes == 2) VCY_CC_BITS(uint16_t, false);
   else VCY_CC_BITS(uint32_t, false);
@@ -395,7 +395,7 @@ int launch_solid_bits(vcy_ctx* c, double iso, unsigned long long* bits) {
 static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* comps, std::vector<int>* slot_of_comp) {
   comps->clear();
   if (slot_of_comp) slot_of_comp->clear();
-  c->cc_slab_labelled = false;
+  c->st.labelling_dropped();
   c->cc_roots_host.clear();
   c->cc_nvox_host.clear();
   c->cc_global_host.clear();
@@ -404,7 +404,7 @@ static int label_components(vcy_ctx* c, double iso, std::vector<vcy_component>* 
   { const int rcf = flush_pending(c); if (rcf != VCY_OK) return rcf; }
   c->cc_labels_valid = true;
   c->cc_n_roots = 0;
-  if (c->fresh) {  // nothing carved since the fill: no voxel is solid, and the lazy fill stays lazy
+  if (c->st.fresh) {  // nothing carved since the fill: no voxel is solid, and the lazy fill stays lazy
     c->cc_labels_empty = true;
     return VCY_OK;
   }
@@ -524,8 +524,10 @@ static int launch_filter(vcy_ctx* c, const std::vector<uint8_t>& removed, int ke
   const int nzl = c->nz_local();
   const int nbw = (c->nx + 7) / 8, nby = (c->ny + 7) / 8, nbz = (nzl + 7) / 8;
   const int64_t nbricks = (int64_t)nbw * nby * nbz;
-  float* bmin = c->brick_min_valid && c->d_brick_min ? c->d_brick_min : nullptr;
-  ++c->state_epoch;  // (solid voxels go: the bit planes of the ray-cast are stale)
+  float* bmin = c->st.brick_min_valid && c->d_brick_min ? c->d_brick_min : nullptr;
+  // solid voxels go: the ray-cast's bit planes and a slab's labelling are stale, and so are the two slices the slab above
+  // keeps of this one.  The kernel keeps the brick minima where they were valid.
+  c->st.written(StateWrite::filter());
   hipLaunchKernelGGL(cc::cc_filter_kernel, dim3((unsigned)((nbricks + 3) / 4)), dim3(256), 0, c->stream, c->owned_slab_sdf(),
                      (const int*)c->d_cc_labels, c->nx, c->ny, nzl, nbw, nby, nbricks, d_roots, (int)nc, d_removed, keep0,
                      fill_sdf, bmin);
@@ -551,15 +553,9 @@ static int host_slot_of(const vcy_ctx* c, int64_t root) {
 
 // the seam calls need the labelling vcy_label_components_slab left, of the state as it is now
 static int check_slab_labelled(const vcy_ctx* c, const char* who) {
-  if (!c->cc_slab_labelled || !c->cc_labels_valid) {
-    set_error("%s: vcy_label_components_slab has not labelled this context", who);
-    return VCY_ERR_INVALID_ARG;
-  }
-  if (!c->pending.empty() || c->views_carved != c->cc_views_at_label) {
-    set_error("%s: views have been carved since vcy_label_components_slab: label again", who);
-    return VCY_ERR_INVALID_ARG;
-  }
-  return VCY_OK;
+  if (c->st.seams_current(c->pending.empty()) && c->cc_labels_valid) return VCY_OK;
+  set_error("%s: vcy_label_components_slab has not labelled this context as its state is now: label again", who);
+  return VCY_ERR_INVALID_ARG;
 }
 
 namespace {
@@ -718,9 +714,7 @@ int vcy_label_components_slab(vcy_ctx* c, double iso_level, vcy_component** out,
   std::vector<vcy_component> comps;
   { const int rc = label_components(c, iso_level, &comps, nullptr); if (rc != VCY_OK) return rc; }
   { const int rc = finish_timer(c); if (rc != VCY_OK) return rc; }
-  c->cc_slab_labelled = true;
-  c->cc_iso = iso_level;
-  c->cc_views_at_label = c->views_carved;
+  c->st.slab_labelled(iso_level);
   if (comps.empty()) return VCY_OK;
   vcy_component* p = (vcy_component*)std::malloc(sizeof(vcy_component) * comps.size());
   if (!p) {
@@ -870,9 +864,9 @@ int vcy_keep_components_slab(vcy_ctx* c, float fill_sdf, int64_t n_remove, const
   }
   if (removed_voxels) *removed_voxels = 0;
   { const int rc = check_slab_labelled(c, "vcy_keep_components_slab"); if (rc != VCY_OK) return rc; }
-  if (!std::isfinite(fill_sdf) || !((double)fill_sdf >= c->cc_iso)) {
+  if (!std::isfinite(fill_sdf) || !((double)fill_sdf >= c->st.cc_iso)) {
     set_error("vcy_keep_components_slab: fill_sdf %g must be finite and not below the iso level %g of the labelling",
-              (double)fill_sdf, c->cc_iso);
+              (double)fill_sdf, c->st.cc_iso);
     return VCY_ERR_INVALID_ARG;
   }
   if (n_remove < 0 || (n_remove > 0 && !remove_provisional_labels)) {
@@ -905,12 +899,12 @@ int vcy_keep_components_slab(vcy_ctx* c, float fill_sdf, int64_t n_remove, const
     c->cc_timed = true;
     { const int rc = launch_filter(c, removed, keep0, fill_sdf); if (rc != VCY_OK) return rc; }
     { const int rc = finish_timer(c); if (rc != VCY_OK) return rc; }  // (waits: `removed` is read until then)
-    // the labels stay those from before the removal (vcy_download_labels), but no second filter may lean on them
-    c->cc_slab_labelled = false;
+    // (the labels stay those from before the removal (vcy_download_labels), but no second filter may lean on them: the
+    // filter's own write has made the labelling stale)
   }
   // step 5 of the slab flow: the slab below has run its own filter as well, so the two slices kept from it are stale
   // whether or not anything went HERE -- as after a carve, extraction refuses until the halos are exchanged again
-  if (c->halo_lo > 0) c->halo_valid = false;
+  c->st.halo_stale();
   if (removed_voxels) *removed_voxels = rv_n;
   return VCY_OK;
 }

@@ -119,7 +119,7 @@ static int kept_voxel_ids(vcy_ctx* c, int inside_empty, HostIds* out_ids) {
     if (rcf != VCY_OK) return rcf;
   }
   // the on-surface test looks at the voxel below: for a slab above another one that is the halo slice z0 - 1
-  if (inside_empty && c->halo_lo > 0 && !c->halo_valid) {
+  if (inside_empty && c->halo_lo > 0 && !c->st.halo_valid) {
     set_error("halo slices not installed (call vcy_halo_unpack / vcy_halo_allgather before extracting from a slab)");
     return VCY_ERR_NOT_INITIALIZED;
   }
@@ -129,7 +129,7 @@ static int kept_voxel_ids(vcy_ctx* c, int inside_empty, HostIds* out_ids) {
   HostIds& ids = *out_ids;
   vcy::mesh_host_free(ids.release());
   // ---- device: keep bits -> block counts -> scan -> kept voxel ids ---------------------------------
-  if (!c->fresh) {  // a fresh grid is untouched everywhere: nothing is kept under either predicate
+  if (!c->st.fresh) {  // a fresh grid is untouched everywhere: nothing is kept under either predicate
     const int64_t nblocks = (n + 255) / 256;
     const size_t sz_bits = align256(sizeof(u64) * (size_t)nblocks * 4);
     const size_t sz_counts = align256(sizeof(u64) * ((size_t)nblocks + 1));

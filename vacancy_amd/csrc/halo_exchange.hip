@@ -80,7 +80,7 @@ int vcy_halo_allgather(vcy_ctx* const* slabs, int n_slabs) {
     return VCY_ERR_INVALID_ARG;
   }
   if (n_slabs == 1) {
-    slabs[0]->halo_valid = true;  // a whole grid: nothing below
+    slabs[0]->st.halo_installed();  // a whole grid: nothing below
     return VCY_OK;
   }
   std::lock_guard<std::mutex> lock(g_rccl_mutex);
@@ -234,7 +234,7 @@ int vcy_halo_allgather_ranks(vcy_comm* cm, vcy_ctx* const* my_slabs, int n_my_sl
     }
   const int k = n_my_slabs, world = cm->world;
   if (world * k == 1) {
-    my_slabs[0]->halo_valid = true;
+    my_slabs[0]->st.halo_installed();
     return VCY_OK;
   }
   std::lock_guard<std::mutex> lock(g_rccl_mutex);

@@ -131,7 +131,7 @@ struct Extraction {
       const int64_t want = ((int64_t)(p.L + 1) * q.groups + VCY_SWEEP_TARGET_WGS - 1) / VCY_SWEEP_TARGET_WGS;
       q.layers = (int)std::min<int64_t>(std::max<int64_t>(want, 8), 64);
       q.dl = p.zs0 - p.zc0 + 1;
-      q.cnt_slices = c->cnt_implied ? 0 : p.nslices;
+      q.cnt_slices = c->st.cnt_implied ? 0 : p.nslices;
       while ((1 << q.wshift) < p.Wr) ++q.wshift;
       chain.sweep = &q;
     }
@@ -468,7 +468,7 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
   out->vertices = nullptr;  // an empty mesh has no arrays
   out->faces = nullptr;
   out->edge_keys = nullptr;
-  if (c->halo_lo && !c->halo_valid) {
+  if (c->halo_lo && !c->st.halo_valid) {
     set_error("halo slices not installed: call vcy_halo_pack / all-gather / vcy_halo_unpack first");
     return VCY_ERR_NOT_INITIALIZED;
   }

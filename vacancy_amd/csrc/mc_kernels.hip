@@ -1331,17 +1331,17 @@ void launch_planes(const vcy_ctx* c, McParams& p, const ChainLaunch& a) {
   const int64_t halo_words = (int64_t)c->halo_lo * p.ny * p.Wr;
   u64* d_tc = a.tc;
   // a whole grid whose state implies TC == OK: no third plane at all
-  if (c->cnt_implied && whole_words && c->halo_lo == 0) {
+  if (c->st.cnt_implied && whole_words && c->halo_lo == 0) {
     p.tc = a.ok;
     d_tc = nullptr;
   }
-  if (c->cnt_implied && whole_words) {
+  if (c->st.cnt_implied && whole_words) {
     launch_bits(s, p, c->cnt_bytes, 0, halo_words, false, a.in, a.ok, d_tc);
     const int nbw = (p.nx + 7) / 8, nby = (p.ny + 7) / 8, nbz = (c->nz_local() + 7) / 8;
     // (rows of 16 words and more: at 512^3 -- 8 words, 4096 brick rows -- the dense pass is the faster one, 0.197 against
     // 0.210 ms per extraction in the default mode, 0.233 against 0.271 after a weighted-average carve; "mcskip" 2 forces
     // the brick rows on any size for the tests)
-    if (c->mc_skip && (p.Wr >= 16 || c->mc_skip > 1) && c->brick_min_valid && !c->fresh && c->d_brick_min &&
+    if (c->mc_skip && (p.Wr >= 16 || c->mc_skip > 1) && c->st.brick_min_valid && !c->st.fresh && c->d_brick_min &&
         nbw <= kBricksMaxNbw && nbz <= 65535) {
       // the owned slices, bricks the carve kernels left entirely outside the surface not read ("mcskip")
       const float* sdf0 = p.sdf + halo_words * 64;

@@ -10,7 +10,7 @@
 //                     tiles per workgroup, the view in blockIdx.z: a batch is one launch.  The plane tables sit in LDS
 //                     when they fit.  No atomics: every pixel has one writer.  For vcy_hull_agreement the same kernel ends
 //                     in three ballots per wave and one 64-bit atomic add per counter per wave.
-// 1 and 2 are kept on the context and redone when vcy_ctx::state_epoch or the iso level has moved.
+// 1 and 2 are kept on the context and redone when StateFlags::epoch or the iso level has moved.
 //
 // The walk.  The path of a ray is the merge by (t, axis) of three monotone sequences t_a(k) = (P_a[k] - o_a) * inv_a, each
 // computed from the integer k.  A lane holds its cell (i_x, i_y, i_z) and the t of the next plane on every axis, and a
@@ -346,7 +346,7 @@ int cell_planes(const float bb_min[3], const float bb_max[3], float resolution, 
 
 // Bit planes of the current state at `iso`, when the kept ones describe another state.
 int ensure_bits(vcy_ctx* c, double iso) {
-  if (c->rn_bits_valid && c->rn_epoch == c->state_epoch && c->rn_iso == iso) return VCY_OK;
+  if (c->rn_bits_valid && c->rn_epoch == c->st.epoch && c->rn_iso == iso) return VCY_OK;
   c->rn_bits_valid = false;
   const int Wr = (c->nx + 63) / 64;
   const int nzl = c->nz_local();  // (launch_solid_bits covers the owned slices; bricks are counted from z0)
@@ -360,7 +360,7 @@ int ensure_bits(vcy_ctx* c, double iso) {
                      nzl, Wr, nbx, nby, nbricks, bits + nwords);
   VCY_HIP_CHECK(hipGetLastError());
   c->rn_bits_valid = true;
-  c->rn_epoch = c->state_epoch;
+  c->rn_epoch = c->st.epoch;
   c->rn_iso = iso;
   return VCY_OK;
 }
@@ -426,7 +426,7 @@ int render(vcy_ctx* c, double iso, int n_views, const vcy_view* views, float* co
   g.total = c->nx + c->ny + c->nz + 3;
   g.Wr = (c->nx + 63) / 64;
   g.nbx = (c->nx + 7) / 8, g.nby = (c->ny + 7) / 8;
-  g.empty = c->fresh ? 1 : 0;  // nothing carved since the fill: no voxel is solid, and the lazy fill stays lazy
+  g.empty = c->st.fresh ? 1 : 0;  // nothing carved since the fill: no voxel is solid, and the lazy fill stays lazy
   g.z0 = c->z0, g.z1 = c->z1;
   g.planes = c->d_rn_planes;
   const bool lds = g.total <= rn::kLdsPlanes;

@@ -85,7 +85,7 @@ static int enqueue_view(vcy_ctx* c, const vcy_view* view, DeviceBuf<float> d_img
   if (!c->pending.empty() && (c->pending.front().view.is_ortho != 0) != (view->is_ortho != 0)) rc = flush_pending(c, true);
   if (rc == VCY_OK) {
     c->pending.push_back(vcy_ctx::PendingView{*view, std::move(d_img)});
-    c->halo_valid = false;
+    c->st.halo_stale();  // the neighbour below queues the view too: what was taken from it will not be its last two slices
     if ((int)c->pending.size() >= kMaxPendingViews) rc = flush_pending(c, true);
   } else {
     c->sdf_pool.push_back(std::move(d_img));

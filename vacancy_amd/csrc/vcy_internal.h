@@ -33,6 +33,7 @@ constexpr float kInvalidSdf = -3.402823466e+38f;
 }  // namespace vcy
 
 #include "vcy_resources.h"  // DeviceBuf, PinnedBuf, Event, Stream: what owns the context's resources
+#include "state_flags.h"    // StateFlags: what the context knows about its voxel state, and who may say so
 
 // The device-resident voxel grid of one z-slab.
 //
@@ -56,11 +57,7 @@ struct vcy_ctx {
   int nx = 0, ny = 0, nz = 0;  // global dims
   int z0 = 0, z1 = 0;          // owned slab [z0, z1)
   int halo_lo = 0;             // slices stored below z0
-  bool halo_valid = false;
-  // Lazy initialisation: after vcy_create / vcy_reset the slab is KNOWN to be sdf = lowest(),
-  // update_num = 0 without having been written.  The fused carve starts from that knowledge
-  // (no state read, no fill pass); everything else calls materialize() first.
-  bool fresh = false;
+  vcy::StateFlags st;          // fresh, halo_valid, cnt_implied, brick_min_valid, views_carved, epoch: read everywhere, changed only through its functions
   int64_t slice = 0;           // nx*ny
   // Counter width, lazily widened (round 5): update_num of a voxel cannot exceed the number of views applied since the
   // fill, so the array is u8 while at most 255 views have been applied (or uploaded counts are <= 255), u16 up to 65535,
@@ -116,9 +113,8 @@ struct vcy_ctx {
   float h_px_min = 0, h_px_max = 0, h_py_min = 0, h_py_max = 0;  // extreme voxel centres
   std::vector<float> h_pz;            // host copy of d_pz (per-view z tables of the fused carve)
   vcy::DeviceBuf<> d_fused_scratch;   // view blocks + z tables of the fused carve kernel
-  bool cnt_implied = true;            // update_num == 0 implies sdf == lowest(): no vcy_upload since the fill
   vcy::DeviceBuf<float> d_brick_min;  // min(sdf) of every 8x8x8 wave brick of the slab [bz][by][bxw], kept by the fused carve
-  bool brick_min_valid = false;       // ... and current: no write to the state since has bypassed the fused kernel
+                                      // (current while st.brick_min_valid)
   vcy::DeviceBuf<int> d_wg_list;      // live workgroups of a carve launch of few views ([0] = count), live_workgroups_kernel
   bool time_carve = false;            // vcy_set_param("carvetimer", 1): events around pre-pass and carve kernel of every fused launch
   struct CarveStamp {                 // one chunk of one fused launch
@@ -193,15 +189,12 @@ struct vcy_ctx {
   std::vector<int> cc_roots_host;     // slab-local roots, ascending
   std::vector<int64_t> cc_nvox_host;  // voxels of each root's piece
   std::vector<int64_t> cc_global_host;  // the installed map (vcy_resolve_components_slab): global label per slot; empty: none
-  bool cc_slab_labelled = false;      // the last labelling was vcy_label_components_slab's: the seam calls may follow
-  double cc_iso = 0.0;                // ... at this iso level
-  int64_t cc_views_at_label = 0;      // ... with this many views applied (a carve in between makes the labels stale)
+                                      // (whether the seam calls may follow the last labelling: st.seams_current)
   vcy::DeviceBuf<> d_cc_seam;         // seam pairs: [the lower slab's top plane, int64 per voxel | counter | pairs] (grow-only)
 
   // ray-cast of the hull (render.hip); everything grow-only
-  int64_t state_epoch = 0;            // bumped by everything that may change which voxels are solid: a carve, vcy_upload, the fill, the component filter
   vcy::DeviceBuf<> d_rn_bits;         // [solid bit of every voxel, 64-voxel words along x | one bit per 8 x 8 x 8 brick that holds a solid voxel]
-  bool rn_bits_valid = false;         // ... describe the state of epoch rn_epoch at the iso level rn_iso
+  bool rn_bits_valid = false;         // ... describe the state of epoch rn_epoch (against st.epoch) at the iso level rn_iso
   int64_t rn_epoch = -1;
   double rn_iso = 0.0;
   vcy::DeviceBuf<float> d_rn_planes;  // the cell planes of the three axes one behind the other (vcy_cell_planes), nx + ny + nz + 3 floats
@@ -239,9 +232,6 @@ struct vcy_ctx {
   vcy::Event ev_dq[2];                // around the quadric stage of vcy_decimate_mesh_quadric (vcy_last_quadric_ms)
   float last_quadric_ms = 0.0f;
 
-  // upper bound on any voxel's update_num (each carved view adds at most one)
-  int64_t views_carved = 0;
-
   float* owned_slab_sdf() const { return d_sdf + (int64_t)halo_lo * slice; }
   void* owned_slab_cnt() const { return (char*)d_cnt + (int64_t)halo_lo * slice * cnt_bytes; }
   int nz_local() const { return z1 - z0; }
@@ -251,12 +241,14 @@ struct vcy_ctx {
 namespace vcy {
 
 // carve_kernels.hip
-int launch_carve(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* sdf_dev);
+// `queued`: the views are those of vcy_ctx::pending (flush_pending alone says so)
+int launch_carve(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* sdf_dev, bool queued = false);
 // carve_fused.hip (host side and pre-pass of the fused carve step; the kernel: carve_fused_kernel.h)
 struct GridParams;
 struct ViewParams;
 bool fused_eligible(const vcy_ctx* ctx, int n_views, const vcy_view* views);
-int launch_carve_fused(vcy_ctx* ctx, const GridParams& g, int n_views, const ViewParams* vp);
+// `views_before`: views applied since the fill when this launch starts (the caller has declared its whole call already)
+int launch_carve_fused(vcy_ctx* ctx, const GridParams& g, int n_views, const ViewParams* vp, int64_t views_before);
 int fused_max_views();
 int plan_layer_pairs(vcy_ctx* ctx, int n_views, const ViewParams* vp, int stride, std::vector<double>* pairs,
                      int64_t* bricks_per_layer);  // the slab planner's estimate (carve_fused.hip)
@@ -347,7 +339,8 @@ void mesh_pool_trim();  // frees the pool's idle buffers (vcy_destroy, when the 
 // vcy_state.hip: counter widths, the lazy fill, vcy_reset, download / upload / positions / voxels, vcy_state_equal and
 // the vcy_halo_* functions
 int ensure_count_width(vcy_ctx* ctx, int64_t max_count);  // d_cnt wide enough for counts up to max_count
-int set_count_width(vcy_ctx* ctx, int bytes);  // d_cnt at `bytes` per counter, what it holds converted (vcy_set_param "lazycount")
+// d_cnt at `bytes` per counter, what it holds converted (vcy_set_param "lazycount") or, `keep_contents` false, dropped
+int set_count_width(vcy_ctx* ctx, int bytes, bool keep_contents = true);
 int count_width_for(const vcy_ctx* ctx, int64_t max_count);
 int convert_counts(hipStream_t stream, const void* src, int src_bytes, void* dst, int dst_bytes, int64_t n);  // saturating
 int fill_state(vcy_ctx* ctx);   // marks the slab fresh (lazy)

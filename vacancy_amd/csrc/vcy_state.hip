@@ -68,11 +68,12 @@ int count_width_for(const vcy_ctx* c, int64_t max_count) {
   return std::min(w, c->cnt_bytes_wire);
 }
 
-// Switches d_cnt to `bytes` per counter, converting what it holds (nothing on a fresh slab).  The array of the other
-// width is KEPT (d_cnt_spare) once both exist: a vcy_reset followed by a carve across the 256th view used to pay two
-// allocations of 1 - 2 GB, two device-wide synchronisations (hipFree) and a pipeline stall per cycle.  The conversion is
-// ordered on the context's stream like every other access to the counters, so nothing waits here either.
-int set_count_width(vcy_ctx* c, int bytes) {
+// Switches d_cnt to `bytes` per counter, converting what it holds: everything, on a fresh slab only a valid halo, and
+// nothing at all when the caller is about to overwrite every counter (`keep_contents` false: the robust carve).  The array
+// of the other width is KEPT (d_cnt_spare) once both exist: a vcy_reset followed by a carve across the 256th view used to
+// pay two allocations of 1 - 2 GB, two device-wide synchronisations (hipFree) and a pipeline stall per cycle.  The
+// conversion is ordered on the context's stream like every other access to the counters, so nothing waits here either.
+int set_count_width(vcy_ctx* c, int bytes, bool keep_contents) {
   if (bytes == c->cnt_bytes) return VCY_OK;
   const int64_t nvox = c->slice * (int64_t)(c->halo_lo + c->nz_local());
   const size_t need = (size_t)nvox * bytes;
@@ -82,12 +83,8 @@ int set_count_width(vcy_ctx* c, int bytes) {
   } else {
     VCY_HIP_CHECK(d_new.alloc(need));
   }
-  int rc = VCY_OK;
-  if (!c->fresh) {
-    rc = convert_counts(c->stream, c->d_cnt, c->cnt_bytes, d_new, bytes, nvox);
-  } else if (c->halo_lo && c->halo_valid) {
-    rc = convert_counts(c->stream, c->d_cnt, c->cnt_bytes, d_new, bytes, c->slice * (int64_t)c->halo_lo);
-  }
+  const int64_t keep = !keep_contents ? 0 : !c->st.fresh ? nvox : c->st.halo_valid ? c->slice * (int64_t)c->halo_lo : 0;
+  const int rc = convert_counts(c->stream, c->d_cnt, c->cnt_bytes, d_new, bytes, keep);  // (nothing to keep: no launch)
   if (rc != VCY_OK) {
     (void)hipStreamSynchronize(c->stream);
     return rc;  // (d_new goes back to the allocator)
@@ -118,14 +115,8 @@ int fill_state(vcy_ctx* c) {
   discard_pending(c);  // whatever they would have carved is wiped
   c->deferred_rc = VCY_OK;
   c->deferred_msg.clear();
-  c->fresh = true;  // written lazily, see vcy_ctx::fresh
-  ++c->state_epoch;
-  c->brick_min_valid = false;
+  c->st.filled();
   if (c->h_live_hint) c->h_live_hint[0] = c->h_live_hint[1] = 0;
-  c->views_carved = 0;
-  c->cc_slab_labelled = false;  // (the seam calls of components.hip speak about the state that was labelled)
-  c->halo_valid = false;
-  c->cnt_implied = true;
   // counters start over at one byte (fresh: nothing to convert; the wide array is kept as the spare)
   if (c->d_cnt && c->cnt_bytes != count_width_for(c, 0)) return set_count_width(c, count_width_for(c, 0));
   return VCY_OK;
@@ -136,14 +127,14 @@ int materialize(vcy_ctx* c) {
     const int rcf = flush_pending(c);  // every reader of the state comes through here
     if (rcf != VCY_OK) return rcf;
   }
-  if (!c->fresh) return VCY_OK;
+  if (!c->st.fresh) return VCY_OK;
   // only the owned slab: halo slices are written by vcy_halo_install / _unpack
   const int64_t n = c->slab_voxels();
   const int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 32);
   hipLaunchKernelGGL(fill_f32_kernel, dim3(grid), dim3(256), 0, c->stream, c->owned_slab_sdf(), kInvalidSdf, n);
   VCY_HIP_CHECK(hipGetLastError());
   VCY_HIP_CHECK(hipMemsetAsync(c->owned_slab_cnt(), 0, (size_t)n * c->cnt_bytes, c->stream));
-  c->fresh = false;
+  c->st.stored();
   return VCY_OK;
 }
 
@@ -187,15 +178,11 @@ int vcy_download(vcy_ctx* c, float* sdf, int32_t* update_num) {
 int vcy_upload(vcy_ctx* c, const float* sdf, const int32_t* update_num) {
   if (!c) return VCY_ERR_NOT_INITIALIZED;
   VCY_HIP_CHECK(hipSetDevice(c->device));
-  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
-  VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
+  // refused before anything is touched: a bad counter leaves the state and everything kept beside it as they were
   const int64_t n = c->slab_voxels();
-  ++c->state_epoch;
-  if (sdf)
-    VCY_HIP_CHECK(hipMemcpy(c->owned_slab_sdf(), sdf, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+  int64_t mx = 0;
   if (update_num) {
     const int64_t cap = (int64_t)c->opt.update_option.voxel_max_update_num + 1;
-    int64_t mx = 0;
     for (int64_t i = 0; i < n; ++i) {
       const int32_t v = update_num[i];
       if (v < 0 || v > cap) {
@@ -204,7 +191,15 @@ int vcy_upload(vcy_ctx* c, const float* sdf, const int32_t* update_num) {
       }
       mx = v > mx ? v : mx;
     }
-    { const int rcw = ensure_count_width(c, std::max<int64_t>(mx, c->views_carved)); if (rcw != VCY_OK) return rcw; }
+  }
+  { int rcm = materialize(c); if (rcm != VCY_OK) return rcm; }
+  VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
+  // arbitrary state from outside: nothing kept beside it survives
+  c->st.written(StateWrite::upload(std::max(c->st.views_carved, mx)));
+  if (sdf)
+    VCY_HIP_CHECK(hipMemcpy(c->owned_slab_sdf(), sdf, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+  if (update_num) {
+    { const int rcw = ensure_count_width(c, c->st.views_carved); if (rcw != VCY_OK) return rcw; }
     // (a widening converts the old counters on the context's stream; the copy below is not ordered behind that stream and
     // must not be overtaken by it)
     VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -216,12 +211,7 @@ int vcy_upload(vcy_ctx* c, const float* sdf, const int32_t* update_num) {
       else ((int32_t*)raw.data())[i] = v;
     }
     VCY_HIP_CHECK(hipMemcpy(c->owned_slab_cnt(), raw.data(), raw.size(), hipMemcpyHostToDevice));
-    c->views_carved = std::max<int64_t>(c->views_carved, mx);
   }
-  c->halo_valid = false;
-  c->cnt_implied = false;  // arbitrary state from outside
-  c->brick_min_valid = false;
-  c->cc_slab_labelled = false;
   return VCY_OK;
 }
 
@@ -275,7 +265,7 @@ int vcy_halo_install(vcy_ctx* c, const void* prev_pack) {
   if (!c) return VCY_ERR_INVALID_ARG;
   VCY_HIP_CHECK(hipSetDevice(c->device));
   if (c->halo_lo == 0) {
-    c->halo_valid = true;  // first slab: nothing below
+    c->st.halo_installed();  // first slab: nothing below
     return VCY_OK;
   }
   if (!prev_pack) return VCY_ERR_INVALID_ARG;
@@ -284,14 +274,14 @@ int vcy_halo_install(vcy_ctx* c, const void* prev_pack) {
   VCY_HIP_CHECK(hipMemcpyAsync(c->d_sdf, src, 2 * s * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   { const int rcc = convert_counts(c->stream, src + 2 * s * sizeof(float), c->cnt_bytes_wire, c->d_cnt, c->cnt_bytes, 2 * s);
     if (rcc != VCY_OK) return rcc; }
-  c->halo_valid = true;
+  c->st.halo_installed();
   return VCY_OK;
 }
 
 int vcy_halo_copy_from(vcy_ctx* c, vcy_ctx* below) {
   if (!c) return VCY_ERR_INVALID_ARG;
   if (c->halo_lo == 0) {
-    c->halo_valid = true;
+    c->st.halo_installed();
     return VCY_OK;
   }
   if (!below || below->z1 != c->z0 || below->nx != c->nx || below->ny != c->ny ||
@@ -322,7 +312,7 @@ int vcy_halo_copy_from(vcy_ctx* c, vcy_ctx* below) {
     const int rcc = convert_counts(c->stream, c->d_halo_tmp, below->cnt_bytes, c->d_cnt, c->cnt_bytes, 2 * s);
     if (rcc != VCY_OK) return rcc;
   }
-  c->halo_valid = true;
+  c->st.halo_installed();
   return VCY_OK;
 }
 
@@ -330,7 +320,7 @@ int vcy_halo_unpack(vcy_ctx* c, const void* gathered, int rank, int world) {
   if (!c || !gathered || rank < 0 || rank >= world) return VCY_ERR_INVALID_ARG;
   VCY_HIP_CHECK(hipSetDevice(c->device));
   if (c->halo_lo == 0) {
-    c->halo_valid = true;
+    c->st.halo_installed();
     return VCY_OK;
   }
   if (rank == 0) {
@@ -342,7 +332,7 @@ int vcy_halo_unpack(vcy_ctx* c, const void* gathered, int rank, int world) {
   VCY_HIP_CHECK(hipMemcpyAsync(c->d_sdf, src, 2 * s * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   { const int rcc = convert_counts(c->stream, src + 2 * s * sizeof(float), c->cnt_bytes_wire, c->d_cnt, c->cnt_bytes, 2 * s);
     if (rcc != VCY_OK) return rcc; }
-  c->halo_valid = true;
+  c->st.halo_installed();
   return VCY_OK;
 }
 
