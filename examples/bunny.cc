@@ -4,6 +4,8 @@
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --tolerate M [--blank-view I]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --smooth N [--lambda L --mu M]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --decimate CELLS [--decimate-mode mean|nearest|first|quadric [--quadric-reg R]]
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] --redistance R [--offset MM]
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] --close VOXELS
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
 //   --render DIR (DIR must exist) writes DIR/hull_<view>.png, the silhouette of the carved hull as every input camera
@@ -25,6 +27,13 @@
 //   (binary, with normals); with slabs the merged mesh goes through ShardedVoxelCarver::DecimateMesh as well and is compared.
 //   --decimate-mode quadric puts every cluster at its quadric-error representative instead (VoxelCarver::DecimateMeshQuadric,
 //   regularisation --quadric-reg R in [0, 1], by default 0.001) and prints how many output vertices kept the mean.
+//   --redistance R (after the ordinary carve and --keep-largest) rewrites the state as the metric distance field of the hull
+//   (VoxelCarver::Redistance, exact up to R voxels), extracts the iso-surface at --offset MM (world units, by default 0:
+//   the hull itself; positive grows it, negative shrinks it; |MM| < (R - 0.5) * resolution), writes it as
+//   <out_dir>/surface_offset.ply and prints its size.
+//   --close VOXELS (in the same place, before --redistance if both are given) closes the hull by a ball of VOXELS voxels
+//   (VoxelCarver::CloseHull: 1.3, 2.3, ... -- not 1.5, 2.5, on which the closing ties) and prints the solid voxels before
+//   and after; the later extractions are those of the closed hull.
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -79,6 +88,9 @@ int main(int argc, char* argv[]) {
   int decimate_mode = 0;   // --decimate-mode mean|nearest|first|quadric (3: VoxelCarver::DecimateMeshQuadric)
   float quadric_reg = 1e-3f;  // --quadric-reg R
   bool quadric_reg_given = false;
+  int redistance = 0;      // --redistance R: the state becomes the metric distance field of the hull, exact up to R voxels
+  float offset_mm = 0.0f;  // --offset MM: the iso level of the surface extracted from it
+  float close_voxels = 0.0f;  // --close VOXELS: morphological closing of the hull first
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
@@ -105,6 +117,19 @@ int main(int argc, char* argv[]) {
         }
         if (std::string(argv[i]) == "--smooth") smooth = std::atoi(argv[i + 1]);
         else (std::string(argv[i]) == "--lambda" ? smooth_lambda : smooth_mu) = (float)std::atof(argv[i + 1]);
+        ++i;
+      } else if (std::string(argv[i]) == "--redistance" || std::string(argv[i]) == "--offset" || std::string(argv[i]) == "--close") {
+        if (i + 1 >= argc) {
+          std::fprintf(stderr, "%s needs a number\n", argv[i]);
+          return 10;
+        }
+        if (std::string(argv[i]) == "--redistance") redistance = std::atoi(argv[i + 1]);
+        else (std::string(argv[i]) == "--offset" ? offset_mm : close_voxels) = (float)std::atof(argv[i + 1]);
+        if ((std::string(argv[i]) == "--redistance" && (redistance < 1 || redistance > 127)) ||
+            (std::string(argv[i]) == "--close" && !(close_voxels > 0.0f))) {
+          std::fprintf(stderr, "%s needs %s\n", argv[i], std::string(argv[i]) == "--close" ? "a positive number" : "a radius in [1, 127]");
+          return 10;
+        }
         ++i;
       } else if (std::string(argv[i]) == "--decimate") {
         if (i + 1 >= argc) {
@@ -403,6 +428,33 @@ int main(int argc, char* argv[]) {
       std::printf("COMPONENTSSHARDED slabs %d before %zu after %zu kept verts %zu faces %zu single verts %zu faces %zu identical %d\n",
                   sharded->slab_count(), sbefore.size(), safter.size(), skept.vertices().size(), skept.vertex_indices().size(),
                   kept.vertices().size(), kept.vertex_indices().size(), same ? 1 : 0);
+    }
+  }
+  if (close_voxels > 0.0f || redistance > 0) {
+    auto count_solid = [&](long long* solid) {
+      std::vector<std::int32_t> d2;
+      if (!carver.DistanceField(&d2, 0.0, 1)) return false;
+      *solid = 0;
+      for (std::int32_t v : d2) *solid += v < 0 ? 1 : 0;
+      return true;
+    };
+    if (close_voxels > 0.0f) {
+      long long before = 0, after = 0;
+      if (!count_solid(&before) || !carver.CloseHull(close_voxels) || !count_solid(&after)) return 13;
+      std::printf("CLOSE voxels %g solid before %lld after %lld\n", static_cast<double>(close_voxels), before, after);
+    }
+    if (redistance > 0) {
+      if (std::fabs(offset_mm) >= (static_cast<float>(redistance) - 0.5f) * resolution) {
+        std::fprintf(stderr, "--offset %g is beyond the field's cap (%d - 0.5) * %g\n", static_cast<double>(offset_mm), redistance,
+                     static_cast<double>(resolution));
+        return 10;
+      }
+      vacancy::Mesh grown;
+      if (!carver.Redistance(0.0, redistance)) return 13;
+      carver.ExtractIsoSurface(&grown, static_cast<double>(offset_mm));
+      grown.WritePly(out_dir + "/surface_offset.ply");
+      std::printf("REDISTANCE radius %d offset %g verts %zu faces %zu\n", redistance, static_cast<double>(offset_mm),
+                  grown.vertices().size(), grown.vertex_indices().size());
     }
   }
   if (!poses.empty()) {

@@ -59,6 +59,12 @@ class ShardedVoxelCarver {
   // stale after the filter as after a Carve(); the extractions exchange them before they read them.
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
+  // VoxelCarver::DistanceField / Redistance / CloseHull for a grid of ONE slab.  The transform of a z-slab needs `radius`
+  // slices of its neighbours per seam, which nothing exchanges yet: with more than one slab the three log that and return
+  // false, the state untouched.
+  bool DistanceField(std::vector<std::int32_t>* d2, double iso_level = 0.0, int radius = 8);
+  bool Redistance(double iso_level = 0.0, int radius = 8);
+  bool CloseHull(float radius_voxels, double iso_level = 0.0);
   // VoxelCarver::SmoothMesh for the merged mesh: the call needs a device and a stream, not the voxels, so the first slab's
   // context runs it (vcy_smooth_mesh).  The same bits as VoxelCarver::SmoothMesh and Mesh::Smooth.
   bool SmoothMesh(Mesh* mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool pin_boundary = false,

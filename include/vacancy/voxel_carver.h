@@ -137,6 +137,20 @@ class VoxelCarver {
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
 
+  // The Euclidean distance field of the hull, on the device (the definitions are in vacancy_hip.h, "distance field of the
+  // hull").  DistanceField (vcy_distance_field): per voxel, in reference order, the signed squared distance in voxels to
+  // the nearest voxel of the other class -- negative where solid --, exact up to radius * radius, radius * radius + 1
+  // beyond; the state is not changed.  Redistance (vcy_redistance) rewrites sdf of every touched voxel to
+  // (sqrt(min(d2, radius^2)) - 0.5) * resolution, negated where solid: ExtractIsoSurface(mesh, +r) is then the hull grown
+  // by r, (mesh, -r) the hull shrunk by r, for |r| < (radius - 0.5) * resolution.  CloseHull is the morphological closing
+  // by a ball of radius_voxels voxels -- Redistance(iso_level, R), Redistance(r, R), Redistance(-r, R) with
+  // r = radius_voxels * resolution, R = ceil(radius_voxels) + 2 -- which bridges the gaps and pits of up to about twice
+  // that width; it refuses a radius on which the closing ties ((radius_voxels + 0.5)^2 a sum of three squares, such as
+  // 1.5: pick 1.3, 2.3, ...).  false + LOGE on an error.  ShardedVoxelCarver has the three members for one slab.
+  bool DistanceField(std::vector<std::int32_t>* d2, double iso_level = 0.0, int radius = 8);
+  bool Redistance(double iso_level = 0.0, int radius = 8);
+  bool CloseHull(float radius_voxels, double iso_level = 0.0);
+
   // The hull as camera `camera` sees it (vcy_render_hull: the first solid voxel on every pixel's ray, exact -- the
   // definition is in vacancy_hip.h): depth = camera depth of the hit, +inf where the ray meets no solid voxel;
   // silhouette (optional) = 255 where it does.  The images get the camera's width x height, the ROI is the whole image.

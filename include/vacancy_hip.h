@@ -540,6 +540,69 @@ int  vcy_resolve_components_slab(vcy_ctx* ctx, int64_t n, const int64_t* provisi
 int  vcy_keep_components_slab(vcy_ctx* ctx, float fill_sdf, int64_t n_remove, const int64_t* remove_provisional_labels,
                               int64_t* removed_voxels);
 
+/* ---- distance field of the hull ------------------------------------------- */
+
+/* The voxel state after a carve is no distance field: a kMax context holds the maximum over the views of 2-D silhouette
+ * distances in image units, a weighted-average context a blend of them.  These calls give every voxel its Euclidean
+ * distance to the surface of the hull, exact up to a cap, in integers (no reference counterpart).
+ *   solid     update_num >= 1 && (double)sdf < iso_level -- the labelling's predicate; an untouched voxel and a NaN are
+ *             not solid;
+ *   touched   update_num >= 1;
+ *   d2(v)     for a voxel v of class c (solid or not solid): the minimum of dx*dx + dy*dy + dz*dz, in voxel indices, over
+ *             all voxels INSIDE THE GRID of the other class.  Untouched voxels count as not solid; nothing outside the grid
+ *             counts as anything, so a solid block that touches the grid's border is not "near the outside" on that side;
+ *   radius    an integer R, 1 <= R <= 127 (VCY_ERR_INVALID_ARG otherwise, nothing touched).  A d2 <= R*R is exact; a
+ *             larger one, and "no voxel of the other class at all", is reported as FAR = R*R + 1;
+ *   field     int32 per voxel in reference order (z*nx*ny + y*nx + x): -d2 for a solid voxel, +d2 for any other.  d2 >= 1
+ *             always, so the sign is never ambiguous;
+ *   phi       the metric value: with d2c = min(d2, R*R) as a float (exact), phi = (sqrtf(d2c) - 0.5f) * resolution, every
+ *             operation rounded once, nothing contracted; negated for a solid voxel (inside is negative here).  A solid
+ *             voxel next to one that is not gets -0.5 * resolution and its neighbour +0.5 * resolution: marching cubes at
+ *             iso 0 with linear interpolation puts the surface half-way between the two.
+ * The evaluation is separable and exact under the cap:
+ *   x pass  g(x,y,z) = the squared distance along the row to the nearest voxel of the other class, or FAR when there is
+ *           none within R;
+ *   y pass  h = min over |dy| <= R, y + dy inside the grid, of (class(x,y+dy,z) != c ? 0 : g(x,y+dy,z)) + dy*dy;
+ *   z pass  the y pass over h, along z; then every value > R*R becomes FAR.
+ * "0 where the neighbour is itself of the other class" makes ONE field and the solid bits enough for both signs.  The
+ * device, the host function below and the numpy restatement of the tests give the same integers and the same float bits. */
+
+/* Applies queued views, builds the signed integer field on the device and copies it to d2_host (nx*ny*nz int32).  Reads
+ * the state and declares nothing: brick minima, bit planes, labellings and halos stay what they were.  A context nothing
+ * has been carved into since vcy_create / vcy_reset returns +FAR everywhere without its lazy fill being written.  Device
+ * memory kept by the context: 1 bit + 1 + 2 bytes of scratch and the 4 bytes of the field per voxel.
+ * VCY_ERR_UNSUPPORTED, state untouched, for a context that does not own the whole grid (the transform of a z-slab needs
+ * R slices of its neighbours per seam). */
+int vcy_distance_field(vcy_ctx* ctx, double iso_level, int radius, int32_t* d2_host);
+/* A state WRITER: every touched voxel gets sdf = phi (negated where solid) of the field above; update_num, untouched
+ * voxels and every other byte of the state stay as they were.  *n_rewritten (may be NULL): the touched voxels.  A context
+ * known to hold no touched voxel (nothing carved since vcy_create / vcy_reset, or an upload of zero counts) launches
+ * nothing, declares nothing and reports 0.  Afterwards vcy_extract_iso at iso +r is the hull grown by r, at -r the hull
+ * shrunk by r, at 0 the hull itself -- valid for |r| < (R - 0.5) * resolution, beyond which the cap shows.  The brick
+ * minima are LOST (the final kernel works on columns along z, not on bricks, and does not reduce them again): the next
+ * extraction reads every brick and the next fused carve rebuilds them.  Bit planes of the ray-cast, a slab labelling and
+ * the halo are stale as after any write.  Views carved afterwards mix image-unit samples into a metric field: that is
+ * the caller's business.  VCY_ERR_UNSUPPORTED, state untouched, for a context that does not own the whole grid. */
+int vcy_redistance(vcy_ctx* ctx, double iso_level, int radius, int64_t* n_rewritten);
+/* The definition, serial, on the host: no GPU, no context.  sdf / update_num in vcy_download's layout for the whole grid
+ * of `option`; d2: the signed integer field (may be NULL); sdf_out (may be NULL, may be sdf itself): the state's sdf
+ * after vcy_redistance -- phi where touched, the input's bits elsewhere.  The device calls equal it bit for bit. */
+int vcy_distance_field_host(const vcy_carver_option* option, const float* sdf, const int32_t* update_num, double iso_level,
+                            int radius, int32_t* d2, float* sdf_out);
+/* Device milliseconds between HIP events around the launches (solid bits, the three passes) of the last
+ * vcy_distance_field (its copy to the host not included) or vcy_redistance on this context; 0 when nothing was launched.
+ *
+ * Closing the hull (VoxelCarver::CloseHull, vacancy_amd.carver.VoxelCarver.CloseHull; a composition, written once per
+ * language): with r = radius_voxels * resolution and R = ceil(radius_voxels) + 2,
+ *   vcy_redistance(iso_level, R), vcy_redistance(r, R), vcy_redistance(-r, R)
+ * -- the metric field, the field of the hull grown by r, the field of that shrunk by r again: the state ends as the
+ * metric field of the closed hull with its surface at iso 0.  Tie rule: a voxel is dilated when phi < r, that is
+ * sqrt(d2) < radius_voxels + 0.5.  When (radius_voxels + 0.5)^2 is an integer that is a sum of three squares, voxels sit
+ * exactly on both thresholds and `<` sends the growing and the shrinking step the same way: the closing is then no
+ * longer extensive (with 1.5 voxels, two 5^3 blocks two voxels apart shrink from 250 solid voxels to 90; with 1.3 exactly
+ * the 50 gap voxels are filled).  The wrappers refuse such radii; pick 1.3, 2.3, ... */
+int vcy_last_distance_ms(const vcy_ctx* ctx, float* device_ms);
+
 /* ---- ray-cast of the hull into a view ------------------------------------- */
 
 /* What the hull looks like from a camera: per pixel, the first SOLID voxel on the pixel's ray (no reference counterpart:

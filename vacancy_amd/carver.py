@@ -284,6 +284,49 @@ def carve_depth_host(option, views, depths, band, sdf, update_num, z_range=None)
     return sdf, update_num
 
 
+def distance_field_host(option, sdf, update_num, iso_level=0.0, radius=8):
+    """vcy_distance_field_host: the distance field of the hull (definition: include/vacancy_hip.h, "distance field of the
+    hull") serially on the host, no GPU needed.  `sdf` (float32) and `update_num` (int32) in download()'s layout for the
+    whole grid of `option`.  Returns (d2, sdf_out): the signed int32 field and the sdf Redistance would leave.
+    RuntimeError (with .rc) on a refusal."""
+    lib = capi.load()
+    s = np.ascontiguousarray(sdf, np.float32).reshape(-1)
+    u = np.ascontiguousarray(update_num, np.int32).reshape(-1)
+    dims = (C.c_int32 * 3)()
+    if lib.vcy_compute_dims(option.bb_min, option.bb_max, option.resolution, dims) != 0:
+        raise RuntimeError(last_error())
+    if s.size != u.size or s.size != int(dims[0]) * int(dims[1]) * int(dims[2]):
+        raise ValueError("sdf and update_num hold one entry per voxel of the grid")
+    d2, out = np.empty(s.size, np.int32), np.empty(s.size, np.float32)
+    rc = lib.vcy_distance_field_host(C.byref(option), _p(s), _p(u), float(iso_level), int(radius), _p(d2), _p(out))
+    if rc != 0:
+        e = RuntimeError(last_error())
+        e.rc = rc
+        raise e
+    return d2, out
+
+
+def close_hull_plan(radius_voxels, resolution):
+    """(r, R) of CloseHull: r = radius_voxels * resolution in world units and the transform's radius
+    R = ceil(radius_voxels) + 2.  ValueError when (radius_voxels + 0.5)^2 is an integer that is a sum of three squares:
+    voxels then sit exactly on the thresholds of the growing and of the shrinking step, `<` sends both the same way and the
+    closing is not extensive (include/vacancy_hip.h, the tie rule) -- pick 1.3, 2.3, ..."""
+    rv = float(radius_voxels)
+    big_r = int(np.ceil(rv)) + 2
+    if not rv > 0.0 or big_r > 127:
+        raise ValueError("CloseHull: radius_voxels = %g must be positive and at most 125" % rv)
+    t = (rv + 0.5) ** 2
+    n = int(round(t))
+    if abs(t - n) <= 1e-9 * t:
+        m = n
+        while m % 4 == 0:
+            m //= 4
+        if m % 8 != 7:  # Legendre: n is a sum of three squares
+            raise ValueError("CloseHull: radius_voxels = %g ties: (radius + 0.5)^2 = %d is a squared voxel distance, and the "
+                             "growing and the shrinking step would treat it alike; pick e.g. %g" % (rv, n, rv - 0.2))
+    return rv * float(resolution), big_r
+
+
 class VoxelCarver:
     def __init__(self, option=None, device_id=0, z_range=None):
         self._lib = capi.load()
@@ -708,6 +751,37 @@ class VoxelCarver:
     def last_components_ms(self):
         ms = C.c_float()
         self._lib.vcy_last_components_ms(self._ctx, C.byref(ms))
+        return ms.value
+
+    # -- distance field of the hull (no reference counterpart; definitions: include/vacancy_hip.h)
+    def DistanceField(self, iso_level=0.0, radius=8):
+        """vcy_distance_field: the signed squared Euclidean distance, in voxels, of every voxel to the nearest voxel of
+        the other class (solid: update_num >= 1 and sdf < iso_level), built on the device: int32 per voxel, -d2 where
+        solid, +d2 elsewhere, exact up to radius * radius, radius * radius + 1 beyond.  The state is not changed."""
+        d2 = np.empty(self.slab_voxels, np.int32)
+        if self._lib.vcy_distance_field(self._ctx, float(iso_level), int(radius), _p(d2)) != 0:
+            raise RuntimeError(last_error())
+        return d2
+
+    def Redistance(self, iso_level=0.0, radius=8):
+        """vcy_redistance: every touched voxel gets sdf = (sqrt(min(d2, radius^2)) - 0.5) * resolution, negated where
+        solid, in place: ExtractIsoSurface(+r) is then the hull grown by r, (-r) the hull shrunk by r, for
+        |r| < (radius - 0.5) * resolution.  Returns {"rewritten", "device_ms"}."""
+        n = C.c_int64(0)
+        if self._lib.vcy_redistance(self._ctx, float(iso_level), int(radius), C.byref(n)) != 0:
+            raise RuntimeError(last_error())
+        return {"rewritten": int(n.value), "device_ms": self.last_distance_ms()}
+
+    def CloseHull(self, radius_voxels, iso_level=0.0):
+        """Morphological closing of the hull by a ball of radius_voxels voxels: three Redistance calls (the metric field,
+        the field of the hull grown by r, the field of that shrunk by r).  The state ends as the metric field of the closed
+        hull with its surface at iso 0.  ValueError for a radius on which the closing ties (close_hull_plan)."""
+        r, big_r = close_hull_plan(radius_voxels, self.option.resolution)
+        return [self.Redistance(iso_level, big_r), self.Redistance(r, big_r), self.Redistance(-r, big_r)]
+
+    def last_distance_ms(self):
+        ms = C.c_float()
+        self._lib.vcy_last_distance_ms(self._ctx, C.byref(ms))
         return ms.value
 
     # -- ray-cast of the hull into views (no reference counterpart; definitions: include/vacancy_hip.h)

@@ -28,6 +28,8 @@ struct StateWrite {
   static StateWrite robust(int64_t n_views) { return {kMinimaLost, kCountsImplied, 0, n_views, kHaloStale}; }
   static StateWrite upload(int64_t max_count) { return {kMinimaLost, kCountsArbitrary, 0, max_count, kHaloStale}; }
   static StateWrite filter() { return {kMinimaKept, kCountsLeft, 0, -1, kHaloStale}; }
+  // (its final kernel writes columns along z and does not reduce the bricks' minima again)
+  static StateWrite redistance() { return {kMinimaLost, kCountsLeft, 0, -1, kHaloStale}; }
 };
 
 struct StateFlags {

@@ -192,6 +192,11 @@ struct vcy_ctx {
                                       // (whether the seam calls may follow the last labelling: st.seams_current)
   vcy::DeviceBuf<> d_cc_seam;         // seam pairs: [the lower slab's top plane, int64 per voxel | counter | pairs] (grow-only)
 
+  // distance field of the hull (distance.hip); grow-only
+  vcy::DeviceBuf<> d_df_buf;          // [solid bits | row distances, 1 B | y-pass values, 2 B | phi table | counters | the int32 field]
+  vcy::Event ev_df_begin, ev_df_end;  // around the launches of the last vcy_distance_field / vcy_redistance
+  float last_distance_device_ms = 0.0f;
+
   // ray-cast of the hull (render.hip); everything grow-only
   vcy::DeviceBuf<> d_rn_bits;         // [solid bit of every voxel, 64-voxel words along x | one bit per 8 x 8 x 8 brick that holds a solid voxel]
   bool rn_bits_valid = false;         // ... describe the state of epoch rn_epoch (against st.epoch) at the iso level rn_iso
@@ -272,6 +277,8 @@ int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int 
 // the solid bit of every voxel of the owned slices in 64-voxel words along x, (nx + 63) / 64 words per row (cc_bits_kernel);
 // the state must be materialised.  Shared by the labelling and the ray-cast (render.hip).
 int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
+// distance.hip: vcy_distance_field, vcy_redistance, vcy_last_distance_ms; distance_host.hip (host code only):
+// vcy_distance_field_host; what the two share: distance_field.h
 // render.hip: vcy_render_hull, vcy_hull_agreement, vcy_render_hull_slab, vcy_cell_planes, vcy_last_render_ms
 // vcy_render_hull's depth images of up to 64 views (one launch), left in device memory: depth_dev[i] points into
 // vcy_ctx::d_rn_out and holds until the context next renders; waits for the launch; vcy_last_render_ms as for the render

@@ -2,7 +2,11 @@
 // ROI as a vcy_view, a VoxelCarverOption as a vcy_carver_option.  One statement for VoxelCarver and ShardedVoxelCarver.
 #pragma once
 
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
 #include <cstring>
+#include <string>
 
 #include "vacancy/voxel_carver.h"
 #include "vacancy_hip.h"
@@ -63,6 +67,44 @@ inline vcy_carver_option ToC(const VoxelCarverOption& o) {
   c.update_option.use_truncation = o.update_option.use_truncation ? 1 : 0;
   c.update_option.truncation_band = o.update_option.truncation_band;
   return c;
+}
+
+// CloseHull of both carvers on one context that owns the whole grid (the composition and the tie rule: vacancy_hip.h,
+// "distance field of the hull"): r = radius_voxels * resolution, R = ceil(radius_voxels) + 2, then the metric field, the
+// field of the hull grown by r, the field of that shrunk by r.  false with *error set when the radius ties or a call fails.
+inline bool CloseHullOn(vcy_ctx* ctx, float radius_voxels, double iso_level, float resolution, std::string* error) {
+  const double rv = static_cast<double>(radius_voxels);
+  const int big_r = static_cast<int>(std::ceil(rv)) + 2;
+  char msg[256];
+  if (!(rv > 0.0) || big_r > 127) {
+    std::snprintf(msg, sizeof(msg), "CloseHull: radius_voxels = %g must be positive and at most 125", rv);
+    *error = msg;
+    return false;
+  }
+  const double t = (rv + 0.5) * (rv + 0.5);
+  const double nearest = std::floor(t + 0.5);
+  if (std::fabs(t - nearest) <= 1e-9 * t) {
+    long long m = static_cast<long long>(nearest);
+    while (m % 4 == 0) m /= 4;
+    if (m % 8 != 7) {  // Legendre: a sum of three squares, so a squared voxel distance
+      std::snprintf(msg, sizeof(msg),
+                    "CloseHull: radius_voxels = %g ties: (radius + 0.5)^2 = %lld is a squared voxel distance, and the growing "
+                    "and the shrinking step would treat it alike; pick e.g. %g",
+                    rv, static_cast<long long>(nearest), rv - 0.2);
+      *error = msg;
+      return false;
+    }
+  }
+  const double r = rv * static_cast<double>(resolution);
+  const double iso[3] = {iso_level, r, -r};
+  for (double level : iso) {
+    std::int64_t n = 0;
+    if (vcy_redistance(ctx, level, big_r, &n) != VCY_OK) {
+      *error = vcy_last_error();
+      return false;
+    }
+  }
+  return true;
 }
 
 }  // namespace detail

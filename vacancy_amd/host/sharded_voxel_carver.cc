@@ -440,6 +440,46 @@ bool ShardedVoxelCarver::DecimateMeshQuadric(Mesh* mesh, float cell, float regul
   return ok;
 }
 
+namespace {
+
+// the distance field needs the whole grid in one context
+bool OneSlab(const std::vector<vcy_ctx*>& slabs, const char* who) {
+  if (slabs.size() == 1) return true;
+  if (slabs.empty()) LOGE("voxel grid has not been initialized\n");
+  else LOGE("%s: the grid is cut into %d z-slabs; the distance field needs the whole grid in one context\n", who,
+            static_cast<int>(slabs.size()));
+  return false;
+}
+
+}  // namespace
+
+bool ShardedVoxelCarver::DistanceField(std::vector<std::int32_t>* d2, double iso_level, int radius) {
+  if (!d2 || !OneSlab(impl_->slabs, "DistanceField")) return false;
+  std::int32_t dims[3] = {0, 0, 0};
+  vcy_grid_dims(impl_->slabs[0], dims);
+  d2->resize(static_cast<size_t>(dims[0]) * dims[1] * dims[2]);
+  if (vcy_distance_field(impl_->slabs[0], iso_level, radius, d2->data()) == VCY_OK) return true;
+  LOGE("%s\n", vcy_last_error());
+  d2->clear();
+  return false;
+}
+
+bool ShardedVoxelCarver::Redistance(double iso_level, int radius) {
+  if (!OneSlab(impl_->slabs, "Redistance")) return false;
+  std::int64_t n = 0;
+  if (vcy_redistance(impl_->slabs[0], iso_level, radius, &n) == VCY_OK) return true;
+  LOGE("%s\n", vcy_last_error());
+  return false;
+}
+
+bool ShardedVoxelCarver::CloseHull(float radius_voxels, double iso_level) {
+  if (!OneSlab(impl_->slabs, "CloseHull")) return false;
+  std::string error;
+  const bool ok = detail::CloseHullOn(impl_->slabs[0], radius_voxels, iso_level, impl_->option.resolution, &error);
+  if (!ok) LOGE("%s\n", error.c_str());
+  return ok;
+}
+
 bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!std::isfinite(fill_sdf) || !(static_cast<double>(fill_sdf) >= iso_level)) {
     LOGE("KeepLargestComponents: fill_sdf %g must be finite and not below the iso level %g\n", static_cast<double>(fill_sdf),

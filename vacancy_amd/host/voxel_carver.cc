@@ -606,6 +606,54 @@ bool VoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, do
   return true;
 }
 
+bool VoxelCarver::DistanceField(std::vector<std::int32_t>* d2, double iso_level, int radius) {
+  if (!impl_->ctx || !d2) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  std::int32_t dims[3] = {0, 0, 0};
+  vcy_grid_dims(impl_->ctx, dims);
+  d2->resize(static_cast<size_t>(dims[0]) * dims[1] * dims[2]);
+  const int rc = vcy_distance_field(impl_->ctx, iso_level, radius, d2->data());
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    d2->clear();
+    return false;
+  }
+  return true;
+}
+
+bool VoxelCarver::Redistance(double iso_level, int radius) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  std::int64_t n = 0;
+  const int rc = vcy_redistance(impl_->ctx, iso_level, radius, &n);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  float ms = 0.0f;
+  vcy_last_distance_ms(impl_->ctx, &ms);
+  LOGI("Redistance rewrote %lld voxels %02f\n", static_cast<long long>(n), static_cast<double>(ms));
+  return true;
+}
+
+bool VoxelCarver::CloseHull(float radius_voxels, double iso_level) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  std::string error;
+  const bool ok = detail::CloseHullOn(impl_->ctx, radius_voxels, iso_level, impl_->option.resolution, &error);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (!ok) LOGE("%s\n", error.c_str());
+  return ok;
+}
+
 void VoxelCarver::ExtractVoxel(Mesh* mesh, bool inside_empty) {
   mesh->Clear();
   if (!impl_->ctx) return;

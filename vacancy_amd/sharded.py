@@ -337,6 +337,27 @@ class ShardedVoxelCarver:
         return vdist.keep_components_slabs(self.slabs, 0, 1, iso_level, largest, min_voxels, fill_sdf,
                                            each=self._each_slab)
 
+    # -- the distance field of the hull (include/vacancy_hip.h): the transform of a z-slab needs `radius` slices of its
+    # neighbours per seam, which nothing exchanges yet -- the one-slab case only
+    ONE_SLAB_ONLY = "%s: the grid is cut into %d z-slabs; the distance field needs the whole grid in one context"
+
+    def _whole_grid(self, who):
+        if len(self.slabs) != 1:
+            raise RuntimeError(self.ONE_SLAB_ONLY % (who, len(self.slabs)))
+        return self.slabs[0]
+
+    def DistanceField(self, iso_level=0.0, radius=8):
+        """VoxelCarver.DistanceField on a grid of one slab; RuntimeError on more."""
+        return self._whole_grid("DistanceField").DistanceField(iso_level, radius)
+
+    def Redistance(self, iso_level=0.0, radius=8):
+        """VoxelCarver.Redistance on a grid of one slab; RuntimeError on more."""
+        return self._whole_grid("Redistance").Redistance(iso_level, radius)
+
+    def CloseHull(self, radius_voxels, iso_level=0.0):
+        """VoxelCarver.CloseHull on a grid of one slab; RuntimeError on more."""
+        return self._whole_grid("CloseHull").CloseHull(radius_voxels, iso_level)
+
     # -- the ray-cast of the hull over the slabs (include/vacancy_hip.h): every slab renders its own slices on its device
     # -- no halo exchange --, depth images (or, for the agreement, one hit bit per pixel) go through the host, which
     # merges them by the rule of vcy_render_merge_host: exactly what VoxelCarver returns on the whole grid
