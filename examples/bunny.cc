@@ -34,6 +34,8 @@
 //   --close VOXELS (in the same place, before --redistance if both are given) closes the hull by a ball of VOXELS voxels
 //   (VoxelCarver::CloseHull: 1.3, 2.3, ... -- not 1.5, 2.5, on which the closing ties) and prints the solid voxels before
 //   and after; the later extractions are those of the closed hull.
+//   With n_slabs > 0 both run through the sharded carver as well (CloseHullSlabs, RedistanceSlabs) and its stitched mesh is
+//   compared with the single context's: one more line each, SLAB_CLOSE ... / SLAB_REDISTANCE ..., ending in "identical 1".
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -438,10 +440,34 @@ int main(int argc, char* argv[]) {
       for (std::int32_t v : d2) *solid += v < 0 ? 1 : 0;
       return true;
     };
+    // with slabs the sharded carver takes the same steps through its ...Slabs members (the seam planes of the transform go
+    // through the host), and its stitched mesh must equal the single context's, vertex for vertex
+    auto same_mesh = [](const vacancy::Mesh& a, const vacancy::Mesh& b) {
+      bool same = a.vertices().size() == b.vertices().size() && a.vertex_indices().size() == b.vertex_indices().size();
+      for (size_t k = 0; same && k < a.vertices().size(); ++k)
+        for (int c = 0; c < 3; ++c) same = same && a.vertices()[k][c] == b.vertices()[k][c];
+      for (size_t k = 0; same && k < a.vertex_indices().size(); ++k)
+        for (int c = 0; c < 3; ++c) same = same && a.vertex_indices()[k][c] == b.vertex_indices()[k][c];
+      return same;
+    };
     if (close_voxels > 0.0f) {
       long long before = 0, after = 0;
       if (!count_solid(&before) || !carver.CloseHull(close_voxels) || !count_solid(&after)) return 13;
       std::printf("CLOSE voxels %g solid before %lld after %lld\n", static_cast<double>(close_voxels), before, after);
+      if (sharded) {
+        if (!sharded->CloseHullSlabs(close_voxels)) return 13;
+        std::vector<std::int32_t> d2;
+        if (!sharded->DistanceFieldSlabs(&d2, 0.0, 1)) return 13;
+        long long solid = 0;
+        for (std::int32_t v : d2) solid += v < 0 ? 1 : 0;
+        vacancy::Mesh closed, sclosed;
+        carver.ExtractIsoSurface(&closed, 0.0);
+        sharded->ExtractIsoSurface(&sclosed, 0.0);
+        const bool same = solid == after && same_mesh(closed, sclosed);
+        std::printf("SLAB_CLOSE slabs %d voxels %g solid %lld verts %zu identical %d\n", sharded->slab_count(),
+                    static_cast<double>(close_voxels), solid, sclosed.vertices().size(), same ? 1 : 0);
+        if (!same) return 14;
+      }
     }
     if (redistance > 0) {
       if (std::fabs(offset_mm) >= (static_cast<float>(redistance) - 0.5f) * resolution) {
@@ -455,6 +481,17 @@ int main(int argc, char* argv[]) {
       grown.WritePly(out_dir + "/surface_offset.ply");
       std::printf("REDISTANCE radius %d offset %g verts %zu faces %zu\n", redistance, static_cast<double>(offset_mm),
                   grown.vertices().size(), grown.vertex_indices().size());
+      if (sharded) {
+        std::int64_t rewritten = 0;
+        vacancy::Mesh sgrown;
+        if (!sharded->RedistanceSlabs(0.0, redistance, &rewritten)) return 13;
+        sharded->ExtractIsoSurface(&sgrown, static_cast<double>(offset_mm));
+        const bool same = same_mesh(grown, sgrown);
+        std::printf("SLAB_REDISTANCE slabs %d radius %d offset %g rewritten %lld verts %zu identical %d\n", sharded->slab_count(),
+                    redistance, static_cast<double>(offset_mm), static_cast<long long>(rewritten), sgrown.vertices().size(),
+                    same ? 1 : 0);
+        if (!same) return 14;
+      }
     }
   }
   if (!poses.empty()) {

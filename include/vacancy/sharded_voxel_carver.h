@@ -60,11 +60,22 @@ class ShardedVoxelCarver {
   bool LabelComponents(std::vector<VoxelComponent>* components, double iso_level = 0.0);
   bool KeepLargestComponents(int largest = 1, std::int64_t min_voxels = 0, double iso_level = 0.0, float fill_sdf = 1.0f);
   // VoxelCarver::DistanceField / Redistance / CloseHull for a grid of ONE slab.  The transform of a z-slab needs `radius`
-  // slices of its neighbours per seam, which nothing exchanges yet: with more than one slab the three log that and return
-  // false, the state untouched.
+  // slices of its neighbours per seam, which these three do not exchange (the ...Slabs members below do): with more than
+  // one slab the three log that and return false, the state untouched.
   bool DistanceField(std::vector<std::int32_t>* d2, double iso_level = 0.0, int radius = 8);
   bool Redistance(double iso_level = 0.0, int radius = 8);
   bool CloseHull(float radius_voxels, double iso_level = 0.0);
+  // The same three for ANY number of slabs, with the results of a single VoxelCarver on the whole grid, bit for bit: every
+  // slab runs the x and the y pass over its own slices on its device (vcy_distance_slab_begin), its lowest and highest
+  // min(radius, own slices) planes of 16-bit values go through the host -- never a slab's volume; a slab thinner than the
+  // radius passes its neighbours' planes on --, and every slab finishes with the z pass over its columns extended by those
+  // planes (vcy_distance_field_slab / vcy_redistance_slab).  Every slab finishes one step before any slab begins the next.
+  // DistanceFieldSlabs: the slabs' fields one behind the other in z order.  RedistanceSlabs: *n_rewritten (may be null) the
+  // touched voxels of the grid; the halos are stale afterwards as after a Carve().  CloseHullSlabs: the three steps and the
+  // tie rule of VoxelCarver::CloseHull; a refused radius leaves the state untouched.
+  bool DistanceFieldSlabs(std::vector<std::int32_t>* d2, double iso_level = 0.0, int radius = 8);
+  bool RedistanceSlabs(double iso_level = 0.0, int radius = 8, std::int64_t* n_rewritten = nullptr);
+  bool CloseHullSlabs(float radius_voxels, double iso_level = 0.0);
   // VoxelCarver::SmoothMesh for the merged mesh: the call needs a device and a stream, not the voxels, so the first slab's
   // context runs it (vcy_smooth_mesh).  The same bits as VoxelCarver::SmoothMesh and Mesh::Smooth.
   bool SmoothMesh(Mesh* mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool pin_boundary = false,

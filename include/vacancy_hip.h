@@ -603,6 +603,54 @@ int vcy_distance_field_host(const vcy_carver_option* option, const float* sdf, c
  * the 50 gap voxels are filled).  The wrappers refuse such radii; pick 1.3, 2.3, ... */
 int vcy_last_distance_ms(const vcy_ctx* ctx, float* device_ms);
 
+/* The same field for a grid cut into z-slabs.  The x pass and the y pass never leave an xy slice; only the z pass looks
+ * across a seam, R slices deep, and what it needs from there is the y pass's output
+ *   h(v) = class(v) << 15 | the y pass's value (1 .. FAR, 15 bits), uint16, nx*ny per slice ("a plane").
+ * The order of the calls, every slab finishing one step before any slab begins the next:
+ *   1. vcy_distance_slab_begin on every slab;
+ *   2. vcy_distance_slab_planes: every slab hands out its lowest and its highest min(R, own slices) planes; the host puts
+ *      together, for slab [z0, z1), the planes of the global slices [z0 - min(R, z0), z0) and [z1, z1 + min(R, nz - z1)),
+ *      from as many neighbours as that takes (vacancy_amd.dist.distance_halos, ShardedVoxelCarver);
+ *   3. vcy_distance_field_slab or vcy_redistance_slab on every slab.
+ * With exactly those planes at the ends of the slab's columns the z pass's bounds are the whole grid's own for every
+ * step <= R: the results equal vcy_distance_field / vcy_redistance of one context for the slab's slices, bit for bit.
+ *
+ * Step 1: applies queued views, runs the solid bits, the x pass and the y pass over the slab's OWN slices and keeps h in
+ * the context's distance pool (2 bytes per voxel of the slab and of the planes to come), tagged with (iso_level, radius,
+ * the state as it is now).  Reads the state and declares nothing; the context's 2 halo slices are not looked at.  A
+ * context nothing has been carved into since vcy_create / vcy_reset gets class 0, FAR everywhere without its lazy fill
+ * being written.  radius as above.  Works on a context that owns the whole grid too (no planes at either end).  A second
+ * call replaces the tag. */
+int vcy_distance_slab_begin(vcy_ctx* ctx, double iso_level, int radius);
+/* Step 2: the kept planes of the global slices [z_begin, z_end), which must lie among the context's own, to h_host in
+ * slice order.  VCY_ERR_INVALID_ARG without a vcy_distance_slab_begin, or when the state has been written (or a view
+ * queued) since. */
+int vcy_distance_slab_planes(const vcy_ctx* ctx, int z_begin, int z_end, uint16_t* h_host);
+/* Step 3.  below: the planes of the global slices [z0 - n_below, z0), above: [z1, z1 + n_above), both in ascending z;
+ * n_below == min(R, z0) and n_above == min(R, nz - z1) with the R of step 1, and the tag of step 1 still describes the
+ * state -- VCY_ERR_INVALID_ARG with nothing touched otherwise.  A pointer may be NULL where its count is 0.
+ * vcy_distance_field_slab: the signed field of the slab's slices (nx*ny*(z1 - z0) int32) to d2_host; reads the state's
+ * tag only and declares nothing.
+ * vcy_redistance_slab: a state WRITER, exactly vcy_redistance for the slab's slices -- sdf = +-phi where update_num >= 1,
+ * *n_rewritten (may be NULL) the touched voxels, brick minima lost, halo stale; a context known to hold no touched voxel
+ * launches nothing, declares nothing and reports 0.  The write ends the tag: another step 1 precedes another step 3.
+ * vcy_last_distance_ms after any of step 1 and step 3: the launches of that call (step 1: solid bits, x pass, y pass;
+ * step 3: the z pass; the copies of planes not included). */
+int vcy_distance_field_slab(vcy_ctx* ctx, const uint16_t* below, int n_below, const uint16_t* above, int n_above,
+                            int32_t* d2_host);
+int vcy_redistance_slab(vcy_ctx* ctx, const uint16_t* below, int n_below, const uint16_t* above, int n_above,
+                        int64_t* n_rewritten);
+/* The two halves serially on the host: no GPU, no context; they share their arithmetic with vcy_distance_field_host,
+ * which is the two over the whole grid.  sdf_slab / update_num_slab: vcy_download's layout for the slices [z_begin, z_end)
+ * of the grid of `option`.  planes: h of those slices.  finish: d2 (may be NULL) the signed field of the slab, sdf_out (may
+ * be NULL, may be sdf_slab itself) the slab's sdf after vcy_redistance_slab; sdf_slab and update_num_slab may be NULL when
+ * sdf_out is.  The counts n_below / n_above are checked as in step 3. */
+int vcy_distance_slab_planes_host(const vcy_carver_option* option, int z_begin, int z_end, const float* sdf_slab,
+                                  const int32_t* update_num_slab, double iso_level, int radius, uint16_t* h);
+int vcy_distance_slab_finish_host(const vcy_carver_option* option, int z_begin, int z_end, const uint16_t* h,
+                                  const uint16_t* below, int n_below, const uint16_t* above, int n_above, int radius,
+                                  const int32_t* update_num_slab, const float* sdf_slab, int32_t* d2, float* sdf_out);
+
 /* ---- ray-cast of the hull into a view ------------------------------------- */
 
 /* What the hull looks like from a camera: per pixel, the first SOLID voxel on the pixel's ray (no reference counterpart:
@@ -1132,7 +1180,8 @@ int vcy_set_param(vcy_ctx* ctx, const char* name, int value);
 /* Reads a knob back ("fused", "cull", "tile", "defer", "shortdiv", "mcsweep", "mcskip", "mcdirect", "rowkernel", "oneview", "eagerstate", "listrecords", "ntstore", "livelist", "livesync", "coopstore", "meshkeys",
  * "lazycount", "carvetimer"), "count_bytes" / "count_bytes_final" / "carvelog_dropped" (see above), "div_level": the
  * division sequence the last fused launch was instantiated with (2: 4 instructions, 1: 6, 0: full IEEE expansion), or
- * "brick_min_valid": 1 while the brick minima describe the state (every write since the fill went through the fused kernel). */
+ * "brick_min_valid": 1 while the brick minima describe the state (every write since the fill went through the fused kernel),
+ * "fresh": 1 while the fill of vcy_create / vcy_reset is known, not written (nothing has been carved or uploaded since). */
 int vcy_get_param(vcy_ctx* ctx, const char* name, int* value);
 /* Use an existing hipStream_t (e.g. torch's current stream) for all launches. */
 int vcy_set_stream(vcy_ctx* ctx, void* hip_stream);

@@ -10,7 +10,13 @@ Run from the repository root on the GPU:  python profiles/distance/measure_dista
 (arguments: the sizes to run, by default bunny2.5 512 1024; HOST_CALL_LIMIT_S, by default 4: a host call that takes longer
 than this many seconds is measured ONCE and marked "(1 call)", and HOST_VOXEL_RADIUS_LIMIT, by default 1e10: the host
 function is not run where voxels * R exceeds it, and the line says so.)
-Every other figure: median [min..max] of 7 calls after 2 warm-up calls, milliseconds."""
+Every other figure: median [min..max] of 7 calls after 2 warm-up calls, milliseconds.
+With --slabs (python profiles/distance/measure_distance.py --slabs [sizes] > profiles/distance/measure_distance_slabs.txt):
+the same scenes cut into 1, 2 and 4 z-slabs on one device (ShardedVoxelCarver.RedistanceSlabs): device ms of the begin
+calls (solid bits, x pass, y pass) and of the finishing calls (the z pass over the extended columns), each summed over the
+slabs, the bytes of planes that cross the host, the wall time of the whole RedistanceSlabs, and next to them the whole-grid
+vcy_redistance of the same visit with the ratio of the two device times and the ratio the 2 R extra slices staged per seam
+let one expect, 1 + 2 R (slabs - 1) / nz."""
 import os, sys, time
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, "tests")
 import shutil, subprocess
@@ -18,7 +24,8 @@ import numpy as np
 from vacancy_amd import carver as vc, synth
 import bunny_data as B
 RADII = (4, 16, 64)
-SIZES = sys.argv[1:] or ["bunny2.5", "512", "1024"]
+SLABS = "--slabs" in sys.argv[1:]
+SIZES = [a for a in sys.argv[1:] if a != "--slabs"] or ["bunny2.5", "512", "1024"]
 HOST_CALL_LIMIT_S = float(os.environ.get("HOST_CALL_LIMIT_S", "4"))
 HOST_VOXEL_RADIUS_LIMIT = float(os.environ.get("HOST_VOXEL_RADIUS_LIMIT", "1e10"))
 def med(x): x = sorted(x); return "%.3f [%.3f..%.3f]" % (x[len(x)//2], x[0], x[-1])
@@ -35,6 +42,35 @@ print("GPU agents as rocminfo names them: %s" % (", ".join(gpus) or "unknown"), 
 print(vc.capi.load().vcy_version().decode(), flush=True)
 read_gbs, copy_gbs = vc.measure_bandwidth()
 print("vcy_measure_bandwidth: read %.0f GB/s, device-to-device copy %.0f GB/s" % (read_gbs, copy_gbs), flush=True)
+def measure_slabs(name):
+    from vacancy_amd import sharded as vs
+    opt, cams, masks = scene(name)
+    d = vc.VoxelCarver(opt); assert d.Init(), vc.last_error()
+    assert d.CarveBatchSilhouettes(cams, masks), vc.last_error()
+    nz = d.dims[2]
+    print("%s: %d x %d x %d voxels, %d views" % ((name,) + d.dims + (len(cams),)), flush=True)
+    whole = {}
+    for radius in RADII:  # (the rewrite keeps the solid set: every call does the same work)
+        w = [d.Redistance(0.0, radius)["device_ms"] for rep in range(9)][2:]
+        whole[radius] = mid(w)
+        print("  whole grid  R %2d  redistance %s ms" % (radius, med(w)), flush=True)
+    d.close()
+    for count in (1, 2, 4):
+        sv = vs.ShardedVoxelCarver(opt, [0], count); assert sv.Init(), vc.last_error()
+        assert sv.CarveBatchSilhouettes(cams, masks), vc.last_error()
+        for radius in RADII:
+            begin, finish, wall = [], [], []
+            for rep in range(9):
+                t0 = time.perf_counter(); r = sv.RedistanceSlabs(0.0, radius); t = time.perf_counter() - t0
+                if rep >= 2: begin.append(r["begin_ms"]); finish.append(r["finish_ms"]); wall.append(t * 1e3)
+            both = mid(begin) + mid(finish)
+            print("  slabs %d  R %2d  begin %s ms  finish %s ms  sum %.3f ms  = %.3f x whole grid (staged slices: %.3f)   "
+                  "planes through the host %d bytes   wall %s ms" % (count, radius, med(begin), med(finish), both,
+                  both / whole[radius], 1.0 + 2.0 * radius * (count - 1) / nz, r["plane_bytes"], med(wall)), flush=True)
+        sv.close()
+if SLABS:
+    for name in SIZES: measure_slabs(name)
+    sys.exit(0)
 for name in SIZES:
     opt, cams, masks = scene(name)
     d = vc.VoxelCarver(opt); assert d.Init(), vc.last_error()

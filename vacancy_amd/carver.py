@@ -306,6 +306,70 @@ def distance_field_host(option, sdf, update_num, iso_level=0.0, radius=8):
     return d2, out
 
 
+def _raise_rc(rc):
+    e = RuntimeError(last_error())
+    e.rc = rc
+    raise e
+
+
+def _slab_slice(option, z_range):
+    """(voxels of an xy slice, slices of the slab) of the slab z_range of the grid of `option`"""
+    dims = (C.c_int32 * 3)()
+    if capi.load().vcy_compute_dims(option.bb_min, option.bb_max, option.resolution, dims) != 0:
+        raise RuntimeError(last_error())
+    return int(dims[0]) * int(dims[1]), max(int(z_range[1]) - int(z_range[0]), 0)
+
+
+def _planes_arg(planes, slice_voxels):
+    """(array to keep alive, pointer or None, count) of a stack of uint16 planes (None: no planes)"""
+    if planes is None:
+        return None, None, 0
+    a = np.ascontiguousarray(planes, np.uint16).reshape(-1)
+    if a.size % slice_voxels:
+        raise ValueError("planes hold nx * ny uint16 each")
+    return a, (_p(a) if a.size else None), a.size // slice_voxels
+
+
+def distance_slab_planes_host(option, z_range, sdf, update_num, iso_level=0.0, radius=8):
+    """vcy_distance_slab_planes_host: the first half of the distance field of a z-slab on the host, no GPU needed -- the x
+    and the y pass over the slices z_range = (z_begin, z_end) of the grid of `option`, `sdf` / `update_num` in download()'s
+    layout for those slices.  Returns the planes, uint16 [slices, nx * ny]: class in bit 15, the capped squared 2-D
+    distance below it.  RuntimeError (with .rc) on a refusal."""
+    sl, nzl = _slab_slice(option, z_range)
+    s = np.ascontiguousarray(sdf, np.float32).reshape(-1)
+    u = np.ascontiguousarray(update_num, np.int32).reshape(-1)
+    if s.size != u.size or s.size != sl * nzl:
+        raise ValueError("sdf and update_num hold one entry per voxel of the slices [%d, %d)" % tuple(z_range))
+    h = np.empty((nzl, sl), np.uint16)
+    rc = capi.load().vcy_distance_slab_planes_host(C.byref(option), int(z_range[0]), int(z_range[1]), _p(s), _p(u),
+                                                   float(iso_level), int(radius), _p(h))
+    if rc != 0:
+        _raise_rc(rc)
+    return h
+
+
+def distance_slab_finish_host(option, z_range, h, below, above, radius, sdf, update_num):
+    """vcy_distance_slab_finish_host: the second half -- the z pass over the slab's planes `h` with the planes of the
+    global slices [z_begin - n, z_begin) in `below` and [z_end, z_end + m) in `above` (None: none), n = min(radius,
+    z_begin), m = min(radius, nz - z_end).  Returns (d2, sdf_out) of the slab as distance_field_host does of the grid.
+    RuntimeError (with .rc) on a refusal."""
+    sl, nzl = _slab_slice(option, z_range)
+    hh = np.ascontiguousarray(h, np.uint16).reshape(-1)
+    s = np.ascontiguousarray(sdf, np.float32).reshape(-1)
+    u = np.ascontiguousarray(update_num, np.int32).reshape(-1)
+    if not (hh.size == s.size == u.size == sl * nzl):
+        raise ValueError("h, sdf and update_num hold one entry per voxel of the slices [%d, %d)" % tuple(z_range))
+    kb, pb, nb = _planes_arg(below, sl)
+    ka, pa, na = _planes_arg(above, sl)
+    d2, out = np.empty(s.size, np.int32), np.empty(s.size, np.float32)
+    rc = capi.load().vcy_distance_slab_finish_host(C.byref(option), int(z_range[0]), int(z_range[1]), _p(hh), pb, nb, pa, na,
+                                                   int(radius), _p(u), _p(s), _p(d2), _p(out))
+    del kb, ka
+    if rc != 0:
+        _raise_rc(rc)
+    return d2, out
+
+
 def close_hull_plan(radius_voxels, resolution):
     """(r, R) of CloseHull: r = radius_voxels * resolution in world units and the transform's radius
     R = ceil(radius_voxels) + 2.  ValueError when (radius_voxels + 0.5)^2 is an integer that is a sum of three squares:
@@ -778,6 +842,51 @@ class VoxelCarver:
         hull with its surface at iso 0.  ValueError for a radius on which the closing ties (close_hull_plan)."""
         r, big_r = close_hull_plan(radius_voxels, self.option.resolution)
         return [self.Redistance(iso_level, big_r), self.Redistance(r, big_r), self.Redistance(-r, big_r)]
+
+    # ... of a z-slab: DistanceSlabBegin on every slab, the slabs' planes through the host (vacancy_amd.dist.distance_halos),
+    # then DistanceFieldSlab or RedistanceSlab on every slab (include/vacancy_hip.h; composed in vacancy_amd.dist)
+    def DistanceSlabBegin(self, iso_level=0.0, radius=8):
+        """vcy_distance_slab_begin: the x and the y pass over the slab's own slices, kept on the device.  Returns the
+        device ms.  RuntimeError (with .rc) on a refusal."""
+        rc = self._lib.vcy_distance_slab_begin(self._ctx, float(iso_level), int(radius))
+        if rc != 0:
+            _raise_rc(rc)
+        return self.last_distance_ms()
+
+    def DistanceSlabPlanes(self, z_begin, z_end):
+        """vcy_distance_slab_planes: the kept planes of the global slices [z_begin, z_end) of the slab, uint16
+        [slices, nx * ny].  RuntimeError (with .rc) without a DistanceSlabBegin or after a write of the state."""
+        h = np.empty((max(int(z_end) - int(z_begin), 0), self.dims[0] * self.dims[1]), np.uint16)
+        rc = self._lib.vcy_distance_slab_planes(self._ctx, int(z_begin), int(z_end), _p(h))
+        if rc != 0:
+            _raise_rc(rc)
+        return h
+
+    def DistanceFieldSlab(self, below=None, above=None):
+        """vcy_distance_field_slab: DistanceField of the slab's slices as the whole grid's context would return them, from
+        the planes of its neighbours (None: none).  RuntimeError (with .rc) on a refusal."""
+        sl = self.dims[0] * self.dims[1]
+        kb, pb, nb = _planes_arg(below, sl)
+        ka, pa, na = _planes_arg(above, sl)
+        d2 = np.empty(self.slab_voxels, np.int32)
+        rc = self._lib.vcy_distance_field_slab(self._ctx, pb, nb, pa, na, _p(d2))
+        del kb, ka
+        if rc != 0:
+            _raise_rc(rc)
+        return d2
+
+    def RedistanceSlab(self, below=None, above=None):
+        """vcy_redistance_slab: Redistance of the slab's slices as the whole grid's context would leave them.  Returns
+        {"rewritten", "device_ms"}.  RuntimeError (with .rc) on a refusal; the state is then untouched."""
+        sl = self.dims[0] * self.dims[1]
+        kb, pb, nb = _planes_arg(below, sl)
+        ka, pa, na = _planes_arg(above, sl)
+        n = C.c_int64(0)
+        rc = self._lib.vcy_redistance_slab(self._ctx, pb, nb, pa, na, C.byref(n))
+        del kb, ka
+        if rc != 0:
+            _raise_rc(rc)
+        return {"rewritten": int(n.value), "device_ms": self.last_distance_ms()}
 
     def last_distance_ms(self):
         ms = C.c_float()

@@ -37,5 +37,25 @@ inline int check_radius(const char* who, int radius) {
   return VCY_ERR_INVALID_ARG;
 }
 
+// The planes of its neighbours a slab [z_begin, z_end) of nz slices needs at either end: min(R, what the grid has there)
+inline int halo_below(int radius, int z_begin) { return radius < z_begin ? radius : z_begin; }
+inline int halo_above(int radius, int z_end, int nz) { return radius < nz - z_end ? radius : nz - z_end; }
+
+// ... and the finishing calls' check of what they were handed
+inline int check_halo(const char* who, int radius, int z_begin, int z_end, int nz, int n_below, int n_above, const void* below,
+                      const void* above) {
+  const int want_below = halo_below(radius, z_begin), want_above = halo_above(radius, z_end, nz);
+  if (n_below != want_below || n_above != want_above) {
+    set_error("%s: %d planes below and %d above; the slab [%d, %d) of %d slices needs %d and %d at radius %d", who, n_below,
+              n_above, z_begin, z_end, nz, want_below, want_above, radius);
+    return VCY_ERR_INVALID_ARG;
+  }
+  if ((n_below > 0 && !below) || (n_above > 0 && !above)) {
+    set_error("%s: null pointer", who);
+    return VCY_ERR_INVALID_ARG;
+  }
+  return VCY_OK;
+}
+
 }  // namespace df
 }  // namespace vcy

@@ -377,6 +377,7 @@ int vcy_get_param(vcy_ctx* c, const char* name, int* value) {
   else if (std::strcmp(name, "coopstore") == 0) *value = c->coop_store;
   else if (std::strcmp(name, "livesync") == 0) *value = c->live_sync ? 1 : 0;
   else if (std::strcmp(name, "brick_min_valid") == 0) *value = c->st.brick_min_valid && !c->st.fresh ? 1 : 0;
+  else if (std::strcmp(name, "fresh") == 0) *value = c->st.fresh ? 1 : 0;  // the fill has not been written yet
   else if (std::strcmp(name, "meshkeys") == 0) *value = c->mesh_keys ? 1 : 0;
   else if (std::strcmp(name, "rayskip") == 0) *value = c->ray_skip;
   else if (std::strcmp(name, "smoothpad") == 0) *value = c->smooth_pad;

@@ -196,6 +196,11 @@ struct vcy_ctx {
   vcy::DeviceBuf<> d_df_buf;          // [solid bits | row distances, 1 B | y-pass values, 2 B | phi table | counters | the int32 field]
   vcy::Event ev_df_begin, ev_df_end;  // around the launches of the last vcy_distance_field / vcy_redistance
   float last_distance_device_ms = 0.0f;
+  // ... of a z-slab (vcy_distance_slab_begin and what follows it): the part of the pool that outlives a call
+  vcy::DeviceBuf<> d_df_h;            // [planes of the neighbours below | the slab's y-pass values | planes of those above], 2 B each
+  int64_t df_epoch = -1;              // d_df_h's middle describes the state of this epoch (against st.epoch; -1: nothing kept) ...
+  double df_iso = 0.0;                // ... at this iso level ...
+  int df_radius = 0;                  // ... and radius, which also fixes the planes in front and behind
 
   // ray-cast of the hull (render.hip); everything grow-only
   vcy::DeviceBuf<> d_rn_bits;         // [solid bit of every voxel, 64-voxel words along x | one bit per 8 x 8 x 8 brick that holds a solid voxel]
@@ -278,7 +283,8 @@ int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int 
 // the state must be materialised.  Shared by the labelling and the ray-cast (render.hip).
 int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
 // distance.hip: vcy_distance_field, vcy_redistance, vcy_last_distance_ms; distance_host.hip (host code only):
-// vcy_distance_field_host; what the two share: distance_field.h
+// vcy_distance_field_host; what the two share: distance_field.h.  The z-slab form in both: vcy_distance_slab_begin,
+// vcy_distance_slab_planes, vcy_distance_field_slab, vcy_redistance_slab; vcy_distance_slab_planes_host, _finish_host
 // render.hip: vcy_render_hull, vcy_hull_agreement, vcy_render_hull_slab, vcy_cell_planes, vcy_last_render_ms
 // vcy_render_hull's depth images of up to 64 views (one launch), left in device memory: depth_dev[i] points into
 // vcy_ctx::d_rn_out and holds until the context next renders; waits for the launch; vcy_last_render_ms as for the render

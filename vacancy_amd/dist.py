@@ -439,3 +439,95 @@ def hull_agreement_slabs(carvers, rank=0, world=1, views=(), masks=(), iso_level
     for j, (v, m) in enumerate(zip(vs, ms)):
         counts[j] = _vc.hull_agreement_host(v, [bits[s][j] for s in range(world * k)], m)
     return counts
+
+
+# ---- distance field of the hull of a grid in z-slabs (the order of the calls: include/vacancy_hip.h) ------------------
+
+def distance_halos(z_ranges, radius, bottoms, tops):
+    """The pure assembly of the seam planes.  `z_ranges`: [(z0, z1)] of every slab of the grid in z order; bottoms[s] /
+    tops[s]: the lowest / highest min(radius, z1 - z0) planes of slab s, uint16 [planes, nx * ny] in ascending z (None
+    where nobody needs them: the bottom of the first slab, the top of the last).  Returns [(below, above)] per slab: the
+    planes of the global slices [z0 - min(radius, z0), z0) and [z1, z1 + min(radius, nz - z1)), from as many neighbours
+    as that takes -- a slab thinner than `radius` passes its neighbours' planes on --, None where there are none."""
+    nz = z_ranges[-1][1]
+    out = []
+    for i, (z0, z1) in enumerate(z_ranges):
+        lo, hi = z0 - min(radius, z0), z1 + min(radius, nz - z1)
+        below, above = [], []
+        for j in range(i - 1, -1, -1):  # downwards, until slice `lo` is covered
+            a0, a1 = z_ranges[j]
+            if a1 <= lo:
+                break
+            m = a1 - max(a0, lo)
+            below.insert(0, tops[j][len(tops[j]) - m:])
+        for j in range(i + 1, len(z_ranges)):
+            a0, a1 = z_ranges[j]
+            if a0 >= hi:
+                break
+            above.append(bottoms[j][:min(a1, hi) - a0])
+        out.append((np.concatenate(below) if below else None, np.concatenate(above) if above else None))
+    return out
+
+
+def _distance_slabs(carvers, rank, world, iso_level, radius, each, finish):
+    """begin on every slab, the planes through the host, finish(i, carver, below, above) on every slab.  Returns
+    ([finish's results], device ms of this rank's begins, bytes of planes this rank's slabs handed out)."""
+    k = len(carvers)
+    ids = [rank + i * world for i in range(k)]
+    count = world * k
+
+    def begin(i, c):
+        ms = c.DistanceSlabBegin(iso_level, radius)
+        z0, z1 = c.z_range
+        m = min(radius, z1 - z0)
+        bottom = c.DistanceSlabPlanes(z0, z0 + m) if ids[i] > 0 else None
+        top = c.DistanceSlabPlanes(z1 - m, z1) if ids[i] + 1 < count else None
+        return (z0, z1), bottom, top, ms
+
+    begun = each(carvers, begin)
+    got = _gather_by_slab(dict(zip(ids, [b[:3] for b in begun])), world)
+    halos = distance_halos([got[s][0] for s in range(count)], radius, [got[s][1] for s in range(count)],
+                           [got[s][2] for s in range(count)])
+    done = each(carvers, lambda i, c: finish(i, c, *halos[ids[i]]))
+    nbytes = sum(p.nbytes for b in begun for p in b[1:3] if p is not None)
+    return done, float(sum(b[3] for b in begun)), int(nbytes)
+
+
+def distance_field_slabs(carvers, rank=0, world=1, iso_level=0.0, radius=8, each=_each):
+    """DistanceField of a grid cut into z-slabs.  `carvers`, `each` as for label_components_slabs.  Every slab runs the x
+    and the y pass over its own slices on its device; its lowest and highest min(radius, own slices) planes of 16-bit
+    values are gathered as Python objects -- never a slab's volume --, every rank puts its slabs' halos together
+    (distance_halos) and every slab finishes with the z pass.  Every slab finishes one step before any slab begins the
+    next.  Returns {"fields": [the int32 field of each of this rank's slabs], "device_ms": the sum over this rank's slabs,
+    "plane_bytes": what this rank's slabs sent through the host}; the fields equal VoxelCarver.DistanceField of the
+    whole grid."""
+    ms = [0.0] * len(carvers)
+
+    def finish(i, c, below, above):
+        d2 = c.DistanceFieldSlab(below, above)
+        ms[i] = c.last_distance_ms()
+        return d2
+
+    fields, begin_ms, nbytes = _distance_slabs(carvers, rank, world, iso_level, radius, each, finish)
+    return {"fields": fields, "device_ms": begin_ms + float(sum(ms)), "plane_bytes": nbytes}
+
+
+def redistance_slabs(carvers, rank=0, world=1, iso_level=0.0, radius=8, each=_each):
+    """Redistance of a grid cut into z-slabs, by the steps of distance_field_slabs: every slab's state ends as the whole
+    grid's context would leave its slices.  The halos below the slabs are stale afterwards, as after a carve.  Returns
+    {"rewritten": [per slab of this rank], "device_ms": the sum over this rank's slabs, "begin_ms" / "finish_ms": its two
+    parts, "plane_bytes"}."""
+    parts, begin_ms, nbytes = _distance_slabs(carvers, rank, world, iso_level, radius, each,
+                                              lambda i, c, below, above: c.RedistanceSlab(below, above))
+    finish_ms = float(sum(p["device_ms"] for p in parts))
+    return {"rewritten": [p["rewritten"] for p in parts], "device_ms": begin_ms + finish_ms, "begin_ms": begin_ms,
+            "finish_ms": finish_ms, "plane_bytes": nbytes}
+
+
+def close_hull_slabs(carvers, rank=0, world=1, iso_level=0.0, radius_voxels=1.3, each=_each):
+    """CloseHull of a grid cut into z-slabs: the three steps of VoxelCarver.CloseHull, each a redistance_slabs, with the
+    plan and the tie rule of vacancy_amd.carver.close_hull_plan (ValueError, state untouched, for a radius on which the
+    closing ties).  Returns the three redistance_slabs dicts."""
+    from . import carver as _vc
+    r, big_r = _vc.close_hull_plan(radius_voxels, carvers[0].option.resolution)
+    return [redistance_slabs(carvers, rank, world, level, big_r, each) for level in (iso_level, r, -r)]

@@ -69,10 +69,12 @@ inline vcy_carver_option ToC(const VoxelCarverOption& o) {
   return c;
 }
 
-// CloseHull of both carvers on one context that owns the whole grid (the composition and the tie rule: vacancy_hip.h,
-// "distance field of the hull"): r = radius_voxels * resolution, R = ceil(radius_voxels) + 2, then the metric field, the
-// field of the hull grown by r, the field of that shrunk by r.  false with *error set when the radius ties or a call fails.
-inline bool CloseHullOn(vcy_ctx* ctx, float radius_voxels, double iso_level, float resolution, std::string* error) {
+// CloseHull of both carvers (the composition and the tie rule: vacancy_hip.h, "distance field of the hull"):
+// r = radius_voxels * resolution, R = ceil(radius_voxels) + 2, then step(level, R) for the metric field, the field of the
+// hull grown by r, the field of that shrunk by r.  `step` answers false with *error set.  false with *error set when the
+// radius ties -- before any step has run -- or a step fails.
+template <typename Step>
+inline bool CloseHullSteps(float radius_voxels, double iso_level, float resolution, std::string* error, Step step) {
   const double rv = static_cast<double>(radius_voxels);
   const int big_r = static_cast<int>(std::ceil(rv)) + 2;
   char msg[256];
@@ -97,14 +99,19 @@ inline bool CloseHullOn(vcy_ctx* ctx, float radius_voxels, double iso_level, flo
   }
   const double r = rv * static_cast<double>(resolution);
   const double iso[3] = {iso_level, r, -r};
-  for (double level : iso) {
-    std::int64_t n = 0;
-    if (vcy_redistance(ctx, level, big_r, &n) != VCY_OK) {
-      *error = vcy_last_error();
-      return false;
-    }
-  }
+  for (double level : iso)
+    if (!step(level, big_r)) return false;
   return true;
+}
+
+// ... on one context that owns the whole grid
+inline bool CloseHullOn(vcy_ctx* ctx, float radius_voxels, double iso_level, float resolution, std::string* error) {
+  return CloseHullSteps(radius_voxels, iso_level, resolution, error, [ctx, error](double level, int big_r) {
+    std::int64_t n = 0;
+    if (vcy_redistance(ctx, level, big_r, &n) == VCY_OK) return true;
+    *error = vcy_last_error();
+    return false;
+  });
 }
 
 }  // namespace detail

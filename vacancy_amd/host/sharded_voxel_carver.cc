@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 #include <array>
+#include <functional>
 #include <future>
 #include <limits>
 #include <string>
@@ -58,6 +59,10 @@ struct ShardedVoxelCarver::Impl {
     std::vector<int64_t> global;         // merged label of every piece
   };
   bool LabelSlabs(double iso_level, Labelled* out);
+  // the distance field over the slabs: vcy_distance_slab_begin on every slab, the seam planes through the host, then
+  // finish(slab, below, n_below, above, n_above) -- a C-ABI status -- on every slab
+  bool DistanceSlabs(double iso_level, int radius, const char* who,
+                     const std::function<int(size_t, const uint16_t*, int, const uint16_t*, int)>& finish);
   ~Impl() {
     for (vcy_ctx* c : slabs) vcy_destroy(c);
   }
@@ -476,6 +481,99 @@ bool ShardedVoxelCarver::CloseHull(float radius_voxels, double iso_level) {
   if (!OneSlab(impl_->slabs, "CloseHull")) return false;
   std::string error;
   const bool ok = detail::CloseHullOn(impl_->slabs[0], radius_voxels, iso_level, impl_->option.resolution, &error);
+  if (!ok) LOGE("%s\n", error.c_str());
+  return ok;
+}
+
+// Every slab finishes one step before any slab begins the next.  What a slab hands out: its lowest and its highest
+// min(radius, own slices) planes of 16-bit values; what it gets: the planes of the global slices [z0 - min(radius, z0), z0)
+// and [z1, z1 + min(radius, nz - z1)), from as many neighbours as that takes -- a slab thinner than the radius passes its
+// neighbours' planes on.
+bool ShardedVoxelCarver::Impl::DistanceSlabs(double iso_level, int radius, const char* who,
+                                             const std::function<int(size_t, const uint16_t*, int, const uint16_t*, int)>& finish) {
+  const size_t ns = slabs.size();
+  if (ns == 0) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  if (!ForEachSlab(ns, who, [&](size_t s) { return vcy_distance_slab_begin(slabs[s], iso_level, radius); })) return false;
+  const int nz = bounds[ns];
+  const size_t plane = static_cast<size_t>(slice);
+  auto edge = [&](size_t s) { return std::min(radius, bounds[s + 1] - bounds[s]); };
+  std::vector<std::vector<uint16_t>> bottoms(ns), tops(ns);
+  if (!ForEachSlab(ns, who, [&](size_t s) {
+        const int m = edge(s);
+        if (s > 0) {
+          bottoms[s].resize(plane * m);
+          const int rc = vcy_distance_slab_planes(slabs[s], bounds[s], bounds[s] + m, bottoms[s].data());
+          if (rc != VCY_OK) return rc;
+        }
+        if (s + 1 < ns) {
+          tops[s].resize(plane * m);
+          return vcy_distance_slab_planes(slabs[s], bounds[s + 1] - m, bounds[s + 1], tops[s].data());
+        }
+        return static_cast<int>(VCY_OK);
+      }))
+    return false;
+  // the plane of the global slice z, which lies below (from the owner's top planes) or above (bottom planes) the asker
+  auto plane_of = [&](int z, bool from_top) -> const uint16_t* {
+    const size_t j = static_cast<size_t>(std::upper_bound(bounds.begin(), bounds.end(), z) - bounds.begin()) - 1;
+    return from_top ? tops[j].data() + plane * static_cast<size_t>(z - (bounds[j + 1] - edge(j)))
+                    : bottoms[j].data() + plane * static_cast<size_t>(z - bounds[j]);
+  };
+  std::vector<std::vector<uint16_t>> below(ns), above(ns);
+  std::vector<int> n_below(ns), n_above(ns);
+  for (size_t s = 0; s < ns; ++s) {
+    const int z0 = bounds[s], z1 = bounds[s + 1];
+    n_below[s] = std::min(radius, z0), n_above[s] = std::min(radius, nz - z1);
+    below[s].resize(plane * n_below[s]);
+    above[s].resize(plane * n_above[s]);
+    for (int k = 0; k < n_below[s]; ++k)
+      std::memcpy(below[s].data() + plane * k, plane_of(z0 - n_below[s] + k, true), plane * sizeof(uint16_t));
+    for (int k = 0; k < n_above[s]; ++k)
+      std::memcpy(above[s].data() + plane * k, plane_of(z1 + k, false), plane * sizeof(uint16_t));
+  }
+  return ForEachSlab(ns, who, [&](size_t s) {
+    return finish(s, n_below[s] ? below[s].data() : nullptr, n_below[s], n_above[s] ? above[s].data() : nullptr, n_above[s]);
+  });
+}
+
+bool ShardedVoxelCarver::DistanceFieldSlabs(std::vector<std::int32_t>* d2, double iso_level, int radius) {
+  if (!d2 || impl_->slabs.empty()) {
+    LOGE("ShardedVoxelCarver::DistanceFieldSlabs needs an output and an initialized carver\n");
+    return false;
+  }
+  const std::vector<int>& b = impl_->bounds;
+  d2->resize(static_cast<size_t>(impl_->slice) * b.back());
+  const bool ok = impl_->DistanceSlabs(iso_level, radius, "DistanceFieldSlabs",
+                                       [&](size_t s, const uint16_t* below, int nb, const uint16_t* above, int na) {
+                                         return vcy_distance_field_slab(impl_->slabs[s], below, nb, above, na,
+                                                                        d2->data() + impl_->slice * b[s]);
+                                       });
+  if (!ok) d2->clear();
+  return ok;
+}
+
+bool ShardedVoxelCarver::RedistanceSlabs(double iso_level, int radius, std::int64_t* n_rewritten) {
+  std::vector<std::int64_t> n(impl_->slabs.size(), 0);
+  const bool ok = impl_->DistanceSlabs(iso_level, radius, "RedistanceSlabs",
+                                       [&](size_t s, const uint16_t* below, int nb, const uint16_t* above, int na) {
+                                         return vcy_redistance_slab(impl_->slabs[s], below, nb, above, na, &n[s]);
+                                       });
+  if (ok && n_rewritten) {
+    *n_rewritten = 0;
+    for (std::int64_t k : n) *n_rewritten += k;
+  }
+  return ok;
+}
+
+bool ShardedVoxelCarver::CloseHullSlabs(float radius_voxels, double iso_level) {
+  std::string error;
+  const bool ok = detail::CloseHullSteps(radius_voxels, iso_level, impl_->option.resolution, &error, [&](double level, int big_r) {
+    if (RedistanceSlabs(level, big_r, nullptr)) return true;
+    error = "CloseHullSlabs: a step failed";
+    return false;
+  });
   if (!ok) LOGE("%s\n", error.c_str());
   return ok;
 }

@@ -338,7 +338,8 @@ class ShardedVoxelCarver:
                                            each=self._each_slab)
 
     # -- the distance field of the hull (include/vacancy_hip.h): the transform of a z-slab needs `radius` slices of its
-    # neighbours per seam, which nothing exchanges yet -- the one-slab case only
+    # neighbours per seam, which these three do not exchange -- the one-slab case only (any number of slabs: the ...Slabs
+    # members below)
     ONE_SLAB_ONLY = "%s: the grid is cut into %d z-slabs; the distance field needs the whole grid in one context"
 
     def _whole_grid(self, who):
@@ -357,6 +358,25 @@ class ShardedVoxelCarver:
     def CloseHull(self, radius_voxels, iso_level=0.0):
         """VoxelCarver.CloseHull on a grid of one slab; RuntimeError on more."""
         return self._whole_grid("CloseHull").CloseHull(radius_voxels, iso_level)
+
+    # ... and over any number of slabs: every slab runs the x and the y pass on its device, up to `radius` planes of
+    # 16-bit values per seam go through the host, every slab finishes with the z pass
+    # (vacancy_amd.dist.distance_field_slabs) -- exactly what VoxelCarver returns on the whole grid
+    def DistanceFieldSlabs(self, iso_level=0.0, radius=8):
+        """VoxelCarver.DistanceField of the whole grid: the slabs' fields concatenated in z order."""
+        import numpy as np
+        r = vdist.distance_field_slabs(self.slabs, 0, 1, iso_level, radius, each=self._each_slab)
+        return np.concatenate(r["fields"])
+
+    def RedistanceSlabs(self, iso_level=0.0, radius=8):
+        """VoxelCarver.Redistance of the whole grid: {"rewritten": [per slab], "device_ms": the sum over the slabs,
+        "begin_ms", "finish_ms", "plane_bytes"}.  The halos go stale, as after a carve."""
+        return vdist.redistance_slabs(self.slabs, 0, 1, iso_level, radius, each=self._each_slab)
+
+    def CloseHullSlabs(self, radius_voxels, iso_level=0.0):
+        """VoxelCarver.CloseHull of the whole grid: the three RedistanceSlabs dicts.  ValueError, state untouched, for a
+        radius on which the closing ties."""
+        return vdist.close_hull_slabs(self.slabs, 0, 1, iso_level, radius_voxels, each=self._each_slab)
 
     # -- the ray-cast of the hull over the slabs (include/vacancy_hip.h): every slab renders its own slices on its device
     # -- no halo exchange --, depth images (or, for the agreement, one hit bit per pixel) go through the host, which
