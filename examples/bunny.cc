@@ -4,6 +4,7 @@
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --tolerate M [--blank-view I]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --smooth N [--lambda L --mu M]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --decimate CELLS [--decimate-mode mean|nearest|first|quadric [--quadric-reg R]]
+//        bunny <data_dir> <out_dir> [resolution] --smooth N ... --decimate CELLS ... --chain
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --redistance R [--offset MM]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --close VOXELS
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
@@ -27,6 +28,10 @@
 //   (binary, with normals); with slabs the merged mesh goes through ShardedVoxelCarver::DecimateMesh as well and is compared.
 //   --decimate-mode quadric puts every cluster at its quadric-error representative instead (VoxelCarver::DecimateMeshQuadric,
 //   regularisation --quadric-reg R in [0, 1], by default 0.001) and prints how many output vertices kept the mean.
+//   --chain (with --smooth and / or --decimate, single carver) runs extraction, smoothing and decimation as ONE call
+//   (VoxelCarver::ExtractIsoSurfaceChain: the mesh stays on the device between the stages) and again as the separate calls,
+//   prints the chain's sizes and timings with `identical 1` when the two agree bit for bit, and writes the chain's mesh as
+//   <out_dir>/surface_chain.ply.
 //   --redistance R (after the ordinary carve and --keep-largest) rewrites the state as the metric distance field of the hull
 //   (VoxelCarver::Redistance, exact up to R voxels), extracts the iso-surface at --offset MM (world units, by default 0:
 //   the hull itself; positive grows it, negative shrinks it; |MM| < (R - 0.5) * resolution), writes it as
@@ -90,6 +95,7 @@ int main(int argc, char* argv[]) {
   int decimate_mode = 0;   // --decimate-mode mean|nearest|first|quadric (3: VoxelCarver::DecimateMeshQuadric)
   float quadric_reg = 1e-3f;  // --quadric-reg R
   bool quadric_reg_given = false;
+  bool chain = false;      // --chain: extraction, --smooth and --decimate in one call, against the separate calls
   int redistance = 0;      // --redistance R: the state becomes the metric distance field of the hull, exact up to R voxels
   float offset_mm = 0.0f;  // --offset MM: the iso level of the surface extracted from it
   float close_voxels = 0.0f;  // --close VOXELS: morphological closing of the hull first
@@ -98,6 +104,7 @@ int main(int argc, char* argv[]) {
     int n = 1;
     for (int i = 1; i < argc; ++i) {
       if (std::string(argv[i]) == "--keep-largest") keep_largest = true;
+      else if (std::string(argv[i]) == "--chain") chain = true;
       else if (std::string(argv[i]) == "--fuse-depth") fuse_depth = true;
       else if (std::string(argv[i]) == "--render") {
         if (i + 1 >= argc) {
@@ -163,6 +170,10 @@ int main(int argc, char* argv[]) {
       } else argv[n++] = argv[i];
     }
     argc = n;
+    if (chain && smooth < 0 && !(decimate > 0.0f)) {
+      std::fprintf(stderr, "--chain goes with --smooth and / or --decimate\n");
+      return 10;
+    }
     if (quadric_reg_given && decimate_mode != 3) {
       std::fprintf(stderr, "--quadric-reg goes with --decimate-mode quadric\n");
       return 10;
@@ -364,6 +375,43 @@ int main(int argc, char* argv[]) {
         same = std::memcmp(&sm.vertex_indices()[k], &mesh.vertex_indices()[k], 12) == 0;
       std::printf("DECIMATESHARDED slabs %d verts %zu identical %d\n", sharded->slab_count(), sm.vertices().size(), same ? 1 : 0);
     }
+  }
+
+  if (chain) {  // extraction, smoothing and decimation in ONE call, the mesh staying on the device, against the calls above
+    const bool quadric = decimate_mode == 3;
+    vacancy::ChainOption co;
+    co.smooth = smooth >= 0;
+    co.iterations = smooth >= 0 ? smooth : 0;
+    co.lambda = smooth_lambda;
+    co.mu = smooth_mu;
+    co.decimate = decimate > 0.0f ? (quadric ? 2 : 1) : 0;
+    co.cell = decimate * resolution;
+    co.mode = quadric ? 0 : decimate_mode;
+    co.regularize = quadric_reg;
+    vacancy::Mesh got, want;
+    vacancy::ChainReport report;
+    if (!carver.ExtractIsoSurfaceChain(&got, co, &report)) return 19;
+    const std::array<float, 8> ms = carver.last_chain_ms();
+    std::int64_t n_fallback = 0;
+    carver.ExtractIsoSurface(&want, 0.0);
+    if (smooth >= 0 && !carver.SmoothMesh(&want, smooth, smooth_lambda, smooth_mu, false, co.decimate == 0)) return 19;
+    if (co.decimate != 0 && !(quadric ? carver.DecimateMeshQuadric(&want, co.cell, quadric_reg, true, &n_fallback)
+                                      : carver.DecimateMesh(&want, co.cell, decimate_mode, true)))
+      return 19;
+    bool same = got.vertices().size() == want.vertices().size() && got.vertex_indices().size() == want.vertex_indices().size() &&
+                got.normals().size() == want.normals().size() && got.face_normals().size() == want.face_normals().size() &&
+                report.n_fallback == n_fallback;
+    for (size_t k = 0; same && k < got.vertices().size(); ++k)
+      same = std::memcmp(&got.vertices()[k], &want.vertices()[k], 12) == 0 && std::memcmp(&got.normals()[k], &want.normals()[k], 12) == 0;
+    for (size_t k = 0; same && k < got.vertex_indices().size(); ++k)
+      same = std::memcmp(&got.vertex_indices()[k], &want.vertex_indices()[k], 12) == 0 &&
+             std::memcmp(&got.face_normals()[k], &want.face_normals()[k], 12) == 0;
+    got.WritePlyBinary(out_dir + "/surface_chain.ply");
+    std::printf("CHAIN smooth %d decimate %d extracted %lld %lld verts %zu faces %zu fallback %lld extract_ms %.4f table_ms %.4f "
+                "passes_ms %.4f cluster_ms %.4f quadric_ms %.4f faces_emit_ms %.4f normals_ms %.4f wall_ms %.4f identical %d\n",
+                smooth, co.decimate, (long long)report.n_extracted_vertices, (long long)report.n_extracted_faces, got.vertices().size(),
+                got.vertex_indices().size(), (long long)report.n_fallback, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms[7],
+                same ? 1 : 0);
   }
 
   if (!render_dir.empty()) {  // what the hull looks like from every input camera (vcy_render_hull / vcy_hull_agreement)

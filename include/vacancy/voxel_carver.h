@@ -90,6 +90,28 @@ struct ColorOption {
   Eigen::Vector3f fallback = Eigen::Vector3f(128.0f, 128.0f, 128.0f);  // colour of a vertex no view sees
 };
 
+// The stages of VoxelCarver::ExtractIsoSurfaceChain and what it reports beside the mesh.  No counterpart in the reference.
+struct ChainOption {
+  double iso_level{0.0};
+  bool linear_interp{true};
+  bool smooth{false};           // SmoothMesh(iterations, lambda, mu, pin_boundary)
+  int iterations{10};
+  float lambda{0.5f};
+  float mu{-0.53f};
+  bool pin_boundary{false};
+  int decimate{0};              // 0 none, 1 DecimateMesh(cell, mode), 2 DecimateMeshQuadric(cell, regularize)
+  float cell{0.0f};
+  int mode{0};
+  float regularize{1e-3f};
+  bool maps{false};             // fill ChainReport::vertex_map / face_source (decimate != 0)
+};
+struct ChainReport {
+  std::int64_t n_extracted_vertices{0}, n_extracted_faces{0};  // of the mesh ExtractIsoSurface would have returned
+  std::int64_t n_fallback{0};                                  // decimate == 2: output vertices that kept the mean
+  std::vector<std::int32_t> vertex_map;   // per extracted vertex: its output vertex or -1
+  std::vector<std::int32_t> face_source;  // per output face: the extracted face it was
+};
+
 // One 6-connected component of the solid voxels (update_num >= 1 and sdf < iso_level): vcy_component of vacancy_hip.h.
 // No counterpart in the reference.
 struct VoxelComponent {
@@ -214,6 +236,14 @@ class VoxelCarver {
   bool DecimateMeshQuadric(Mesh* mesh, float cell, float regularize = 1e-3f, bool with_normals = false,
                            std::int64_t* n_fallback = nullptr);
   float last_quadric_ms() const;
+
+  // ExtractIsoSurface, SmoothMesh, DecimateMesh[Quadric] and Mesh::CalcNormal() in one call (vcy_extract_iso_chain), the
+  // mesh staying on the device between the stages: the bits of the separate members in that order, smoothing first.  The
+  // mesh gets vertices, faces and normals as ExtractIsoSurface(..., with_normals = true) gives them.  false + LOGE on an
+  // error, the mesh is then empty.  last_chain_ms(): device milliseconds of the extraction, the corner table, the passes,
+  // the clusters, the quadric stage inside them, faces + emit, the normals, and the call's wall time.
+  bool ExtractIsoSurfaceChain(Mesh* mesh, const ChainOption& option, ChainReport* report = nullptr);
+  std::array<float, 8> last_chain_ms() const;
 
   // grid access for host-side consumers: global dims and the voxel state in id order
   Eigen::Vector3i voxel_num() const;

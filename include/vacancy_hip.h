@@ -1018,6 +1018,58 @@ int vcy_decimate_mesh_quadric(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces,
  * 0 after one that had nothing to do.  vcy_last_decimate_ms reports that call's four groups, this stage inside "clusters". */
 int vcy_last_quadric_ms(const vcy_ctx* ctx, float* device_ms);
 
+/* ---- extraction chain: extract, smooth, decimate and normals in one call, the mesh staying on the device ----- */
+/* The result is BY DEFINITION the bits of the separate calls run in this order: vcy_extract_iso; if `smooth`,
+ * vcy_smooth_mesh on its output; if `decimate`, vcy_decimate_mesh (1) or vcy_decimate_mesh_quadric (2, with `regularize`)
+ * on that; Mesh::CalcNormal (vcy_mesh_normals_host) of the last mesh for the arrays `which` names.  The order is fixed:
+ * smoothing first, then decimation.  With both stages off the call is vcy_extract_iso_normals (which = 0: vcy_extract_iso,
+ * without edge keys).  Only the final mesh, its normals and -- `maps` = 1 -- the decimation's two maps cross to the host;
+ * the extracted mesh is staged in device memory whatever "mcdirect" says, the stages read it there, and the vertex ->
+ * incident-corner table of the extracted mesh is built once and serves the smoothing, the quadric stage and the normals
+ * of an undecimated result.  The call waits for the extraction's counts, for the decimation's counts, and for the output.
+ *
+ * An empty extraction yields an empty mesh and VCY_OK.  VCY_ERR_UNSUPPORTED for a context that owns a z-slab (a slab's
+ * mesh is a part; the merged mesh exists only on the host) and for one that returns edge keys (vcy_set_param "meshkeys"
+ * 1: the chain's mesh has none).  Option errors are the refusals of the separate calls with their codes, reported before
+ * any launch and before the context is looked at; a stage that is off is not checked.  An extracted mesh beyond
+ * vcy_mesh_index_limits is refused with the separate calls' VCY_ERR_UNSUPPORTED before a stage is launched on it (not with
+ * both stages off: the extraction takes it).  `smooth`, `maps` outside 0 / 1, `decimate` outside 0 .. 2 or `which` outside
+ * the VCY_NORMALS_* bits: VCY_ERR_INVALID_ARG. */
+typedef struct vcy_chain_option {
+  int32_t smooth;                       /* 0 / 1 */
+  vcy_smooth_option smooth_option;
+  int32_t decimate;                     /* 0 none, 1 vertex clustering, 2 quadric representatives */
+  vcy_decimate_option decimate_option;
+  float   regularize;                   /* decimate = 2 */
+  int32_t which;                        /* VCY_NORMALS_* of the final mesh */
+  int32_t maps;                         /* 1: the report carries vertex_map and face_source (decimate != 0) */
+} vcy_chain_option;   /* 56 bytes */
+typedef struct vcy_chain_report {
+  int64_t n_extracted_vertices, n_extracted_faces;  /* of the mesh vcy_extract_iso would have returned */
+  int64_t n_fallback;                   /* decimate = 2: output vertices that keep the mean; else 0 */
+  int32_t* vertex_map;                  /* [n_extracted_vertices] output index or -1; NULL unless maps and decimate */
+  int32_t* face_source;                 /* [out->n_faces] index of the extracted face; NULL unless maps and decimate */
+} vcy_chain_report;   /* 40 bytes; the arrays are the library's: vcy_chain_report_free */
+/* out: as vcy_extract_iso's (vcy_mesh_free), edge_keys NULL and n_foreign_vertices 0.  normals may be NULL when which is 0
+ * (vcy_mesh_normals_free); report may be NULL. */
+int vcy_extract_iso_chain(vcy_ctx* ctx, double iso_level, int linear_interp, const vcy_chain_option* option, vcy_mesh* out,
+                          vcy_mesh_normals* normals, vcy_chain_report* report);
+void vcy_chain_report_free(vcy_chain_report* report);
+/* The size of a mesh the mesh operators of this header take: VCY_OK, or VCY_ERR_UNSUPPORTED for more than 2^31 - 1 vertices
+ * or more than (2^31 - 3) / 3 faces -- vertex ids and corner ids 3 f + j are 32 bits wide in their tables.  It is the check
+ * vcy_smooth_mesh[_host] and vcy_decimate_mesh[_quadric][_host] apply to their input and vcy_extract_iso_chain applies to
+ * the mesh it has extracted (which may be larger: the extraction counts faces in 32 bits unsigned), before any stage is
+ * launched on it.  Negative counts: VCY_ERR_INVALID_ARG.  No context, no GPU. */
+int vcy_mesh_index_limits(int64_t n_vertices, int64_t n_faces);
+/* Times of the last vcy_extract_iso_chain, device milliseconds but the last: the extraction's kernels; the shared corner
+ * table (count, scan, fill, and the smoothing's row sort and gather rows); the smoothing passes; the decimation's cluster
+ * group (the quadric stage inside it); the quadric stage alone; its faces and emit groups together; the normals of the
+ * final mesh; and the call's wall time on the host.  A stage that did not run reports 0, and so does every stage after a
+ * call that was refused for its context; a call refused for its arguments leaves the times of the call before.  Any output
+ * may be NULL. */
+int vcy_last_chain_ms(const vcy_ctx* ctx, float* extract_ms, float* table_ms, float* passes_ms, float* cluster_ms,
+                      float* quadric_ms, float* faces_emit_ms, float* normals_ms, float* wall_ms);
+
 /* ---- state access (tests, ExtractVoxel on the host, checkpoint) ---------- */
 
 /* Copies the slab's voxel state to the host: sdf[nx*ny*nz_local] and
@@ -1174,6 +1226,10 @@ int vcy_reset(vcy_ctx* ctx);
  * "smoothpad" (default 0): 1 keeps the positions of vcy_smooth_mesh's passes at 16 bytes per vertex (one 16-byte gather)
  * instead of 12 (three 4-byte gathers); measured slower at every size (profiles/smooth/measure_smooth.txt).  Results
  * identical (readable through vcy_get_param).
+ * "chainrows" (default 1): the corner table of vcy_extract_iso_chain comes from the cells of the extraction (the walk of the
+ * vertex normals: no atomics; rows ascending as written, though the stages sort them regardless); 0: from the faces, as
+ * vcy_smooth_mesh builds it.  1 is the faster one at 512^3 and 1024^3 by more than the run-to-run spread
+ * (profiles/chain/measure_chain.txt).  Results identical (readable through vcy_get_param).
  * "inject_carve_failure" (test hook, default 0): the next `value` applications of views fail with
  * VCY_ERR_INTERNAL before anything is launched -- how the tests exercise the error contract of vcy_carve. */
 int vcy_set_param(vcy_ctx* ctx, const char* name, int value);

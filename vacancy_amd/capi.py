@@ -132,6 +132,30 @@ class DecimateOption(C.Structure):
         super().__init__(cell, (C.c_float * 3)(*origin), mode)
 
 
+class ChainOption(C.Structure):
+    """vcy_chain_option: the stages of vcy_extract_iso_chain."""
+    _fields_ = [
+        ("smooth", C.c_int32),
+        ("smooth_option", SmoothOption),
+        ("decimate", C.c_int32),
+        ("decimate_option", DecimateOption),
+        ("regularize", C.c_float),
+        ("which", C.c_int32),
+        ("maps", C.c_int32),
+    ]
+
+
+class ChainReport(C.Structure):
+    """vcy_chain_report: the extracted mesh's counts, the fallbacks and the decimation's maps (vcy_chain_report_free)."""
+    _fields_ = [
+        ("n_extracted_vertices", C.c_int64),
+        ("n_extracted_faces", C.c_int64),
+        ("n_fallback", C.c_int64),
+        ("vertex_map", C.POINTER(C.c_int32)),
+        ("face_source", C.POINTER(C.c_int32)),
+    ]
+
+
 class Component(C.Structure):
     """vcy_component: one 6-connected component of the solid voxels (vcy_label_components)."""
     _fields_ = [
@@ -257,6 +281,10 @@ def load():
         "vcy_decimate_mesh_quadric": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(DecimateOption), C.c_float, vp, vp,
                                                 P(C.c_int64), P(C.c_int64), vp, vp, vp, vp, P(C.c_int64)]),
         "vcy_last_quadric_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_extract_iso_chain": (C.c_int, [vp, C.c_double, C.c_int, P(ChainOption), P(Mesh), P(MeshNormals), P(ChainReport)]),
+        "vcy_chain_report_free": (None, [P(ChainReport)]),
+        "vcy_mesh_index_limits": (C.c_int, [C.c_int64, C.c_int64]),
+        "vcy_last_chain_ms": (C.c_int, [vp] + [P(C.c_float)] * 8),
         "vcy_mesh_normals_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "vcy_mesh_normals_host_seam": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
         "vcy_mesh_normals_seam_sum": (C.c_int, [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),

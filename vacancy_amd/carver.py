@@ -1028,6 +1028,66 @@ class VoxelCarver:
         out["cluster_ms"], out["faces_ms"], out["emit_ms"], out["normals_ms"], out["quadric_ms"] = (m.value for m in ms)
         return out
 
+    # -- extract, smooth, decimate and normals in one call, the mesh staying on the device (definition: include/vacancy_hip.h)
+    CHAIN_MS = ("extract_ms", "table_ms", "passes_ms", "cluster_ms", "quadric_ms", "faces_emit_ms", "normals_ms", "wall_ms")
+
+    def chain_option(self, smooth=None, decimate=None, normals=True, maps=False):
+        """The vcy_chain_option of ExtractIsoChain's arguments.  smooth: None or a dict of SmoothMesh's keywords
+        (iterations, lam, mu, pin_boundary).  decimate: None or a dict with cell and either mode (DecimateMesh) or
+        regularize (DecimateMeshQuadric), and optionally origin (default: the carver's bb_min)."""
+        o = capi.ChainOption()
+        if smooth is not None:
+            o.smooth = 1
+            o.smooth_option = SmoothOption(int(smooth["iterations"]), float(smooth.get("lam", 0.5)), float(smooth.get("mu", -0.53)),
+                                           int(smooth.get("pin_boundary", False)))
+        if decimate is not None:
+            quadric = "regularize" in decimate
+            o.decimate = 2 if quadric else 1
+            origin = decimate.get("origin")
+            origin = tuple(self.option.bb_min) if origin is None else origin
+            o.decimate_option = DecimateOption(float(decimate["cell"]), [float(x) for x in origin],
+                                               int(decimate.get("mode", capi.VCY_DECIMATE_MEAN)))
+            o.regularize = float(decimate["regularize"]) if quadric else 0.0
+        o.which = (capi.VCY_NORMALS_VERTEX | capi.VCY_NORMALS_FACE) if normals else 0
+        o.maps = int(bool(maps))
+        return o
+
+    def ExtractIsoChain(self, iso_level=0.0, linear_interp=True, smooth=None, decimate=None, normals=True, maps=False):
+        """vcy_extract_iso_chain: the bits of ExtractIsoSurface -> SmoothMesh -> DecimateMesh[Quadric] -> normals of the last
+        mesh, without the mesh leaving the device in between (arguments: chain_option).  Needs a whole-grid context with
+        "meshkeys" 0.  Returns {"vertices", "faces"}, with normals "normals" and "face_normals", with a decimation and
+        maps=True "vertex_map" and "face_source" (numbered by the extracted mesh), with quadric representatives
+        "n_fallback", then "extracted": (vertices, faces) of the extracted mesh and the times of CHAIN_MS.  RuntimeError
+        (with .rc) on a refusal."""
+        o = self.chain_option(smooth, decimate, normals, maps)
+        m, mn, rep = Mesh(), capi.MeshNormals(), capi.ChainReport()
+        rc = self._lib.vcy_extract_iso_chain(self._ctx, iso_level, int(linear_interp), C.byref(o), C.byref(m), C.byref(mn),
+                                             C.byref(rep))
+        if rc != 0:
+            e = RuntimeError(last_error())
+            e.rc = rc
+            raise e
+        nv, nf = m.n_vertices, m.n_faces
+        out = {"vertices": _mesh_array(m.vertices, nv, 3, np.float32), "faces": _mesh_array(m.faces, nf, 3, np.int32)}
+        if normals:
+            out["normals"] = _mesh_array(mn.vertex_normals, nv, 3, np.float32)
+            out["face_normals"] = _mesh_array(mn.face_normals, nf, 3, np.float32)
+        out["extracted"] = (int(rep.n_extracted_vertices), int(rep.n_extracted_faces))
+        if o.decimate and maps:
+            out["vertex_map"] = (_mesh_array(rep.vertex_map, out["extracted"][0], 1, np.int32).reshape(-1)
+                                 if rep.vertex_map else np.full(out["extracted"][0], -1, np.int32))
+            out["face_source"] = _mesh_array(rep.face_source, nf, 1, np.int32).reshape(-1)
+        if o.decimate == 2:
+            out["n_fallback"] = int(rep.n_fallback)
+        self._lib.vcy_mesh_free(C.byref(m))
+        self._lib.vcy_mesh_normals_free(C.byref(mn))
+        self._lib.vcy_chain_report_free(C.byref(rep))
+        ms = [C.c_float() for _ in self.CHAIN_MS]
+        self._lib.vcy_last_chain_ms(self._ctx, *[C.byref(x) for x in ms])
+        for key, x in zip(self.CHAIN_MS, ms):
+            out[key] = x.value
+        return out
+
     # -- state access
     def download(self):
         n = self.slab_voxels

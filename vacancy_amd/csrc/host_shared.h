@@ -53,6 +53,18 @@ inline int dims_from_option(const float bb_min[3], const float bb_max[3], float 
   return VCY_OK;
 }
 
+// The size of an indexed mesh the mesh operators take: vertex ids and corner ids 3 f + j are 32 bits wide in their tables.
+// The ONE place the bound lives: vcy_smooth_mesh[_host], vcy_decimate_mesh[_quadric][_host] (their argument checks), the
+// extraction chain for the mesh it has just extracted (mesh_chain.hip), and vcy_mesh_index_limits.
+inline int mesh_index_limits(const char* who, int64_t n_vertices, int64_t n_faces) {
+  constexpr int64_t kMax = std::numeric_limits<int32_t>::max();
+  if (n_faces > (kMax - 2) / 3 || n_vertices > kMax) {
+    set_error("%s: %lld vertices, %lld faces: corner and vertex ids are 32 bits wide", who, (long long)n_vertices, (long long)n_faces);
+    return VCY_ERR_UNSUPPORTED;
+  }
+  return VCY_OK;
+}
+
 // The part of a carve view's checks that needs no context: image size and ROI.
 inline int check_view_static(const vcy_view* v) {
   if (!v || v->width <= 0 || v->height <= 0) {

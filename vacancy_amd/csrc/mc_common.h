@@ -252,5 +252,44 @@ struct NormalsLaunch {
 };
 hipError_t launch_normals(hipStream_t stream, const McParams& p, const NormalsLaunch& a);
 
+// mc_normals.hip: the vertex -> incident-corner table of the mesh an extraction of a WHOLE grid has left (rows of corner
+// ids 3 f + j by vertex faces[3 f + j], every row ascending: mesh_rows.h's table after its sort) from the cells instead of
+// from the faces.  The thread that owns a grid edge walks the cells around it as mc_vertex_normals_kernel does, so a row
+// comes out in ascending corner id without atomics and without a sort.  The counts are the host's (the extraction has been
+// waited for and fitted its capacities).  Three launches the caller puts its scan between:
+//   launch_corner_rows_count  mc_face_base (the first face of every active cell: the block's offset plus mc_emit's block
+//                             scan of the triangle counts) into `face_base`, and the row lengths into `deg`
+//   -- the caller: exclusive scan of deg[0 .. n_vertices], row offsets into `off` --
+//   launch_corner_rows_fill   the rows into `items`
+struct CornerRowsLaunch {
+  const McTables* T;
+  const u64* act;
+  const u64* cell_list;
+  int64_t n_cells, n_vertices, n_faces;
+  const uint32_t* info;
+  const u64* block_offs;
+  const uint32_t* word_cell_off;
+  const u64* block_cell_offs;
+  uint32_t* face_base;  // [n_cells]
+  u64* deg;             // [n_vertices + 1], cleared by the caller
+  const int* off;       // [n_vertices + 1]
+  int* items;           // [3 n_faces]
+};
+hipError_t launch_corner_rows_count(hipStream_t stream, const McParams& p, const CornerRowsLaunch& a);
+hipError_t launch_corner_rows_fill(hipStream_t stream, const McParams& p, const CornerRowsLaunch& a);
+
 }  // namespace mc
+
+// mc_extract.hip: extract_iso with the mesh left where mc_emit wrote it, the device staging vcy_ctx::d_mc_out, whatever
+// "mcdirect" says (valid until the context next extracts): a whole-grid context without edge keys.  The first stage of the
+// extraction chain (mesh_chain.hip).  The counts are those of the extraction's own wait.
+struct StagedMesh {
+  const float* vertices;  // device, 3 floats per vertex; null when the mesh is empty
+  const int32_t* faces;   // device, 3 ints per face
+  int64_t n_vertices, n_faces;
+  mc::McParams p;             // the cell-word layout of the extraction ...
+  mc::CornerRowsLaunch cells; // ... and its cell arrays (face_base .. items are the caller's to fill in)
+};
+int extract_iso_staged(vcy_ctx* ctx, double iso, int linear_interp, StagedMesh* staged);
+
 }  // namespace vcy

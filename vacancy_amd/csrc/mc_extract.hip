@@ -84,6 +84,7 @@ struct Extraction {
   bool end_recorded = false, normals_timed = false;
   // number of active cells and what they produce
   int64_t ncells = 0, nv = 0, nf = 0, nforeign = 0, first_layer_faces = 0, last_layer_faces = 0;
+  StagedMesh* staged = nullptr;  // extract_iso_staged: the mesh stays in the device staging, nothing is delivered
   bool timing = false;
   double t_begin = 0.0, t_ph[5] = {0, 0, 0, 0, 0};
 
@@ -242,7 +243,7 @@ struct Extraction {
     const size_t sz_f = align256(sizeof(int) * 3 * (size_t)std::max<int64_t>(cap_f, 1));
     // (with normals the mesh is staged on the device: mc_face_normals reads the emitted arrays, and must not read them
     // back over PCIe)
-    if (!wants_normals() && (int64_t)(sz_v + sz_f + (c->mesh_keys ? sz_k : 0)) <= c->mc_direct_bytes) {
+    if (!wants_normals() && !staged && (int64_t)(sz_v + sz_f + (c->mesh_keys ? sz_k : 0)) <= c->mc_direct_bytes) {
       bool pinned = true, pk = true, pf = true;
       out->vertices = (float*)mesh_host_alloc(sz_v, &pinned);
       out->faces = (int32_t*)mesh_host_alloc(sz_f, &pf);
@@ -456,6 +457,13 @@ struct Extraction {
     VCY_HIP_CHECK(hipEventSynchronize(c->ev_mc_end));
     VCY_HIP_CHECK(hipEventElapsedTime(&c->last_extract_device_ms, c->ev_mc_begin, c->ev_mc_end));
     if (timing) t_ph[3] = now_us();
+    if (staged) {  // (the counts of the one wait above; an empty mesh has no arrays)
+      const bool any = ncells > 0 && nv > 0 && nf > 0;
+      *staged = StagedMesh{any ? chain.verts : nullptr, any ? chain.faces : nullptr, any ? nv : 0, any ? nf : 0, p,
+                           CornerRowsLaunch{chain.T, chain.act, chain.cell_list, ncells, nv, nf, chain.info, chain.block_offs,
+                                            chain.word_cell_off, chain.block_cells, nullptr, nullptr, nullptr, nullptr}};
+      return VCY_OK;
+    }
     return deliver();
   }
 };
@@ -476,6 +484,16 @@ int extract_iso(vcy_ctx* c, double iso, int linear_interp, vcy_mesh* out, int wh
   const int rc = x.run(iso, linear_interp);
   if (rc == VCY_OK) x.host.armed = false;
   return rc;
+}
+
+// The extraction of extract_iso with the mesh left where mc_emit wrote it, the device staging vcy_ctx::d_mc_out, whatever
+// "mcdirect" says: the extraction chain's first stage (mesh_chain.hip).  The counts are those of the extraction's own wait.
+int extract_iso_staged(vcy_ctx* c, double iso, int linear_interp, StagedMesh* staged) {
+  *staged = StagedMesh{};
+  vcy_mesh none{};
+  Extraction x(c, &none, 0, nullptr, nullptr);
+  x.staged = staged;
+  return x.run(iso, linear_interp);
 }
 
 }  // namespace vcy

@@ -226,7 +226,95 @@ __global__ __launch_bounds__(256) void mc_layer_faces_kernel(McParams p, Normals
   }
 }
 
+// ---- the vertex -> incident-corner table from the cells (CornerRowsLaunch, mc_common.h) ---------------------------
+// The first face of every active cell, as mc_emit numbers them: the offset of the cell's block of 256 list entries plus the
+// triangles of the cells before it in the block.  Precondition: a WHOLE grid.  A z-slab's list begins with its ghost cells,
+// which are active and have a case but no faces (mc_emit: `li > 0`); they are not told apart here, and mc_corner_rows below
+// does not walk the ghost layer either.  vcy_extract_iso_chain refuses a slab before it gets here.
+__global__ __launch_bounds__(256) void mc_face_base_kernel(CornerRowsLaunch a) {
+  __shared__ int sm[4];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int ntri = i < a.n_cells ? a.T->ntri[(a.info[i] >> 12) & 0xFF] : 0;
+  int tot;
+  const int before = block_exclusive_scan(ntri, &tot, sm);
+  if (i < a.n_cells) a.face_base[i] = (uint32_t)(a.block_offs[i >> 8] & 0xFFFFFFFFull) + (uint32_t)before;
+}
+
+// One thread per active cell, the edges it owns, the walk of mc_vertex_normals_kernel: the cells around the edge in raster
+// order -- so ascending face index --, in each the triangles that name the edge, in each triangle the corners in ascending j.
+// FILL false: the number of corners into deg[vertex]; true: the corners 3 (face base + t) + j into the vertex's row.  No
+// positions, no case recomputed: a neighbour's case and face base come from its list entry, found through its ACT word as
+// mc_emit finds an owner.  As compiled for gfx950: see DESIGN.md, "extraction chain".
+template <bool FILL>
+__global__ __launch_bounds__(256) void mc_corner_rows_kernel(McParams p, CornerRowsLaunch a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_cells) return;
+  const int64_t slot = (int64_t)a.cell_list[i];
+  Cell c;
+  int w;
+  decode_word(p, slot >> 6, &c.li, &c.cy, &w);
+  c.x = w * 64 + (int)(slot & 63);
+  const uint32_t inf = a.info[i];
+  const int owned = inf & 0xFFF, code = (inf >> 12) & 0xFF;
+  if (owned == 0 || c.li < 1) return;
+  const int64_t v0 = (int64_t)(a.block_offs[i >> 8] >> 32) + (int64_t)(inf >> 20);  // first vertex of this cell
+  const int64_t n_items = 3 * a.n_faces;
+  for (int e = 0; e < 12; ++e) {
+    if (!((owned >> e) & 1)) continue;
+    const int64_t vid = v0 + __popc(owned & (int)a.T->prec[code][e]);
+    if (vid >= a.n_vertices) continue;  // (never, for the mesh these arrays describe)
+    const int axis = kGrp[e][0], me = kGrp[e][1];
+    const int64_t row = FILL ? (int64_t)a.off[vid] : 0;
+    int count = 0;
+    // this cell owns the edge: the cells before it around the edge are not active
+    for (int k = me; k < 4; ++k) {
+      int scode = code;
+      int64_t si = i;
+      if (k > me) {
+        const Cell s = group_cell(c, axis, me, k);
+        if (s.li < 1 || s.li > p.L || s.cy < 0 || s.cy >= p.Y || s.x < 1 || s.x >= p.nx) continue;
+        const int64_t cw = word_index(p, s.li, s.cy, s.x >> 6);
+        const u64 aw = a.act[cw];
+        if (!((aw >> (s.x & 63)) & 1ull)) continue;
+        si = (int64_t)a.block_cell_offs[cw >> 8] + a.word_cell_off[cw] + __popcll(aw & ((1ull << (s.x & 63)) - 1ull));
+        if (si >= a.n_cells) continue;  // (never)
+        scode = (a.info[si] >> 12) & 0xFF;
+      }
+      const int se = kGrpEdge[axis][k];
+      const uint4 trow = *reinterpret_cast<const uint4*>(&a.T->tri[scode][0]);
+      const int ntri = a.T->ntri[scode];
+      const int64_t fb = FILL ? (int64_t)a.face_base[si] : 0;
+      for (int t = 0; t < ntri; ++t) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          // corner j of the face reads entry 3t + (2 - j) (marching_cubes.cc:199-206)
+          const int idx = 3 * t + (2 - j);
+          const uint32_t word = (idx < 4) ? trow.x : (idx < 8) ? trow.y : (idx < 12) ? trow.z : trow.w;
+          if ((int)((word >> (8 * (idx & 3))) & 0xFFu) != se) continue;
+          if (FILL && row + count < n_items) a.items[row + count] = (int)(3 * (fb + t) + j);
+          ++count;
+        }
+      }
+    }
+    if (!FILL) a.deg[vid] = (u64)count;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_corner_rows_count(hipStream_t stream, const McParams& p, const CornerRowsLaunch& a) {
+  if (a.n_cells <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((a.n_cells + 255) / 256));
+  hipLaunchKernelGGL(mc_face_base_kernel, grid, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(mc_corner_rows_kernel<false>, grid, dim3(256), 0, stream, p, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_corner_rows_fill(hipStream_t stream, const McParams& p, const CornerRowsLaunch& a) {
+  if (a.n_cells <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mc_corner_rows_kernel<true>, dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, stream, p, a);
+  return hipGetLastError();
+}
 
 hipError_t launch_normals(hipStream_t stream, const McParams& p, const NormalsLaunch& a) {
   if (a.face_normals != nullptr && a.cap_faces > 0)

@@ -36,6 +36,7 @@
 #include <algorithm>
 
 #include "mesh_decimate.h"
+#include "mesh_ops.h"
 #include "mesh_quadric.h"
 #include "mesh_rows.h"
 #include "vcy_internal.h"
@@ -388,18 +389,23 @@ struct Report {
   dc::u64 fallbacks;  // the output vertices that keep the mean
 };
 
-// `regularize` non-NULL: quadric representatives (MEAN, then the quadric stage), their fallbacks into `n_fallback`
-int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
-                    const vcy_decimate_option& o, const float* regularize, float* vertices_out, int32_t* faces_out,
-                    int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
-                    float* vertex_normals_out, float* face_normals_out, int64_t* n_fallback) {
+}  // namespace
+
+// The pool, the input, the three groups of launches, the wait for flags and counts, the normals: see mesh_ops.h.  With the
+// caller's host arrays the layout and the launches are what the entry points have always had; a mesh on the device is read
+// where it lies, and a corner table it brings takes the place of the quadric stage's own.
+int decimate_launch(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
+                    const DecimateInput* in, const vcy_decimate_option& o, const float* regularize, bool vertex_normals,
+                    bool face_normals, DecimateResult* res) {
   VCY_HIP_CHECK(hipSetDevice(c->device));
   for (vcy::Event& e : c->ev_dc) VCY_HIP_CHECK(e.ensure());
   const bool quadric = regularize != nullptr;
   if (quadric)
     for (vcy::Event& e : c->ev_dq) VCY_HIP_CHECK(e.ensure());
   const size_t n = (size_t)n64, nf = (size_t)nf64, nc = 3 * nf;
-  const bool normals = vertex_normals_out || face_normals_out;
+  const bool normals = vertex_normals || face_normals;
+  const bool own = in == nullptr;  // (positions and faces in this pool)
+  const bool own_corners = own || in->corner == nullptr;
   const bool rows = o.mode != VCY_DECIMATE_FIRST;
   const size_t vslots = table_slots(n), fslots = table_slots(nf);
 
@@ -408,14 +414,14 @@ int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, cons
   //  16 per face; quadric representatives add [coff | corners | Qv | fell]: 77 bytes per vertex and 12 per face (the corner
   //  table's counts and cursors are the member table's, free again by then)
   PoolLayout at;
-  const size_t at_report = at.take(sizeof(Report)), at_faces = at.take(4 * nc), at_pos = at.take(12 * n), at_key = at.take(12 * n),
+  const size_t at_report = at.take(sizeof(Report)), at_faces = at.take(own ? 4 * nc : 0), at_pos = at.take(own ? 12 * n : 0), at_key = at.take(12 * n),
                at_vslot = at.take(4 * n), at_vtable = at.take(4 * vslots), at_vflag = at.take(8 * (n + 1)), at_cluster = at.take(4 * n),
                at_rep = at.take(4 * n), at_deg = at.take(8 * (n + 1)), at_off = at.take(4 * (n + 1)), at_cursor = at.take(4 * n),
                at_member = at.take(4 * n), at_cpos = at.take(12 * n), at_long = at.take(4 * (n / dc::kLongRow + 1)), at_fcanon = at.take(4 * nc), at_fslot = at.take(4 * nf),
                at_ftable = at.take(4 * fslots), at_fflag = at.take(8 * (nf + 1)), at_used = at.take(8 * (n + 1)),
                at_scan = at.take(8 * scan_scratch_words(std::max(n, nf) + 1)), at_pos_out = at.take(12 * n),
                at_faces_out = at.take(4 * nc), at_vmap = at.take(4 * n), at_fsrc = at.take(4 * nf);
-  const size_t at_coff = at.take(quadric ? 4 * (n + 1) : 0), at_corner = at.take(quadric ? 4 * nc : 0),
+  const size_t at_coff = at.take(quadric && own_corners ? 4 * (n + 1) : 0), at_corner = at.take(quadric && own_corners ? 4 * nc : 0),
                at_qv = at.take(quadric ? 72 * n : 0), at_fell = at.take(quadric ? n : 0);
   VCY_HIP_CHECK(c->d_dc_buf.grow(at.total(), c->stream));
   char* base = (char*)c->d_dc_buf;
@@ -426,7 +432,7 @@ int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, cons
   dc::Dec d{};
   d.n = (int)n, d.nf = (int)nf, d.mode = o.mode;
   d.cell = o.cell, d.origin[0] = o.origin[0], d.origin[1] = o.origin[1], d.origin[2] = o.origin[2];
-  d.pos = (const float*)(base + at_pos), d.faces = (const int*)(base + at_faces);
+  d.pos = own ? (const float*)(base + at_pos) : in->vertices, d.faces = own ? (const int*)(base + at_faces) : in->faces;
   d.key = (int*)(base + at_key), d.vslot = (int*)(base + at_vslot);
   d.vtable = (int*)(base + at_vtable), d.vmask = (unsigned)(vslots - 1);
   d.vflag = (dc::u64*)(base + at_vflag), d.cluster = (int*)(base + at_cluster), d.rep = (int*)(base + at_rep);
@@ -440,11 +446,13 @@ int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, cons
   d.vmap = (int*)(base + at_vmap), d.fsrc = (int*)(base + at_fsrc);
   d.err = d_report->err, d.totals = d_report->totals;
   d.regularize = quadric ? *regularize : 0.0f;
-  d.coff = (int*)(base + at_coff), d.corner = (int*)(base + at_corner), d.qv = (double*)(base + at_qv);
+  d.coff = own_corners ? (int*)(base + at_coff) : in->coff, d.corner = own_corners ? (int*)(base + at_corner) : in->corner, d.qv = (double*)(base + at_qv);
   d.fell = (unsigned char*)(base + at_fell), d.fallbacks = &d_report->fallbacks;
 
-  VCY_HIP_CHECK(hipMemcpyAsync(base + at_pos, vertices, 12 * n, hipMemcpyHostToDevice, s));
-  VCY_HIP_CHECK(hipMemcpyAsync(base + at_faces, faces, 4 * nc, hipMemcpyHostToDevice, s));
+  if (own) {
+    VCY_HIP_CHECK(hipMemcpyAsync(base + at_pos, vertices, 12 * n, hipMemcpyHostToDevice, s));
+    VCY_HIP_CHECK(hipMemcpyAsync(base + at_faces, faces, 4 * nc, hipMemcpyHostToDevice, s));
+  }
 
   const dim3 blk(256), grid_v((unsigned)((n + 255) / 256)), grid_v1((unsigned)((n + 256) / 256)),
       grid_f((unsigned)((nf + 255) / 256)), grid_f1((unsigned)((nf + 256) / 256));
@@ -477,8 +485,11 @@ int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, cons
     if (quadric) {
       VCY_HIP_CHECK(hipGetLastError());
       VCY_HIP_CHECK(hipEventRecord(c->ev_dq[0], s));
-      const rows::Table corners{d.n, (int)nc, d.faces, d.deg, d.coff, d.cursor, d.corner, d.err + dc::kErrFace};
-      { const int rc = rows::fill<true>(s, corners, &d_report->corners, scan); if (rc != VCY_OK) return rc; }
+      if (own_corners) {
+        const rows::Table corners{d.n, (int)nc, d.faces, d.deg, d.coff, d.cursor, d.corner, d.err + dc::kErrFace};
+        const int rc = rows::fill<true>(s, corners, &d_report->corners, scan);
+        if (rc != VCY_OK) return rc;
+      }
       hipLaunchKernelGGL(dc::dc_qv_kernel, grid_v, blk, 0, s, d);
       hipLaunchKernelGGL(dc::dc_qsolve_kernel, grid_v, blk, 0, s, d);
       VCY_HIP_CHECK(hipEventRecord(c->ev_dq[1], s));
@@ -524,30 +535,54 @@ int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, cons
   }
   const size_t nvo = (size_t)r.totals[2], nfo = (size_t)r.totals[1];
 
-  // ---- normals of the output mesh, then the results into the caller's arrays
+  // ---- normals of the output mesh, launched behind the wait
   float *d_fn = nullptr, *d_vn = nullptr;
   VCY_HIP_CHECK(hipEventRecord(c->ev_dc[4], s));
   if (normals && nfo > 0) {
-    const int rc = mesh_normals_device(c, (int64_t)nvo, (int64_t)nfo, d.pos_out, d.faces_out, vertex_normals_out != nullptr, &d_fn, &d_vn);
+    const int rc = mesh_normals_device(c, (int64_t)nvo, (int64_t)nfo, d.pos_out, d.faces_out, vertex_normals, &d_fn, &d_vn);
     if (rc != VCY_OK) return rc;
   }
   VCY_HIP_CHECK(hipEventRecord(c->ev_dc[5], s));
-  if (nfo > 0) {
-    VCY_HIP_CHECK(hipMemcpyAsync(vertices_out, d.pos_out, 12 * nvo, hipMemcpyDeviceToHost, s));
-    VCY_HIP_CHECK(hipMemcpyAsync(faces_out, d.faces_out, 12 * nfo, hipMemcpyDeviceToHost, s));
-    if (face_source) VCY_HIP_CHECK(hipMemcpyAsync(face_source, d.fsrc, 4 * nfo, hipMemcpyDeviceToHost, s));
-    if (vertex_normals_out && d_vn) VCY_HIP_CHECK(hipMemcpyAsync(vertex_normals_out, d_vn, 12 * nvo, hipMemcpyDeviceToHost, s));
-    if (face_normals_out && d_fn) VCY_HIP_CHECK(hipMemcpyAsync(face_normals_out, d_fn, 12 * nfo, hipMemcpyDeviceToHost, s));
-  }
-  if (vertex_map) VCY_HIP_CHECK(hipMemcpyAsync(vertex_map, d.vmap, 4 * n, hipMemcpyDeviceToHost, s));
-  VCY_HIP_CHECK(hipStreamSynchronize(s));  // (the host arrays are written until here)
+  *res = DecimateResult{(int64_t)nvo, (int64_t)nfo, (int64_t)r.fallbacks, d.pos_out, d.faces_out, d.vmap, d.fsrc, d_fn,
+                        vertex_normals ? d_vn : nullptr};
+  return VCY_OK;
+}
+
+int decimate_read_times(vcy_ctx* c, bool normals, bool quadric) {
   for (int k = 0; k < 3; ++k) VCY_HIP_CHECK(hipEventElapsedTime(&c->last_decimate_ms[k], c->ev_dc[k], c->ev_dc[k + 1]));
   c->last_decimate_ms[3] = 0.0f;
   if (normals) VCY_HIP_CHECK(hipEventElapsedTime(&c->last_decimate_ms[3], c->ev_dc[4], c->ev_dc[5]));
   if (quadric) VCY_HIP_CHECK(hipEventElapsedTime(&c->last_quadric_ms, c->ev_dq[0], c->ev_dq[1]));
-  *n_vertices_out = (int64_t)nvo;
-  *n_faces_out = (int64_t)nfo;
-  if (n_fallback) *n_fallback = (int64_t)r.fallbacks;
+  return VCY_OK;
+}
+
+namespace {
+
+// vcy_decimate_mesh[_quadric]: the input from the caller's arrays into the pool, the launches, the results into the
+// caller's arrays, sized by the counts; a refused call copies nothing.  `regularize` non-NULL: quadric representatives
+// (MEAN, then the quadric stage), their fallbacks into `n_fallback`
+int decimate_device(const char* who, vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
+                    const vcy_decimate_option& o, const float* regularize, float* vertices_out, int32_t* faces_out,
+                    int64_t* n_vertices_out, int64_t* n_faces_out, int32_t* vertex_map, int32_t* face_source,
+                    float* vertex_normals_out, float* face_normals_out, int64_t* n_fallback) {
+  const size_t n = (size_t)n64;
+  hipStream_t s = c->stream;
+  DecimateResult r{};
+  { const int rc = decimate_launch(who, c, n64, nf64, vertices, faces, nullptr, o, regularize, vertex_normals_out != nullptr, face_normals_out != nullptr, &r); if (rc != VCY_OK) return rc; }
+  const size_t nvo = (size_t)r.n_vertices, nfo = (size_t)r.n_faces;
+  if (nfo > 0) {
+    VCY_HIP_CHECK(hipMemcpyAsync(vertices_out, r.vertices, 12 * nvo, hipMemcpyDeviceToHost, s));
+    VCY_HIP_CHECK(hipMemcpyAsync(faces_out, r.faces, 12 * nfo, hipMemcpyDeviceToHost, s));
+    if (face_source) VCY_HIP_CHECK(hipMemcpyAsync(face_source, r.face_source, 4 * nfo, hipMemcpyDeviceToHost, s));
+    if (vertex_normals_out && r.vertex_normals) VCY_HIP_CHECK(hipMemcpyAsync(vertex_normals_out, r.vertex_normals, 12 * nvo, hipMemcpyDeviceToHost, s));
+    if (face_normals_out && r.face_normals) VCY_HIP_CHECK(hipMemcpyAsync(face_normals_out, r.face_normals, 12 * nfo, hipMemcpyDeviceToHost, s));
+  }
+  if (vertex_map) VCY_HIP_CHECK(hipMemcpyAsync(vertex_map, r.vertex_map, 4 * n, hipMemcpyDeviceToHost, s));
+  VCY_HIP_CHECK(hipStreamSynchronize(s));  // (the host arrays are written until here)
+  { const int rc = decimate_read_times(c, vertex_normals_out || face_normals_out, regularize != nullptr); if (rc != VCY_OK) return rc; }
+  *n_vertices_out = r.n_vertices;
+  *n_faces_out = r.n_faces;
+  if (n_fallback) *n_fallback = r.n_fallback;
   return VCY_OK;
 }
 

@@ -11,6 +11,7 @@
 
 #include "mesh_decimate.h"
 #include "mesh_quadric.h"
+#include "host_shared.h"
 #include "vacancy_hip.h"
 
 namespace vcy {
@@ -48,10 +49,7 @@ int decimate_check_args(const char* who, int64_t n_vertices, int64_t n_faces, co
     set_error("%s: mode %d outside 0 .. 2", who, o->mode);
     return VCY_ERR_INVALID_ARG;
   }
-  if (n_faces > (INT32_MAX - 2) / 3 || n_vertices > INT32_MAX) {
-    set_error("%s: %lld vertices, %lld faces: corner and vertex ids are 32 bits wide", who, (long long)n_vertices, (long long)n_faces);
-    return VCY_ERR_UNSUPPORTED;
-  }
+  { const int rc = mesh_index_limits(who, n_vertices, n_faces); if (rc != VCY_OK) return rc; }
   return VCY_OK;
 }
 

@@ -15,6 +15,7 @@
 // gather) instead of 12 (three dword gathers); the results are the same bits.
 #include <algorithm>
 
+#include "mesh_ops.h"
 #include "mesh_rows.h"
 #include "vcy_internal.h"
 
@@ -155,45 +156,52 @@ __global__ __launch_bounds__(256) void sm_unpad_kernel(int n, const float* __res
 
 }  // namespace sm
 
-namespace {
-
-int smooth_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
-                  const vcy_smooth_option& o, float* vertices_out, float* vertex_normals_out, float* face_normals_out) {
+// The pool, the input into it, and every launch: see mesh_ops.h.  With the caller's host arrays the layout and the launches
+// are what vcy_smooth_mesh has always had; a mesh on the device brings its faces and its table, which take no room here.
+int smooth_launch(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces, const SmoothInput* in,
+                  const vcy_smooth_option& o, bool vertex_normals, bool face_normals, SmoothResult* res) {
   VCY_HIP_CHECK(hipSetDevice(c->device));
   for (vcy::Event& e : c->ev_sm) VCY_HIP_CHECK(e.ensure());
   const size_t n = (size_t)n64, nf = (size_t)nf64, nc = 3 * nf;
-  const bool normals = vertex_normals_out || face_normals_out;
+  const bool normals = vertex_normals || face_normals;
   const int n_passes = 2 * o.iterations;
   const bool pad = c->smooth_pad != 0 && n_passes > 0;
   const size_t stride = pad ? 4 : 3;
+  const bool own = in == nullptr;  // (faces and table in this pool)
 
   // [faces | positions as given (and the result) | the passes' arrays | deg, scan scratch, total | off | cursor | corners |
   //  gather | pinned | face normals | vertex normals]
   PoolLayout at;
-  const size_t at_faces = at.take(4 * nc), at_p3 = at.take(12 * n),
+  const size_t at_faces = at.take(own ? 4 * nc : 0), at_p3 = at.take(12 * n),
                at_a = at.take(pad ? 16 * n : 0),  // (pad only; otherwise the passes start from p3)
-               at_b = at.take(4 * stride * n), at_deg = at.take(8 * (n + 1)), at_scan = at.take(8 * scan_scratch_words(n + 1)),
-               at_total = at.take(8), at_off = at.take(4 * (n + 1)), at_cursor = at.take(4 * n), at_corners = at.take(4 * nc),
+               at_b = at.take(4 * stride * n), at_deg = at.take(own ? 8 * (n + 1) : 0),
+               at_scan = at.take(own ? 8 * scan_scratch_words(n + 1) : 0), at_total = at.take(own ? 8 : 0),
+               at_off = at.take(own ? 4 * (n + 1) : 0), at_cursor = at.take(own ? 4 * n : 0), at_corners = at.take(own ? 4 * nc : 0),
                at_gather = at.take(8 * nc), at_pinned = at.take(n), at_fn = at.take(normals ? 12 * nf : 0),
                at_vn = at.take(normals ? 12 * n : 0);
   VCY_HIP_CHECK(c->d_sm_buf.grow(at.total(), c->stream));
   char* base = (char*)c->d_sm_buf;
   hipStream_t s = c->stream;
 
-  const rows::Table t{(int)n, (int)nc, (const int*)(base + at_faces), (rows::u64*)(base + at_deg), (int*)(base + at_off),
-                      (int*)(base + at_cursor), (int*)(base + at_corners)};
+  const rows::Table t = own ? rows::Table{(int)n, (int)nc, (const int*)(base + at_faces), (rows::u64*)(base + at_deg),
+                                          (int*)(base + at_off), (int*)(base + at_cursor), (int*)(base + at_corners)}
+                            : *in->table;
   int* gather = (int*)(base + at_gather);
   uint8_t* pinned = (uint8_t*)(base + at_pinned);
   float* p3 = (float*)(base + at_p3);
 
-  VCY_HIP_CHECK(hipMemcpyAsync(p3, vertices, 12 * n, hipMemcpyHostToDevice, s));
-  if (nc > 0) VCY_HIP_CHECK(hipMemcpyAsync(base + at_faces, faces, 4 * nc, hipMemcpyHostToDevice, s));
+  if (own) {
+    VCY_HIP_CHECK(hipMemcpyAsync(p3, vertices, 12 * n, hipMemcpyHostToDevice, s));
+    if (nc > 0) VCY_HIP_CHECK(hipMemcpyAsync(base + at_faces, faces, 4 * nc, hipMemcpyHostToDevice, s));
+  } else {
+    VCY_HIP_CHECK(hipMemcpyAsync(p3, in->vertices, 12 * n, hipMemcpyDeviceToDevice, s));
+  }
 
   const dim3 blk(256), grid_v((unsigned)((n + 255) / 256));
 
   // ---- build
   VCY_HIP_CHECK(hipEventRecord(c->ev_sm[0], s));
-  { const int rc = rows::fill(s, t, (rows::u64*)(base + at_total), (rows::u64*)(base + at_scan)); if (rc != VCY_OK) return rc; }
+  if (own) { const int rc = rows::fill(s, t, (rows::u64*)(base + at_total), (rows::u64*)(base + at_scan)); if (rc != VCY_OK) return rc; }
   if (o.pin_boundary) hipLaunchKernelGGL(sm::sm_rows_kernel<true>, grid_v, blk, 0, s, t, gather, pinned);
   else hipLaunchKernelGGL(sm::sm_rows_kernel<false>, grid_v, blk, 0, s, t, gather, pinned);
   VCY_HIP_CHECK(hipGetLastError());
@@ -218,16 +226,32 @@ int smooth_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, 
   VCY_HIP_CHECK(hipEventRecord(c->ev_sm[2], s));
   float* fn = (float*)(base + at_fn);
   float* vn = (float*)(base + at_vn);
-  if (normals) { const int rc = launch_mesh_normals(s, n64, nf64, p3, t.key, t.off, t.items, fn, vertex_normals_out ? vn : nullptr); if (rc != VCY_OK) return rc; }
+  if (normals) { const int rc = launch_mesh_normals(s, n64, nf64, p3, t.key, t.off, t.items, fn, vertex_normals ? vn : nullptr); if (rc != VCY_OK) return rc; }
   VCY_HIP_CHECK(hipEventRecord(c->ev_sm[3], s));
+  *res = SmoothResult{p3, normals ? fn : nullptr, vertex_normals ? vn : nullptr};
+  return VCY_OK;
+}
 
-  VCY_HIP_CHECK(hipMemcpyAsync(vertices_out, p3, 12 * n, hipMemcpyDeviceToHost, s));
-  if (vertex_normals_out) VCY_HIP_CHECK(hipMemcpyAsync(vertex_normals_out, vn, 12 * n, hipMemcpyDeviceToHost, s));
-  if (face_normals_out && nf > 0) VCY_HIP_CHECK(hipMemcpyAsync(face_normals_out, fn, 12 * nf, hipMemcpyDeviceToHost, s));
-  VCY_HIP_CHECK(hipStreamSynchronize(s));  // (the host arrays are read and written until here)
+int smooth_read_times(vcy_ctx* c, bool normals) {
   for (int k = 0; k < 3; ++k) VCY_HIP_CHECK(hipEventElapsedTime(&c->last_smooth_ms[k], c->ev_sm[k], c->ev_sm[k + 1]));
   if (!normals) c->last_smooth_ms[2] = 0.0f;
   return VCY_OK;
+}
+
+namespace {
+
+// vcy_smooth_mesh: the input from the caller's arrays into the pool, the launches, the results into the caller's arrays
+int smooth_device(vcy_ctx* c, int64_t n64, int64_t nf64, const float* vertices, const int32_t* faces,
+                  const vcy_smooth_option& o, float* vertices_out, float* vertex_normals_out, float* face_normals_out) {
+  const size_t n = (size_t)n64, nf = (size_t)nf64;
+  hipStream_t s = c->stream;
+  SmoothResult r{};
+  { const int rc = smooth_launch(c, n64, nf64, vertices, faces, nullptr, o, vertex_normals_out != nullptr, face_normals_out != nullptr, &r); if (rc != VCY_OK) return rc; }
+  VCY_HIP_CHECK(hipMemcpyAsync(vertices_out, r.vertices, 12 * n, hipMemcpyDeviceToHost, s));
+  if (vertex_normals_out) VCY_HIP_CHECK(hipMemcpyAsync(vertex_normals_out, r.vertex_normals, 12 * n, hipMemcpyDeviceToHost, s));
+  if (face_normals_out && nf > 0) VCY_HIP_CHECK(hipMemcpyAsync(face_normals_out, r.face_normals, 12 * nf, hipMemcpyDeviceToHost, s));
+  VCY_HIP_CHECK(hipStreamSynchronize(s));  // (the host arrays are read and written until here)
+  return smooth_read_times(c, vertex_normals_out || face_normals_out);
 }
 
 }  // namespace

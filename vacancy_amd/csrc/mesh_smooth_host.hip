@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "host_shared.h"
 #include "vacancy_hip.h"
 
 namespace vcy {
@@ -33,10 +34,7 @@ int smooth_check_args(const char* who, int64_t n_vertices, int64_t n_faces, cons
     set_error("%s: pin_boundary %d is neither 0 nor 1", who, o->pin_boundary);
     return VCY_ERR_INVALID_ARG;
   }
-  if (n_faces > (INT32_MAX - 2) / 3 || n_vertices > INT32_MAX) {
-    set_error("%s: %lld vertices, %lld faces: corner and vertex ids are 32 bits wide", who, (long long)n_vertices, (long long)n_faces);
-    return VCY_ERR_UNSUPPORTED;
-  }
+  { const int rc = mesh_index_limits(who, n_vertices, n_faces); if (rc != VCY_OK) return rc; }
   for (int64_t i = 0; i < 3 * n_faces; ++i)
     if (faces[i] < 0 || faces[i] >= n_vertices) {
       set_error("%s: face %lld names vertex %d of %lld", who, (long long)(i / 3), faces[i], (long long)n_vertices);

@@ -242,6 +242,12 @@ struct vcy_ctx {
   vcy::Event ev_dq[2];                // around the quadric stage of vcy_decimate_mesh_quadric (vcy_last_quadric_ms)
   float last_quadric_ms = 0.0f;
 
+  // extraction chain (mesh_chain.hip); grow-only
+  vcy::DeviceBuf<> d_ch_buf;          // the vertex -> incident-corner table of the extracted mesh, shared by the stages
+  vcy::Event ev_ch[2];                // around the table's count, scan and fill
+  int chain_rows = 1;                 // "chainrows": 1 the table from the cells (mc_corner_rows, mc_normals.hip), 0 from the faces (mesh_rows.h)
+  float last_chain_ms[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // vcy_last_chain_ms, in its order
+
   float* owned_slab_sdf() const { return d_sdf + (int64_t)halo_lo * slice; }
   void* owned_slab_cnt() const { return (char*)d_cnt + (int64_t)halo_lo * slice * cnt_bytes; }
   int nz_local() const { return z1 - z0; }
@@ -277,6 +283,7 @@ int carve_log_open(vcy_ctx* ctx, bool first_chunk);          // next slot of vcy
 // that owns a z-slab then gets the slab instance of the vertex normals (seam vertices left at zero)
 int extract_iso(vcy_ctx* ctx, double iso, int linear_interp, vcy_mesh* out, int which = 0,
                 vcy_mesh_normals* normals_out = nullptr, int64_t* layer_faces = nullptr);
+// ... and with the mesh left in the device staging, for the extraction chain: extract_iso_staged (mc_common.h)
 // components.hip: vcy_label_components, vcy_keep_components, vcy_download_labels, vcy_last_components_ms, the _slab
 // entries of a z-slab context and the seam merge on the host (vcy_merge_components_host)
 // the solid bit of every voxel of the owned slices in 64-voxel words along x, (nx + 63) / 64 words per row (cc_bits_kernel);

@@ -587,6 +587,66 @@ float VoxelCarver::last_quadric_ms() const {
   return ms;
 }
 
+bool VoxelCarver::ExtractIsoSurfaceChain(Mesh* mesh, const ChainOption& option, ChainReport* report) {
+  if (report) *report = ChainReport();
+  if (!mesh) {
+    LOGE("VoxelCarver::ExtractIsoSurfaceChain needs a mesh\n");
+    return false;
+  }
+  mesh->Clear();
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  const double t0 = NowMs();
+  vcy_chain_option o;
+  std::memset(&o, 0, sizeof(o));
+  o.smooth = option.smooth ? 1 : 0;
+  o.smooth_option.iterations = option.iterations;
+  o.smooth_option.lambda = option.lambda;
+  o.smooth_option.mu = option.mu;
+  o.smooth_option.pin_boundary = option.pin_boundary ? 1 : 0;
+  o.decimate = option.decimate;
+  o.decimate_option.cell = option.cell;
+  for (int k = 0; k < 3; ++k) o.decimate_option.origin[k] = impl_->option.bb_min[k];  // (as DecimateMesh: cells line up with voxels)
+  o.decimate_option.mode = option.mode;
+  o.regularize = option.regularize;
+  o.which = VCY_NORMALS_VERTEX | VCY_NORMALS_FACE;
+  o.maps = report && option.maps ? 1 : 0;
+  vcy_mesh m;
+  vcy_mesh_normals n;
+  vcy_chain_report r;
+  const int rc = vcy_extract_iso_chain(impl_->ctx, option.iso_level, option.linear_interp ? 1 : 0, &o, &m, &n, &r);
+  LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
+  if (rc != VCY_OK) {
+    LOGE("%s\n", vcy_last_error());
+    return false;
+  }
+  detail::CopyTriples(mesh->mutable_vertices(), m.vertices, static_cast<size_t>(m.n_vertices));
+  detail::CopyTriples(mesh->mutable_vertex_indices(), m.faces, static_cast<size_t>(m.n_faces));
+  detail::CopyTriples(mesh->mutable_normals(), n.vertex_normals, static_cast<size_t>(m.n_vertices));
+  detail::CopyTriples(mesh->mutable_face_normals(), n.face_normals, static_cast<size_t>(m.n_faces));
+  mesh->set_normal_indices(mesh->vertex_indices());
+  if (report) {
+    report->n_extracted_vertices = r.n_extracted_vertices;
+    report->n_extracted_faces = r.n_extracted_faces;
+    report->n_fallback = r.n_fallback;
+    if (r.vertex_map) report->vertex_map.assign(r.vertex_map, r.vertex_map + r.n_extracted_vertices);
+    if (r.face_source) report->face_source.assign(r.face_source, r.face_source + m.n_faces);
+  }
+  vcy_mesh_free(&m);
+  vcy_mesh_normals_free(&n);
+  vcy_chain_report_free(&r);
+  LOGI("MarchingCubes, smoothing %d, decimation %d, normals %02f\n", o.smooth, o.decimate, NowMs() - t0);
+  return true;
+}
+
+std::array<float, 8> VoxelCarver::last_chain_ms() const {
+  std::array<float, 8> ms = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
+  if (impl_->ctx) vcy_last_chain_ms(impl_->ctx, &ms[0], &ms[1], &ms[2], &ms[3], &ms[4], &ms[5], &ms[6], &ms[7]);
+  return ms;
+}
+
 bool VoxelCarver::KeepLargestComponents(int largest, std::int64_t min_voxels, double iso_level, float fill_sdf) {
   if (!impl_->ctx) {
     LOGE("voxel grid has not been initialized\n");
