@@ -2,6 +2,8 @@
 // with its tuning defaults, the records that cross from the host and the pre-pass to carve_fused_kernel, the bits of
 // `state_flags`, and the description of one launch (CarveLaunch).
 //   carve_fused.h          this file
+//   carve_fused_plan.h     the decisions of a launch as pure host code (plan_fused_launch), and the constants they share with the kernels
+//   carve_fused_state.h    what a context keeps between launches (vcy_ctx::fused)
 //   carve_fused_device.h   device helpers shared by the carve kernel and the pre-pass (sampling, tiles, footprints)
 //   carve_fused_kernel.h   carve_fused_kernel and the dispatch that picks its instance
 //   carve_fused_u8.hip     the instances with update_num in one byte, behind launch_fused_counts8
@@ -12,17 +14,12 @@
 #include <cstdint>
 
 #include "carve_common.h"
+#include "carve_fused_plan.h"
 
 namespace vcy {
 
-// Waves per workgroup.  The waves never talk to each other, so 1 and 2 are just as correct; measured, they are
-// 3 % slower in the default mode (four bricks adjacent in x start together and share rows and footprints).
-#ifndef VCY_WG_WAVES
-#define VCY_WG_WAVES 4   // (development builds: 8 is 7 % faster for single-view weighted-average launches, 7 % slower for the fused 32-view launch)
-#endif
-constexpr int kWgWaves = VCY_WG_WAVES;
-constexpr int BX = 8 * kWgWaves, BY = 8, BZ = 8;  // voxels per workgroup: kWgWaves 8x8x8 wave bricks along x
-constexpr int WX = 8;                    // wave brick is WX x BY x BZ, lane = (y & 7) | (z << 3), WX voxels per lane
+// (kWgWaves, BX / BY / BZ, WX, the few-view flavour's kRowMaxViews / kRowBricks / kRowWaves, kLiveEntryWords, the kState*
+// bits, CarveFlavour and kUpdateWaUnitWeight: carve_fused_plan.h, which the host's launch plan shares)
 constexpr int kMaxFusedViews = 64;         // one prologue lane per view
 // Raw-pixel tile (the default: footprints up to 15 x 15 taps): 16 x 16 pixels of the image, pitch 16, 1 KB.
 // The pixels go from global memory straight into LDS (global_load_lds_dword: lane L of the r-th load
@@ -41,7 +38,7 @@ constexpr int tile_f4_per_wave() { return TQ == kTileRaw ? kRawBuffers * 64 : TQ
 constexpr int kTileBig = 512;            // (in float4 units)
 constexpr int kBigPixels = 4 * kTileBig;
 
-// Cooperative write-back (kStateCoopStore, launch_carve_fused): the four waves of a workgroup hand their bricks' state
+// Cooperative write-back (kStateCoopStore, plan_fused_launch): the four waves of a workgroup hand their bricks' state
 // to each other through LDS and every store instruction then writes whole 128-byte (sdf) / 64-byte (update_num) row
 // segments instead of 64 scattered 16-byte pieces -- see the write-back of carve_fused_kernel.  Row pitches padded by
 // 16 bytes so that the 16-byte LDS accesses of both directions spread over the banks.
@@ -80,15 +77,6 @@ constexpr size_t coop_lds_bytes() {
 // Two bricks per wave and four waves per workgroup (8 KB, 5 waves per SIMD) come closest (2.91 / 1.91 / 0.67 ms) and
 // amortise next to nothing (592 + 324 per brick); workgroups of one or two waves are slower again (dispatch rate).
 // So the flavour is OFF by default ("rowkernel" 0), kept and tested as the second implementation of few-view launches.
-constexpr int kRowMaxViews = 8;          // pairs are numbered 8 j + v
-#ifndef VCY_ROW_BRICKS
-#define VCY_ROW_BRICKS 4
-#endif
-#ifndef VCY_ROW_WAVES
-#define VCY_ROW_WAVES 2
-#endif
-constexpr int kRowBricks = VCY_ROW_BRICKS;
-constexpr int kRowWaves = VCY_ROW_WAVES;
 template <typename CountT, int NB>
 constexpr size_t row_lds_bytes_per_wave() {  // two raw tiles, NB x 8 TileInfo, the state of NB bricks, NB changed-lane masks
   return (size_t)kRawBuffers * 1024 + (size_t)NB * kRowMaxViews * 56 /* sizeof(TileInfo) */ +
@@ -167,9 +155,6 @@ struct TileInfo {
 };
 static_assert(sizeof(TileInfo) == 56, "row_lds_bytes_per_wave");
 
-// Internal update mode: kWeightedAverage with voxel_update_weight == 1.0f (the default weight).
-constexpr int kUpdateWaUnitWeight = 2;
-
 // ---- footprint records (raw-tile kernels) ------------------------------------------------------
 // What footprint_of finds for a (wave brick, view) pair does not depend on the voxel state, and inside the carve
 // kernel it is the worst kind of work: one lane per view (half the wave idle at 32 views, 63 of 64 lanes for a
@@ -185,6 +170,7 @@ constexpr int kUpdateWaUnitWeight = 2;
 struct FootprintRecord {
   uint32_t w0, w1;
 };
+static_assert(sizeof(FootprintRecord) == kFootprintRecordBytes, "plan_fused_launch's chunk size");
 
 __device__ __forceinline__ FootprintRecord pack_footprint(const TileInfo& ti, const ViewParams& v) {
   uint32_t b = __float_as_uint(ti.ub);
@@ -368,26 +354,6 @@ inline BlockDecode make_block_decode(unsigned grid_x, int nbx, int nby) {
   d.dnby = make_fast_div_u32((uint32_t)std::max(nby, 1));
   return d;
 }
-
-// Ints per entry of a live list whose entries carry records (live_workgroups_kernel): {id, live waves, kWgWaves records}.
-constexpr int kLiveEntryWords = 2 + 2 * kWgWaves;
-
-// The bits of carve_fused_kernel's `state_flags`: what launch_carve_fused knows about the slab and asks of the launch.
-constexpr int kStateFresh = 1;          // the slab is fresh: known sdf = lowest(), update_num = 0, never written
-constexpr int kStateCountImplied = 2;   // update_num == 0 implies sdf == lowest() (no vcy_upload since the fill)
-constexpr int kStateBrickMinValid = 4;  // the brick minima are valid: every write to the state since the slab was fresh
-                                        // went through a fused launch
-constexpr int kStateCoopStore = 8;      // cooperative write-back: whole row segments, through LDS (kCoopSdfPitch above)
-constexpr int kStateStreamStore = 16;   // ... with streaming stores ("ntstore")
-constexpr int kStateEager = 32;         // one-view launch: the state is requested next to the footprint record ("eagerstate")
-constexpr int kStateListRecords = 64;   // one-view launch: the entries of wg_list carry the bricks' records (kLiveEntryWords)
-
-// Which structure of carve_fused_kernel a launch takes (its template parameter NB: 1, 0, kRowBricks).
-enum class CarveFlavour {
-  kGeneral,  // a brick per wave, any number of views
-  kOneView,  // the same for a launch of ONE view, the view count a compile-time constant
-  kRows,     // the few-view flavour: a wave walks a segment of kRowBricks bricks (kRowBricks above)
-};
 
 // One launch of carve_fused_kernel, filled per chunk by launch_carve_fused and handed to the unit that holds the
 // instances for the counter width (launch_fused_counts8 / 16), whose dispatch turns the selection into template arguments.

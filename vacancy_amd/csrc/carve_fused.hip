@@ -1,6 +1,7 @@
 // K1 (fused), host side: what a fused carve launch needs before carve_fused_kernel (carve_fused_kernel.h) runs -- the view
-// records, the window maxima, the footprint pre-pass, the live list -- the launch itself (launch_carve_fused), and the slab
-// planner.  The pre-pass kernels live here, next to the only code that launches them.
+// records, the window maxima, the footprint pre-pass, the live list -- the launch itself (launch_carve_fused: the stages
+// that enqueue what carve_fused_plan.h has decided), and the slab planner.  The pre-pass kernels live here, next to the
+// only code that launches them.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -16,8 +17,6 @@ namespace vcy {
 namespace {
 
 constexpr int kWmaxPlanes = 2;           // window sizes 4 and 8
-constexpr int kLiveListMaxViews = 8;      // launches of up to this many views over a carved grid list their live workgroups first
-constexpr int64_t kRecordBytesMax = (int64_t)2 << 30;  // footprint records of one carve launch (see launch_carve_fused)
 
 // ---- window maxima (FusedView::wmax) --------------------------------------------------------
 // Each thread produces four consecutive pixels of a row; blockIdx.y = view.  Rows are read as float4
@@ -302,6 +301,38 @@ bool fused_eligible(const vcy_ctx* c, int n_views, const vcy_view* views) {
   return true;
 }
 
+// ---- what a context keeps between launches (carve_fused_state.h) ------------------------------------------------------
+bool FusedViewCache::matches(const FusedViewKey& k, const void* vp_now, size_t vp_bytes) const {
+  return valid && vp.size() == vp_bytes && std::memcmp(vp.data(), vp_now, vp_bytes) == 0 && key == k;
+}
+void FusedViewCache::remember(const FusedViewKey& k, const void* vp_now, size_t vp_bytes, bool samef_now, int max_quads_now) {
+  vp.assign((const char*)vp_now, (const char*)vp_now + vp_bytes);
+  key = k, samef = samef_now, max_quads = max_quads_now;
+  valid = true;
+}
+
+int FusedViewStage::next(size_t bytes, void** out) {
+  if (h[1].bytes() < bytes) {  // (the second is allocated last, after both events: where it is large enough, everything is there)
+    for (int q = 0; q < 2; ++q) {
+      if (ev[q]) (void)hipEventSynchronize(ev[q]);
+      (void)h[q].reset();
+    }
+    const size_t room = bytes + bytes / 2 + 4096;
+    for (int q = 0; q < 2; ++q) {
+      VCY_HIP_CHECK(ev[q].ensure(hipEventDisableTiming));
+      VCY_HIP_CHECK(h[q].alloc(room));
+    }
+  }
+  idx ^= 1;
+  VCY_HIP_CHECK(hipEventSynchronize(ev[idx]));  // (the copy of two launches ago: long made)
+  *out = h[idx];
+  return VCY_OK;
+}
+int FusedViewStage::copied(hipStream_t stream) {
+  VCY_HIP_CHECK(hipEventRecord(ev[idx], stream));
+  return VCY_OK;
+}
+
 // What a fused launch derives from its views, resident on the device (the context's staging buffer):
 struct PreparedViews {
   float* d_c2;          // c0 records, [view][x brick][kC0Stride]
@@ -310,143 +341,94 @@ struct PreparedViews {
   int max_quads;        // threads per view of the window-maximum kernels (0: no planes)
 };
 
+namespace {
+
+// The view blocks of a launch, built in the staging buffer `fv`: the views' parameters and, with planes, their addresses
+// and the rectangle of slices [zlo, zhi) in every view.
+void fill_view_blocks(const vcy_ctx* c, int n_views, const ViewParams* vp, bool ortho, bool need_bound, bool need_lower,
+                      int zlo, int zhi, FusedView* fv, bool* samef_out, int* max_quads_out) {
+  std::memset((void*)fv, 0, sizeof(FusedView) * (size_t)n_views);
+  bool samef = true;
+  for (int vi = 0; vi < n_views; ++vi) {
+    fv[vi].v = vp[vi];
+    samef = samef && (vp[vi].fx == vp[vi].fy);
+  }
+  int max_quads = 0;  // threads of the window-maximum kernels, per view
+  if (need_bound && c->fused.d_wmax) {
+    const int planes = need_lower ? 2 * kWmaxPlanes : kWmaxPlanes;
+    const double X[2] = {c->h_px_min, c->h_px_max}, Y[2] = {c->h_py_min, c->h_py_max};
+    const double Z[2] = {c->h_pz[zlo], c->h_pz[zhi - 1]};
+    size_t off = 0;
+    for (int vi = 0; vi < n_views; ++vi) {
+      const int npx = vp[vi].width * vp[vi].height;
+      fv[vi].wmax = c->fused.d_wmax + off;
+      fv[vi].wmax_plane = npx;
+      fv[vi].has_lower = need_lower ? 1 : 0;
+      off += ((size_t)planes * npx + 3) & ~(size_t)3;  // every view 16-byte aligned
+      const ImageRect r = slab_image_rect(vp[vi], ortho, X, Y, Z, vp[vi].width, vp[vi].height);
+      for (int i = 0; i < 4; ++i) fv[vi].wrect[i] = r.wrect[i];
+      max_quads = std::max(max_quads, r.quads);
+    }
+  }
+  *samef_out = samef, *max_quads_out = max_quads;
+}
+
+}  // namespace
+
 // `need_bound`: window-maximum planes for the view-dropping bounds (kMax or truncation, see the kernel; without the memory
 // for them the kernel scans the footprints instead, results are the same either way).  `need_lower`: two more planes, of
 // the negated image (FusedView::has_lower).  [zlo, zhi): the slices whose image-space bounding box the planes must
 // cover -- the context's slab for a carve, the whole grid for the slab planner.
-int prepare_views(vcy_ctx* c, int n_views, const ViewParams* vp, bool need_bound, bool need_lower, int zlo, int zhi,
-                  PreparedViews* out) {
+int prepare_views(vcy_ctx* c, int n_views, const ViewParams* vp, bool ortho, bool need_bound, bool need_lower, int zlo,
+                  int zhi, PreparedViews* out) {
+  FusedState& f = c->fused;
   // per-view records of c0 = R[i][0] * px[x] for every wave brick along x (layout: kC0Stride above);
   // columns beyond nx repeat the last one
   const int nxp = (c->nx + WX - 1) / WX * WX, nbw = nxp / WX;
-  const size_t c2_floats = (size_t)n_views * nbw * kC0Stride;
-  const size_t c2_bytes = c2_floats * sizeof(float);
+  const size_t c2_bytes = (size_t)n_views * nbw * kC0Stride * sizeof(float);
   const size_t fv_bytes = sizeof(FusedView) * (size_t)n_views;
   const size_t vp_bytes = sizeof(ViewParams) * (size_t)n_views;
-  const int planes = need_lower ? 2 * kWmaxPlanes : kWmaxPlanes;
   if (need_bound) {
+    const int planes = need_lower ? 2 * kWmaxPlanes : kWmaxPlanes;
     size_t total = 0;
     for (int vi = 0; vi < n_views; ++vi) total += ((size_t)planes * vp[vi].width * vp[vi].height + 3) & ~(size_t)3;
-    if (c->d_wmax.bytes() < total * sizeof(float)) {
+    if (f.d_wmax.bytes() < total * sizeof(float)) {
       VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
-      if (c->d_wmax.alloc(total * sizeof(float)) != hipSuccess) (void)hipGetLastError();  // (best effort: the kernel scans the footprints)
+      if (f.d_wmax.alloc(total * sizeof(float)) != hipSuccess) (void)hipGetLastError();  // (best effort: the kernel scans the footprints)
     }
   }
   // staging buffer owned by the context, grown on demand
   {
-    const size_t had = c->d_fused_scratch.bytes();
-    const hipError_t eg = c->d_fused_scratch.grow(c2_bytes + fv_bytes, c->stream);
-    if (eg != hipSuccess || c->d_fused_scratch.bytes() != had) c->fused_cache_valid = false;  // (the buffer moved)
+    const size_t had = f.d_scratch.bytes();
+    const hipError_t eg = f.d_scratch.grow(c2_bytes + fv_bytes, c->stream);
+    if (eg != hipSuccess || f.d_scratch.bytes() != had) f.cache.valid = false;  // (the buffer moved)
     VCY_HIP_CHECK(eg);
   }
-  float* d_c2 = (float*)c->d_fused_scratch;
-  FusedView* d_views = (FusedView*)((char*)c->d_fused_scratch + c2_bytes);
-  // Everything derived from the views -- the c0 records (n_views * nx products), the image-space bounding box of the
-  // slab in every view, the device copies -- depends on nothing but the views' parameters (image pointers included),
-  // the planes' address and two mode flags: a launch with the SAME views as the last one (the reference's loop carves a
-  // sequence of grids with one camera rig; the benchmark repeats its step) takes all of it as it is.  Comparing 4 KB
-  // instead of rebuilding and comparing 0.5 MB took 0.1 ms of host time out of every launch, which is what a z-slab
-  // of an 8-GPU run pays 10 % of its step for.
-  const bool cached = c->fused_cache_valid && c->fused_cache_vp.size() == vp_bytes &&
-                      std::memcmp(c->fused_cache_vp.data(), vp, vp_bytes) == 0 && c->fused_cache_wmax == c->d_wmax &&
-                      c->fused_cache_bound == need_bound && c->fused_cache_lower == need_lower &&
-                      c->fused_cache_ortho == c->fused_ortho && c->fused_cache_at == (void*)d_c2 &&
-                      c->fused_cache_z[0] == zlo && c->fused_cache_z[1] == zhi;
-  if (!cached) {
-    // The view blocks are built in page-locked host memory -- two buffers taken in turn, each with an event that says
-    // when the copy out of it has been made -- and the c0 records by a kernel behind that copy: a launch with new
-    // views queues behind the previous one like any other work on the stream (round 5; until then this path waited
-    // for the stream twice and uploaded the c0 records, 0.5 MB at 1024^3 x 32, from a host vector).
+  float* d_c2 = (float*)f.d_scratch;
+  FusedView* d_views = (FusedView*)((char*)f.d_scratch + c2_bytes);
+  const FusedViewKey key{f.d_wmax, (void*)d_c2, need_bound, need_lower, ortho, zlo, zhi};
+  if (!f.cache.matches(key, vp, vp_bytes)) {
+    // The view blocks go through page-locked memory (FusedViewStage) and the c0 records are made by a kernel behind that
+    // copy: a launch with new views queues behind the previous one like any other work on the stream (round 5; until then
+    // this path waited for the stream twice and uploaded the c0 records, 0.5 MB at 1024^3 x 32, from a host vector).
     static_assert(kC0Stride == 32 && WX == 8, "c0_records_kernel's record layout");
-    if (c->h_fused_stage[1].bytes() < fv_bytes) {  // (the second is allocated last, after both events: where it is large enough, everything is there)
-      for (int q = 0; q < 2; ++q) {
-        if (c->ev_fused_stage[q]) (void)hipEventSynchronize(c->ev_fused_stage[q]);
-        (void)c->h_fused_stage[q].reset();
-      }
-      const size_t room = fv_bytes + fv_bytes / 2 + 4096;
-      for (int q = 0; q < 2; ++q) {
-        VCY_HIP_CHECK(c->ev_fused_stage[q].ensure(hipEventDisableTiming));
-        VCY_HIP_CHECK(c->h_fused_stage[q].alloc(room));
-      }
-    }
-    c->fused_stage_idx ^= 1;
-    VCY_HIP_CHECK(hipEventSynchronize(c->ev_fused_stage[c->fused_stage_idx]));  // (the copy of two launches ago: long made)
-    FusedView* fv = (FusedView*)c->h_fused_stage[c->fused_stage_idx];
-    std::memset((void*)fv, 0, fv_bytes);
+    void* stage = nullptr;
+    { const int rcs = f.stage.next(fv_bytes, &stage); if (rcs != VCY_OK) return rcs; }
     bool samef = true;
-    for (int vi = 0; vi < n_views; ++vi) {
-      fv[vi].v = vp[vi];
-      samef = samef && (vp[vi].fx == vp[vi].fy);
-    }
-    int max_quads = 0;  // threads of the window-maximum kernels, per view
-    if (need_bound && c->d_wmax) {
-      size_t off = 0;
-      for (int vi = 0; vi < n_views; ++vi) {
-        const int npx = vp[vi].width * vp[vi].height;
-        fv[vi].wmax = c->d_wmax + off;
-        fv[vi].wmax_plane = npx;
-        fv[vi].has_lower = need_lower ? 1 : 0;
-        off += ((size_t)planes * npx + 3) & ~(size_t)3;  // every view 16-byte aligned
-        // image-space bounding box of the slab (double precision, 16 px border; the footprints the
-        // kernel looks up lie within a fraction of a pixel of the exact hull, their windows inside them)
-        const int w = vp[vi].width, h = vp[vi].height;
-        int rx0 = 0, ry0 = 0, rx1 = w, ry1 = h;
-        {
-          const double X[2] = {c->h_px_min, c->h_px_max}, Y[2] = {c->h_py_min, c->h_py_max};
-          const double Z[2] = {c->h_pz[zlo], c->h_pz[zhi - 1]};
-          double umin = 1e300, umax = -1e300, wmin = 1e300, wmax = -1e300;
-          bool whole = false;
-          for (int cr = 0; cr < 8; ++cr) {
-            const double x = X[cr & 1], y = Y[(cr >> 1) & 1], z = Z[cr >> 2];
-            double pc[3];
-            for (int i = 0; i < 3; ++i)
-              pc[i] = (double)vp[vi].t[i] + ((double)vp[vi].r[i][0] * x + (double)vp[vi].r[i][1] * y + (double)vp[vi].r[i][2] * z);
-            double uu = pc[0], ww = pc[1];
-            if (!c->fused_ortho) {
-              if (!(pc[2] > 1e-30)) { whole = true; break; }
-              uu = (double)vp[vi].fx / pc[2] * pc[0] + vp[vi].cx;
-              ww = (double)vp[vi].fy / pc[2] * pc[1] + vp[vi].cy;
-            }
-            if (!(std::fabs(uu) < 1e9) || !(std::fabs(ww) < 1e9)) { whole = true; break; }
-            umin = std::min(umin, uu), umax = std::max(umax, uu);
-            wmin = std::min(wmin, ww), wmax = std::max(wmax, ww);
-          }
-          if (!whole) {
-            rx0 = std::max(0, (int)std::floor(umin) - 16) & ~3;
-            ry0 = std::max(0, (int)std::floor(wmin) - 16);
-            rx1 = std::min((w + 3) & ~3, ((int)std::floor(umax) + 16 + 4) & ~3);
-            ry1 = std::min(h, (int)std::floor(wmax) + 16 + 1);
-            if (rx1 < rx0) rx1 = rx0;
-            if (ry1 < ry0) ry1 = ry0;
-          } else {
-            rx1 = (w + 3) & ~3;
-          }
-        }
-        fv[vi].wrect[0] = rx0, fv[vi].wrect[1] = ry0, fv[vi].wrect[2] = rx1, fv[vi].wrect[3] = ry1;
-        max_quads = std::max(max_quads, ((rx1 - rx0) / 4) * (ry1 - ry0));
-      }
-    }
+    int max_quads = 0;
+    fill_view_blocks(c, n_views, vp, ortho, need_bound, need_lower, zlo, zhi, (FusedView*)stage, &samef, &max_quads);
     // (the scratch may still be read by the previous launch: the copy and the kernel are queued behind it on the stream)
-    VCY_HIP_CHECK(hipMemcpyAsync(d_views, fv, fv_bytes, hipMemcpyHostToDevice, c->stream));
-    VCY_HIP_CHECK(hipEventRecord(c->ev_fused_stage[c->fused_stage_idx], c->stream));
+    VCY_HIP_CHECK(hipMemcpyAsync(d_views, stage, fv_bytes, hipMemcpyHostToDevice, c->stream));
+    { const int rcs = f.stage.copied(c->stream); if (rcs != VCY_OK) return rcs; }
     hipLaunchKernelGGL(c0_records_kernel, dim3((unsigned)((nbw * WX + 255) / 256), (unsigned)n_views), dim3(256), 0, c->stream,
                        d_views, c->d_px, c->nx, nbw, d_c2);
     VCY_HIP_CHECK(hipGetLastError());
-    c->fused_cache_vp.assign((const char*)vp, (const char*)vp + vp_bytes);
-    c->fused_cache_wmax = c->d_wmax;
-    c->fused_cache_bound = need_bound;
-    c->fused_cache_lower = need_lower;
-    c->fused_cache_ortho = c->fused_ortho;
-    c->fused_cache_at = (void*)d_c2;
-    c->fused_cache_z[0] = zlo, c->fused_cache_z[1] = zhi;
-    c->fused_cache_samef = samef;
-    c->fused_cache_max_quads = max_quads;
-    c->fused_cache_valid = true;
+    f.cache.remember(key, vp, vp_bytes, samef, max_quads);
   }
   out->d_c2 = d_c2;
   out->d_views = d_views;
-  out->samef = c->fused_cache_samef;
-  out->max_quads = c->fused_cache_max_quads;
+  out->samef = f.cache.samef;
+  out->max_quads = f.cache.max_quads;
   return VCY_OK;
 }
 
@@ -461,87 +443,68 @@ void build_window_planes(vcy_ctx* c, const PreparedViews& pv, int n_views, bool 
   }
 }
 
-// Carves views[0..n_views) (n_views <= 32, max_sdf already resolved) in one launch.  The caller has declared the write
-// (StateFlags::written, once for all its launches); `views_before`: views applied since the fill when this one starts.
-int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewParams* vp, int64_t views_before) {
-  const vcy_update_option& u = c->opt.update_option;
-  const int nzl = c->nz_local();
-  const int nxp = (c->nx + WX - 1) / WX * WX, nbw = nxp / WX;
-  const bool need_bound = c->use_cull && (u.voxel_update == VCY_UPDATE_MAX || u.use_truncation);
-  // (two more planes, of the negated image, for the truncating unit-weight average: FusedView::has_lower)
-  const bool need_lower = need_bound && u.use_truncation && u.voxel_update == VCY_UPDATE_WEIGHTED_AVERAGE;
-  PreparedViews pv;
-  {
-    const int rcp = prepare_views(c, n_views, vp, need_bound, need_lower, c->z0, c->z1, &pv);
-    if (rcp != VCY_OK) return rcp;
-  }
-  float* d_c2 = pv.d_c2;
-  FusedView* d_views = pv.d_views;
-  const bool samef = pv.samef;
+// ---- launch_carve_fused and its stages ----------------------------------------------------------------------------------
+// Which instance runs over which grid with which flags is decided by carve_fused_plan.h; the stages below enqueue.
+namespace {
 
-  // ("carvetimer" 1: every chunk of every fused launch leaves three events in the context's log -- before what runs
-  // ahead of the carve kernel (window maxima, pre-pass, live list), before the carve kernel, after it -- read WITHOUT
-  // having synchronised in between by vcy_carve_log; vcy_last_carve_ms sums the last launch's chunks)
-  const bool timed = c->time_carve;
+// ("carvetimer" 1: every chunk of every fused launch leaves three events in the context's log -- before what runs
+// ahead of the carve kernel (window maxima, pre-pass, live list), before the carve kernel, after it -- read WITHOUT
+// having synchronised in between by vcy_carve_log; vcy_last_carve_ms sums the last launch's chunks)
+// (a launch that fails between opening a record and its last event leaves no half-recorded triplet behind:
+// vcy_carve_log would fail on it, or report the times of whatever used those events before)
+struct CarveLogScope {
+  vcy_ctx* c;
+  int n0, last0;
   int stamp = -1;
-  // (a launch that fails between opening a record and its last event leaves no half-recorded triplet behind:
-  // vcy_carve_log would fail on it, or report the times of whatever used those events before)
-  struct LogGuard {
-    vcy_ctx* c;
-    int n0, last0;
-    bool done;
-    ~LogGuard() { if (!done) c->carve_log_n = n0, c->carve_log_last = last0; }
-  } log_guard{c, c->carve_log_n, c->carve_log_last, false};
-  if (timed) {
-    stamp = carve_log_open(c, true);
-    if (stamp >= 0) VCY_HIP_CHECK(hipEventRecord(c->carve_log[stamp].ev[0], c->stream));
+  bool done = false;
+  explicit CarveLogScope(vcy_ctx* ctx) : c(ctx), n0(ctx->carve_log_n), last0(ctx->carve_log_last) {}
+  ~CarveLogScope() { if (!done) c->carve_log_n = n0, c->carve_log_last = last0; }
+  int open(bool first_chunk) {  // the chunk's record, and its first event
+    if (!c->time_carve) return VCY_OK;
+    stamp = carve_log_open(c, first_chunk);
+    return mark(0);
   }
-  build_window_planes(c, pv, n_views, need_lower);  // the images may have changed since the last call: rebuild every time
-  const int nbx = (c->nx + BX - 1) / BX, nby = (c->ny + BY - 1) / BY, nbz = (nzl + BZ - 1) / BZ;
-  if ((int64_t)nbx * nby * nbz > 0x7fffffffLL) {
-    set_error("slab too large for one launch");
-    return VCY_ERR_TOO_MANY_VOXELS;
+  int mark(int i) {
+    if (stamp >= 0) VCY_HIP_CHECK(hipEventRecord(c->carve_log[stamp].ev[i], c->stream));
+    return VCY_OK;
   }
-  ModeParams m{u.voxel_update, u.sdf_interp, u.update_outside, u.use_truncation ? 1 : 0, c->fused_ortho ? 1 : 0, 0};
-  // shortest division sequence that is exact for every focal length of this batch (checked on the device)
-  if (!c->fused_ortho && c->use_short_div) {
-    int level = 2;
-    for (int vi = 0; vi < n_views && level > 0; ++vi) {
-      level = std::min(level, div_level(c, vp[vi].fx));
-      if (vp[vi].fy != vp[vi].fx && level > 0) level = std::min(level, div_level(c, vp[vi].fy));
-    }
-    m.div_level = level;
+};
+
+FusedPlanInput plan_input(const vcy_ctx* c, const GridParams& g, int n_views, const ViewParams* vp, bool ortho,
+                          int64_t views_before) {
+  const vcy_update_option& u = c->opt.update_option;
+  FusedPlanInput in;
+  in.update = u.voxel_update, in.trunc = u.use_truncation, in.interp = u.sdf_interp;
+  in.max_update_num = (int64_t)u.voxel_max_update_num, in.weight = g.weight;
+  in.nx = c->nx, in.ny = c->ny, in.nz_local = c->nz_local();
+  in.fresh = c->st.fresh, in.cnt_implied = c->st.cnt_implied, in.brick_min_valid = c->st.brick_min_valid;
+  in.have_brick_min = c->d_brick_min != nullptr;
+  in.views_before = views_before, in.n_views = n_views, in.ortho = ortho;
+  const float x[2] = {c->h_px_min, c->h_px_max}, y[2] = {c->h_py_min, c->h_py_max};
+  const float z[2] = {c->h_pz[c->z0], c->h_pz[c->z1 - 1]};
+  in.worst = worst_pixels_per_voxel(vp, n_views, ortho, c->opt.resolution, x, y, z);
+  in.knobs = c->fused.knobs;
+  return in;
+}
+
+// shortest division sequence that is exact for every focal length of this batch (checked on the device)
+int launch_div_level(vcy_ctx* c, int n_views, const ViewParams* vp, bool ortho) {
+  if (ortho || !c->fused.knobs.use_short_div) return 0;
+  int level = 2;
+  for (int vi = 0; vi < n_views && level > 0; ++vi) {
+    level = std::min(level, div_level(c, vp[vi].fx));
+    if (vp[vi].fy != vp[vi].fx && level > 0) level = std::min(level, div_level(c, vp[vi].fy));
   }
-  c->last_div_level = m.div_level;
-  // update_num can only exceed voxel_max_update_num after more than that many views
-  const bool checkmax = views_before + n_views > (int64_t)u.voxel_max_update_num;
-  // Tile kind: footprint of an 8x8x8 wave brick in pixels ~ (8*sqrt(3)*pixels_per_voxel + 3)^2.  The raw
-  // 16 x 16 pixel tile covers voxels up to ~0.85 px; the 2048-pixel tile filled in place up to ~3 px; wider
-  // footprints take the generic path inside the kernel either way.
-  bool big = false;
-  {
-    const float res = c->opt.resolution;
-    float worst = 0.0f;
-    for (int vi = 0; vi < n_views; ++vi) {
-      // pixels per voxel at the centre of the slab (bricks much closer to the camera than that
-      // overflow the tile and take the generic path on their own)
-      const float X = 0.5f * (c->h_px_min + c->h_px_max), Y = 0.5f * (c->h_py_min + c->h_py_max);
-      const float Z = 0.5f * (c->h_pz[c->z0] + c->h_pz[c->z1 - 1]);
-      const float pz = vp[vi].t[2] + (vp[vi].r[2][0] * X + (vp[vi].r[2][1] * Y + vp[vi].r[2][2] * Z));
-      const float f = std::max(vp[vi].fx, vp[vi].fy);
-      // orthographic: one pixel per world unit
-      worst = std::max(worst, c->fused_ortho ? res : (pz > 0.0f ? f * res / pz : INFINITY));
-    }
-    const float side = 8.0f * 1.7320508f * worst + 3.0f;
-    big = side > 15.0f;
-    if (c->tile_mode == 1) big = false;
-    if (c->tile_mode == 2) big = true;
-  }
+  return level;
+}
+
+// The buffers a launch needs beside the views': brick minima, footprint records, pair counters.
+int ensure_launch_buffers(vcy_ctx* c, const FusedLaunchPlan& plan, int n_views) {
   // min(sdf) per wave brick (vcy_ctx::d_brick_min): 4 bytes per 512 voxels, allocated on first use; without it
   // nothing is dropped before the state is read and marching cubes reads every brick
+  const int64_t nb = (int64_t)plan.nbw * plan.nby * plan.nbz;
   if (!c->d_brick_min) {
-    const size_t bytes = sizeof(float) * (size_t)nbw * nby * nbz;
-    if (c->d_brick_min.alloc(bytes) != hipSuccess) (void)hipGetLastError();
+    if (c->d_brick_min.alloc(sizeof(float) * (size_t)nb) != hipSuccess) (void)hipGetLastError();
   }
   // (st.brick_min_valid is only ever true with the array allocated and cnt_implied: StateFlags)
   // Not every wave of the launches below rewrites its entry: a wave whose every view lies below the truncation limit
@@ -551,175 +514,144 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
   // lowest(): "a voxel of this brick may be untouched", which never drops a view and never lets marching cubes skip
   // the brick.  (A fresh slab needs nothing: there every wave runs and stores its minimum.)
   if (c->d_brick_min && !c->st.fresh && !c->st.brick_min_valid && c->st.cnt_implied) {
-    const int64_t nb = (int64_t)nbw * nby * nbz;
     hipLaunchKernelGGL(fill_lowest_kernel, dim3((unsigned)std::min<int64_t>((nb + 255) / 256, 4096)), dim3(256), 0,
                        c->stream, c->d_brick_min, nb);
     VCY_HIP_CHECK(hipGetLastError());
   }
-  // Cooperative write-back (carve_fused_kernel): pays where a launch moves the state for little arithmetic -- few views
-  // over a carved grid (1024^3, one view per launch: weighted average 4.39 -> 3.41 ms, kMax 0.89 -> 0.84), and the first
-  // single-view launch on a fresh grid, which stores every voxel once (2.48 -> 1.95 ms: 6.4 GB at 3.3 instead of
-  // 2.6 TB/s).  "coopstore": -1 that rule, 0 never, 1 always when the layout allows it: rows of whole bricks, four
-  // waves per workgroup, raw tiles.
-  // (kMax: only single-view launches -- with 4 or 8 views per launch the waves of a workgroup process different numbers
-  // of views and the barrier costs 3 - 4 %, profiles/r04/coop_store_batches.txt; weighted average: up to 8 views, 0 ... +2 %;
-  // a fresh grid: single-view launches in either mode -- the fused 32-view launch gained nothing from whole-segment
-  // stores in round 3)
-  // The few-view flavour (kRowBricks: a wave walks the bricks of a row segment): launches of up to kRowMaxViews views with
-  // raw tiles and records from the pre-pass, over rows of whole bricks, no update limit in reach.  "rowkernel" -1 that
-  // rule, 0 never (the NB = 1 kernel with its cooperative write-back), n > 0: launches of up to min(n, 8) views.
-  const int row_views = c->row_kernel < 0 ? kRowMaxViews : std::min(c->row_kernel, kRowMaxViews);
-  const bool rows = !big && !checkmax && (c->nx & (WX - 1)) == 0 && n_views <= row_views && c->prologue_mode != 1;
-  const int nseg = (nbw + kRowBricks - 1) / kRowBricks;  // segments per brick row
-  // a launch of ONE view through the kernel instance that knows it ("oneview" 0: the general instance)
-  const bool one_view = c->one_view && n_views == 1 && !rows && !big && !checkmax && c->prologue_mode != 1;
-  const bool coop_ok = (kWgWaves == 4 || kWgWaves == 8) && (c->nx & (WX - 1)) == 0 && !big && !rows;
-  const int coop_views = c->st.fresh ? 1 : (u.voxel_update == VCY_UPDATE_MAX ? 1 : kLiveListMaxViews);
-  const bool coop = coop_ok && (c->coop_store > 0 || (c->coop_store < 0 && n_views <= coop_views));
-  // "ntstore": streaming stores whenever the cooperative write-back runs (0: never) -- whole 128-byte segments that this
-  // launch does not read again: 0.5 - 1.5 % on single-view launches (profiles/r06/nontemporal.txt)
-  const bool nt = coop && c->nt_store != 0;
-  // (kStateEager and kStateListRecords are decided per chunk below: they depend on whether the launch is a listed one)
-  const int state_flags_base = (c->st.fresh ? kStateFresh : 0) | (c->st.cnt_implied ? kStateCountImplied : 0) |
-                               (c->st.brick_min_valid && !c->st.fresh ? kStateBrickMinValid : 0) |
-                               (coop ? kStateCoopStore : 0) | (nt ? kStateStreamStore : 0);
-  // Raw tiles: the footprint records of every (wave brick, view) pair come from a pre-pass (footprint_records_kernel),
-  // 8 bytes per pair.  The slab is carved in chunks of whole brick layers so that the records of a chunk stay
-  // below kRecordBytesMax (1024^3 x 32 views: 0.5 GiB, one chunk; 2048^3 x 64: nine).
-  const int64_t layer_bricks = (int64_t)nbw * nby;
-  int chunk_layers = nbz;
-  // Footprints from the pre-pass (records) or from the carve kernel's own prologue?  The pre-pass: its threads are all
-  // busy where the prologue would use nviews lanes of 64, it runs at full occupancy, and the records are what the live
-  // list and the early return read.  Round 5 tried the prologue for the one launch whose records are large -- 2048^3 x 64
-  // views: 8.6 GB of them, written and read back in chunks, 9.1 of the step's 81.8 ms; every lane of the prologue has a
-  // view there and the step becomes ONE launch -- and measured 92.8 ms: the footprints cost 20 ms in the kernel (two
-  // dependent round trips in front of every wave, at the carve kernel's occupancy) against 9 in the pre-pass
-  // (profiles/r05/bench_2048x64_config4_*.json).  So: "prologue" 0 or 2 records (chunks of at most kRecordBytesMax: four
-  // at that shape), 1 in the kernel.
-  const int64_t rec_cap = c->record_bytes_max > 0 ? c->record_bytes_max : kRecordBytesMax;  // ("recordbytes": tests force several chunks)
-  const bool in_kernel_prologue = !big && c->prologue_mode == 1;
-  if (!big && !in_kernel_prologue) {
-    const int64_t per_layer = layer_bricks * n_views * (int64_t)sizeof(FootprintRecord);
-    const int64_t cap = rec_cap;
-    chunk_layers = (int)std::max<int64_t>(1, std::min<int64_t>(nbz, cap / std::max<int64_t>(per_layer, 1)));
-    const size_t need = (size_t)(per_layer * chunk_layers);
-    VCY_HIP_CHECK(c->d_records.grow(need, c->stream));
+  if (plan.records) VCY_HIP_CHECK(c->fused.d_records.grow((size_t)plan.record_bytes, c->stream));
+  if (c->fused.knobs.count_pairs) {  // "paircount" 1: one counter per brick layer of the slab, cleared by every launch
+    const size_t bytes = sizeof(unsigned long long) * (size_t)plan.nbz;
+    VCY_HIP_CHECK(c->fused.d_pair_count.grow(bytes, c->stream));
+    VCY_HIP_CHECK(hipMemsetAsync(c->fused.d_pair_count, 0, bytes, c->stream));
+    c->fused.pair_count_views = n_views;
   }
-  if (c->count_pairs) {  // "paircount" 1: one counter per brick layer of the slab, cleared by every launch
-    VCY_HIP_CHECK(c->d_pair_count.grow(sizeof(unsigned long long) * (size_t)nbz, c->stream));
-    VCY_HIP_CHECK(hipMemsetAsync(c->d_pair_count, 0, sizeof(unsigned long long) * (size_t)nbz, c->stream));
-    c->pair_count_views = n_views;
-  }
-  const bool gen = m.ortho != 0 || m.interp == VCY_INTERP_NN;
-  const bool want_lower = need_bound && u.use_truncation && u.voxel_update != VCY_UPDATE_MAX;
-  for (int l0 = 0; l0 < nbz; l0 += chunk_layers) {
-    const int layers = std::min(chunk_layers, nbz - l0);
-    GridParams gc = g;  // this chunk: brick layers [l0, l0 + layers)
-    gc.sdf = g.sdf + (int64_t)l0 * BZ * c->slice;
-    gc.cnt = (char*)g.cnt + (int64_t)l0 * BZ * c->slice * c->cnt_bytes;
-    gc.z0 = g.z0 + l0 * BZ;
-    gc.nz_local = std::min(layers * BZ, nzl - l0 * BZ);
-    const int64_t nbricks = layer_bricks * layers;
-    FootprintRecord* recs = in_kernel_prologue ? nullptr : (FootprintRecord*)c->d_records;
-    float* bmin = c->d_brick_min ? c->d_brick_min + (int64_t)l0 * layer_bricks : nullptr;
-    unsigned long long* pcnt = c->count_pairs && c->d_pair_count ? c->d_pair_count + l0 : nullptr;  // ("paircount" 1)
-    if (timed && l0 > 0) {
-      stamp = carve_log_open(c, false);
-      if (stamp >= 0) VCY_HIP_CHECK(hipEventRecord(c->carve_log[stamp].ev[0], c->stream));
-    }
-    if (!big && !in_kernel_prologue) {
-      const dim3 pgrid((unsigned)((nbricks + 255) / 256), (unsigned)n_views);
-      const FastDivU32 div_nbw = make_fast_div_u32((uint32_t)nbw), div_nby = make_fast_div_u32((uint32_t)nby);
-#define VCY_PREPASS(SF, GN)                                                                                       \
-  hipLaunchKernelGGL((footprint_records_kernel<SF, GN>), pgrid, dim3(256), 0, c->stream, gc, d_views, nbw, nby,   \
-                     nbricks, m, need_bound ? 1 : 0, want_lower ? 1 : 0, recs, div_nbw, div_nby,                  \
-                     nbricks < 0xffffffffLL ? 1 : 0)
-      if (samef) { if (gen) VCY_PREPASS(true, true); else VCY_PREPASS(true, false); }
-      else { if (gen) VCY_PREPASS(false, true); else VCY_PREPASS(false, false); }
+  return VCY_OK;
+}
+
+// One chunk of a launch: brick layers [l0, l0 + layers) of the slab, and what of the launch's buffers is theirs.
+struct ChunkOperands {
+  GridParams g;
+  int64_t nbricks;
+  FootprintRecord* recs;
+  float* bmin;
+  unsigned long long* pcnt;
+};
+ChunkOperands chunk_operands(const vcy_ctx* c, const GridParams& g, const FusedLaunchPlan& plan, int l0, int layers) {
+  const int64_t layer_bricks = (int64_t)plan.nbw * plan.nby;
+  ChunkOperands o;
+  o.g = g;
+  o.g.sdf = g.sdf + (int64_t)l0 * BZ * c->slice;
+  o.g.cnt = (char*)g.cnt + (int64_t)l0 * BZ * c->slice * c->cnt_bytes;
+  o.g.z0 = g.z0 + l0 * BZ;
+  o.g.nz_local = std::min(layers * BZ, c->nz_local() - l0 * BZ);
+  o.nbricks = layer_bricks * layers;
+  o.recs = plan.in_kernel_prologue ? nullptr : (FootprintRecord*)c->fused.d_records;
+  o.bmin = c->d_brick_min ? c->d_brick_min + (int64_t)l0 * layer_bricks : nullptr;
+  o.pcnt = c->fused.knobs.count_pairs && c->fused.d_pair_count ? c->fused.d_pair_count + l0 : nullptr;  // ("paircount" 1)
+  return o;
+}
+
+// The footprint records of the chunk's (wave brick, view) pairs.
+int run_prepass(vcy_ctx* c, const FusedLaunchPlan& plan, const ChunkOperands& o, const PreparedViews& pv, int n_views,
+                const ModeParams& m) {
+  const dim3 pgrid((unsigned)((o.nbricks + 255) / 256), (unsigned)n_views);
+  const FastDivU32 div_nbw = make_fast_div_u32((uint32_t)plan.nbw), div_nby = make_fast_div_u32((uint32_t)plan.nby);
+#define VCY_PREPASS(SF, GN)                                                                                          \
+  hipLaunchKernelGGL((footprint_records_kernel<SF, GN>), pgrid, dim3(256), 0, c->stream, o.g, pv.d_views, plan.nbw, \
+                     plan.nby, o.nbricks, m, plan.need_bound ? 1 : 0, plan.want_lower ? 1 : 0, o.recs, div_nbw,     \
+                     div_nby, o.nbricks < 0xffffffffLL ? 1 : 0)
+  if (pv.samef) { if (plan.gen) VCY_PREPASS(true, true); else VCY_PREPASS(true, false); }
+  else { if (plan.gen) VCY_PREPASS(false, true); else VCY_PREPASS(false, false); }
 #undef VCY_PREPASS
-      VCY_HIP_CHECK(hipGetLastError());
-    }
-    // units of the launch: workgroup blocks of kWgWaves bricks, or the segments of the few-view flavour (one per wave)
-    const int unit_bricks = rows ? kRowBricks : kWgWaves;
-    const int units_x = rows ? nseg : nbx;
-    const dim3 grid((unsigned)((int64_t)units_x * nby * layers));
-    auto groups_of = [&](unsigned units) {  // workgroups that hold `units` listed units
-      return rows ? dim3((units + kRowWaves - 1) / kRowWaves) : dim3(units);
-    };
-    // (unlisted launch of the few-view flavour: unit (g mod 8) + 8 (kRowWaves (g / 8) + wave) of workgroup g)
-    dim3 launch_grid = rows ? dim3(8u * ((grid.x + 8u * kRowWaves - 1) / (8u * kRowWaves))) : grid;
-    // few views over a carved grid: only the workgroups with a live (brick, view) pair (live_workgroups_kernel)
-    const int* wgl = nullptr;
-    int list_entry_words = 0;
-    const bool have_min = u.voxel_update == VCY_UPDATE_MAX && (state_flags_base & kStateBrickMinValid) != 0 && bmin != nullptr;
-    // (not when the list of the previous such launch held most workgroups anyway -- a weighted-average carve touches
-    // nearly every brick with every view, and the list pass is then 4 % on top; the count arrives by an asynchronous
-    // copy into page-locked memory and is only a hint: reading an older value is harmless)
-    const bool list_pays = c->h_live_hint == nullptr || c->h_live_hint[1] <= 0 ||
-                           (double)c->h_live_hint[0] < 0.6 * (double)c->h_live_hint[1];
-    ++c->live_list_age;
-    if (!big && recs != nullptr && c->use_live_list && need_bound && !c->st.fresh && n_views <= kLiveListMaxViews && (m.trunc != 0 || have_min) &&
-        (list_pays || c->live_list_age % 16 == 0)) {  // (every 16th launch looks again)
-      const int nwg = (int)grid.x;
-      // (a launch of ONE view: entries {id, live waves, the four records} -- "listrecords" 0: ids only)
-      list_entry_words = one_view && c->list_records != 0 ? kLiveEntryWords : 0;
-      const size_t need = list_entry_words ? sizeof(int) * (2 + (size_t)nwg * kLiveEntryWords) : sizeof(int) * ((size_t)nwg + 1);  // (the hint below: a race with its copy is benign, it only
-      // decides whether the NEXT launch lists its workgroups; with several chunks it reflects the last one)
-      VCY_HIP_CHECK(c->d_wg_list.grow(need, c->stream));
-      VCY_HIP_CHECK(hipMemsetAsync(c->d_wg_list, 0, sizeof(int), c->stream));
-      hipLaunchKernelGGL(live_workgroups_kernel, dim3((unsigned)((nwg + kLiveThreads - 1) / kLiveThreads)), dim3(kLiveThreads), 0, c->stream, recs, nbricks,
-                         n_views, have_min ? bmin : nullptr, m.trunc, units_x, nby, nbw, nwg, c->d_wg_list, unit_bricks,
-                         list_entry_words);
-      launch_grid = groups_of((unsigned)nwg);  // (every unit started unless the count below arrives)
-      VCY_HIP_CHECK(hipGetLastError());
-      wgl = c->d_wg_list;
-      if (!c->h_live_hint && c->h_live_hint.alloc(2 * sizeof(int)) != hipSuccess) (void)hipGetLastError();
-      if (c->h_live_hint) {
-        c->h_live_hint[1] = nwg;
-        (void)hipMemcpyAsync(&c->h_live_hint[0], c->d_wg_list, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        // The carve kernel is launched over the listed workgroups only: the host waits for the count (the list pass is
-        // 60 us of device time behind it) instead of starting every workgroup of the slab to have all but the listed
-        // ones read list[0] and leave -- 512 K workgroups that do nothing else are 0.115 ms at 1024^3
-        // (profiles/tools/per_view_floor.py), a sixth of a single-view launch.  ("livesync" 0: the full grid, no wait.)
-        if (c->live_sync && hipStreamSynchronize(c->stream) == hipSuccess) {
-          const int live = c->h_live_hint[0];
-          if (live >= 0 && live <= nwg) launch_grid = groups_of((unsigned)live);
-        } else {
-          (void)hipGetLastError();
-        }
-      }
-    }
-    // "eagerstate": the workgroups of a one-view launch over a carved grid request their bricks' state next to the
-    // footprint records when nearly all of them will need it: a listed launch (only live workgroups are started), or one
-    // that skipped its list because the last one held most workgroups (-1 that rule, 0 never, 1 every one-view launch).
-    // 1024^3, one view per launch: weighted average 2.51 -> 2.46 ms, kMax 0.521 -> 0.487 (profiles/r06/eager_state.txt).
-    const bool nearly_all_live = wgl != nullptr ? launch_grid.x < grid.x || !list_pays : !list_pays;
-    const bool eager_state = !c->st.fresh && one_view &&
-                             (c->eager_state > 0 || (c->eager_state < 0 && nearly_all_live));
-    CarveLaunch launch;
-    launch.update = u.voxel_update == VCY_UPDATE_MAX ? VCY_UPDATE_MAX
-                    : gc.weight == 1.0f             ? kUpdateWaUnitWeight
-                                                    : VCY_UPDATE_WEIGHTED_AVERAGE;
-    launch.trunc = m.trunc != 0, launch.samef = samef, launch.checkmax = checkmax, launch.big = big;
-    launch.gen = gen, launch.div_level = m.div_level;
-    launch.flavour = rows ? CarveFlavour::kRows : (one_view ? CarveFlavour::kOneView : CarveFlavour::kGeneral);
-    launch.g = gc, launch.views = d_views, launch.c0_all = d_c2, launch.n_views = n_views, launch.mode = m;
-    launch.nbx = units_x, launch.nby = nby, launch.cull = c->use_cull ? 1 : 0;
-    launch.state_flags = state_flags_base | (eager_state ? kStateEager : 0) |
-                         (wgl != nullptr && list_entry_words ? kStateListRecords : 0);
-    launch.records = recs, launch.nbricks = nbricks, launch.brick_min = bmin, launch.wg_list = wgl, launch.pair_count = pcnt;
-    launch.grid_x = launch_grid.x, launch.stream = c->stream, launch.row_units = (int)grid.x;
-    if (stamp >= 0) VCY_HIP_CHECK(hipEventRecord(c->carve_log[stamp].ev[1], c->stream));
-    if (launch_grid.x == 0) {
-      // (no workgroup is live: nothing to launch)
-    } else if (c->cnt_bytes == 1)
-      launch_fused_counts8(launch);
-    else
-      launch_fused_counts16(launch);
-    VCY_HIP_CHECK(hipGetLastError());
-    if (stamp >= 0) VCY_HIP_CHECK(hipEventRecord(c->carve_log[stamp].ev[2], c->stream));
+  VCY_HIP_CHECK(hipGetLastError());
+  return VCY_OK;
+}
+
+// Lists the chunk's live workgroups (live_workgroups_kernel) and copies their number into the hint; *live: that number
+// when the host has waited for it ("livesync"), else kLiveNotWaited.
+int list_live_workgroups(vcy_ctx* c, const FusedLaunchPlan& plan, const FusedChunkPlan& chunk, const ChunkOperands& o,
+                         int n_views, int trunc, int* live) {
+  FusedState& f = c->fused;
+  const int nwg = chunk.units;
+  // (the hint below: a race with its copy is benign, it only decides whether the NEXT launch lists its workgroups; with
+  // several chunks it reflects the last one)
+  VCY_HIP_CHECK(f.d_wg_list.grow(chunk.list_bytes, c->stream));
+  VCY_HIP_CHECK(hipMemsetAsync(f.d_wg_list, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(live_workgroups_kernel, dim3((unsigned)((nwg + kLiveThreads - 1) / kLiveThreads)), dim3(kLiveThreads), 0,
+                     c->stream, o.recs, o.nbricks, n_views, chunk.have_min ? o.bmin : nullptr, trunc, chunk.units_x, plan.nby,
+                     plan.nbw, nwg, f.d_wg_list, chunk.unit_bricks, chunk.list_entry_words);
+  VCY_HIP_CHECK(hipGetLastError());
+  if (!f.h_live_hint && f.h_live_hint.alloc(2 * sizeof(int)) != hipSuccess) (void)hipGetLastError();
+  if (f.h_live_hint) {
+    f.h_live_hint[1] = nwg;
+    (void)hipMemcpyAsync(&f.h_live_hint[0], f.d_wg_list, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    // (the wait, and what it buys: finish_fused_chunk)
+    if (f.knobs.live_sync && hipStreamSynchronize(c->stream) == hipSuccess) *live = f.h_live_hint[0];
+    else (void)hipGetLastError();
   }
-  log_guard.done = true;
+  return VCY_OK;
+}
+
+// Fills the CarveLaunch of a chunk from the two plans and hands it to the unit that holds the instances.
+int launch_chunk(vcy_ctx* c, const FusedLaunchPlan& plan, const FusedChunkPlan& chunk, const FusedChunkLaunch& fin,
+                 const ChunkOperands& o, const PreparedViews& pv, int n_views, const ModeParams& m, CarveLogScope* log) {
+  CarveLaunch launch;
+  launch.update = plan.update;
+  launch.trunc = m.trunc != 0, launch.samef = pv.samef, launch.checkmax = plan.checkmax, launch.big = plan.big;
+  launch.gen = plan.gen, launch.div_level = m.div_level;
+  launch.flavour = plan.flavour;
+  launch.g = o.g, launch.views = pv.d_views, launch.c0_all = pv.d_c2, launch.n_views = n_views, launch.mode = m;
+  launch.nbx = chunk.units_x, launch.nby = plan.nby, launch.cull = c->fused.knobs.use_cull ? 1 : 0;
+  launch.state_flags = fin.state_flags;
+  launch.records = o.recs, launch.nbricks = o.nbricks, launch.brick_min = o.bmin;
+  const int* list = c->fused.d_wg_list;
+  launch.wg_list = chunk.listed ? list : nullptr, launch.pair_count = o.pcnt;
+  launch.grid_x = fin.grid_x, launch.stream = c->stream, launch.row_units = chunk.units;
+  { const int rcl = log->mark(1); if (rcl != VCY_OK) return rcl; }
+  if (fin.grid_x == 0) {
+    // (no workgroup is live: nothing to launch)
+  } else if (c->cnt_bytes == 1)
+    launch_fused_counts8(launch);
+  else
+    launch_fused_counts16(launch);
+  VCY_HIP_CHECK(hipGetLastError());
+  return log->mark(2);
+}
+
+}  // namespace
+
+// Carves views[0..n_views) (n_views <= 32, max_sdf already resolved) in one launch.  The caller has declared the write
+// (StateFlags::written, once for all its launches); `views_before`: views applied since the fill when this one starts.
+int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewParams* vp, bool ortho, int64_t views_before) {
+  const vcy_update_option& u = c->opt.update_option;
+  FusedPlanInput in = plan_input(c, g, n_views, vp, ortho, views_before);
+  const FusedLaunchPlan plan = plan_fused_launch(in);
+  PreparedViews pv;
+  { const int rc = prepare_views(c, n_views, vp, ortho, plan.need_bound, plan.need_lower, c->z0, c->z1, &pv); if (rc != VCY_OK) return rc; }
+  CarveLogScope log(c);
+  { const int rc = log.open(true); if (rc != VCY_OK) return rc; }
+  build_window_planes(c, pv, n_views, plan.need_lower);  // the images may have changed since the last call: rebuild every time
+  if ((int64_t)plan.nbx * plan.nby * plan.nbz > 0x7fffffffLL) {
+    set_error("slab too large for one launch");
+    return VCY_ERR_TOO_MANY_VOXELS;
+  }
+  ModeParams m{u.voxel_update, u.sdf_interp, u.update_outside, u.use_truncation ? 1 : 0, ortho ? 1 : 0, 0};
+  m.div_level = launch_div_level(c, n_views, vp, ortho);
+  c->fused.last_div_level = m.div_level;
+  { const int rc = ensure_launch_buffers(c, plan, n_views); if (rc != VCY_OK) return rc; }
+  in.have_brick_min = c->d_brick_min != nullptr;  // (allocated just now, perhaps)
+  for (int l0 = 0; l0 < plan.nbz; l0 += plan.chunk_layers) {
+    const int layers = std::min(plan.chunk_layers, plan.nbz - l0);
+    const ChunkOperands o = chunk_operands(c, g, plan, l0, layers);
+    if (l0 > 0) { const int rc = log.open(false); if (rc != VCY_OK) return rc; }
+    if (plan.records) { const int rc = run_prepass(c, plan, o, pv, n_views, m); if (rc != VCY_OK) return rc; }
+    const FusedChunkPlan chunk = plan_fused_chunk(plan, in, layers, c->fused.h_live_hint, ++c->fused.live_list_age);
+    int live = kLiveNotWaited;
+    if (chunk.listed) { const int rc = list_live_workgroups(c, plan, chunk, o, n_views, m.trunc, &live); if (rc != VCY_OK) return rc; }
+    const FusedChunkLaunch fin = finish_fused_chunk(plan, in, chunk, live);
+    { const int rc = launch_chunk(c, plan, chunk, fin, o, pv, n_views, m, &log); if (rc != VCY_OK) return rc; }
+  }
+  log.done = true;
   c->st.stored();  // the launches store every voxel of a fresh slab
   // (every wave that ran to its end wrote its entry; the others' entries were valid on entry or hold lowest(), see above)
   c->st.minima_rebuilt(c->d_brick_min != nullptr);
@@ -784,18 +716,18 @@ __global__ __launch_bounds__(256) void plan_cost_kernel(GridParams g, const Fuse
 
 // pairs[l] = estimated (brick, view) pairs a fused carve of these views processes in brick layer l of the WHOLE grid,
 // scaled from the sampled bricks to the layer's bricks; bricks_per_layer as the carve kernel counts them.
-int plan_layer_pairs(vcy_ctx* c, int n_views, const ViewParams* vp, int stride, std::vector<double>* pairs,
+int plan_layer_pairs(vcy_ctx* c, int n_views, const ViewParams* vp, bool ortho, int stride, std::vector<double>* pairs,
                      int64_t* bricks_per_layer) {
   const vcy_update_option& u = c->opt.update_option;
   const int nxp = (c->nx + WX - 1) / WX * WX, nbw = nxp / WX, nby = (c->ny + BY - 1) / BY, nbz = (c->nz + BZ - 1) / BZ;
   *bricks_per_layer = (int64_t)nbw * nby;
   pairs->assign((size_t)nbz, (double)n_views * (double)nbw * nby);  // nothing dropped: every pair
-  const bool drops = c->use_cull && (u.voxel_update == VCY_UPDATE_MAX || u.use_truncation);
+  const bool drops = c->fused.knobs.use_cull && (u.voxel_update == VCY_UPDATE_MAX || u.use_truncation);
   if (!drops) return VCY_OK;
   if (stride < 1) stride = 1;
   PreparedViews pv;
   {
-    const int rcp = prepare_views(c, n_views, vp, true, true, 0, c->nz, &pv);
+    const int rcp = prepare_views(c, n_views, vp, ortho, true, true, 0, c->nz, &pv);
     if (rcp != VCY_OK) return rcp;
   }
   if (pv.max_quads <= 0) return VCY_OK;  // no memory for the planes: no estimate, equal layers
@@ -804,7 +736,7 @@ int plan_layer_pairs(vcy_ctx* c, int n_views, const ViewParams* vp, int stride, 
   std::memset(&g, 0, sizeof(g));
   g.px = c->d_px, g.py = c->d_py, g.pz = c->d_pz;
   g.nx = c->nx, g.ny = c->ny, g.z0 = 0, g.nz_local = c->nz;
-  ModeParams m{u.voxel_update, u.sdf_interp, u.update_outside, u.use_truncation ? 1 : 0, c->fused_ortho ? 1 : 0, 0};
+  ModeParams m{u.voxel_update, u.sdf_interp, u.update_outside, u.use_truncation ? 1 : 0, ortho ? 1 : 0, 0};
   const int sxn = (nbw + stride - 1) / stride, syn = (nby + stride - 1) / stride;
   const int64_t nsample = (int64_t)sxn * syn * nbz;
   DeviceBuf<unsigned long long> d_out;

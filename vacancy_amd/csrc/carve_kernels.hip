@@ -225,14 +225,14 @@ int launch_carve(vcy_ctx* c, int n_views, const vcy_view* views, const float* co
   const int64_t before = c->st.views_carved;
   c->st.written(StateWrite::silhouettes(n_views, fused, queued));
   if (fused) {
-    c->fused_ortho = views[0].is_ortho != 0;
+    const bool ortho = views[0].is_ortho != 0;
     const int chunk = fused_max_views();
     for (int i = 0; i < n_views; i += chunk) {
       const int m = std::min(chunk, n_views - i);
       int rc = ensure_count_width(c, before + i + m);  // (update_num <= views applied: u8 up to the 255th view)
       if (rc != VCY_OK) return rc;
       g.cnt = c->owned_slab_cnt();
-      rc = launch_carve_fused(c, g, m, &vp[i], before + i);
+      rc = launch_carve_fused(c, g, m, &vp[i], ortho, before + i);
       if (rc != VCY_OK) return rc;
     }
   } else {
@@ -311,10 +311,9 @@ int plan_z_slabs(vcy_ctx* c, int n_views, const vcy_view* views, const float* co
     std::vector<ViewParams> vp;
     int rc = resolve_views(c, n_views, views, sdf_dev, &vp);
     if (rc != VCY_OK) return rc;
-    c->fused_ortho = views[0].is_ortho != 0;
     std::vector<double> pairs;
     int64_t bricks = 0;
-    rc = plan_layer_pairs(c, n_views, vp.data(), stride > 0 ? stride : 2, &pairs, &bricks);
+    rc = plan_layer_pairs(c, n_views, vp.data(), views[0].is_ortho != 0, stride > 0 ? stride : 2, &pairs, &bricks);
     if (rc != VCY_OK) return rc;
     const double bc = brick_cost > 0.0f ? brick_cost : kPlanBrickCost;
     for (int l = 0; l < L; ++l) cost[(size_t)l] = bc * (double)bricks + pairs[(size_t)l];

@@ -256,15 +256,15 @@ int vcy_set_param(vcy_ctx* c, const char* name, int value) {
   }
   if (std::strcmp(name, "tile") == 0) {
     if (value < 0 || value > 2) return VCY_ERR_INVALID_ARG;
-    c->tile_mode = value;
+    c->fused.knobs.tile_mode = value;
     return VCY_OK;
   }
   if (std::strcmp(name, "shortdiv") == 0) {
-    c->use_short_div = value != 0;
+    c->fused.knobs.use_short_div = value != 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "cull") == 0) {
-    c->use_cull = value != 0;
+    c->fused.knobs.use_cull = value != 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "mcsweep") == 0) {
@@ -278,48 +278,48 @@ int vcy_set_param(vcy_ctx* c, const char* name, int value) {
     return VCY_OK;
   }
   if (std::strcmp(name, "paircount") == 0) {
-    c->count_pairs = value != 0;
+    c->fused.knobs.count_pairs = value != 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "recordbytes") == 0) {
-    c->record_bytes_max = value > 0 ? value : 0;
+    c->fused.knobs.record_bytes_max = value > 0 ? value : 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "livelist") == 0) {
-    c->use_live_list = value != 0;
+    c->fused.knobs.use_live_list = value != 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "prologue") == 0) {
     if (value < 0 || value > 2) return VCY_ERR_INVALID_ARG;
-    c->prologue_mode = value;
+    c->fused.knobs.prologue_mode = value;
     return VCY_OK;
   }
   if (std::strcmp(name, "livesync") == 0) {
-    c->live_sync = value != 0;
+    c->fused.knobs.live_sync = value != 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "coopstore") == 0) {
-    c->coop_store = value < 0 ? -1 : (value != 0 ? 1 : 0);
+    c->fused.knobs.coop_store = value < 0 ? -1 : (value != 0 ? 1 : 0);
     return VCY_OK;
   }
   if (std::strcmp(name, "listrecords") == 0) {
-    c->list_records = value != 0;
+    c->fused.knobs.list_records = value != 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "eagerstate") == 0) {
-    c->eager_state = value < 0 ? -1 : (value != 0 ? 1 : 0);
+    c->fused.knobs.eager_state = value < 0 ? -1 : (value != 0 ? 1 : 0);
     return VCY_OK;
   }
   if (std::strcmp(name, "oneview") == 0) {
-    c->one_view = value != 0 ? 1 : 0;
+    c->fused.knobs.one_view = value != 0 ? 1 : 0;
     return VCY_OK;
   }
   if (std::strcmp(name, "ntstore") == 0) {
-    c->nt_store = value < 0 ? -1 : (value != 0 ? 1 : 0);
+    c->fused.knobs.nt_store = value < 0 ? -1 : (value != 0 ? 1 : 0);
     return VCY_OK;
   }
   if (std::strcmp(name, "rowkernel") == 0) {
-    c->row_kernel = value < 0 ? -1 : value;
+    c->fused.knobs.row_kernel = value < 0 ? -1 : value;
     return VCY_OK;
   }
   if (std::strcmp(name, "mcskip") == 0) {
@@ -363,23 +363,23 @@ int vcy_set_param(vcy_ctx* c, const char* name, int value) {
 int vcy_get_param(vcy_ctx* c, const char* name, int* value) {
   if (!c || !name || !value) return VCY_ERR_INVALID_ARG;
   if (std::strcmp(name, "fused") == 0) *value = c->use_fused ? 1 : 0;
-  else if (std::strcmp(name, "cull") == 0) *value = c->use_cull ? 1 : 0;
-  else if (std::strcmp(name, "tile") == 0) *value = c->tile_mode;
+  else if (std::strcmp(name, "cull") == 0) *value = c->fused.knobs.use_cull ? 1 : 0;
+  else if (std::strcmp(name, "tile") == 0) *value = c->fused.knobs.tile_mode;
   else if (std::strcmp(name, "defer") == 0) *value = c->defer ? 1 : 0;
-  else if (std::strcmp(name, "shortdiv") == 0) *value = c->use_short_div ? 1 : 0;
-  else if (std::strcmp(name, "div_level") == 0) *value = c->last_div_level;
+  else if (std::strcmp(name, "shortdiv") == 0) *value = c->fused.knobs.use_short_div ? 1 : 0;
+  else if (std::strcmp(name, "div_level") == 0) *value = c->fused.last_div_level;
   else if (std::strcmp(name, "mcsweep") == 0) *value = c->mc_sweep ? 1 : 0;
   else if (std::strcmp(name, "mcskip") == 0) *value = c->mc_skip;
-  else if (std::strcmp(name, "rowkernel") == 0) *value = c->row_kernel;
-  else if (std::strcmp(name, "ntstore") == 0) *value = c->nt_store;
-  else if (std::strcmp(name, "oneview") == 0) *value = c->one_view;
-  else if (std::strcmp(name, "eagerstate") == 0) *value = c->eager_state;
-  else if (std::strcmp(name, "listrecords") == 0) *value = c->list_records;
+  else if (std::strcmp(name, "rowkernel") == 0) *value = c->fused.knobs.row_kernel;
+  else if (std::strcmp(name, "ntstore") == 0) *value = c->fused.knobs.nt_store;
+  else if (std::strcmp(name, "oneview") == 0) *value = c->fused.knobs.one_view;
+  else if (std::strcmp(name, "eagerstate") == 0) *value = c->fused.knobs.eager_state;
+  else if (std::strcmp(name, "listrecords") == 0) *value = c->fused.knobs.list_records;
   else if (std::strcmp(name, "mcdirect") == 0) *value = (int)std::min<int64_t>(c->mc_direct_bytes, 0x7fffffff);
-  else if (std::strcmp(name, "livelist") == 0) *value = c->use_live_list ? 1 : 0;
-  else if (std::strcmp(name, "prologue") == 0) *value = c->prologue_mode;
-  else if (std::strcmp(name, "coopstore") == 0) *value = c->coop_store;
-  else if (std::strcmp(name, "livesync") == 0) *value = c->live_sync ? 1 : 0;
+  else if (std::strcmp(name, "livelist") == 0) *value = c->fused.knobs.use_live_list ? 1 : 0;
+  else if (std::strcmp(name, "prologue") == 0) *value = c->fused.knobs.prologue_mode;
+  else if (std::strcmp(name, "coopstore") == 0) *value = c->fused.knobs.coop_store;
+  else if (std::strcmp(name, "livesync") == 0) *value = c->fused.knobs.live_sync ? 1 : 0;
   else if (std::strcmp(name, "brick_min_valid") == 0) *value = c->st.brick_min_valid && !c->st.fresh ? 1 : 0;
   else if (std::strcmp(name, "fresh") == 0) *value = c->st.fresh ? 1 : 0;  // the fill has not been written yet
   else if (std::strcmp(name, "meshkeys") == 0) *value = c->mesh_keys ? 1 : 0;
@@ -474,14 +474,14 @@ int vcy_carve_log(vcy_ctx* c, int max_records, float* begin_ms, float* prepass_m
 
 int vcy_last_carve_pairs(vcy_ctx* c, int64_t* processed, int64_t* total, int64_t* per_layer, int max_layers, int* n_layers) {
   if (!c) return VCY_ERR_NOT_INITIALIZED;
-  if (!c->count_pairs || !c->d_pair_count) {
+  if (!c->fused.knobs.count_pairs || !c->fused.d_pair_count) {
     set_error("vcy_last_carve_pairs: no fused launch since vcy_set_param(\"paircount\", 1)");
     return VCY_ERR_INVALID_ARG;
   }
   VCY_HIP_CHECK(hipSetDevice(c->device));
   const int nbz = (c->nz_local() + 7) / 8;
   std::vector<unsigned long long> h((size_t)nbz, 0ull);
-  VCY_HIP_CHECK(hipMemcpyAsync(h.data(), c->d_pair_count, sizeof(unsigned long long) * (size_t)nbz, hipMemcpyDeviceToHost, c->stream));
+  VCY_HIP_CHECK(hipMemcpyAsync(h.data(), c->fused.d_pair_count, sizeof(unsigned long long) * (size_t)nbz, hipMemcpyDeviceToHost, c->stream));
   VCY_HIP_CHECK(hipStreamSynchronize(c->stream));
   int64_t sum = 0;
   for (int l = 0; l < nbz; ++l) {
@@ -489,7 +489,7 @@ int vcy_last_carve_pairs(vcy_ctx* c, int64_t* processed, int64_t* total, int64_t
     if (per_layer && l < max_layers) per_layer[l] = (int64_t)h[(size_t)l];
   }
   if (processed) *processed = sum;
-  if (total) *total = (int64_t)((c->nx + 7) / 8) * ((c->ny + 7) / 8) * nbz * c->pair_count_views;
+  if (total) *total = (int64_t)((c->nx + 7) / 8) * ((c->ny + 7) / 8) * nbz * c->fused.pair_count_views;
   if (n_layers) *n_layers = nbz;
   return VCY_OK;
 }

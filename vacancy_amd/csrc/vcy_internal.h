@@ -34,6 +34,7 @@ constexpr float kInvalidSdf = -3.402823466e+38f;
 
 #include "vcy_resources.h"  // DeviceBuf, PinnedBuf, Event, Stream: what owns the context's resources
 #include "state_flags.h"    // StateFlags: what the context knows about its voxel state, and who may say so
+#include "carve_fused_state.h"  // FusedState: what the fused carve keeps between its launches
 
 // The device-resident voxel grid of one z-slab.
 //
@@ -52,6 +53,7 @@ struct vcy_ctx {
   vcy::Stream stream;
   vcy::Stream aux_stream;             // producer stream of the streamed batch (uploads + SDF build)
   vcy::Event ev_begin, ev_end;
+  vcy::FusedState fused;              // the fused carve's knobs, buffers and view cache (carve_fused_state.h): after the streams, so destroyed before them
 
   vcy_carver_option opt{};
   int nx = 0, ny = 0, nz = 0;  // global dims
@@ -80,15 +82,8 @@ struct vcy_ctx {
   vcy::DeviceBuf<float> d_px, d_py, d_pz;
 
   bool mesh_keys = true;              // vcy_extract_iso also returns the edge key of every vertex (vcy_set_param "meshkeys")
-  int list_records = 1;               // "listrecords": the live list of a one-view launch carries the footprint records and per-wave live bits (0: workgroup ids only)
-  int eager_state = -1;               // "eagerstate": few-view launches request a brick's state next to its footprint record instead of behind the early-return test (-1: when most workgroups were live last time, 0 never, 1 always)
-  int one_view = 1;                   // "oneview": single-view launches take the kernel instance compiled for one view (carve_fused_kernel NB == 0)
-  int nt_store = -1;                  // "ntstore": streaming stores in the cooperative write-back (-1 / 1: whenever it runs -- 0.5 - 1.5 % on single-view launches; 0 never)
-  int row_kernel = 0;                 // "rowkernel": launches of up to this many views take the few-view flavour of the fused kernel (a wave walks the bricks of a row segment); -1 = up to 8, 0 = never (the default: measured slower, carve_fused.h kRowBricks)
   int mc_skip = 1;                    // marching cubes: bricks whose kept minimum is above the iso level are not read (vcy_set_param "mcskip": 0 never, 1 where it pays -- rows of 1024 voxels and more --, 2 wherever possible)
   bool mc_sweep = false;              // marching cubes: cell search in one sweep with the bit planes in LDS where the row shape allows (vcy_set_param "mcsweep")
-  int tile_mode = 0;                  // 0 auto, 1 the 16 x 16 pixel tile, 2 the 2048-pixel tile filled in place (vcy_set_param "tile")
-  bool use_cull = true;               // vcy_set_param("cull", 0): never drop provably idle views
   // Views accepted by the per-view entry points (vcy_carve, vcy_carve_device, vcy_carve_silhouette) but
   // not applied yet: they are carved together, in order, by ONE fused launch when the state is next
   // needed (extraction, download, halo, timer, sync ...) or when 32 are waiting -- the reference's
@@ -106,16 +101,12 @@ struct vcy_ctx {
   int deferred_rc = 0;
   int inject_fail = 0;                // test hook: the next n applications of views fail (vcy_set_param "inject_carve_failure")
   std::string deferred_msg;
-  int last_div_level = 0;             // division variant of the last fused launch (vcy_get_param "div_level")
-  bool use_short_div = true;          // vcy_set_param("shortdiv", 0): always the full division sequence
   bool use_fused = true;              // vcy_set_option("fused", 0) forces the per-view kernel
   std::vector<float> h_px;            // host copy of the x axis table (c0 tables of the fused carve)
   float h_px_min = 0, h_px_max = 0, h_py_min = 0, h_py_max = 0;  // extreme voxel centres
   std::vector<float> h_pz;            // host copy of d_pz (per-view z tables of the fused carve)
-  vcy::DeviceBuf<> d_fused_scratch;   // view blocks + z tables of the fused carve kernel
   vcy::DeviceBuf<float> d_brick_min;  // min(sdf) of every 8x8x8 wave brick of the slab [bz][by][bxw], kept by the fused carve
                                       // (current while st.brick_min_valid)
-  vcy::DeviceBuf<int> d_wg_list;      // live workgroups of a carve launch of few views ([0] = count), live_workgroups_kernel
   bool time_carve = false;            // vcy_set_param("carvetimer", 1): events around pre-pass and carve kernel of every fused launch
   struct CarveStamp {                 // one chunk of one fused launch
     vcy::Event ev[3];                 // before window maxima / pre-pass, before the carve kernel, after it
@@ -126,29 +117,6 @@ struct vcy_ctx {
   int carve_log_last = 0;             // index of the first chunk of the last launch
   int carve_log_dropped = 0;          // chunks that found the log full since it was cleared (vcy_get_param "carvelog_dropped")
   bool carve_log_last_dropped = false;  // ... the last launch among them: vcy_last_carve_ms has nothing to report
-  vcy::PinnedBuf<int> h_live_hint;    // page-locked {live workgroups, workgroups} of the last listed launch (a hint, see launch_carve_fused)
-  int64_t live_list_age = 0;
-  bool use_live_list = true;          // vcy_set_param("livelist", 0): every workgroup is launched and decides for itself
-  bool live_sync = true;              // vcy_set_param("livesync", 0): the carve kernel of a listed launch starts every workgroup instead of waiting for the list's length
-  int coop_store = -1;                // vcy_set_param("coopstore"): write-back of a workgroup's bricks through LDS in whole row segments; -1 = where it pays (launch_carve_fused), 0 / 1 = never / whenever possible
-  bool count_pairs = false;           // vcy_set_param("paircount", 1): the fused kernel counts the (brick, view) pairs it processes
-  vcy::DeviceBuf<unsigned long long> d_pair_count;  // ... per brick layer of the slab, of the last fused launch (vcy_last_carve_pairs)
-  int pair_count_views = 0;
-  int64_t record_bytes_max = 0;       // vcy_set_param("recordbytes", n): footprint records per launch chunk (0: 2 GiB)
-  int prologue_mode = 0;              // vcy_set_param("prologue"): 0 / 2 footprint records from the pre-pass (chunked); 1 footprints in the carve kernel's prologue (slower at every shape measured)
-  vcy::DeviceBuf<> d_records;         // footprint records of one fused launch, 8 bytes per (wave brick, view)
-  vcy::DeviceBuf<float> d_wmax;       // window-maximum planes of the views of one fused launch
-  bool fused_ortho = false;           // projection model of the launch being prepared
-  vcy::PinnedBuf<> h_fused_stage[2];  // page-locked staging of the view blocks, taken in turn (prepare_views)
-  vcy::Event ev_fused_stage[2];       // "the copy out of staging buffer q has been made"
-  int fused_stage_idx = 0;
-  bool fused_cache_valid = false;     // d_fused_scratch holds what these view parameters give (launch_carve_fused)
-  std::vector<char> fused_cache_vp;   // the ViewParams of the launch that filled it
-  const float* fused_cache_wmax = nullptr;
-  void* fused_cache_at = nullptr;
-  bool fused_cache_bound = false, fused_cache_lower = false, fused_cache_ortho = false, fused_cache_samef = true;
-  int fused_cache_max_quads = 0;
-  int fused_cache_z[2] = {0, 0};
   vcy::DeviceBuf<> d_stream_pool;     // staging of vcy_carve_batch_silhouettes (masks, SDFs, scratch)
   vcy::Event ev_ready[2], ev_consumed[2], ev_uploaded[2];
   std::vector<vcy::Event> stream_events;  // four per chunk of the last streamed batch (vcy_last_stream_ms)
@@ -263,10 +231,11 @@ int launch_carve(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* 
 struct GridParams;
 struct ViewParams;
 bool fused_eligible(const vcy_ctx* ctx, int n_views, const vcy_view* views);
-// `views_before`: views applied since the fill when this launch starts (the caller has declared its whole call already)
-int launch_carve_fused(vcy_ctx* ctx, const GridParams& g, int n_views, const ViewParams* vp, int64_t views_before);
+// `ortho`: the projection model of the views (one per launch); `views_before`: views applied since the fill when this
+// launch starts (the caller has declared its whole call already)
+int launch_carve_fused(vcy_ctx* ctx, const GridParams& g, int n_views, const ViewParams* vp, bool ortho, int64_t views_before);
 int fused_max_views();
-int plan_layer_pairs(vcy_ctx* ctx, int n_views, const ViewParams* vp, int stride, std::vector<double>* pairs,
+int plan_layer_pairs(vcy_ctx* ctx, int n_views, const ViewParams* vp, bool ortho, int stride, std::vector<double>* pairs,
                      int64_t* bricks_per_layer);  // the slab planner's estimate (carve_fused.hip)
 void partition_layers(const double* cost, int n_layers, int n_slabs, int nz, int32_t* z_bounds);  // carve_kernels.hip
 int plan_z_slabs(vcy_ctx* ctx, int n_views, const vcy_view* views, const float* const* sdf_dev, int n_slabs, int stride,

@@ -116,7 +116,7 @@ int fill_state(vcy_ctx* c) {
   c->deferred_rc = VCY_OK;
   c->deferred_msg.clear();
   c->st.filled();
-  if (c->h_live_hint) c->h_live_hint[0] = c->h_live_hint[1] = 0;
+  c->fused.forget_live_hint();
   // counters start over at one byte (fresh: nothing to convert; the wide array is kept as the spare)
   if (c->d_cnt && c->cnt_bytes != count_width_for(c, 0)) return set_count_width(c, count_width_for(c, 0));
   return VCY_OK;
