@@ -1214,6 +1214,13 @@ int vcy_reset(vcy_ctx* ctx);
  * "prologue" (default 0): where a raw-tile launch gets its footprints: 0 or 2 = from the pre-pass's records; 1 = computed
  * in the carve kernel's prologue, one lane per view (one launch whatever the size, and slower: 92.8 against 81.8 ms per
  * step at 2048^3 x 64 views).  Results identical.
+ * "recordcache" (default 1): a context remembers which launch its footprint records describe -- the cameras (everything of
+ * the views but the images and max_sdf), the slab, the buffer.  A kMax launch of the general flavour with raw tiles, view
+ * dropping on, records from the pre-pass in one chunk, window planes and no live list that finds them there skips the
+ * pre-pass: the geometry of a record does not depend on the images, and the carve kernel's prologue looks the bounds up
+ * itself, with the lookups of the pre-pass.  The first such launch, and every launch after anything of the key has
+ * changed, runs the pre-pass as before.  0: every launch runs it.  Results and dropped pairs identical;
+ * vcy_get_param "recordcache_hits" counts the launches that reused their records.
  * "carvetimer" (default 0): 1 records HIP events around what runs before the carve kernel (window maxima, pre-pass)
  * and around the carve kernel of every fused launch (vcy_last_carve_ms, vcy_carve_log); setting it clears the log.
  * "lazycount" (default 1): update_num is stored in one byte until more than 255 views have been applied since the fill
@@ -1234,7 +1241,7 @@ int vcy_reset(vcy_ctx* ctx);
  * VCY_ERR_INTERNAL before anything is launched -- how the tests exercise the error contract of vcy_carve. */
 int vcy_set_param(vcy_ctx* ctx, const char* name, int value);
 /* Reads a knob back ("fused", "cull", "tile", "defer", "shortdiv", "mcsweep", "mcskip", "mcdirect", "rowkernel", "oneview", "eagerstate", "listrecords", "ntstore", "livelist", "livesync", "coopstore", "meshkeys",
- * "lazycount", "carvetimer"), "count_bytes" / "count_bytes_final" / "carvelog_dropped" (see above), "div_level": the
+ * "lazycount", "carvetimer", "recordcache"), "recordcache_hits", "count_bytes" / "count_bytes_final" / "carvelog_dropped" (see above), "div_level": the
  * division sequence the last fused launch was instantiated with (2: 4 instructions, 1: 6, 0: full IEEE expansion), or
  * "brick_min_valid": 1 while the brick minima describe the state (every write since the fill went through the fused kernel),
  * "fresh": 1 while the fill of vcy_create / vcy_reset is known, not written (nothing has been carved or uploaded since). */

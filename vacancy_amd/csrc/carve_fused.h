@@ -167,16 +167,26 @@ static_assert(sizeof(TileInfo) == 56, "row_lds_bytes_per_wave");
 //           bits 3..0 th, bit 4 / 5: the tile ends at the ROI's last column / row (TileInfo::hi_x / hi_y)
 //   word 1: bits 12..0 tx0, 25..13 ty0, 29..26 tw (0: no tile), 31..30 TileInfo::sure
 // (raw tiles: tw, th <= 15; images up to 8192 x 8192: fused_eligible)
+// Everything but the bound is geometry: it depends on the camera, the grid and the slab, not on the image.  A launch that
+// finds the records of its own cameras in the buffer ("recordcache", carve_fused_plan.h) takes the geometry as it is; the
+// bound in them is then an earlier image's, and the kernel's prologue replaces it (kStateStaleBounds).
 struct FootprintRecord {
   uint32_t w0, w1;
 };
 static_assert(sizeof(FootprintRecord) == kFootprintRecordBytes, "plan_fused_launch's chunk size");
 
-__device__ __forceinline__ FootprintRecord pack_footprint(const TileInfo& ti, const ViewParams& v) {
-  uint32_t b = __float_as_uint(ti.ub);
-  if (!(fabsf(ti.ub) <= 3.402823466e+38f)) b = 0x7f800000u;       // +inf / NaN: no bound
+// Bits 31..6 of word 0: the bound rounded UP to 26 bits.  (Shared by the pre-pass and by the carve kernel's prologue
+// where it bounds the footprints of kept records itself -- kStateStaleBounds: the same truncation by construction.)
+__device__ __forceinline__ uint32_t pack_footprint_ub(float ub) {
+  uint32_t b = __float_as_uint(ub);
+  if (!(fabsf(ub) <= 3.402823466e+38f)) b = 0x7f800000u;          // +inf / NaN: no bound
   else if (b & 0x80000000u) b &= ~63u;                            // negative: towards zero is up
   else b = (b + 63u) & ~63u;                                      // (may carry into +inf: no bound)
+  return b;
+}
+
+__device__ __forceinline__ FootprintRecord pack_footprint(const TileInfo& ti, const ViewParams& v) {
+  const uint32_t b = pack_footprint_ub(ti.ub);
   FootprintRecord r;
   const int tx1 = ti.tx0 + ti.tw - 1, ty1 = ti.ty0 + ti.th - 1;
   r.w0 = b | (uint32_t)ti.th | (ti.nq && tx1 == v.roi_max_xi ? 16u : 0u) | (ti.nq && ty1 == v.roi_max_yi ? 32u : 0u);

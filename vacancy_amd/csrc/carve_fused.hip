@@ -4,6 +4,7 @@
 // only code that launches them.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -567,6 +568,40 @@ int run_prepass(vcy_ctx* c, const FusedLaunchPlan& plan, const ChunkOperands& o,
   return VCY_OK;
 }
 
+// What the geometry of the launch's footprint records depends on, as bytes (FusedRecordCache, carve_fused_state.h).
+std::vector<char> record_key(const vcy_ctx* c, const FusedLaunchPlan& plan, const PreparedViews& pv, int n_views,
+                             const ViewParams* vp, const ModeParams& m) {
+  struct Head {
+    int n_views, samef, gen, ortho, outside, z0, z1, nbw, nby, nbz;
+    const void* at;
+    size_t bytes;
+  } h;
+  std::memset((void*)&h, 0, sizeof(h));  // (padding is compared too)
+  h.n_views = n_views, h.samef = pv.samef ? 1 : 0, h.gen = plan.gen ? 1 : 0, h.ortho = m.ortho, h.outside = m.outside;
+  h.z0 = c->z0, h.z1 = c->z1, h.nbw = plan.nbw, h.nby = plan.nby, h.nbz = plan.nbz;
+  h.at = (const void*)c->fused.d_records, h.bytes = c->fused.d_records.bytes();
+  std::vector<char> key(sizeof(Head) + sizeof(ViewParams) * (size_t)n_views);
+  std::memcpy(key.data(), &h, sizeof(Head));
+  for (int vi = 0; vi < n_views; ++vi) {
+    // (the bytes as FusedViewCache compares them, with what only the bound depends on blanked: the image, max_sdf)
+    char* dst = key.data() + sizeof(Head) + sizeof(ViewParams) * (size_t)vi;
+    std::memcpy(dst, &vp[vi], sizeof(ViewParams));
+    std::memset(dst + offsetof(ViewParams, sdf), 0, sizeof(vp[vi].sdf));
+    std::memset(dst + offsetof(ViewParams, max_sdf), 0, sizeof(vp[vi].max_sdf));
+  }
+  return key;
+}
+
+// The one place that writes the record buffer: it forgets which launch the buffer described, runs the pre-pass, and
+// remembers this launch's key when a later launch may reuse the records (`key` non-null: fused_records_cacheable).
+int write_records(vcy_ctx* c, const FusedLaunchPlan& plan, const ChunkOperands& o, const PreparedViews& pv, int n_views,
+                  const ModeParams& m, std::vector<char>* key) {
+  c->fused.rec_cache.forget();
+  { const int rc = run_prepass(c, plan, o, pv, n_views, m); if (rc != VCY_OK) return rc; }
+  if (key != nullptr) c->fused.rec_cache.remember(std::move(*key));
+  return VCY_OK;
+}
+
 // Lists the chunk's live workgroups (live_workgroups_kernel) and copies their number into the hint; *live: that number
 // when the host has waited for it ("livesync"), else kLiveNotWaited.
 int list_live_workgroups(vcy_ctx* c, const FusedLaunchPlan& plan, const FusedChunkPlan& chunk, const ChunkOperands& o,
@@ -644,11 +679,27 @@ int launch_carve_fused(vcy_ctx* c, const GridParams& g, int n_views, const ViewP
     const int layers = std::min(plan.chunk_layers, plan.nbz - l0);
     const ChunkOperands o = chunk_operands(c, g, plan, l0, layers);
     if (l0 > 0) { const int rc = log.open(false); if (rc != VCY_OK) return rc; }
-    if (plan.records) { const int rc = run_prepass(c, plan, o, pv, n_views, m); if (rc != VCY_OK) return rc; }
     const FusedChunkPlan chunk = plan_fused_chunk(plan, in, layers, c->fused.h_live_hint, ++c->fused.live_list_age);
+    // The footprint records: the last launch's, when they describe this launch's cameras and slab ("recordcache": the
+    // kernel's prologue then looks the bounds up, kStateStaleBounds), else from the pre-pass.
+    bool reuse = false;
+    if (plan.records) {
+      const bool have_planes = pv.max_quads > 0;
+      const bool cacheable = fused_records_cacheable(plan, in, chunk, have_planes);
+      std::vector<char> key;
+      if (cacheable) key = record_key(c, plan, pv, n_views, vp, m);
+      reuse = fused_reuses_records(plan, in, chunk, have_planes, cacheable && c->fused.rec_cache.matches(key));
+      if (reuse) {
+        ++c->fused.rec_cache.hits;
+      } else {
+        const int rc = write_records(c, plan, o, pv, n_views, m, cacheable ? &key : nullptr);
+        if (rc != VCY_OK) return rc;
+      }
+    }
     int live = kLiveNotWaited;
     if (chunk.listed) { const int rc = list_live_workgroups(c, plan, chunk, o, n_views, m.trunc, &live); if (rc != VCY_OK) return rc; }
-    const FusedChunkLaunch fin = finish_fused_chunk(plan, in, chunk, live);
+    FusedChunkLaunch fin = finish_fused_chunk(plan, in, chunk, live);
+    if (reuse) fin.state_flags |= kStateStaleBounds;
     { const int rc = launch_chunk(c, plan, chunk, fin, o, pv, n_views, m, &log); if (rc != VCY_OK) return rc; }
   }
   log.done = true;

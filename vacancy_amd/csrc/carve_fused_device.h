@@ -410,6 +410,108 @@ __device__ __forceinline__ void tile_fill(const ViewParams& v, const TileInfo& t
   raw_tile_wait();
 }
 
+// ---- the upper bound of a footprint's samples, from the window-maximum planes ------------------------------------------
+// Two callers make these lookups: footprint_of (the pre-pass, the kernel prologues that bound their footprints
+// themselves, the slab planner) and the prologue of the carve kernels that keep their records, where a launch reuses the
+// records of an earlier one and only their bounds are stale (kStateStaleBounds).  Both go through the helpers below --
+// which pixels a tap of the tile can read, how the windows are placed over them, the lookups, the bound and (carve_fused.h:
+// pack_footprint_ub) its truncation into the record -- so what the second caller finds IS what the pre-pass would write.
+//
+// The pixels a tap of the tile [tx0, tx1] x [ty0, ty1] can read are pw x ph (one more column and row, up to the ROI's
+// last); window maxima of side k = 8 when both sides reach 8, else 4; nxw x nyw windows placed inside that rectangle (a
+// side shorter than k gets one window that sticks out of it: a maximum over more pixels is still an upper bound, and the
+// planes are filled well beyond any footprint, FusedView::wrect).
+struct FootprintWindows {
+  int pw, ph;
+  int L;         // log2 of the windows' side: 3 or 2
+  int nxw, nyw;  // windows along x and y
+};
+__device__ __forceinline__ FootprintWindows footprint_windows(int tx0, int ty0, int tx1, int ty1, int roi_max_xi,
+                                                              int roi_max_yi) {
+  FootprintWindows fw;
+  fw.pw = min(tx1 + 1, roi_max_xi) - tx0 + 1;
+  fw.ph = min(ty1 + 1, roi_max_yi) - ty0 + 1;
+  fw.L = min(fw.pw, fw.ph) >= 8 ? 3 : 2;
+  const int k = 1 << fw.L;
+  fw.nxw = (fw.pw + k - 1) >> fw.L, fw.nyw = (fw.ph + k - 1) >> fw.L;
+  return fw;
+}
+// The lookups: t[0..9) receive window maxima whose maximum is the maximum over the rectangle (entries that are not
+// requested hold -inf).  `plane_off`: the plane's offset from `wm` in elements, folded into a 32-bit index (images are at
+// most 8192 x 8192 and there are four planes: < 2^28 elements; where `wm` is uniform -- the pre-pass -- the loads take a
+// scalar base and one vector offset.  Width and rows are below 2^24: full-rate 24-bit multiplies).  Nothing here waits for
+// the loads: a caller with other requests to make puts them between this and footprint_window_max.
+// EXACT_COUNTS (the pre-pass: every thread has a pair, the view is uniform): as many lookups as the widest footprint of
+// the wave needs, each behind a uniform test.  Without it (the carve kernel's prologue: one lane per VIEW, half the wave
+// idle, and every instruction of it is paid by a wave that is short of issue slots, not of memory): 2 x 2 lookups in a
+// straight line, or all 3 x 3 when some lane needs a third window -- one test instead of nine.  A window that a lane does
+// not need repeats its last one, so the maximum is the same either way.
+template <bool EXACT_COUNTS = true>
+__device__ __forceinline__ void footprint_window_requests(gfloat_ptr wm, unsigned width, unsigned plane_off, int tx0, int ty0,
+                                                          const FootprintWindows& fw, float t[9]) {
+  const int L = fw.L, k = 1 << L, pw = fw.pw, ph = fw.ph;
+  const unsigned origin = __umul24(width, (unsigned)ty0) + (unsigned)tx0 + plane_off;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) t[q] = -INFINITY;
+  // the largest window counts (up to 3) among the lanes that take the 3 x 3 path below: wave-uniform
+  const bool small = fw.nxw <= 3 && fw.nyw <= 3;
+  int ux, uy;
+  if (EXACT_COUNTS) {
+    ux = __any(small && fw.nxw >= 3) ? 3 : (__any(small && fw.nxw >= 2) ? 2 : 1);
+    uy = __any(small && fw.nyw >= 3) ? 3 : (__any(small && fw.nyw >= 2) ? 2 : 1);
+  } else {
+    ux = uy = __any(small && (fw.nxw >= 3 || fw.nyw >= 3)) ? 3 : 2;
+  }
+  if (small) {
+    // the usual case (footprints up to 24 pixels wide): as many lookups as the widest footprint among
+    // the wave's lanes needs (uniform counts ux x uy, typically 2 x 2; narrower ones repeat their last
+    // window), all requested before the first is used.  As a per-lane loop each load waited for the one
+    // before; nine unconditional ones cost the memory system twice what is needed (measured at
+    // 2048^3 x 64: 157 ms instead of 108).
+    auto look = [&](int aq, int bq) {
+      const unsigned ro = origin + __umul24(width, (unsigned)min(bq << L, max(ph - k, 0)));
+      t[3 * bq + aq] = load_u32_index(wm, ro + (unsigned)min(aq << L, max(pw - k, 0)));
+    };
+    if (EXACT_COUNTS) {
+#pragma unroll
+      for (int bq = 0; bq < 3; ++bq) {
+#pragma unroll
+        for (int aq = 0; aq < 3; ++aq)
+          if (aq < ux && bq < uy) look(aq, bq);
+      }
+    } else {
+      // (the four first, the other five behind ONE uniform test: as two alternatives the compiler merged them behind a
+      // flag, and the wait it then put in front of the second alternative's requests -- for registers the first one
+      // loads into -- covered the tile requested in front of these lookups)
+      look(0, 0), look(1, 0), look(0, 1), look(1, 1);
+      if (ux == 3) look(2, 0), look(2, 1), look(0, 2), look(1, 2), look(2, 2);
+    }
+  } else {  // (rare: a long thin footprint, 4 windows along one side)
+    float m = -INFINITY;
+    for (int bq = 0; bq < fw.nyw; ++bq) {
+      const unsigned ro = origin + __umul24(width, (unsigned)min(bq << L, max(ph - k, 0)));
+      for (int aq = 0; aq < fw.nxw; ++aq) m = fmaxf(m, load_u32_index(wm, ro + (unsigned)min(aq << L, max(pw - k, 0))));
+    }
+    t[0] = m;
+  }
+}
+__device__ __forceinline__ float footprint_window_max(const float t[9]) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) m = fmaxf(m, t[q]);
+  return m;
+}
+// TileInfo::ub from the maximum `m` over every pixel a tap can read (`has_nan`: a non-finite pixel was seen -- only the
+// scan of a launch without planes says so; the planes hold +inf there).  Voxels projecting outside the ROI sample max_sdf
+// instead (voxel_carver.cc:469-471) -- not in a `sure` tile: every sample of the brick lies inside it, hence inside the ROI.
+__device__ __forceinline__ float footprint_upper_bound(float m, int has_nan, bool outside_max, bool sure, float max_sdf) {
+  if (outside_max && !sure) {
+    has_nan |= !(fabsf(max_sdf) <= 3.402823466e+38f);
+    m = fmaxf(m, max_sdf);
+  }
+  return has_nan ? INFINITY : (__builtin_fmaf(fabsf(m), 0x1p-20f, m) + 1.0e-30f);
+}
+
 // Footprint of one brick in one view: the tile of SDF pixels its samples read, whether every sample provably
 // lies inside it (`sure`), and bounds of those samples (TileInfo).
 // The brick is convex, so the exact projections of its voxels lie in the hull of the exact
@@ -533,91 +635,37 @@ __device__ __forceinline__ TileInfo footprint_of(const FusedView& fv, float xl, 
       ti.hi_y = (ty1 == v.roi_max_yi) ? v.roi_max_y
                                       : __uint_as_float(__float_as_uint((float)(ty1 + 1)) - 1u);
       if (want_bound) {
-        // maximum over every pixel a tap of this tile can read
-        const int pw = min(tx1 + 1, v.roi_max_xi) - tx0 + 1;
-        const int ph = min(ty1 + 1, v.roi_max_yi) - ty0 + 1;
+        // maximum over every pixel a tap of this tile can read (the lookups: footprint_window_requests above)
+        const FootprintWindows fw = footprint_windows(tx0, ty0, tx1, ty1, v.roi_max_xi, v.roi_max_yi);
+        const int L = fw.L;
         float m = -INFINITY;
         int has_nan = 0;
         gfloat_ptr wm = (gfloat_ptr)fv.wmax;
-        // window maxima: k = 8 when both sides reach 8, else 4; nxw x nyw windows placed inside the rectangle
-        // (a side shorter than k gets one window that sticks out of it: a maximum over more pixels is still
-        // an upper bound, and the planes are filled well beyond any footprint, FusedView::wrect)
-        const int L = min(pw, ph) >= 8 ? 3 : 2;
-        const int k = 1 << L;
-        const int nxw = (pw + k - 1) >> L, nyw = (ph + k - 1) >> L;
-        // the largest window counts (up to 3) among the lanes that take the 3 x 3 path below: wave-uniform
-        const bool small = nxw <= 3 && nyw <= 3;
-        const int ux = __any(small && nxw >= 3) ? 3 : (__any(small && nxw >= 2) ? 2 : 1);
-        const int uy = __any(small && nyw >= 3) ? 3 : (__any(small && nyw >= 2) ? 2 : 1);
         if (wm != nullptr) {
-          gfloat_ptr lvl = wm + (L == 3 ? (size_t)fv.wmax_plane : (size_t)0);
-          // (the 3 x 3 path indexes from `wm` itself with the plane folded into a 32-bit index: in the pre-pass the
-          // view is uniform, so the load takes a scalar base and one vector offset instead of a 64-bit vector address;
-          // images are at most 8192 x 8192 and there are four planes: < 2^28 elements.  Width and rows are below
-          // 2^24: full-rate 24-bit multiplies.)
-          const unsigned origin = __umul24((unsigned)v.width, (unsigned)ty0) + (unsigned)tx0 + (L == 3 ? (unsigned)fv.wmax_plane : 0u);
-          if (nxw <= 3 && nyw <= 3) {
-            // the usual case (footprints up to 24 pixels wide): as many lookups as the widest footprint among
-            // the wave's views needs (uniform counts ux x uy, typically 2 x 2; narrower ones repeat their last
-            // window), all requested before the first is used.  As a per-lane loop each load waited for the one
-            // before; nine unconditional ones cost the memory system twice what is needed (measured at
-            // 2048^3 x 64: 157 ms instead of 108).
-            float t[9];
-#pragma unroll
-            for (int bq = 0; bq < 3; ++bq) {
-              const unsigned ro = origin + __umul24((unsigned)v.width, (unsigned)min(bq << L, max(ph - k, 0)));
-#pragma unroll
-              for (int aq = 0; aq < 3; ++aq) {
-                t[3 * bq + aq] = -INFINITY;
-                if (aq < ux && bq < uy) t[3 * bq + aq] = load_u32_index(wm, ro + (unsigned)min(aq << L, max(pw - k, 0)));
-              }
-            }
-#pragma unroll
-            for (int q = 0; q < 9; ++q) m = fmaxf(m, t[q]);
-          } else {
-            for (int bq = 0; bq < nyw; ++bq) {
-              gfloat_ptr row = lvl + (unsigned)v.width * (unsigned)(ty0 + min(bq << L, max(ph - k, 0)));
-              for (int aq = 0; aq < nxw; ++aq) m = fmaxf(m, row[tx0 + min(aq << L, max(pw - k, 0))]);
-            }
-          }
+          float t[9];
+          footprint_window_requests(wm, (unsigned)v.width, L == 3 ? (unsigned)fv.wmax_plane : 0u, tx0, ty0, fw, t);
+          m = footprint_window_max(t);
         } else {  // no planes (out of memory for them): scan the rectangle
           gfloat_ptr img = (gfloat_ptr)v.sdf;
-          for (int j = 0; j < ph; ++j) {
+          for (int j = 0; j < fw.ph; ++j) {
             gfloat_ptr row = img + ((unsigned)v.width * (unsigned)(ty0 + j) + (unsigned)tx0);
-            for (int i = 0; i < pw; ++i) {
+            for (int i = 0; i < fw.pw; ++i) {
               const float t = row[i];
               has_nan |= !(fabsf(t) <= 3.402823466e+38f);  // NaN or +-inf: 0 * inf = NaN samples
               m = fmaxf(m, t);
             }
           }
         }
-        // voxels projecting outside the ROI sample max_sdf instead (voxel_carver.cc:469-471)
-        // (not in a `sure` tile: every sample of the brick lies inside it, hence inside the ROI)
-        if (outside_max && !ti.sure) {
-          has_nan |= !(fabsf(v.max_sdf) <= 3.402823466e+38f);
-          m = fmaxf(m, v.max_sdf);
-        }
-        ti.ub = has_nan ? INFINITY : (__builtin_fmaf(fabsf(m), 0x1p-20f, m) + 1.0e-30f);
+        ti.ub = footprint_upper_bound(m, has_nan, outside_max, ti.sure != 0, v.max_sdf);
         // Lower bound of the samples, by the mirrored argument: with every tap >= mn the sample is
         // >= mn - 2^-22 |mn|.  If that is >= -1 no voxel of this tile is skipped by the truncation test
         // (`dist < -1`, voxel_carver.cc:478) and the test is compiled out of the run over it (sure bit 1).
         // Voxels outside the ROI are not an issue: a `sure` tile has none.
         // (not looked up for a tile the upper bound already drops: `ub < -1`, the view is never processed)
-        if (want_lower && ti.sure && !(ti.ub < -1.0f) && wm != nullptr && fv.has_lower && nxw <= 3 && nyw <= 3) {
-          const unsigned origin = __umul24((unsigned)v.width, (unsigned)ty0) + (unsigned)tx0 +
-                                  (L == 3 ? 3u : 2u) * (unsigned)fv.wmax_plane;  // planes 2 / 3: of the negated image
-          float t[9], mneg = -INFINITY;  // max of -g = -(min of g)
-#pragma unroll
-          for (int bq = 0; bq < 3; ++bq) {
-            const unsigned ro = origin + __umul24((unsigned)v.width, (unsigned)min(bq << L, max(ph - k, 0)));
-#pragma unroll
-            for (int aq = 0; aq < 3; ++aq) {
-              t[3 * bq + aq] = -INFINITY;
-              if (aq < ux && bq < uy) t[3 * bq + aq] = load_u32_index(wm, ro + (unsigned)min(aq << L, max(pw - k, 0)));
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < 9; ++q) mneg = fmaxf(mneg, t[q]);
+        if (want_lower && ti.sure && !(ti.ub < -1.0f) && wm != nullptr && fv.has_lower && fw.nxw <= 3 && fw.nyw <= 3) {
+          float t[9];  // planes 2 / 3: of the negated image -- max of -g = -(min of g)
+          footprint_window_requests(wm, (unsigned)v.width, (L == 3 ? 3u : 2u) * (unsigned)fv.wmax_plane, tx0, ty0, fw, t);
+          const float mneg = footprint_window_max(t);
           const float neg_lb = __builtin_fmaf(fabsf(mneg), 0x1p-20f, mneg);  // -(lower bound); +inf: none
           if (neg_lb <= 1.0f) ti.sure |= 2;
           if (lower_out) *lower_out = -neg_lb;  // (the slab planner, plan_cost_kernel)
@@ -644,6 +692,28 @@ __device__ __forceinline__ FusedView load_fused_view(const FusedView* __restrict
   FusedView fv;
   __builtin_memcpy(&fv, raw, sizeof(FusedView));
   return fv;
+}
+
+// What lane `vi` needs of its view to bound the footprint of a kept record (kStateStaleBounds): the planes, the image
+// width, the ROI's last column and row, and the view's current max_sdf.  Per-lane loads; the caller pins them next to
+// its record's load so that they are one batch behind one wait.
+struct BoundView {
+  gfloat_ptr wmax;
+  unsigned wmax_plane, width;
+  int roi_max_xi, roi_max_yi;
+  float max_sdf;
+};
+__device__ __forceinline__ BoundView load_bound_view(const FusedView* __restrict__ views, int vi) {
+  // (a 32-bit byte offset from the uniform base, view_byte_offset: one vector offset instead of a 64-bit address)
+  typedef const char __attribute__((address_space(1))) * gchar_ptr;
+  typedef const FusedView __attribute__((address_space(1))) * gview_ptr;
+  const FusedView __attribute__((address_space(1)))& fv = *(gview_ptr)((gchar_ptr)views + view_byte_offset(vi));
+  BoundView b;
+  b.wmax = (gfloat_ptr)fv.wmax;
+  b.wmax_plane = (unsigned)fv.wmax_plane, b.width = (unsigned)fv.v.width;
+  b.roi_max_xi = fv.v.roi_max_xi, b.roi_max_yi = fv.v.roi_max_yi;
+  b.max_sdf = fv.v.max_sdf;
+  return b;
 }
 
 // (through an LDS-typed pointer: ds_write_b128, not flat stores)

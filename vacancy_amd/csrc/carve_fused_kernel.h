@@ -157,6 +157,15 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     return unpack_footprint_scalar((uint32_t)__builtin_amdgcn_readlane((int)rec_w0, p),
                                    (uint32_t)__builtin_amdgcn_readlane((int)rec_w1, p));
   };
+  // kRecRegs, kStateStaleBounds: the launch reuses an earlier launch's records -- same cameras, same slab -- and only the
+  // bound in word 0 is stale (it came from that launch's images).  Lane v then bounds the footprint of view v itself: the
+  // lookups footprint_of makes for the pre-pass (footprint_window_requests), in the prologue, where the sixteen state
+  // registers are not live yet and nothing of it stays.  On a fresh slab without truncation no bound is compared before
+  // the first run, so the first view is known -- view 0 -- and its tile is requested IN FRONT of the lookups: the two
+  // share a round trip, and the wait for the lookups is the wait for the tile that begin_view() would make next anyway.
+  // On any other slab the bounds are compared at once (the early-return test): the lookups are a round trip of their own.
+  const bool stale_bounds = kRecRegs && (state_flags & kStateStaleBounds) != 0;
+  int vi_stale = -1;  // the view whose tile that prologue has requested (what vi_pre, below, starts from)
   int cur = 0;  // raw tiles: which of the wave's buffers holds the view being carved
   auto raw_buf = [&](int b) -> float* { return (float*)tile + 256 * b; };
   // requests the raw tile of view / pair p into `buf`
@@ -334,6 +343,40 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
     }
     ti_one = unpack_footprint(rec);
     ub_lane = ti_one.ub;
+  } else if (kRecRegs && stale_bounds) {
+    // The records of an earlier launch with these cameras ("recordcache"): the lane keeps the geometry as it is and looks
+    // the bound up -- what footprint_of does for the pre-pass, through the same helpers, so the words it ends up with are
+    // the words the pre-pass would have written for this launch's images.
+    if constexpr (kRecRegs) {
+      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+      typedef const u32x2 __attribute__((address_space(1))) * grec_ptr;
+      ub_lane = INFINITY;
+      const bool has_view = lane < nviews;
+      const int lv = has_view ? lane : 0;  // (lanes without a view read view 0's record and keep "no tile, no bound")
+      // the record and the lane's view, requested together: one batch of loads behind one wait
+      // (32-bit byte offsets from the uniform bases: the records of a launch in one chunk are at most kRecordBytesMax)
+      typedef const char __attribute__((address_space(1))) * gchar_ptr;
+      static_assert(kRecordBytesMax <= ((int64_t)1 << 31), "the records' byte offset is formed in 32 bits");
+      u32x2 raw = *(grec_ptr)((gchar_ptr)records + (((uint32_t)lv * (uint32_t)nbricks + (uint32_t)brick_lin) << 3));
+      BoundView bv = load_bound_view(views, lv);
+      asm volatile("" : "+v"(raw.x), "+v"(raw.y), "+v"(bv.wmax), "+v"(bv.wmax_plane), "+v"(bv.width), "+v"(bv.roi_max_xi),
+                   "+v"(bv.roi_max_yi), "+v"(bv.max_sdf));
+      if (has_view) rec_w0 = footprint_ub_word(raw.x, raw.y), rec_w1 = footprint_tile_word(raw.x, raw.y);
+      if (fresh && !TRUNC) {  // (uniform) nothing compares a bound before the first run: the first view is view 0
+        vi_stale = 0;
+        prefetch_tile(0, raw_buf(0));
+      }
+      const int tw = (int)((raw.y >> 26) & 15u), th = (int)(raw.x & 15u);
+      if (has_view && tw != 0) {  // (a record without a tile has no bound: footprint_ub_word)
+        const int tx0 = (int)(raw.y & 8191u), ty0 = (int)((raw.y >> 13) & 8191u);
+        const FootprintWindows fw = footprint_windows(tx0, ty0, tx0 + tw - 1, ty0 + th - 1, bv.roi_max_xi, bv.roi_max_yi);
+        float t[9];
+        footprint_window_requests<false>(bv.wmax, bv.width, fw.L == 3 ? bv.wmax_plane : 0u, tx0, ty0, fw, t);
+        const float ub = footprint_upper_bound(footprint_window_max(t), 0, mode.outside == VCY_OUTSIDE_MAX,
+                                               ((raw.y >> 30) & 1u) != 0u, bv.max_sdf);
+        rec_w0 = pack_footprint_ub(ub) | (raw.x & 63u);
+      }
+    }  // (if constexpr: nothing of this is instantiated in the other instances)
   } else if (kRaw && records != nullptr) {
     // raw tiles: the footprints come from the pre-pass (footprint_records_kernel), 8 bytes per view (kRecRegs: and stay
     // as they are in the lane that loaded them)
@@ -451,7 +494,8 @@ __attribute__((amdgpu_waves_per_eu(NB > 1 ? 1 : carve_waves_per_simd<UPDATE, CHE
   // looked at: one memory round trip less in a wave's chain, which is most of what a launch of ONE view consists of.
   // (kMax without valid minima: not known, vi_pre stays -1.  live_views() below decides as before; the request is
   // repeated there if it names another view -- it never does -- and loads complete in order, so the later one wins.)
-  int vi_pre = -1;
+  // (a launch that reuses its records has requested view 0's tile in its prologue on a fresh slab: vi_stale)
+  int vi_pre = kRecRegs ? vi_stale : -1;
   auto prefetch_first_tile = [&]() {
     if constexpr (kRaw) {
       const bool listed_live = kOne && list_entry != nullptr;  // (the list pass has decided: the one view is live)

@@ -52,6 +52,8 @@ constexpr int kStateCoopStore = 8;      // cooperative write-back: whole row seg
 constexpr int kStateStreamStore = 16;   // ... with streaming stores ("ntstore")
 constexpr int kStateEager = 32;         // one-view launch: the state is requested next to the footprint record ("eagerstate")
 constexpr int kStateListRecords = 64;   // one-view launch: the entries of wg_list carry the bricks' records (kLiveEntryWords)
+constexpr int kStateStaleBounds = 128;  // the records are an earlier launch's ("recordcache"): their geometry holds, the bounds
+                                        // in them do not -- the kernel's prologue looks them up (fused_reuses_records)
 
 // Which structure of carve_fused_kernel a launch takes (its template parameter NB: 1, 0, kRowBricks).
 enum class CarveFlavour {
@@ -76,6 +78,7 @@ struct FusedKnobs {
   bool use_cull = true;          // "cull" 0: never drop provably idle views
   bool count_pairs = false;      // "paircount" 1: the fused kernel counts the (brick, view) pairs it processes
   bool use_short_div = true;     // "shortdiv" 0: always the full division sequence
+  bool record_cache = true;      // "recordcache" 0: every launch makes its footprint records anew (fused_reuses_records)
 };
 
 // What the decisions read.  (fx == fy in every view is no decision: it selects a template argument and comes from
@@ -288,6 +291,31 @@ inline FusedChunkLaunch finish_fused_chunk(const FusedLaunchPlan& p, const Fused
   f.state_flags = p.state_flags_base | (f.eager_state ? kStateEager : 0) |
                   (c.listed && c.list_entry_words ? kStateListRecords : 0);
   return f;
+}
+
+// ---- footprint records kept across launches ("recordcache") ------------------------------------------------------------
+// A footprint record is geometry -- the tile's origin and size, the edge bits, `sure` -- and one bound.  The geometry
+// depends on the cameras, the grid and the slab; only the bound depends on the images.  The cameras of a capture rig are
+// calibrated once, so a context that carves the same rig again finds the geometry of its last launch still in its record
+// buffer, and the carve kernel's prologue can look the bounds up itself (kStateStaleBounds): nothing is left of the
+// pre-pass.  That holds for the launches whose kernel instance has such a prologue and whose records are what the last
+// launch left; every other launch runs the pre-pass as it always did.
+//
+// fused_records_cacheable: the launch is of the kind that may reuse records -- and, when it does not (the key of the
+// buffer's contents differs), of the kind whose records a later launch may reuse.  `have_planes`: the window planes of
+// this launch exist.  `c`: the plan of the launch's first chunk (one-chunk launches only, so: of the launch).
+inline bool fused_records_cacheable(const FusedLaunchPlan& p, const FusedPlanInput& in, const FusedChunkPlan& c,
+                                    bool have_planes) {
+  // the instance keeps its records in registers (carve_keeps_records, carve_fused_kernel.h): kMax, raw tiles, a brick per wave
+  const bool keeps_records = p.update == VCY_UPDATE_MAX && !p.big && p.flavour == CarveFlavour::kGeneral;
+  return in.knobs.record_cache && keeps_records && p.need_bound && !p.want_lower &&
+         p.records /* not the kernel's own prologue, "prologue" 1 */ && p.chunk_layers >= p.nbz && have_planes &&
+         !c.listed /* the list pass reads the bounds from the records */;
+}
+// `key_matches`: the record buffer holds what a launch with this one's cameras, slab and buffer left (FusedRecordKey).
+inline bool fused_reuses_records(const FusedLaunchPlan& p, const FusedPlanInput& in, const FusedChunkPlan& c,
+                                 bool have_planes, bool key_matches) {
+  return fused_records_cacheable(p, in, c, have_planes) && key_matches;
 }
 
 // ---- the rectangle the window planes of a view are built in -----------------------------------------------------------

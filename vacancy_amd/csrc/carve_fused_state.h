@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "carve_fused_plan.h"  // FusedKnobs
@@ -39,6 +40,23 @@ struct FusedViewCache {
   void remember(const FusedViewKey& k, const void* vp_now, size_t vp_bytes, bool samef_now, int max_quads_now);
 };
 
+// Which launch the record buffer (FusedState::d_records) describes ("recordcache", fused_reuses_records in
+// carve_fused_plan.h).  The key is everything the GEOMETRY of a footprint record depends on, as bytes (record_key in
+// carve_fused.hip builds it): the view count; of every view the rotation, translation, fx, fy, cx, cy, width, height and
+// the ROI -- not the image pointer, not max_sdf, not the plane addresses, which only the bound depends on; fx == fy in
+// every view, the generic sampler, the projection model and the outside mode; the slab and its bricks; the buffer's
+// address and size (a regrown buffer is another buffer).  Whatever writes the buffer forgets the key first and remembers
+// its own afterwards, if it is of the kind a later launch may reuse (write_records, the one place).  vcy_reset does not
+// touch it: the records do not depend on the voxel state.
+struct FusedRecordCache {
+  bool valid = false;
+  std::vector<char> key;
+  int hits = 0;  // launches that reused the records (vcy_get_param "recordcache_hits")
+  bool matches(const std::vector<char>& k) const { return valid && key == k; }
+  void remember(std::vector<char>&& k) { key = std::move(k), valid = true; }
+  void forget() { valid = false; }
+};
+
 // The view blocks of a launch with new views are built in page-locked host memory -- two buffers taken in turn, each
 // with an event that says when the copy out of it has been made -- so that such a launch queues behind the previous
 // one like any other work on the stream.
@@ -57,6 +75,7 @@ struct FusedState {
   DeviceBuf<> d_scratch;       // c0 records + view blocks of one launch (prepare_views)
   DeviceBuf<float> d_wmax;     // window-maximum planes of the views of one launch
   DeviceBuf<> d_records;       // footprint records of one chunk, 8 bytes per (wave brick, view)
+  FusedRecordCache rec_cache;  // ... and which launch they describe
   DeviceBuf<int> d_wg_list;    // live workgroups of a chunk of few views ([0] = count), live_workgroups_kernel
   PinnedBuf<int> h_live_hint;  // page-locked {live workgroups, workgroups} of the last listed chunk (a hint: plan_fused_chunk)
   int64_t live_list_age = 0;   // chunks launched so far

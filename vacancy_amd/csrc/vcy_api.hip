@@ -298,6 +298,10 @@ int vcy_set_param(vcy_ctx* c, const char* name, int value) {
     c->fused.knobs.live_sync = value != 0;
     return VCY_OK;
   }
+  if (std::strcmp(name, "recordcache") == 0) {
+    c->fused.knobs.record_cache = value != 0;
+    return VCY_OK;
+  }
   if (std::strcmp(name, "coopstore") == 0) {
     c->fused.knobs.coop_store = value < 0 ? -1 : (value != 0 ? 1 : 0);
     return VCY_OK;
@@ -380,6 +384,8 @@ int vcy_get_param(vcy_ctx* c, const char* name, int* value) {
   else if (std::strcmp(name, "prologue") == 0) *value = c->fused.knobs.prologue_mode;
   else if (std::strcmp(name, "coopstore") == 0) *value = c->fused.knobs.coop_store;
   else if (std::strcmp(name, "livesync") == 0) *value = c->fused.knobs.live_sync ? 1 : 0;
+  else if (std::strcmp(name, "recordcache") == 0) *value = c->fused.knobs.record_cache ? 1 : 0;
+  else if (std::strcmp(name, "recordcache_hits") == 0) *value = c->fused.rec_cache.hits;
   else if (std::strcmp(name, "brick_min_valid") == 0) *value = c->st.brick_min_valid && !c->st.fresh ? 1 : 0;
   else if (std::strcmp(name, "fresh") == 0) *value = c->st.fresh ? 1 : 0;  // the fill has not been written yet
   else if (std::strcmp(name, "meshkeys") == 0) *value = c->mesh_keys ? 1 : 0;
