@@ -491,7 +491,8 @@ int  vcy_last_components_ms(const vcy_ctx* ctx, float* device_ms);
  *      slab below: (label below, label above) for the pieces that touch across the seam;
  *   3. vcy_merge_components_host (no GPU): the merged list and, per slab, the global label of every piece;
  *   4. vcy_resolve_components_slab on every slab installs its map: vcy_download_labels then returns merged labels;
- *   5. for the filter, vcy_keep_components_slab on every slab with the pieces that go.
+ *   5. for the filter, vcy_select_components_host (no GPU) says which pieces go, and vcy_keep_components_slab on every slab
+ *      takes its own.
  * Steps 2, 4 and 5 speak about the state step 1 labelled: after a carve, vcy_upload or vcy_reset they return
  * VCY_ERR_INVALID_ARG until the slab is labelled again.  A slab's halo below an upper slab is stale after step 5, as
  * after a carve, and the library enforces it in the same way: every successful vcy_keep_components_slab on an upper
@@ -533,12 +534,23 @@ int  vcy_resolve_components_slab(vcy_ctx* ctx, int64_t n, const int64_t* provisi
 /* The filter of vcy_keep_components on a slab: every voxel of the listed pieces (provisional labels of step 1) gets
  * sdf = fill_sdf, in place, over the slab's own 8 x 8 x 8 bricks; update_num and every other byte of the state stay;
  * valid brick minima are reduced again in the bricks that changed and only there.  Which pieces go is the caller's
- * decision on the MERGED list (the rule of vcy_keep_components).  fill_sdf: finite and not below the iso level of step
+ * decision on the MERGED list (vcy_select_components_host).  fill_sdf: finite and not below the iso level of step
  * 1, VCY_ERR_INVALID_ARG otherwise, as for a label the slab did not report or a slab that has not been labelled --
  * state untouched in every such case.  vcy_download_labels afterwards: the labels from before the removal; a second
  * filter needs a new labelling.  removed_voxels may be NULL.  vcy_last_components_ms: the filter's device time. */
 int  vcy_keep_components_slab(vcy_ctx* ctx, float fill_sdf, int64_t n_remove, const int64_t* remove_provisional_labels,
                               int64_t* removed_voxels);
+/* The rule of vcy_keep_components, host arithmetic only (no GPU, no context): of `components`, a list in the order of
+ * vcy_label_components, entry i stays iff (keep_largest <= 0 or i < keep_largest) and n_voxels >= min_voxels.
+ * removed[i] = 1 where it goes, 0 where it stays (caller-allocated, n_components entries); removed_components /
+ * removed_voxels (either may be NULL): what went.  With the global_labels of vcy_merge_components_host as
+ * piece_global_labels (n_pieces entries, the slabs' pieces one behind the other), piece_removed[k] = 1 iff piece k belongs
+ * to a component that goes: slab s then hands vcy_keep_components_slab the provisional labels of its flagged pieces.
+ * Callers without pieces pass NULL, 0, NULL.  fill_sdf is not this call's business: every filter checks it before
+ * anything is labelled.  VCY_ERR_INVALID_ARG for a negative count or a NULL array with a positive one. */
+int  vcy_select_components_host(const vcy_component* components, int64_t n_components, int keep_largest, int64_t min_voxels,
+                                uint8_t* removed, int64_t* removed_components, int64_t* removed_voxels,
+                                const int64_t* piece_global_labels, int64_t n_pieces, uint8_t* piece_removed);
 
 /* ---- distance field of the hull ------------------------------------------- */
 
@@ -590,18 +602,23 @@ int vcy_redistance(vcy_ctx* ctx, double iso_level, int radius, int64_t* n_rewrit
 int vcy_distance_field_host(const vcy_carver_option* option, const float* sdf, const int32_t* update_num, double iso_level,
                             int radius, int32_t* d2, float* sdf_out);
 /* Device milliseconds between HIP events around the launches (solid bits, the three passes) of the last
- * vcy_distance_field (its copy to the host not included) or vcy_redistance on this context; 0 when nothing was launched.
- *
- * Closing the hull (VoxelCarver::CloseHull, vacancy_amd.carver.VoxelCarver.CloseHull; a composition, written once per
- * language): with r = radius_voxels * resolution and R = ceil(radius_voxels) + 2,
+ * vcy_distance_field (its copy to the host not included) or vcy_redistance on this context; 0 when nothing was launched. */
+int vcy_last_distance_ms(const vcy_ctx* ctx, float* device_ms);
+/* Closing the hull (VoxelCarver::CloseHull, vacancy_amd.carver.VoxelCarver.CloseHull and their z-slab forms): three
+ * steps composed by the front end, on the plan of vcy_close_hull_plan.  With r = radius_voxels * resolution and
+ * R = ceil(radius_voxels) + 2,
  *   vcy_redistance(iso_level, R), vcy_redistance(r, R), vcy_redistance(-r, R)
  * -- the metric field, the field of the hull grown by r, the field of that shrunk by r again: the state ends as the
  * metric field of the closed hull with its surface at iso 0.  Tie rule: a voxel is dilated when phi < r, that is
  * sqrt(d2) < radius_voxels + 0.5.  When (radius_voxels + 0.5)^2 is an integer that is a sum of three squares, voxels sit
  * exactly on both thresholds and `<` sends the growing and the shrinking step the same way: the closing is then no
  * longer extensive (with 1.5 voxels, two 5^3 blocks two voxels apart shrink from 250 solid voxels to 90; with 1.3 exactly
- * the 50 gap voxels are filled).  The wrappers refuse such radii; pick 1.3, 2.3, ... */
-int vcy_last_distance_ms(const vcy_ctx* ctx, float* device_ms);
+ * the 50 gap voxels are filled).  Such radii are refused; pick 1.3, 2.3, ...
+ * vcy_close_hull_plan (host arithmetic only: no GPU, no context): *r and *big_r = R for 0 < radius_voxels with R <= 127;
+ * VCY_ERR_INVALID_ARG, with the reason and a radius to pick instead in vcy_last_error, outside that range and for a
+ * radius that ties ((radius_voxels + 0.5)^2 within 1e-9 of such an integer).  radius_voxels is a double: a float
+ * argument is passed widened, and decides as it did as a float. */
+int vcy_close_hull_plan(double radius_voxels, float resolution, double* r, int* big_r);
 
 /* The same field for a grid cut into z-slabs.  The x pass and the y pass never leave an xy slice; only the z pass looks
  * across a seam, R slices deep, and what it needs from there is the y pass's output
@@ -610,7 +627,7 @@ int vcy_last_distance_ms(const vcy_ctx* ctx, float* device_ms);
  *   1. vcy_distance_slab_begin on every slab;
  *   2. vcy_distance_slab_planes: every slab hands out its lowest and its highest min(R, own slices) planes; the host puts
  *      together, for slab [z0, z1), the planes of the global slices [z0 - min(R, z0), z0) and [z1, z1 + min(R, nz - z1)),
- *      from as many neighbours as that takes (vacancy_amd.dist.distance_halos, ShardedVoxelCarver);
+ *      from as many neighbours as that takes (vcy_distance_halo_host);
  *   3. vcy_distance_field_slab or vcy_redistance_slab on every slab.
  * With exactly those planes at the ends of the slab's columns the z pass's bounds are the whole grid's own for every
  * step <= R: the results equal vcy_distance_field / vcy_redistance of one context for the slab's slices, bit for bit.
@@ -650,6 +667,18 @@ int vcy_distance_slab_planes_host(const vcy_carver_option* option, int z_begin, 
 int vcy_distance_slab_finish_host(const vcy_carver_option* option, int z_begin, int z_end, const uint16_t* h,
                                   const uint16_t* below, int n_below, const uint16_t* above, int n_above, int radius,
                                   const int32_t* update_num_slab, const float* sdf_slab, int32_t* d2, float* sdf_out);
+/* Step 2's assembly, host copies only (no GPU, no context).  The grid's n_slabs slabs are [z_bounds[s], z_bounds[s + 1]),
+ * n_slabs + 1 bounds ascending from 0; bottoms[s] / tops[s]: the lowest / highest min(radius, own slices) planes of slab s,
+ * plane_voxels = nx*ny uint16 each, in ascending z.  For slab `slab` = [z0, z1): *n_below = min(radius, z0) and
+ * *n_above = min(radius, nz - z1), and the planes of the global slices [z0 - *n_below, z0) to `below`, [z1, z1 + *n_above)
+ * to `above` (caller-allocated; NULL allowed where the count is 0), from as many neighbours as that takes -- a slab thinner
+ * than the radius passes its neighbours' planes on.  Edge planes nobody reads may be NULL: the bottom of slab 0, the top of
+ * the last slab, and for one `slab` everything out of its reach.  VCY_ERR_INVALID_ARG for bounds that do not ascend from 0,
+ * a slab index out of range, a needed edge pointer that is NULL (the buffers then hold nothing to rely on), a radius outside
+ * [1, 127] or plane_voxels < 1. */
+int vcy_distance_halo_host(int n_slabs, const int32_t* z_bounds, int radius, int64_t plane_voxels,
+                           const uint16_t* const* bottoms, const uint16_t* const* tops, int slab, uint16_t* below,
+                           uint16_t* above, int* n_below, int* n_above);
 
 /* ---- ray-cast of the hull into a view ------------------------------------- */
 

@@ -246,10 +246,13 @@ def load():
         "vcy_merge_components_host": (C.c_int, [C.c_int, vp, vp, vp, vp, P(P(Component)), P(C.c_int64), vp]),
         "vcy_resolve_components_slab": (C.c_int, [vp, C.c_int64, vp, vp]),
         "vcy_keep_components_slab": (C.c_int, [vp, C.c_float, C.c_int64, vp, P(C.c_int64)]),
+        "vcy_select_components_host": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int64, vp, P(C.c_int64), P(C.c_int64), vp,
+                                                 C.c_int64, vp]),
         "vcy_distance_field": (C.c_int, [vp, C.c_double, C.c_int, vp]),
         "vcy_redistance": (C.c_int, [vp, C.c_double, C.c_int, P(C.c_int64)]),
         "vcy_distance_field_host": (C.c_int, [P(CarverOption), vp, vp, C.c_double, C.c_int, vp, vp]),
         "vcy_last_distance_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_close_hull_plan": (C.c_int, [C.c_double, C.c_float, P(C.c_double), P(C.c_int)]),
         "vcy_distance_slab_begin": (C.c_int, [vp, C.c_double, C.c_int]),
         "vcy_distance_slab_planes": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "vcy_distance_field_slab": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
@@ -257,6 +260,8 @@ def load():
         "vcy_distance_slab_planes_host": (C.c_int, [P(CarverOption), C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, vp]),
         "vcy_distance_slab_finish_host": (C.c_int, [P(CarverOption), C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int,
                                                     vp, vp, vp, vp]),
+        "vcy_distance_halo_host": (C.c_int, [C.c_int, vp, C.c_int, C.c_int64, P(vp), P(vp), C.c_int, vp, vp, P(C.c_int),
+                                             P(C.c_int)]),
         "vcy_cell_planes": (C.c_int, [P(C.c_float), P(C.c_float), C.c_float, C.c_int, vp]),
         "vcy_render_hull": (C.c_int, [vp, C.c_double, C.c_int, P(View), P(vp), P(vp), P(vp)]),
         "vcy_hull_agreement": (C.c_int, [vp, C.c_double, C.c_int, P(View), P(vp), vp]),

@@ -371,24 +371,13 @@ def distance_slab_finish_host(option, z_range, h, below, above, radius, sdf, upd
 
 
 def close_hull_plan(radius_voxels, resolution):
-    """(r, R) of CloseHull: r = radius_voxels * resolution in world units and the transform's radius
-    R = ceil(radius_voxels) + 2.  ValueError when (radius_voxels + 0.5)^2 is an integer that is a sum of three squares:
-    voxels then sit exactly on the thresholds of the growing and of the shrinking step, `<` sends both the same way and the
-    closing is not extensive (include/vacancy_hip.h, the tie rule) -- pick 1.3, 2.3, ..."""
-    rv = float(radius_voxels)
-    big_r = int(np.ceil(rv)) + 2
-    if not rv > 0.0 or big_r > 127:
-        raise ValueError("CloseHull: radius_voxels = %g must be positive and at most 125" % rv)
-    t = (rv + 0.5) ** 2
-    n = int(round(t))
-    if abs(t - n) <= 1e-9 * t:
-        m = n
-        while m % 4 == 0:
-            m //= 4
-        if m % 8 != 7:  # Legendre: n is a sum of three squares
-            raise ValueError("CloseHull: radius_voxels = %g ties: (radius + 0.5)^2 = %d is a squared voxel distance, and the "
-                             "growing and the shrinking step would treat it alike; pick e.g. %g" % (rv, n, rv - 0.2))
-    return rv * float(resolution), big_r
+    """(r, R) of CloseHull by vcy_close_hull_plan (no GPU): r = radius_voxels * resolution in world units and the
+    transform's radius R = ceil(radius_voxels) + 2.  ValueError, with the library's text, for a radius out of range or one
+    on which the closing ties (include/vacancy_hip.h, the tie rule) -- pick 1.3, 2.3, ..."""
+    r, big_r = C.c_double(0.0), C.c_int(0)
+    if capi.load().vcy_close_hull_plan(float(radius_voxels), float(resolution), C.byref(r), C.byref(big_r)) != 0:
+        raise ValueError(last_error())
+    return r.value, big_r.value
 
 
 class VoxelCarver:

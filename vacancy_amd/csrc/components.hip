@@ -39,6 +39,7 @@
 #include <cstring>
 #include <vector>
 
+#include "slab_rules.h"
 #include "vcy_internal.h"
 
 namespace vcy {
@@ -667,18 +668,13 @@ int vcy_keep_components(vcy_ctx* c, double iso_level, int keep_largest, int64_t 
   std::vector<int> slot;
   { const int rc = label_components(c, iso_level, &comps, &slot); if (rc != VCY_OK) return rc; }
   const size_t nc = comps.size();
-  std::vector<uint8_t> removed(nc, 0);
+  std::vector<uint8_t> gone(nc), removed(nc, 0);  // by rank in the list, by the filter's slot
   int64_t rc_n = 0, rv_n = 0;
+  slab::select_components(comps.data(), (int64_t)nc, keep_largest, min_voxels, gone.data(), &rc_n, &rv_n);
   int keep0 = -1;
   for (size_t i = 0; i < nc; ++i) {
-    const bool keep = (keep_largest <= 0 || (int64_t)i < (int64_t)keep_largest) && comps[i].n_voxels >= min_voxels;
-    if (keep) {
-      if (keep0 < 0) keep0 = (int)comps[i].label;
-      continue;
-    }
-    removed[(size_t)slot[i]] = 1;
-    ++rc_n;
-    rv_n += comps[i].n_voxels;
+    if (gone[i]) removed[(size_t)slot[i]] = 1;
+    else if (keep0 < 0) keep0 = (int)comps[i].label;
   }
   if (rc_n > 0) {
     const int rc = launch_filter(c, removed, keep0, fill_sdf);
@@ -1008,6 +1004,24 @@ int vcy_merge_components_host(int n_slabs, const vcy_component* lists, const int
   std::memcpy(p, merged.data(), sizeof(vcy_component) * merged.size());
   *merged_out = p;
   *n_merged_out = (int64_t)merged.size();
+  return VCY_OK;
+}
+
+int vcy_select_components_host(const vcy_component* components, int64_t n_components, int keep_largest, int64_t min_voxels,
+                               uint8_t* removed, int64_t* removed_components, int64_t* removed_voxels,
+                               const int64_t* piece_global_labels, int64_t n_pieces, uint8_t* piece_removed) {
+  if (removed_components) *removed_components = 0;
+  if (removed_voxels) *removed_voxels = 0;
+  if (n_components < 0 || n_pieces < 0 || (n_components > 0 && (!components || !removed)) ||
+      (n_pieces > 0 && (!piece_global_labels || !piece_removed))) {
+    set_error("vcy_select_components_host: invalid argument");
+    return VCY_ERR_INVALID_ARG;
+  }
+  int64_t rc_n = 0, rv_n = 0;
+  slab::select_components(components, n_components, keep_largest, min_voxels, removed, &rc_n, &rv_n);
+  slab::select_pieces(components, n_components, removed, piece_global_labels, n_pieces, piece_removed);
+  if (removed_components) *removed_components = rc_n;
+  if (removed_voxels) *removed_voxels = rv_n;
   return VCY_OK;
 }
 

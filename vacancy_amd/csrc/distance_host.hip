@@ -14,6 +14,7 @@
 
 #include "distance_field.h"
 #include "host_shared.h"
+#include "slab_rules.h"
 
 using namespace vcy;
 
@@ -168,4 +169,45 @@ extern "C" int vcy_distance_slab_finish_host(const vcy_carver_option* option, in
   finish_of((int64_t)dims[0] * dims[1], z_end - z_begin, h, below, n_below, above, n_above, radius, option->resolution,
             update_num_slab, sdf_slab, d2, sdf_out);
   return VCY_OK;
+}
+
+/* ---- the host rules of the slabs' front ends (slab_rules.h) ----------------------------------------------------------- */
+
+extern "C" int vcy_close_hull_plan(double radius_voxels, float resolution, double* r, int* big_r) {
+  if (!r || !big_r) {
+    set_error("vcy_close_hull_plan: null pointer");
+    return VCY_ERR_INVALID_ARG;
+  }
+  long long square = 0;
+  switch (slab::close_hull_plan(radius_voxels, resolution, r, big_r, &square)) {
+    case slab::kCloseOk: return VCY_OK;
+    case slab::kCloseOutOfRange:
+      set_error("CloseHull: radius_voxels = %g must be positive and at most 125", radius_voxels);
+      break;
+    case slab::kCloseTies:
+      set_error("CloseHull: radius_voxels = %g ties: (radius + 0.5)^2 = %lld is a squared voxel distance, and the growing "
+                "and the shrinking step would treat it alike; pick e.g. %g",
+                radius_voxels, square, radius_voxels - 0.2);
+      break;
+  }
+  return VCY_ERR_INVALID_ARG;
+}
+
+extern "C" int vcy_distance_halo_host(int n_slabs, const int32_t* z_bounds, int radius, int64_t plane_voxels,
+                                      const uint16_t* const* bottoms, const uint16_t* const* tops, int slab, uint16_t* below,
+                                      uint16_t* above, int* n_below, int* n_above) {
+  const char* who = "vcy_distance_halo_host";
+  { const int rc = df::check_radius(who, radius); if (rc != VCY_OK) return rc; }
+  switch (plane_voxels < 1 ? slab::kHaloBadArgument
+                           : slab::distance_halo(n_slabs, z_bounds, radius, (size_t)plane_voxels, bottoms, tops, slab, below,
+                                                 above, n_below, n_above)) {
+    case slab::kHaloOk: return VCY_OK;
+    case slab::kHaloBadArgument: set_error("%s: invalid argument", who); break;
+    case slab::kHaloBadBounds: set_error("%s: the z bounds of the %d slabs do not ascend from 0", who, n_slabs); break;
+    case slab::kHaloBadSlab: set_error("%s: slab %d of %d", who, slab, n_slabs); break;
+    case slab::kHaloMissingEdge:
+      set_error("%s: slab %d needs the edge planes of a neighbour whose pointer is null", who, slab);
+      break;
+  }
+  return VCY_ERR_INVALID_ARG;
 }

@@ -347,30 +347,45 @@ def label_components_slabs(carvers, rank=0, world=1, iso_level=0.0, each=_each):
     return {"merged": merged, "lists": lists, "maps": maps, "device_ms": float(sum(ms))}
 
 
+def select_components(merged, largest, min_voxels, maps=()):
+    """vcy_select_components_host (no GPU), the keep rule of vcy_keep_components: `merged` a list as LabelComponents returns
+    it, `maps` per slab the merged label of each of its pieces (merge_components).  Returns (bool per component: it goes,
+    [bool per piece of slab s: it goes], removed components, removed voxels)."""
+    from . import capi, carver as _vc
+    flat = np.zeros(len(merged["label"]), _vc._COMPONENT_REC)
+    for key in flat.dtype.names:
+        flat[key] = merged[key]
+    glob = np.ascontiguousarray(np.concatenate([np.zeros(0, np.int64)] + list(maps)), np.int64)
+    gone, pieces = np.zeros(len(flat), np.uint8), np.zeros(len(glob), np.uint8)
+    nc, nv = C.c_int64(0), C.c_int64(0)
+    rc = capi.load().vcy_select_components_host(_vc._p(flat), len(flat), int(largest), int(min_voxels), _vc._p(gone),
+                                                C.byref(nc), C.byref(nv), _vc._p(glob), len(glob), _vc._p(pieces))
+    if rc != 0:
+        _vc._raise_rc(rc)
+    ends = np.cumsum([len(m) for m in maps], dtype=np.int64)
+    return gone != 0, [pieces[e - len(m):e] != 0 for e, m in zip(ends, maps)], nc.value, nv.value
+
+
 def keep_components_slabs(carvers, rank=0, world=1, iso_level=0.0, largest=1, min_voxels=0, fill_sdf=1.0, each=_each):
-    """KeepComponents of a grid cut into z-slabs: label_components_slabs, the rule of vcy_keep_components on the merged
-    list (a component stays iff (largest <= 0 or its rank is below largest) and n_voxels >= min_voxels), then every
-    slab's own filter kernel over the pieces that go.  A slab's halo below an upper slab is stale afterwards, as after a
-    carve: every extraction path here exchanges halos first.  Returns {"removed_components", "removed_voxels" (of the
-    whole grid), "device_ms" (labelling, seams and filter, summed over this rank's slabs)}."""
+    """KeepComponents of a grid cut into z-slabs: label_components_slabs, the library's keep rule on the merged list
+    (vcy_select_components_host, through select_components), then every slab's own filter kernel over its pieces that go.
+    A slab's halo below an upper slab is stale afterwards, as after a carve: every extraction path here exchanges halos
+    first.  Returns {"removed_components", "removed_voxels" (of the whole grid), "device_ms" (labelling, seams and filter,
+    summed over this rank's slabs)}."""
     import math
     if not math.isfinite(fill_sdf) or not float(np.float32(fill_sdf)) >= float(iso_level):
         raise RuntimeError("keep_components_slabs: fill_sdf %g must be finite and not below the iso level %g"
                            % (fill_sdf, iso_level))
     r = label_components_slabs(carvers, rank, world, iso_level, each)
-    merged = r["merged"]
-    n = len(merged["label"])
-    keep = (np.ones(n, bool) if largest <= 0 else np.arange(n) < largest) & (merged["n_voxels"] >= min_voxels)
-    gone = merged["label"][~keep]
+    _, pieces, n_gone, gone_voxels = select_components(r["merged"], largest, min_voxels, r["maps"])
     ids = [rank + i * world for i in range(len(carvers))]
 
     def drop(i, c):
-        mine = r["lists"][ids[i]]["label"][np.isin(r["maps"][ids[i]], gone)]
-        return c.KeepComponentsSlab(mine, fill_sdf)["device_ms"] if len(gone) else 0.0
+        mine = r["lists"][ids[i]]["label"][pieces[ids[i]]]
+        return c.KeepComponentsSlab(mine, fill_sdf)["device_ms"] if n_gone else 0.0
 
     ms = each(carvers, drop)
-    return {"removed_components": int((~keep).sum()), "removed_voxels": int(merged["n_voxels"][~keep].sum()),
-            "device_ms": r["device_ms"] + float(sum(ms))}
+    return {"removed_components": n_gone, "removed_voxels": gone_voxels, "device_ms": r["device_ms"] + float(sum(ms))}
 
 
 # ---- ray-cast of the hull of a grid in z-slabs (the slab image and the merge rule: include/vacancy_hip.h) -----------
@@ -444,28 +459,26 @@ def hull_agreement_slabs(carvers, rank=0, world=1, views=(), masks=(), iso_level
 # ---- distance field of the hull of a grid in z-slabs (the order of the calls: include/vacancy_hip.h) ------------------
 
 def distance_halos(z_ranges, radius, bottoms, tops):
-    """The pure assembly of the seam planes.  `z_ranges`: [(z0, z1)] of every slab of the grid in z order; bottoms[s] /
-    tops[s]: the lowest / highest min(radius, z1 - z0) planes of slab s, uint16 [planes, nx * ny] in ascending z (None
-    where nobody needs them: the bottom of the first slab, the top of the last).  Returns [(below, above)] per slab: the
-    planes of the global slices [z0 - min(radius, z0), z0) and [z1, z1 + min(radius, nz - z1)), from as many neighbours
-    as that takes -- a slab thinner than `radius` passes its neighbours' planes on --, None where there are none."""
-    nz = z_ranges[-1][1]
+    """The assembly of the seam planes, by vcy_distance_halo_host (no GPU) once per slab.  `z_ranges`: [(z0, z1)] of every
+    slab of the grid in z order; bottoms[s] / tops[s]: the lowest / highest min(radius, z1 - z0) planes of slab s, uint16
+    [planes, nx * ny] in ascending z (None where nobody needs them: the bottom of the first slab, the top of the last).
+    Returns [(below, above)] per slab: the planes of the global slices [z0 - min(radius, z0), z0) and
+    [z1, z1 + min(radius, nz - z1)), from as many neighbours as that takes, None where there are none."""
+    from . import capi, carver as _vc
+    ns, nz = len(z_ranges), z_ranges[-1][1]
+    edges = [[None if p is None else np.ascontiguousarray(p, np.uint16) for p in side] for side in (bottoms, tops)]
+    sl = max([p.shape[-1] for side in edges for p in side if p is not None], default=1)
+    ptrs = [(C.c_void_p * ns)(*[None if p is None else p.ctypes.data for p in side]) for side in edges]
+    bounds = np.array([0] + [z1 for _, z1 in z_ranges], np.int32)
     out = []
-    for i, (z0, z1) in enumerate(z_ranges):
-        lo, hi = z0 - min(radius, z0), z1 + min(radius, nz - z1)
-        below, above = [], []
-        for j in range(i - 1, -1, -1):  # downwards, until slice `lo` is covered
-            a0, a1 = z_ranges[j]
-            if a1 <= lo:
-                break
-            m = a1 - max(a0, lo)
-            below.insert(0, tops[j][len(tops[j]) - m:])
-        for j in range(i + 1, len(z_ranges)):
-            a0, a1 = z_ranges[j]
-            if a0 >= hi:
-                break
-            above.append(bottoms[j][:min(a1, hi) - a0])
-        out.append((np.concatenate(below) if below else None, np.concatenate(above) if above else None))
+    for s in range(ns):
+        below, above = np.empty((min(radius, nz), sl), np.uint16), np.empty((min(radius, nz), sl), np.uint16)
+        nb, na = C.c_int(0), C.c_int(0)
+        rc = capi.load().vcy_distance_halo_host(ns, _vc._p(bounds), int(radius), sl, ptrs[0], ptrs[1], s, _vc._p(below),
+                                                _vc._p(above), C.byref(nb), C.byref(na))
+        if rc != 0:
+            _vc._raise_rc(rc)
+        out.append((below[:nb.value] if nb.value else None, above[:na.value] if na.value else None))
     return out
 
 
@@ -526,8 +539,8 @@ def redistance_slabs(carvers, rank=0, world=1, iso_level=0.0, radius=8, each=_ea
 
 def close_hull_slabs(carvers, rank=0, world=1, iso_level=0.0, radius_voxels=1.3, each=_each):
     """CloseHull of a grid cut into z-slabs: the three steps of VoxelCarver.CloseHull, each a redistance_slabs, with the
-    plan and the tie rule of vacancy_amd.carver.close_hull_plan (ValueError, state untouched, for a radius on which the
-    closing ties).  Returns the three redistance_slabs dicts."""
+    plan and the tie rule of vcy_close_hull_plan through vacancy_amd.carver.close_hull_plan (ValueError, state untouched,
+    for a radius on which the closing ties).  Returns the three redistance_slabs dicts."""
     from . import carver as _vc
     r, big_r = _vc.close_hull_plan(radius_voxels, carvers[0].option.resolution)
     return [redistance_slabs(carvers, rank, world, level, big_r, each) for level in (iso_level, r, -r)]

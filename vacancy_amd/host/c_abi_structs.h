@@ -2,9 +2,7 @@
 // ROI as a vcy_view, a VoxelCarverOption as a vcy_carver_option.  One statement for VoxelCarver and ShardedVoxelCarver.
 #pragma once
 
-#include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <string>
 
@@ -69,35 +67,18 @@ inline vcy_carver_option ToC(const VoxelCarverOption& o) {
   return c;
 }
 
-// CloseHull of both carvers (the composition and the tie rule: vacancy_hip.h, "distance field of the hull"):
-// r = radius_voxels * resolution, R = ceil(radius_voxels) + 2, then step(level, R) for the metric field, the field of the
-// hull grown by r, the field of that shrunk by r.  `step` answers false with *error set.  false with *error set when the
-// radius ties -- before any step has run -- or a step fails.
+// CloseHull of both carvers: the plan and the tie rule are the library's (vcy_close_hull_plan; vacancy_hip.h, "Closing
+// the hull"), then step(level, R) for the metric field, the field of the hull grown by r, the field of that shrunk by r.
+// `step` answers false with *error set.  false with *error set when the radius is refused -- before any step has run --
+// or a step fails.
 template <typename Step>
 inline bool CloseHullSteps(float radius_voxels, double iso_level, float resolution, std::string* error, Step step) {
-  const double rv = static_cast<double>(radius_voxels);
-  const int big_r = static_cast<int>(std::ceil(rv)) + 2;
-  char msg[256];
-  if (!(rv > 0.0) || big_r > 127) {
-    std::snprintf(msg, sizeof(msg), "CloseHull: radius_voxels = %g must be positive and at most 125", rv);
-    *error = msg;
+  double r = 0.0;
+  int big_r = 0;
+  if (vcy_close_hull_plan(static_cast<double>(radius_voxels), resolution, &r, &big_r) != VCY_OK) {
+    *error = vcy_last_error();
     return false;
   }
-  const double t = (rv + 0.5) * (rv + 0.5);
-  const double nearest = std::floor(t + 0.5);
-  if (std::fabs(t - nearest) <= 1e-9 * t) {
-    long long m = static_cast<long long>(nearest);
-    while (m % 4 == 0) m /= 4;
-    if (m % 8 != 7) {  // Legendre: a sum of three squares, so a squared voxel distance
-      std::snprintf(msg, sizeof(msg),
-                    "CloseHull: radius_voxels = %g ties: (radius + 0.5)^2 = %lld is a squared voxel distance, and the growing "
-                    "and the shrinking step would treat it alike; pick e.g. %g",
-                    rv, static_cast<long long>(nearest), rv - 0.2);
-      *error = msg;
-      return false;
-    }
-  }
-  const double r = rv * static_cast<double>(resolution);
   const double iso[3] = {iso_level, r, -r};
   for (double level : iso)
     if (!step(level, big_r)) return false;

@@ -401,7 +401,7 @@ bool ShardedVoxelCarver::HullAgreementSlabs(const std::vector<const Camera*>& ca
   return true;
 }
 
-// The rule of vcy_keep_components on the merged list, then every slab's own filter kernel over its pieces of the components
+// The keep rule on the merged list (vcy_select_components_host), then every slab's own filter kernel over its pieces of the components
 // that go.  The two halo slices below every upper slab are stale afterwards, exactly as after a Carve(): ExtractIsoSurface
 // always, and ExtractVoxel whenever it reads the slice below a slab (inside_empty), call ExchangeHalo() before they
 // read them, so nothing has to be exchanged here.
@@ -486,9 +486,8 @@ bool ShardedVoxelCarver::CloseHull(float radius_voxels, double iso_level) {
 }
 
 // Every slab finishes one step before any slab begins the next.  What a slab hands out: its lowest and its highest
-// min(radius, own slices) planes of 16-bit values; what it gets: the planes of the global slices [z0 - min(radius, z0), z0)
-// and [z1, z1 + min(radius, nz - z1)), from as many neighbours as that takes -- a slab thinner than the radius passes its
-// neighbours' planes on.
+// min(radius, own slices) planes of 16-bit values; what it gets, from as many neighbours as that takes, is put together
+// by vcy_distance_halo_host.
 bool ShardedVoxelCarver::Impl::DistanceSlabs(double iso_level, int radius, const char* who,
                                              const std::function<int(size_t, const uint16_t*, int, const uint16_t*, int)>& finish) {
   const size_t ns = slabs.size();
@@ -497,12 +496,10 @@ bool ShardedVoxelCarver::Impl::DistanceSlabs(double iso_level, int radius, const
     return false;
   }
   if (!ForEachSlab(ns, who, [&](size_t s) { return vcy_distance_slab_begin(slabs[s], iso_level, radius); })) return false;
-  const int nz = bounds[ns];
   const size_t plane = static_cast<size_t>(slice);
-  auto edge = [&](size_t s) { return std::min(radius, bounds[s + 1] - bounds[s]); };
   std::vector<std::vector<uint16_t>> bottoms(ns), tops(ns);
   if (!ForEachSlab(ns, who, [&](size_t s) {
-        const int m = edge(s);
+        const int m = std::min(radius, bounds[s + 1] - bounds[s]);
         if (s > 0) {
           bottoms[s].resize(plane * m);
           const int rc = vcy_distance_slab_planes(slabs[s], bounds[s], bounds[s] + m, bottoms[s].data());
@@ -515,23 +512,18 @@ bool ShardedVoxelCarver::Impl::DistanceSlabs(double iso_level, int radius, const
         return static_cast<int>(VCY_OK);
       }))
     return false;
-  // the plane of the global slice z, which lies below (from the owner's top planes) or above (bottom planes) the asker
-  auto plane_of = [&](int z, bool from_top) -> const uint16_t* {
-    const size_t j = static_cast<size_t>(std::upper_bound(bounds.begin(), bounds.end(), z) - bounds.begin()) - 1;
-    return from_top ? tops[j].data() + plane * static_cast<size_t>(z - (bounds[j + 1] - edge(j)))
-                    : bottoms[j].data() + plane * static_cast<size_t>(z - bounds[j]);
-  };
+  std::vector<const uint16_t*> bottom_of(ns), top_of(ns);  // (null where nobody asked for them: an empty vector's data())
+  for (size_t s = 0; s < ns; ++s) bottom_of[s] = bottoms[s].data(), top_of[s] = tops[s].data();
   std::vector<std::vector<uint16_t>> below(ns), above(ns);
   std::vector<int> n_below(ns), n_above(ns);
   for (size_t s = 0; s < ns; ++s) {
-    const int z0 = bounds[s], z1 = bounds[s + 1];
-    n_below[s] = std::min(radius, z0), n_above[s] = std::min(radius, nz - z1);
-    below[s].resize(plane * n_below[s]);
-    above[s].resize(plane * n_above[s]);
-    for (int k = 0; k < n_below[s]; ++k)
-      std::memcpy(below[s].data() + plane * k, plane_of(z0 - n_below[s] + k, true), plane * sizeof(uint16_t));
-    for (int k = 0; k < n_above[s]; ++k)
-      std::memcpy(above[s].data() + plane * k, plane_of(z1 + k, false), plane * sizeof(uint16_t));
+    below[s].resize(plane * std::min(radius, bounds[s]));
+    above[s].resize(plane * std::min(radius, bounds[ns] - bounds[s + 1]));
+    if (vcy_distance_halo_host(static_cast<int>(ns), bounds.data(), radius, slice, bottom_of.data(), top_of.data(),
+                               static_cast<int>(s), below[s].data(), above[s].data(), &n_below[s], &n_above[s]) != VCY_OK) {
+      LOGE("%s: %s\n", who, vcy_last_error());
+      return false;
+    }
   }
   return ForEachSlab(ns, who, [&](size_t s) {
     return finish(s, n_below[s] ? below[s].data() : nullptr, n_below[s], n_above[s] ? above[s].data() : nullptr, n_above[s]);
@@ -586,28 +578,27 @@ bool ShardedVoxelCarver::KeepLargestComponents(int largest, std::int64_t min_vox
   }
   Impl::Labelled l;
   if (!impl_->LabelSlabs(iso_level, &l)) return false;
-  std::vector<int64_t> gone;  // merged labels, ascending
-  std::int64_t gone_voxels = 0;
-  for (size_t i = 0; i < l.merged.size(); ++i) {
-    const bool keep = (largest <= 0 || static_cast<std::int64_t>(i) < static_cast<std::int64_t>(largest)) &&
-                      l.merged[i].n_voxels >= min_voxels;
-    if (!keep) gone.push_back(l.merged[i].label), gone_voxels += l.merged[i].n_voxels;
+  std::vector<uint8_t> gone(l.merged.size()), piece_gone(l.global.size());  // per merged component, per piece of a slab
+  std::int64_t n_gone = 0, gone_voxels = 0;
+  if (vcy_select_components_host(l.merged.data(), static_cast<int64_t>(l.merged.size()), largest, min_voxels, gone.data(),
+                                 &n_gone, &gone_voxels, l.global.data(), static_cast<int64_t>(l.global.size()),
+                                 piece_gone.data()) != VCY_OK) {
+    LOGE("KeepLargestComponents: %s\n", vcy_last_error());
+    return false;
   }
-  std::sort(gone.begin(), gone.end());
-  if (!gone.empty()) {
+  if (n_gone > 0) {
     const size_t ns = impl_->slabs.size();
     std::vector<int64_t> first(ns + 1, 0);
     for (size_t s = 0; s < ns; ++s) first[s + 1] = first[s] + l.counts[s];
     const bool ok = ForEachSlab(ns, "KeepLargestComponents", [&](size_t s) {
       std::vector<int64_t> mine;
       for (int64_t i = first[s]; i < first[s + 1]; ++i)
-        if (std::binary_search(gone.begin(), gone.end(), l.global[static_cast<size_t>(i)]))
-          mine.push_back(l.pieces[static_cast<size_t>(i)].label);
+        if (piece_gone[static_cast<size_t>(i)]) mine.push_back(l.pieces[static_cast<size_t>(i)].label);
       return vcy_keep_components_slab(impl_->slabs[s], fill_sdf, static_cast<int64_t>(mine.size()), mine.data(), nullptr);
     });
     if (!ok) return false;
   }
-  LOGI("KeepLargestComponents removed %lld components, %lld voxels\n", static_cast<long long>(gone.size()),
+  LOGI("KeepLargestComponents removed %lld components, %lld voxels\n", static_cast<long long>(n_gone),
        static_cast<long long>(gone_voxels));
   return true;
 }
