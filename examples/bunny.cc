@@ -5,6 +5,7 @@
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --smooth N [--lambda L --mu M]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --decimate CELLS [--decimate-mode mean|nearest|first|quadric [--quadric-reg R]]
 //        bunny <data_dir> <out_dir> [resolution] --smooth N ... --decimate CELLS ... --chain
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] [--smooth N] [--decimate CELLS] [--chain] --mesh-agreement
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --redistance R [--offset MM]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --close VOXELS
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
@@ -32,6 +33,11 @@
 //   (VoxelCarver::ExtractIsoSurfaceChain: the mesh stays on the device between the stages) and again as the separate calls,
 //   prints the chain's sizes and timings with `identical 1` when the two agree bit for bit, and writes the chain's mesh as
 //   <out_dir>/surface_chain.ply.
+//   --mesh-agreement (after the ordinary carve) rasterises the FINAL mesh -- the iso-surface after --smooth / --decimate, or
+//   the one --chain returned -- into every input camera on the device (VoxelCarver::MeshAgreement) and prints per view
+//   `MESH_AGREEMENT view i both mask_only mesh_only`, the pixel counts against the input silhouette, with the hull's own
+//   `HULL_AGREEMENT view i both mask_only hull_only` (VoxelCarver::HullAgreement) beside it: what smoothing and decimation
+//   cost in reprojection.  With slabs the merged mesh goes through ShardedVoxelCarver::MeshAgreement as well and is compared.
 //   --redistance R (after the ordinary carve and --keep-largest) rewrites the state as the metric distance field of the hull
 //   (VoxelCarver::Redistance, exact up to R voxels), extracts the iso-surface at --offset MM (world units, by default 0:
 //   the hull itself; positive grows it, negative shrinks it; |MM| < (R - 0.5) * resolution), writes it as
@@ -99,12 +105,14 @@ int main(int argc, char* argv[]) {
   int redistance = 0;      // --redistance R: the state becomes the metric distance field of the hull, exact up to R voxels
   float offset_mm = 0.0f;  // --offset MM: the iso level of the surface extracted from it
   float close_voxels = 0.0f;  // --close VOXELS: morphological closing of the hull first
+  bool mesh_agreement = false;  // --mesh-agreement: the final mesh rasterised into the input views, against their silhouettes
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
     for (int i = 1; i < argc; ++i) {
       if (std::string(argv[i]) == "--keep-largest") keep_largest = true;
       else if (std::string(argv[i]) == "--chain") chain = true;
+      else if (std::string(argv[i]) == "--mesh-agreement") mesh_agreement = true;
       else if (std::string(argv[i]) == "--fuse-depth") fuse_depth = true;
       else if (std::string(argv[i]) == "--render") {
         if (i + 1 >= argc) {
@@ -377,6 +385,7 @@ int main(int argc, char* argv[]) {
     }
   }
 
+  vacancy::Mesh chain_mesh;  // (--chain's result, for --mesh-agreement)
   if (chain) {  // extraction, smoothing and decimation in ONE call, the mesh staying on the device, against the calls above
     const bool quadric = decimate_mode == 3;
     vacancy::ChainOption co;
@@ -407,11 +416,51 @@ int main(int argc, char* argv[]) {
       same = std::memcmp(&got.vertex_indices()[k], &want.vertex_indices()[k], 12) == 0 &&
              std::memcmp(&got.face_normals()[k], &want.face_normals()[k], 12) == 0;
     got.WritePlyBinary(out_dir + "/surface_chain.ply");
+    chain_mesh = got;
     std::printf("CHAIN smooth %d decimate %d extracted %lld %lld verts %zu faces %zu fallback %lld extract_ms %.4f table_ms %.4f "
                 "passes_ms %.4f cluster_ms %.4f quadric_ms %.4f faces_emit_ms %.4f normals_ms %.4f wall_ms %.4f identical %d\n",
                 smooth, co.decimate, (long long)report.n_extracted_vertices, (long long)report.n_extracted_faces, got.vertices().size(),
                 got.vertex_indices().size(), (long long)report.n_fallback, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms[7],
                 same ? 1 : 0);
+  }
+
+  if (mesh_agreement) {  // how the final mesh reprojects onto the input silhouettes, beside the hull itself
+    const bool quadric = decimate_mode == 3;
+    vacancy::Mesh mesh;
+    if (chain) {
+      mesh = chain_mesh;
+    } else {
+      carver.ExtractIsoSurface(&mesh, 0.0);
+      if (smooth >= 0 && !carver.SmoothMesh(&mesh, smooth, smooth_lambda, smooth_mu, false, false)) return 20;
+      if (decimate > 0.0f && !(quadric ? carver.DecimateMeshQuadric(&mesh, decimate * resolution, quadric_reg, false)
+                                        : carver.DecimateMesh(&mesh, decimate * resolution, decimate_mode, false)))
+        return 20;
+    }
+    std::vector<std::shared_ptr<vacancy::PinholeCamera>> cams;
+    std::vector<const vacancy::Camera*> cam_ptrs;
+    std::vector<vacancy::Image1b> sils(poses.size() < 6 ? poses.size() : 6);
+    for (size_t i = 0; i < sils.size(); ++i) {
+      cams.push_back(std::make_shared<vacancy::PinholeCamera>(width, height, poses[i], Eigen::Vector2f(159.3f, 127.65f),
+                                                              Eigen::Vector2f(258.65f, 258.25f)));
+      cam_ptrs.push_back(cams.back().get());
+      if (!sils[i].Load(data_dir + "/mask_" + vacancy::zfill(i) + ".png")) return 3;
+    }
+    std::vector<std::array<std::int64_t, 3>> counts, hull_counts;
+    if (!carver.MeshAgreement(mesh, cam_ptrs, sils, &counts) || !carver.HullAgreement(cam_ptrs, sils, &hull_counts)) return 20;
+    for (size_t i = 0; i < counts.size(); ++i) {
+      std::printf("MESH_AGREEMENT view %zu %lld %lld %lld\n", i, (long long)counts[i][0], (long long)counts[i][1], (long long)counts[i][2]);
+      std::printf("HULL_AGREEMENT view %zu %lld %lld %lld\n", i, (long long)hull_counts[i][0], (long long)hull_counts[i][1],
+                  (long long)hull_counts[i][2]);
+    }
+    const std::array<float, 2> ms = carver.last_raster_ms();
+    std::printf("MESH_AGREEMENT verts %zu faces %zu views %zu raster_ms %.4f resolve_ms %.4f\n", mesh.vertices().size(),
+                mesh.vertex_indices().size(), counts.size(), ms[0], ms[1]);
+    if (sharded) {  // the same mesh through the first slab's context: the same counts
+      std::vector<std::array<std::int64_t, 3>> scounts;
+      if (!sharded->MeshAgreement(mesh, cam_ptrs, sils, &scounts)) return 20;
+      std::printf("MESH_AGREEMENTSHARDED slabs %d identical %d\n", sharded->slab_count(), scounts == counts ? 1 : 0);
+      if (scounts != counts) return 21;
+    }
   }
 
   if (!render_dir.empty()) {  // what the hull looks like from every input camera (vcy_render_hull / vcy_hull_agreement)

@@ -86,6 +86,11 @@ class ShardedVoxelCarver {
   // VoxelCarver::DecimateMeshQuadric for the merged mesh, on the first slab's context (vcy_decimate_mesh_quadric): the same bits.
   bool DecimateMeshQuadric(Mesh* mesh, float cell, float regularize = 1e-3f, bool with_normals = false,
                            std::int64_t* n_fallback = nullptr);
+  // VoxelCarver::RenderMesh / MeshAgreement for the merged mesh, on the first slab's context (vcy_raster_mesh,
+  // vcy_mesh_agreement): the same bits.
+  bool RenderMesh(const Mesh& mesh, const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);
+  bool MeshAgreement(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
+                     std::vector<std::array<std::int64_t, 3>>* counts);
   // VoxelCarver::RenderHull / HullAgreement over the slabs: RenderHullSlabs / HullAgreementSlabs below.  These two older
   // names keep logging an error and returning false.
   bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);

@@ -88,6 +88,7 @@ struct ColorOption {
   float depth_tolerance{-1.0f};                         // world units; < 0: 1.5 * the carver's resolution
   float min_cos{0.0f};                                  // kWeighted, kBest: a view contributes iff its weight > min_cos
   Eigen::Vector3f fallback = Eigen::Vector3f(128.0f, 128.0f, 128.0f);  // colour of a vertex no view sees
+  bool occlusion_from_mesh{false};                      // the depth images come from the mesh itself (RenderMesh), not the hull
 };
 
 // The stages of VoxelCarver::ExtractIsoSurfaceChain and what it reports beside the mesh.  No counterpart in the reference.
@@ -184,6 +185,17 @@ class VoxelCarver {
   bool HullAgreement(const std::vector<Camera>& cameras, const std::vector<Image1b>& silhouettes,
                      std::vector<std::array<std::int64_t, 3>>* counts);
 
+  // An indexed mesh as camera `camera` sees it (vcy_raster_mesh: the nearest face over every pixel centre, exact and
+  // watertight -- the definition is in vacancy_hip.h): depth = camera depth, RenderHull's quantity, +inf where no face is
+  // seen; silhouette (optional) = 255 where one is.  Any mesh will do -- smoothed, decimated, edited, merged --, the voxel
+  // state is not touched, there is no near-plane clipping (a face with a vertex behind the camera is not drawn).
+  // MeshAgreement (vcy_mesh_agreement) is HullAgreement for the mesh: per view {mask && mesh, mask && !mesh, !mask && mesh}.
+  // false + LOGE on an error.  last_raster_ms(): device milliseconds of the raster and the resolve launches.
+  bool RenderMesh(const Mesh& mesh, const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);
+  bool MeshAgreement(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
+                     std::vector<std::array<std::int64_t, 3>>* counts);
+  std::array<float, 2> last_raster_ms() const;
+
   // The robust visual hull (vcy_carve_robust_silhouettes; the definition is in vacancy_hip.h): REPLACES the state by, per
   // voxel, the (tolerate + 1)-th largest sample over all cameras instead of the largest, so that a voxel is carved only
   // when more than `tolerate` (0 .. 3) views say outside -- up to `tolerate` wrong masks no longer remove a part of the
@@ -211,6 +223,8 @@ class VoxelCarver {
   // (vcy_color_vertices): a view colours a vertex it sees -- whose camera depth is at most the hull's depth at its pixel,
   // ray-cast here at iso_level, + depth_tolerance.  photos[i] belongs to cameras[i] and gives the view its size; the ROI
   // is the whole image.  Computes the mesh's normals (CalcNormal) if it has none and the mode needs them.
+  // option.occlusion_from_mesh: the depth images are RenderMesh's of the mesh being coloured instead of the hull's -- for
+  // a smoothed or decimated mesh, which the voxel staircase no longer describes; iso_level is not used then.
   // false + LOGE on an error, the colours then stay as they were.
   bool ColorMesh(Mesh* mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
                  const ColorOption& option = ColorOption(), double iso_level = 0.0);

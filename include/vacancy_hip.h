@@ -854,6 +854,75 @@ int vcy_color_vertices(vcy_ctx* ctx, double iso_level, int64_t n_vertices, const
  * not included; the ray-cast of a call without depth images is in vcy_last_render_ms. */
 int vcy_last_color_ms(const vcy_ctx* ctx, float* device_ms);
 
+/* ---- rasterising an indexed mesh into views: depth, face id, hit bits, agreement ----- */
+/* No reference counterpart: this section is the definition.  vcy_raster_mesh_host is it in serial host code,
+ * tests/raster_ref.py restates it in numpy, vcy_raster_mesh runs it on the device; the three agree bit for bit.
+ *
+ * Inputs: n_vertices points (float xyz, world), n_faces int32 triples (f0, f1, f2), n_views views, of which the fields
+ * vcy_render_hull reads are read (roi_min / roi_max, width, height, w2c, the intrinsics, is_ortho) and the views it refuses
+ * are refused.  With R[r][c] = w2c[4 * r + c], t[r] = w2c[4 * r + 3], every step is arithmetic in a fixed order, every
+ * product and every sum rounded on its own (no FMA), division correctly rounded.  Per view:
+ *   1. projection : of a vertex p, the carve's own float arithmetic (step 1 of the colour definition):
+ *                   pc[r] = t[r] + (R[r][0] * px + (R[r][1] * py + R[r][2] * pz)); pinhole u = fx / pc[2] * pc[0] + cx,
+ *                   w = fy / pc[2] * pc[1] + cy; ortho u = pc[0], w = pc[1]; z = pc[2].  The vertex is UNUSABLE in the
+ *                   view when a component of pc, u or w is not finite, on a pinhole view when pc[2] <= 0, on an ortho view
+ *                   when pc[2] < 0.  (u, w, z) is a pure function of (vertex, view): every face that names the vertex
+ *                   sees the same bits.
+ *   2. dropped    : a face is not drawn in the view, class 0, when one of its vertices is unusable -- there is NO
+ *                   near-plane clipping: a face that crosses the camera plane disappears whole --; otherwise, class 1,
+ *                   when it names a vertex twice or its signed area A (step 4) is 0 or not finite.
+ *                   n_dropped[2 * i + c] counts the faces of class c in view i.
+ *   3. edge       : in double, from the float coordinates, canonical per edge: for the vertex indices i < j, a = (u_i, w_i)
+ *                   and b = (u_j, w_j) converted to double, E_ij(p) = (bx - ax) * (py - ay) - (by - ay) * (px - ax).  The
+ *                   face's value for its directed edge f_k -> f_k+1 is E_ij(p) when the face runs from i to j and
+ *                   -E_ij(p) when it runs from j to i.  Two faces that share an edge in opposite directions therefore get
+ *                   exactly opposite values at every p: the image has no hole and no double cover along an interior edge.
+ *   4. area       : A = the face's value for the edge (f0, f1) at p = (u, w) of f2; s = +1 for A > 0, -1 for A < 0.  Both
+ *                   windings are drawn: there is no culling.
+ *   5. candidates : the integer pixels (x, y) -- the carve's and the ray-cast's pixel, data[width * y + x] -- with
+ *                   ceilf(min u) <= x <= floorf(max u), ceilf(min w) <= y <= floorf(max w), inside the ROI
+ *                   (roi_min <= (x, y) <= roi_max).  The box is part of the definition.
+ *   6. coverage   : closed.  With e_0, e_1, e_2 the face's values at p = ((double)x, (double)y) for the edges (f1, f2),
+ *                   (f2, f0), (f0, f1): the pixel is covered iff s * e_k >= 0 for all three.
+ *   7. depth      : l_k = e_k / A.  Pinhole z = 1.0 / ((l_0 * (1.0 / z_0) + l_1 * (1.0 / z_1)) + l_2 * (1.0 / z_2)), ortho
+ *                   z = (l_0 * z_0 + l_1 * z_1) + l_2 * z_2, with z_k = (double)pc[2] of f_k; depth = (float)z, -0 stored
+ *                   as +0.  A fragment whose depth is not finite or < 0 is discarded.
+ *   8. winner     : per pixel, the fragment with the smallest (depth bits as uint32, face index), compared
+ *                   lexicographically -- a rule without an order, so any traversal gives the same image.
+ *   9. outputs    : depth (float)   camera depth of the winner, the quantity of vcy_render_hull's depth; +inf on a miss;
+ *                   face  (int32)   the winner's face index; -1 on a miss;
+ *                   hits  (uint64)  the hit bits of vcy_render_hull_slab, word for word: (width + 63) / 64 words per
+ *                                   row, bit x & 63 of word [y][x >> 6] set iff pixel (x, y) has a winner; every other
+ *                                   bit, the padding of a row included, is 0.  Pixels outside the ROI are misses.
+ * VCY_ERR_INVALID_ARG, nothing written, for a NULL required pointer, negative counts, n_views <= 0, a view vcy_render_hull
+ * would refuse, or a face index outside [0, n_vertices) (the contract of vcy_smooth_mesh); VCY_ERR_UNSUPPORTED beyond
+ * vcy_mesh_index_limits.  A mesh without faces gives all-miss images. */
+
+/* The definition above, serial, on the host (no GPU, no context).  depth / face / hits: arrays of n_views pointers to
+ * width * height floats, width * height int32 and (width + 63) / 64 * height 64-bit words; any of the three arrays, or
+ * single entries, may be NULL.  n_dropped: 2 * n_views counts, or NULL. */
+int vcy_raster_mesh_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces, int n_views,
+                         const vcy_view* views, float* const* depth, int32_t* const* face, uint64_t* const* hits,
+                         int64_t* n_dropped);
+/* The same on the device of `ctx`, on its stream, from and into HOST arrays, bit for bit (a 64-bit key image per view,
+ * 64-bit integer atomic minima; one lane per face with the view loop inside it, faces with large candidate boxes drawn by
+ * their whole wave -- vcy_set_param "rasterwide"; views in chunks of 64, so any n_views >= 1).  The context only names the
+ * device and the stream: any context will do, a z-slab included; the voxel state, queued views and every cache stay
+ * untouched.  Arguments and errors as for the host function; VCY_ERR_NOT_INITIALIZED for a NULL context, behind the
+ * argument checks.  Device memory: the mesh, and per view of a chunk 8 bytes per pixel plus the images asked for, kept by
+ * the context (grow-only). */
+int vcy_raster_mesh(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces, int n_views,
+                    const vcy_view* views, float* const* depth_host, int32_t* const* face_host, uint64_t* const* hits_host,
+                    int64_t* n_dropped);
+/* Rasterises and compares with the silhouettes on the device; no image is downloaded.  masks_host and counts as for
+ * vcy_hull_agreement: counts[3 * i + 0 .. 2] = pixels of view i inside its ROI with {mask && mesh, mask && !mesh,
+ * !mask && mesh}; equal to vcy_hull_agreement_host over the hit bits of vcy_raster_mesh_host. */
+int vcy_mesh_agreement(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces, int n_views,
+                       const vcy_view* views, const uint8_t* const* masks_host, int64_t* counts);
+/* Milliseconds between HIP events of the last vcy_raster_mesh / vcy_mesh_agreement, summed over its chunks of views: the
+ * fill of the key images with the raster launch, and the resolve launch.  Copies are not included.  Either may be NULL. */
+int vcy_last_raster_ms(const vcy_ctx* ctx, float* raster_ms, float* resolve_ms);
+
 /* ---- mesh smoothing: Taubin passes over an indexed mesh, fresh normals ----- */
 /* No reference counterpart: this section is the definition.  vcy_smooth_mesh_host is it in serial host code,
  * tests/smooth_ref.py restates it in numpy, vcy_smooth_mesh runs it on the device; the three agree bit for bit.
@@ -1266,6 +1335,9 @@ int vcy_reset(vcy_ctx* ctx);
  * vertex normals: no atomics; rows ascending as written, though the stages sort them regardless); 0: from the faces, as
  * vcy_smooth_mesh builds it.  1 is the faster one at 512^3 and 1024^3 by more than the run-to-run spread
  * (profiles/chain/measure_chain.txt).  Results identical (readable through vcy_get_param).
+ * "rasterwide" (default 64, >= 0): a face of vcy_raster_mesh / vcy_mesh_agreement whose candidate box in a view holds more
+ * pixels than this is drawn by the 64 lanes of its wave, not by its own lane; 0 sends every face that way.  Results
+ * identical (readable through vcy_get_param).
  * "inject_carve_failure" (test hook, default 0): the next `value` applications of views fail with
  * VCY_ERR_INTERNAL before anything is launched -- how the tests exercise the error contract of vcy_carve. */
 int vcy_set_param(vcy_ctx* ctx, const char* name, int value);

@@ -273,6 +273,10 @@ def load():
         "vcy_color_vertices": (C.c_int, [vp, C.c_double, C.c_int64, vp, vp, C.c_int, P(View), P(vp), P(vp), P(ColorOption),
                                          vp, vp, vp]),
         "vcy_last_color_ms": (C.c_int, [vp, P(C.c_float)]),
+        "vcy_raster_mesh_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, C.c_int, P(View), P(vp), P(vp), P(vp), vp]),
+        "vcy_raster_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, C.c_int, P(View), P(vp), P(vp), P(vp), vp]),
+        "vcy_mesh_agreement": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, C.c_int, P(View), P(vp), vp]),
+        "vcy_last_raster_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float)]),
         "vcy_smooth_mesh_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
         "vcy_smooth_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
         "vcy_last_smooth_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float), P(C.c_float)]),

@@ -157,6 +157,50 @@ def color_vertices_host(vertices, views, photos, depth, normals=None, mode=capi.
     return out
 
 
+def _raster_args(vertices, faces, views, depth=True, face=False, hits=False):
+    """The arrays and ctypes arguments vcy_raster_mesh and vcy_raster_mesh_host share (everything behind the context); the
+    first element keeps every array alive for the call.  The result: one dict per view and the int64 [n_views, 2] drops."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    vs = list(views)
+    n = len(vs)
+    out = [{} for _ in vs]
+    for o, w in zip(out, vs):
+        if depth:
+            o["depth"] = np.empty((w.height, w.width), np.float32)
+        if face:
+            o["face"] = np.empty((w.height, w.width), np.int32)
+        if hits:
+            o["hits"] = np.empty((w.height, (w.width + 63) // 64), np.uint64)
+    dropped = np.zeros((n, 2), np.int64)
+    arr = (View * max(n, 1))(*vs)
+    ptrs = [(C.c_void_p * max(n, 1))(*[o[k].ctypes.data for o in out]) if on else None
+            for k, on in (("depth", depth), ("face", face), ("hits", hits))]
+    args = (len(v), len(f), _p(v), _p(f), n, arr, ptrs[0], ptrs[1], ptrs[2], _p(dropped))
+    return (v, f, arr, ptrs), args, out, dropped
+
+
+def _raster_result(rc, single, out, dropped):
+    if rc != 0:
+        e = RuntimeError(last_error())
+        e.rc = rc
+        raise e
+    for o, d in zip(out, dropped):
+        o["n_dropped"] = d
+    return out[0] if single else out
+
+
+def raster_mesh_host(vertices, faces, views, depth=True, face=True, hits=True):
+    """vcy_raster_mesh_host: the indexed mesh rasterised into `views` (one vcy_view or a list), serial, no GPU needed
+    (definition: include/vacancy_hip.h, "rasterising an indexed mesh").  Per view a dict: "depth" (float32 [height, width],
+    camera depth, +inf on a miss), "face" (int32, the winning face, -1 on a miss), "hits" (uint64 [height, (width + 63) //
+    64], RenderHullSlab's hit bits), each when asked for, and "n_dropped" (int64 [2]: faces with an unusable vertex, faces
+    without area).  A single view returns its dict, a list a list.  RuntimeError (with .rc) on a refusal."""
+    single = isinstance(views, View)
+    keep, args, out, dropped = _raster_args(vertices, faces, [views] if single else views, depth, face, hits)
+    return _raster_result(capi.load().vcy_raster_mesh_host(*args), single, out, dropped)
+
+
 def _smooth_args(vertices, faces, iterations, lam, mu, pin_boundary, normals):
     """The arrays and ctypes arguments vcy_smooth_mesh and vcy_smooth_mesh_host share; the first element keeps every array
     alive for the call."""
@@ -951,18 +995,60 @@ class VoxelCarver:
         self._lib.vcy_last_render_ms(self._ctx, C.byref(ms))
         return ms.value
 
+    # -- rasteriser of an indexed mesh (no reference counterpart; definition: include/vacancy_hip.h)
+    def RenderMesh(self, vertices, faces, views, depth=True, face=False, hits=False):
+        """vcy_raster_mesh: raster_mesh_host on this context's device and stream, the same bits.  The context only names the
+        device: its voxel state is not touched, and a z-slab will do.  Dicts as raster_mesh_host's (a single view returns
+        its dict), each with the call's device times "raster_ms" and "resolve_ms".  RuntimeError (with .rc) on a refusal."""
+        single = isinstance(views, View)
+        keep, args, out, dropped = _raster_args(vertices, faces, [views] if single else views, depth, face, hits)
+        rc = self._lib.vcy_raster_mesh(self._ctx, *args)
+        ms = self.last_raster_ms()
+        for o in out:
+            o["raster_ms"], o["resolve_ms"] = ms
+        return _raster_result(rc, single, out, dropped)
+
+    def MeshAgreement(self, vertices, faces, views, masks):
+        """vcy_mesh_agreement: rasterises the mesh into `views` and compares it with the silhouettes `masks` (non-zero =
+        object) on the device.  int64 [n_views, 3]: pixels inside the ROI with (mask and mesh, mask and not mesh, mesh and
+        not mask) -- HullAgreement's triple for the mesh."""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        vs = list(views)
+        n = len(vs)
+        ms = [np.ascontiguousarray(m, np.uint8) for m in masks]
+        if len(ms) != n or any(m.shape != (w.height, w.width) for m, w in zip(ms, vs)):
+            raise ValueError("one height x width silhouette per view")
+        arr = (View * max(n, 1))(*vs)
+        mp = (C.c_void_p * max(n, 1))(*[m.ctypes.data for m in ms])
+        counts = np.zeros((n, 3), np.int64)
+        if self._lib.vcy_mesh_agreement(self._ctx, len(v), len(f), _p(v), _p(f), n, arr, mp, _p(counts)) != 0:
+            raise RuntimeError(last_error())
+        return counts
+
+    def last_raster_ms(self):
+        ms = [C.c_float(), C.c_float()]
+        self._lib.vcy_last_raster_ms(self._ctx, *[C.byref(m) for m in ms])
+        return ms[0].value, ms[1].value
+
     # -- colour of vertices from the photographs (no reference counterpart; definition: include/vacancy_hip.h)
     def ColorVertices(self, vertices, views, photos, normals=None, depth=None, mode=capi.VCY_COLOR_WEIGHTED,
                       interp=capi.VCY_INTERP_BILINEAR, depth_tolerance=None, min_cos=0.0, fallback=(128, 128, 128),
-                      iso_level=0.0):
+                      iso_level=0.0, mesh_faces=None):
         """vcy_color_vertices: per vertex the mean (VCY_COLOR_MEAN), the mean weighted by |cos| between normal and viewing
         ray (VCY_COLOR_WEIGHTED) or the most frontal sample (VCY_COLOR_BEST) of the photographs of the views that see it.
         A view sees a vertex whose camera depth is at most the hull's depth at its pixel + depth_tolerance (default: 1.5
         voxels).  `depth`: one image per view (RenderHull's, a merged slab render, a sensor's) -- any context will do then;
         None: the hull is ray-cast here at `iso_level` and the depth never leaves the device (whole-grid contexts only).
+        `mesh_faces` (without `depth`): the vertices are those of this indexed mesh, and the occlusion comes from the mesh
+        itself -- RenderMesh's depth images of (vertices, mesh_faces), passed on as `depth`; any context will do.
         Returns {"rgb": float32 [n, 3] in 0 .. 255, "n_used", "best_view" (-1: none): int32 [n], "device_ms"}."""
         if depth_tolerance is None:
             depth_tolerance = 1.5 * self.option.resolution
+        if mesh_faces is not None:
+            if depth is not None:
+                raise ValueError("depth images or mesh_faces, not both")
+            depth = [o["depth"] for o in self.RenderMesh(vertices, mesh_faces, list(views))]
         keep, args, out = _color_args(vertices, views, photos, normals, depth, mode, interp, depth_tolerance, min_cos, fallback)
         if self._lib.vcy_color_vertices(self._ctx, iso_level, *args) != 0:
             raise RuntimeError(last_error())

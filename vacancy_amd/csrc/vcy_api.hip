@@ -346,6 +346,10 @@ int vcy_set_param(vcy_ctx* c, const char* name, int value) {
     c->chain_rows = value != 0 ? 1 : 0;
     return VCY_OK;
   }
+  if (std::strcmp(name, "rasterwide") == 0) {  // candidate pixels above which a face is drawn by its whole wave
+    c->raster_wide = value < 0 ? 0 : value;
+    return VCY_OK;
+  }
   if (std::strcmp(name, "mcdirect") == 0) {  // bytes (of the guessed mesh) up to which mc_emit writes host memory directly
     c->mc_direct_bytes = value < 0 ? 0 : (int64_t)value;
     return VCY_OK;
@@ -392,6 +396,7 @@ int vcy_get_param(vcy_ctx* c, const char* name, int* value) {
   else if (std::strcmp(name, "rayskip") == 0) *value = c->ray_skip;
   else if (std::strcmp(name, "smoothpad") == 0) *value = c->smooth_pad;
   else if (std::strcmp(name, "chainrows") == 0) *value = c->chain_rows;
+  else if (std::strcmp(name, "rasterwide") == 0) *value = c->raster_wide;
   else if (std::strcmp(name, "lazycount") == 0) *value = c->lazy_count ? 1 : 0;
   else if (std::strcmp(name, "carvetimer") == 0) *value = c->time_carve ? 1 : 0;
   else if (std::strcmp(name, "carvelog_dropped") == 0) *value = c->carve_log_dropped;

@@ -186,6 +186,12 @@ struct vcy_ctx {
   vcy::Event ev_cl_begin, ev_cl_end;
   float last_color_device_ms = 0.0f;
 
+  // rasteriser of an indexed mesh (raster.hip); grow-only
+  vcy::DeviceBuf<> d_rs_buf;          // view records, counters, the mesh, and per view of a chunk: key image, depth, face ids, hit bits, silhouette
+  vcy::Event ev_rs[3];                // before the key fill and the raster launch, between raster and resolve, after the resolve
+  float last_raster_ms[2] = {0.0f, 0.0f};  // vcy_last_raster_ms: raster (with the key fill), resolve
+  int raster_wide = 64;               // "rasterwide": a face whose candidate box holds more pixels than this is drawn by its whole wave
+
   // robust carve (carve_robust.hip)
   vcy::Event ev_rb_begin, ev_rb_end;  // around its launch (vcy_last_robust_ms)
   float last_robust_device_ms = 0.0f;
@@ -266,6 +272,10 @@ int launch_solid_bits(vcy_ctx* ctx, double iso, unsigned long long* bits);
 // vcy_ctx::d_rn_out and holds until the context next renders; waits for the launch; vcy_last_render_ms as for the render
 int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* views, const float** depth_dev, const char* who);
 // color.hip: vcy_color_vertices, vcy_color_vertices_host, vcy_last_color_ms
+// raster.hip: vcy_raster_mesh, vcy_mesh_agreement, vcy_last_raster_ms; raster_host.hip (host code only):
+// vcy_raster_mesh_host and the argument checks of the three; what device and host share: raster_fragment.h
+int raster_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                      int n_views, const vcy_view* views);
 // mesh_smooth.hip: vcy_smooth_mesh, vcy_last_smooth_ms; mesh_smooth_host.hip (host code only): vcy_smooth_mesh_host and
 // the argument checks of the two
 int smooth_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,

@@ -13,6 +13,7 @@
 #include "c_abi_structs.h"
 #include "mesh_copy.h"
 #include "mesh_decimate.h"
+#include "mesh_raster.h"
 #include "mesh_smooth.h"
 
 namespace vacancy {
@@ -414,6 +415,23 @@ bool ShardedVoxelCarver::SmoothMesh(Mesh* mesh, int iterations, float lambda, fl
   return detail::SmoothMeshWith(mesh, iterations, lambda, mu, pin_boundary, with_normals,
                                 [ctx](int64_t nv, int64_t nf, const float* v, const int32_t* f, const vcy_smooth_option* o,
                                       float* out, float* vn, float* fn) { return vcy_smooth_mesh(ctx, nv, nf, v, f, o, out, vn, fn); });
+}
+
+bool ShardedVoxelCarver::RenderMesh(const Mesh& mesh, const Camera& camera, Image1f* depth, Image1b* silhouette) {
+  if (impl_->slabs.empty()) {
+    LOGE("ShardedVoxelCarver::RenderMesh needs an initialized carver\n");
+    return false;
+  }
+  return detail::RenderMeshWith(impl_->slabs[0], "ShardedVoxelCarver::RenderMesh", mesh, camera, depth, silhouette);
+}
+
+bool ShardedVoxelCarver::MeshAgreement(const Mesh& mesh, const std::vector<const Camera*>& cameras,
+                                       const std::vector<Image1b>& silhouettes, std::vector<std::array<std::int64_t, 3>>* counts) {
+  if (impl_->slabs.empty()) {
+    LOGE("ShardedVoxelCarver::MeshAgreement needs an initialized carver\n");
+    return false;
+  }
+  return detail::MeshAgreementWith(impl_->slabs[0], "ShardedVoxelCarver::MeshAgreement", mesh, cameras, silhouettes, counts);
 }
 
 bool ShardedVoxelCarver::DecimateMesh(Mesh* mesh, float cell, int mode, bool with_normals) {

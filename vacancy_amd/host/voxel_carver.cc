@@ -9,6 +9,7 @@
 #include "c_abi_structs.h"
 #include "mesh_copy.h"
 #include "mesh_decimate.h"
+#include "mesh_raster.h"
 #include "mesh_smooth.h"
 
 namespace vacancy {
@@ -375,6 +376,29 @@ bool VoxelCarver::HullAgreement(const std::vector<Camera>& cameras, const std::v
   return HullAgreement(ptrs, silhouettes, counts);
 }
 
+bool VoxelCarver::RenderMesh(const Mesh& mesh, const Camera& camera, Image1f* depth, Image1b* silhouette) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  return detail::RenderMeshWith(impl_->ctx, "VoxelCarver::RenderMesh", mesh, camera, depth, silhouette);
+}
+
+bool VoxelCarver::MeshAgreement(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
+                                std::vector<std::array<std::int64_t, 3>>* counts) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  return detail::MeshAgreementWith(impl_->ctx, "VoxelCarver::MeshAgreement", mesh, cameras, silhouettes, counts);
+}
+
+std::array<float, 2> VoxelCarver::last_raster_ms() const {
+  std::array<float, 2> ms = {{0.0f, 0.0f}};
+  if (impl_->ctx) vcy_last_raster_ms(impl_->ctx, &ms[0], &ms[1]);
+  return ms;
+}
+
 bool VoxelCarver::CarveRobust(const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes, int tolerate,
                               std::vector<std::int64_t>* overruled, double iso_level) {
   if (!impl_->ctx) {
@@ -505,9 +529,29 @@ bool VoxelCarver::ColorMesh(Mesh* mesh, const std::vector<const Camera*>& camera
   const float* normals = option.mode != ColorMode::kMean ? reinterpret_cast<const float*>(mesh->normals().data()) : nullptr;
   static_assert(sizeof(Eigen::Vector3f) == 3 * sizeof(float), "packed vector layout");
   std::vector<Eigen::Vector3f> colors(nv);
+  // occlusion from the mesh itself: its depth images, rasterised here and handed on as the caller's would be
+  std::vector<std::vector<float>> depth;
+  std::vector<float*> depth_ptr;
+  if (option.occlusion_from_mesh) {
+    depth.resize(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+      depth[i].resize(static_cast<size_t>(views[i].width) * static_cast<size_t>(views[i].height));
+      depth_ptr.push_back(depth[i].data());
+    }
+    static_assert(sizeof(Eigen::Vector3i) == 3 * sizeof(int32_t), "packed vector layout");
+    const int rcr = vcy_raster_mesh(impl_->ctx, static_cast<int64_t>(nv), static_cast<int64_t>(mesh->vertex_indices().size()),
+                                    reinterpret_cast<const float*>(mesh->vertices().data()),
+                                    reinterpret_cast<const int32_t*>(mesh->vertex_indices().data()), n, views.data(),
+                                    depth_ptr.data(), nullptr, nullptr, nullptr);
+    if (rcr != VCY_OK) {
+      LOGE("%s\n", vcy_last_error());
+      return false;
+    }
+  }
   const int rc = vcy_color_vertices(impl_->ctx, iso_level, static_cast<int64_t>(nv),
                                     reinterpret_cast<const float*>(mesh->vertices().data()), normals, n, views.data(),
-                                    data.data(), nullptr, &o, reinterpret_cast<float*>(colors.data()), nullptr, nullptr);
+                                    data.data(), option.occlusion_from_mesh ? depth_ptr.data() : nullptr, &o,
+                                    reinterpret_cast<float*>(colors.data()), nullptr, nullptr);
   LogAppliedCarves(impl_->ctx, &impl_->carve_timer);
   if (rc != VCY_OK) {
     LOGE("%s\n", vcy_last_error());

@@ -220,6 +220,16 @@ class ShardedVoxelCarver:
         """VoxelCarver.SmoothMesh on the first slab's context: the same dict."""
         return self.slabs[0].SmoothMesh(vertices, faces, iterations, lam, mu, pin_boundary, normals)
 
+    # -- rasteriser of the MERGED mesh (include/vacancy_hip.h, "rasterising an indexed mesh"): as SmoothMesh, on the first
+    # slab's context
+    def RenderMesh(self, vertices, faces, views, depth=True, face=False, hits=False):
+        """VoxelCarver.RenderMesh on the first slab's context: the same dicts."""
+        return self.slabs[0].RenderMesh(vertices, faces, views, depth, face, hits)
+
+    def MeshAgreement(self, vertices, faces, views, masks):
+        """VoxelCarver.MeshAgreement on the first slab's context: the same counts."""
+        return self.slabs[0].MeshAgreement(vertices, faces, views, masks)
+
     # -- vertex-clustering decimation of the MERGED mesh (include/vacancy_hip.h, "mesh decimation"): as SmoothMesh, on the
     # first slab's context
     def DecimateMesh(self, vertices, faces, cell, origin=None, mode=0, normals=False):
