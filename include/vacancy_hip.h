@@ -48,6 +48,13 @@ typedef enum vcy_status {
 enum { VCY_UPDATE_MAX = 0, VCY_UPDATE_WEIGHTED_AVERAGE = 1 };
 enum { VCY_INTERP_NN = 0, VCY_INTERP_BILINEAR = 1 };
 enum { VCY_OUTSIDE_NONE = 0, VCY_OUTSIDE_MAX = 1 };
+/* VCY_OUTSIDE_MAX: a voxel in front of the camera that projects outside the ROI samples max_sdf, which is exactly
+ * *std::max_element over the WHOLE image buffer (voxel_carver.cc:436), not only its ROI:
+ *   - if pixel 0 is a NaN, max_sdf is that NaN (nothing compares greater than it);
+ *   - otherwise a NaN never wins, and of equal maxima the one with the lowest index does; +0 and -0 compare equal, so a
+ *     zero maximum carries the sign of the first maximal zero;
+ *   - +inf and -inf are values like any other (an image of -inf everywhere gives -inf).
+ * Every carve entry point that honours update_outside resolves it this way, per view, on the device. */
 
 /* vacancy::VoxelUpdateOption (voxel_carver.h:43-52), same defaults. */
 typedef struct vcy_update_option {

@@ -4,12 +4,18 @@
 // Every flavour of the fused carve gives the same voxel state, so a driver that picks another flavour passes every
 // state test and only gets slower.  Here every rule of the table of DESIGN.md ("The fused carve's launch plan") is
 // asked on both sides of its edge, and what must come out is written down as literals, per named case.
+// Behind them the one value a launch resolves from its images on the host's account, max_sdf: the two stages of
+// max_reduce_kernel as host loops over the kernel's own pair order (max_element_pair.h), against std::max_element.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
 #include "carve_fused_plan.h"
+#include "max_element_pair.h"
 
 using namespace vcy;
 
@@ -491,6 +497,74 @@ void check_rect() {
   }
 }
 
+// ---- max_sdf: the two stages of max_reduce_kernel (carve_kernels.hip) as host loops, against std::max_element ----------
+// 64 blocks of 256 lanes take the pixels in strides, every block reduces its lanes by a halving tree, one block does
+// the same with the 64 partial pairs and applies the first-pixel rule -- with max_pair and max_first_rule, the functions
+// the kernel is made of (max_element_pair.h).
+void reduce_block(const float* p, const int64_t* pidx, int64_t n, int block, int blocks, float* out, int64_t* out_idx) {
+  float sm[256];
+  int64_t si[256];
+  for (int t = 0; t < 256; ++t) {
+    float m = -INFINITY;
+    int64_t mi = INT64_MAX;
+    for (int64_t i = (int64_t)block * 256 + t; i < n; i += (int64_t)blocks * 256) max_pair(m, mi, p[i], pidx ? pidx[i] : i);
+    sm[t] = m, si[t] = mi;
+  }
+  for (int s = 128; s > 0; s >>= 1)
+    for (int t = 0; t < s; ++t) max_pair(sm[t], si[t], sm[t + s], si[t + s]);
+  *out = sm[0], *out_idx = si[0];
+}
+float max_sdf_by_pairs(const std::vector<float>& img) {
+  float part[64], m;
+  int64_t part_idx[64], mi;
+  for (int b = 0; b < 64; ++b) reduce_block(img.data(), nullptr, (int64_t)img.size(), b, 64, &part[b], &part_idx[b]);
+  reduce_block(part, part_idx, 64, 0, 1, &m, &mi);
+  return max_first_rule(m, img[0]);
+}
+uint32_t bits_of(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
+void expect_max_element(const char* name, const std::vector<float>& img) {
+  g_case = name;
+  const float want = *std::max_element(img.begin(), img.end()), got = max_sdf_by_pairs(img);
+  EXPECT(got != got, want != want);                              // a NaN exactly where std::max_element gives one
+  if (want == want) EXPECT(bits_of(got), bits_of(want));         // else the same bits: the sign of a zero included
+}
+void check_max_element() {
+  uint32_t seed = 12345u;
+  auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (float)(seed >> 8) * (1.0f / 16777216.0f) * 2.0f - 1.0f; };
+  const float nan = std::nanf(""), inf = INFINITY;
+  for (size_t n : {(size_t)1, (size_t)2, (size_t)255, (size_t)256, (size_t)257, (size_t)16387, (size_t)48 * 40, (size_t)1280 * 720}) {
+    std::vector<float> a(n);
+    for (float& v : a) v = rnd();
+    expect_max_element("max_element: noise", a);
+    std::vector<float> b = a;
+    b[n / 2] = b[n - 1] = 3.0f, b[n / 3] = nan;
+    expect_max_element("max_element: tied maxima, a NaN that is not first", b);
+    b[0] = nan;
+    expect_max_element("max_element: the first pixel a NaN", b);
+    std::vector<float> z(n);
+    for (size_t i = 0; i < n; ++i) z[i] = (i % 7 == 3) ? (i % 2 ? 0.0f : -0.0f) : -1.0f - (float)(i % 5);
+    expect_max_element("max_element: zero maximum, a zero of either sign first", z);
+    for (float& v : z) v = -v == 0.0f ? -v : v;                  // every zero's sign flipped
+    expect_max_element("max_element: zero maximum, the other sign first", z);
+    z[0] = -0.0f;
+    expect_max_element("max_element: -0 at the first pixel", z);
+    expect_max_element("max_element: -inf everywhere", std::vector<float>(n, -inf));
+    expect_max_element("max_element: NaN everywhere", std::vector<float>(n, nan));
+    b.assign(n, -inf), b[n - 1] = inf, b[n / 2] = nan;
+    expect_max_element("max_element: +inf the last pixel", b);
+    b.assign(n, nan), b[0] = -2.0f;
+    expect_max_element("max_element: only the first pixel is no NaN", b);
+    b.assign(n, 3.4028234664e38f), b[n / 2] = -3.4028234664e38f;
+    expect_max_element("max_element: FLT_MAX and lowest()", b);
+    b.assign(n, -1e-45f), b[n - 1] = 1e-45f;
+    expect_max_element("max_element: denormals", b);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -510,6 +584,7 @@ int main() {
   check_defaults();
   check_pixels_per_voxel();
   check_rect();
+  check_max_element();
   std::printf("%d checks, %d failures\n", checks, failures);
   return failures ? 1 : 0;
 }

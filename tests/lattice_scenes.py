@@ -162,7 +162,8 @@ def image(name):
                 img[y, x] = MINUS_ONE if k == 0 else BELOW_MINUS_ONE
     if name in ROI_VIEWS:
         _poison_ring(view, img)
-    assert not np.isnan(img[0, 0])  # (std::max_element keeps a NaN only from the first pixel; no scene relies on that)
+    # (std::max_element keeps a NaN only from the first pixel; no scene HERE relies on that -- float_class_scenes.py does)
+    assert not np.isnan(img[0, 0])
     img.setflags(write=False)
     return img
 

@@ -4,7 +4,11 @@ Which instance of the fused carve kernel runs, over which grid, with which state
 layers is decided by pure host code (vacancy_amd/csrc/carve_fused_plan.h: plan_fused_launch, plan_fused_chunk,
 finish_fused_chunk, slab_image_rect).  Every flavour gives the same voxel state, so the GPU tests cannot see a driver
 that picks another one.  tests/fused_plan_host_check.cpp asks every rule of DESIGN.md's table on both sides of its edge
-and compares with literals.  The second test builds the same program with the host sanitizers."""
+and compares with literals.  The second test builds the same program with the host sanitizers.
+
+The program also runs the two stages of the max_sdf reduction (max_reduce_kernel, carve_kernels.hip) as host loops over
+the kernel's own pair order (vacancy_amd/csrc/max_element_pair.h) and compares with std::max_element: a NaN first pixel,
+NaNs elsewhere, tied maxima, zeros of either sign, infinities."""
 import os
 import re
 import shutil

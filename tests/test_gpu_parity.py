@@ -23,6 +23,19 @@ def assert_state_equal(dev, orc, ctx=""):
         "%s sdf bits differ at %d voxels" % (ctx, int((ds.view(np.uint32) != os_.view(np.uint32)).sum()))
 
 
+def assert_state_equal_nan(got, want, ctx=""):
+    """(sdf, update_num) against (sdf, update_num): update_num equal, NaN voxels NaN on both sides, everything else bit for
+    bit.  Sign and payload of a NaN are not defined by IEEE-754 and differ between x86 and gfx950 for generated NaNs
+    (inf - inf).  Shared with test_gpu_float_classes.py."""
+    (ds, du), (os_, ou) = got, want
+    assert np.array_equal(du, ou), (ctx, "update_num differs at %d voxels" % int((du != ou).sum()))
+    nan_d, nan_o = np.isnan(ds), np.isnan(os_)
+    assert np.array_equal(nan_d, nan_o), (ctx, "NaN voxels differ at %d voxels" % int((nan_d != nan_o).sum()))
+    bits_d = np.where(nan_d, 0, ds.view(np.uint32))
+    bits_o = np.where(nan_o, 0, os_.view(np.uint32))
+    assert np.array_equal(bits_d, bits_o), (ctx, "sdf bits differ at %d voxels" % int((bits_d != bits_o).sum()))
+
+
 def assert_mesh_equal(dm, om, ctx=""):
     assert dm["vertices"].shape == om["vertices"].shape, (ctx, dm["vertices"].shape, om["vertices"].shape)
     assert dm["faces"].shape == om["faces"].shape, (ctx, dm["faces"].shape, om["faces"].shape)
@@ -336,15 +349,9 @@ def test_view_dropping_is_exact(kw):
         ds, du = dev.download()
         for d in devs:
             dev.free_device(d)
-        assert np.array_equal(du, ou), (kw, fused, cull, tile, int((du != ou).sum()))
         # NaN voxels (only the NaN/inf-poisoned SDFs produce them) must be NaN on both sides;
-        # their sign/payload is not defined by IEEE-754 and differs between x86 and gfx950
-        # for generated NaNs (inf - inf).  Everything else is compared bit for bit.
-        nan_d, nan_o = np.isnan(ds), np.isnan(os_)
-        assert np.array_equal(nan_d, nan_o), (kw, fused, cull)
-        bits_d = np.where(nan_d, 0, ds.view(np.uint32))
-        bits_o = np.where(nan_o, 0, os_.view(np.uint32))
-        assert np.array_equal(bits_d, bits_o), (kw, fused, cull, int((bits_d != bits_o).sum()))
+        # everything else is compared bit for bit.
+        assert_state_equal_nan((ds, du), (os_, ou), (kw, fused, cull, tile))
 
 
 def test_marching_cubes_random_state():

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "carve_common.h"
+#include "max_element_pair.h"
 
 namespace vcy {
 
@@ -51,21 +52,37 @@ __global__ __launch_bounds__(256) void carve_view_kernel(GridParams g, ViewParam
   }
 }
 
-// max over the whole SDF buffer (voxel_carver.cc:436), only needed for update_outside=kMax
-// (gridDim.x blocks per image, out[blockIdx.x] = maximum of that block's share; a second launch over the
-// partial maxima finishes -- one block per image took 0.3 ms per 1280 x 720 image)
+// *std::max_element over the whole SDF buffer (voxel_carver.cc:436), only needed for update_outside=kMax: the first
+// pixel if that is a NaN (nothing compares greater than it), else the greatest pixel that is no NaN, and of equal
+// maxima the one with the lowest index -- +0 == -0, so a zero maximum carries the sign of the first maximal zero
+// (include/vacancy_hip.h, VCY_OUTSIDE_MAX).  A reduction over (value, index) pairs ordered by value, then by lower
+// index (max_pair, max_element_pair.h), which does not depend on the order of the tree.  gridDim.x blocks per image,
+// out[blockIdx.x] = the best pair of that block's share (pidx == NULL: the index is the position in p); a second launch
+// over the partial pairs finishes and looks at the first pixel -- one block per image took 0.3 ms per 1280 x 720 image.
 constexpr int kMaxReduceBlocks = 64;
-__global__ void max_reduce_kernel(const float* __restrict__ p, int64_t n, float* out) {
+__global__ void max_reduce_kernel(const float* __restrict__ p, const int64_t* __restrict__ pidx, int64_t n,
+                                  float* out, int64_t* out_idx, const float* __restrict__ first) {
   __shared__ float sm[256];
+  __shared__ int64_t si[256];
   float m = -INFINITY;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, p[i]);
+  int64_t mi = INT64_MAX;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    max_pair(m, mi, p[i], pidx ? pidx[i] : i);
   sm[threadIdx.x] = m;
+  si[threadIdx.x] = mi;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sm[threadIdx.x] = fmaxf(sm[threadIdx.x], sm[threadIdx.x + s]);
+    if (threadIdx.x < s) {
+      max_pair(m, mi, sm[threadIdx.x + s], si[threadIdx.x + s]);
+      sm[threadIdx.x] = m;
+      si[threadIdx.x] = mi;
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) out[blockIdx.x] = sm[0];
+  if (threadIdx.x == 0) {
+    out[blockIdx.x] = first ? max_first_rule(m, first[0]) : m;
+    if (out_idx) out_idx[blockIdx.x] = mi;
+  }
 }
 
 static void fill_view(const vcy_view& in, const float* sdf_dev, float max_sdf, ViewParams* v) {
@@ -152,15 +169,20 @@ int resolve_views(vcy_ctx* c, int n_views, const vcy_view* views, const float* c
   // max over the whole SDF buffer (voxel_carver.cc:436); only update_outside = kMax reads it
   std::vector<float> max_sdf((size_t)n_views, 0.0f);
   if (u.update_outside == VCY_OUTSIDE_MAX) {
-    DeviceBuf<float> d_max;
-    VCY_HIP_CHECK(d_max.alloc(sizeof(float) * (size_t)n_views * (1 + kMaxReduceBlocks)));
+    // one allocation: [partial indices, 8 B | the maxima | partial maxima]
+    DeviceBuf<int64_t> d_idx;
+    VCY_HIP_CHECK(d_idx.alloc((sizeof(int64_t) * kMaxReduceBlocks + sizeof(float) * (1 + kMaxReduceBlocks)) * (size_t)n_views));
+    float* d_max = (float*)(d_idx + (size_t)n_views * kMaxReduceBlocks);
     float* d_part = d_max + n_views;
     for (int i = 0; i < n_views; ++i) {
       const int64_t npx = (int64_t)views[i].width * views[i].height;
-      hipLaunchKernelGGL(max_reduce_kernel, dim3(kMaxReduceBlocks), dim3(256), 0, c->stream, sdf_dev[i], npx,
-                         d_part + (size_t)i * kMaxReduceBlocks);
-      hipLaunchKernelGGL(max_reduce_kernel, dim3(1), dim3(256), 0, c->stream, d_part + (size_t)i * kMaxReduceBlocks,
-                         (int64_t)kMaxReduceBlocks, d_max + i);
+      float* part = d_part + (size_t)i * kMaxReduceBlocks;
+      int64_t* part_idx = d_idx + (size_t)i * kMaxReduceBlocks;
+      hipLaunchKernelGGL(max_reduce_kernel, dim3(kMaxReduceBlocks), dim3(256), 0, c->stream, sdf_dev[i],
+                         (const int64_t*)nullptr, npx, part, part_idx, (const float*)nullptr);
+      hipLaunchKernelGGL(max_reduce_kernel, dim3(1), dim3(256), 0, c->stream, (const float*)part,
+                         (const int64_t*)part_idx, (int64_t)kMaxReduceBlocks, d_max + i, (int64_t*)nullptr,
+                         npx > 0 ? sdf_dev[i] : (const float*)nullptr);
     }
     hipError_t e = hipMemcpyAsync(max_sdf.data(), d_max, sizeof(float) * (size_t)n_views,
                                   hipMemcpyDeviceToHost, c->stream);
