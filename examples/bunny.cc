@@ -6,10 +6,14 @@
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --decimate CELLS [--decimate-mode mean|nearest|first|quadric [--quadric-reg R]]
 //        bunny <data_dir> <out_dir> [resolution] --smooth N ... --decimate CELLS ... --chain
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] [--smooth N] [--decimate CELLS] [--chain] --mesh-agreement
+//        bunny <data_dir> <out_dir> [resolution] [n_slabs] [--smooth N] [--decimate CELLS] [--chain] --shade DIR
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --redistance R [--offset MM]
 //        bunny <data_dir> <out_dir> [resolution] [n_slabs] --close VOXELS
 //   n_slabs > 0 additionally runs the same views through ShardedVoxelCarver (that many z-slabs on
 //   device 0) and checks that its stitched mesh is identical to the single-context one.
+//   --shade DIR (DIR must exist) writes DIR/normal_<view>.png, the normal map (127.5 * n + 127.5) of the FINAL mesh -- as
+//   --mesh-agreement takes it -- as every input camera sees it (VoxelCarver::ShadeMesh), and prints `SHADE view i pixels n`,
+//   the pixels the mesh covers, and `SHADE verts .. faces .. views .. raster_ms .. shade_ms ..`.
 //   --render DIR (DIR must exist) writes DIR/hull_<view>.png, the silhouette of the carved hull as every input camera
 //   sees it, and prints per view how it agrees with the input silhouette: the three pixel counts and the IoU.
 //   --tolerate M carves the six views with the robust hull instead (VoxelCarver::CarveRobust: a voxel is carved only when
@@ -106,6 +110,7 @@ int main(int argc, char* argv[]) {
   float offset_mm = 0.0f;  // --offset MM: the iso level of the surface extracted from it
   float close_voxels = 0.0f;  // --close VOXELS: morphological closing of the hull first
   bool mesh_agreement = false;  // --mesh-agreement: the final mesh rasterised into the input views, against their silhouettes
+  std::string shade_dir;   // --shade DIR: the final mesh's normal map as every input camera sees it, as PNG
   std::string render_dir;  // --render DIR: the hull's silhouette of every input view as PNG, and how it agrees with the input
   {
     int n = 1;
@@ -114,7 +119,13 @@ int main(int argc, char* argv[]) {
       else if (std::string(argv[i]) == "--chain") chain = true;
       else if (std::string(argv[i]) == "--mesh-agreement") mesh_agreement = true;
       else if (std::string(argv[i]) == "--fuse-depth") fuse_depth = true;
-      else if (std::string(argv[i]) == "--render") {
+      else if (std::string(argv[i]) == "--shade") {
+        if (i + 1 >= argc) {
+          std::fprintf(stderr, "--shade needs a directory\n");
+          return 1;
+        }
+        shade_dir = argv[++i];
+      } else if (std::string(argv[i]) == "--render") {
         if (i + 1 >= argc) {
           std::fprintf(stderr, "--render needs a directory\n");
           return 10;
@@ -461,6 +472,46 @@ int main(int argc, char* argv[]) {
       std::printf("MESH_AGREEMENTSHARDED slabs %d identical %d\n", sharded->slab_count(), scounts == counts ? 1 : 0);
       if (scounts != counts) return 21;
     }
+  }
+
+  if (!shade_dir.empty()) {  // the final mesh's normal map from every input camera (vcy_shade_mesh)
+    const bool quadric = decimate_mode == 3;
+    vacancy::Mesh mesh;
+    if (chain) {
+      mesh = chain_mesh;
+    } else {
+      carver.ExtractIsoSurface(&mesh, 0.0);
+      if (smooth >= 0 && !carver.SmoothMesh(&mesh, smooth, smooth_lambda, smooth_mu, false, !(decimate > 0.0f))) return 22;
+      if (decimate > 0.0f && !(quadric ? carver.DecimateMeshQuadric(&mesh, decimate * resolution, quadric_reg, true)
+                                        : carver.DecimateMesh(&mesh, decimate * resolution, decimate_mode, true)))
+        return 22;
+    }
+    if (mesh.normals().size() != mesh.vertices().size()) mesh.CalcNormal();
+    float raster_ms = 0.0f, shade_ms = 0.0f;
+    const size_t n_shade = poses.size() < 6 ? poses.size() : 6;
+    for (size_t i = 0; i < n_shade; ++i) {
+      const vacancy::PinholeCamera cam(width, height, poses[i], Eigen::Vector2f(159.3f, 127.65f), Eigen::Vector2f(258.65f, 258.25f));
+      vacancy::Image3b image;
+      if (!carver.ShadeMesh(mesh, cam, &image, true)) return 22;
+      raster_ms += carver.last_shade_ms()[0], shade_ms += carver.last_shade_ms()[1];
+      long long n_px = 0;
+      for (int y = 0; y < image.height(); ++y)
+        for (int x = 0; x < image.width(); ++x) n_px += image.at(x, y, 0) != 0 || image.at(x, y, 1) != 0 || image.at(x, y, 2) != 0;
+      const std::string png = shade_dir + "/normal_" + vacancy::zfill(i) + ".png";
+      if (!image.WritePng(png)) {
+        std::fprintf(stderr, "cannot write %s (--shade does not create its directory)\n", png.c_str());
+        return 22;
+      }
+      std::printf("SHADE view %zu pixels %lld\n", i, n_px);
+      if (sharded) {  // the same mesh through the first slab's context: the same bytes
+        vacancy::Image3b again;
+        if (!sharded->ShadeMesh(mesh, cam, &again, true)) return 22;
+        if (again.data() != image.data()) return 23;
+      }
+    }
+    std::printf("SHADE verts %zu faces %zu views %zu raster_ms %.4f shade_ms %.4f\n", mesh.vertices().size(),
+                mesh.vertex_indices().size(), n_shade, raster_ms, shade_ms);
+    if (sharded) std::printf("SHADESHARDED slabs %d identical 1\n", sharded->slab_count());
   }
 
   if (!render_dir.empty()) {  // what the hull looks like from every input camera (vcy_render_hull / vcy_hull_agreement)

@@ -91,6 +91,12 @@ class ShardedVoxelCarver {
   bool RenderMesh(const Mesh& mesh, const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);
   bool MeshAgreement(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image1b>& silhouettes,
                      std::vector<std::array<std::int64_t, 3>>* counts);
+  // VoxelCarver::ShadeMesh / MeshPhotoError for the merged mesh, on the first slab's context (vcy_shade_mesh,
+  // vcy_mesh_photo_error): the same bits and sums.
+  bool ShadeMesh(const Mesh& mesh, const Camera& camera, Image3b* image, bool from_normals = false);
+  bool MeshPhotoError(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
+                      const std::vector<Image1b>& silhouettes, std::vector<std::array<std::int64_t, 7>>* sums);
+  std::array<float, 2> last_shade_ms() const;
   // VoxelCarver::RenderHull / HullAgreement over the slabs: RenderHullSlabs / HullAgreementSlabs below.  These two older
   // names keep logging an error and returning false.
   bool RenderHull(const Camera& camera, Image1f* depth, Image1b* silhouette = nullptr);

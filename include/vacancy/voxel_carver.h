@@ -196,6 +196,18 @@ class VoxelCarver {
                      std::vector<std::array<std::int64_t, 3>>* counts);
   std::array<float, 2> last_raster_ms() const;
 
+  // The mesh as a picture (vcy_shade_mesh: per-vertex attributes interpolated, perspective-correct, at the face RenderMesh
+  // sees in every pixel -- the definition is in vacancy_hip.h): image = the rounded vertex colours (ColorVertices fills
+  // them), or with from_normals the normal map 127.5 * n + 127.5 of normals(); black where no face is seen.  The call
+  // refuses a mesh whose chosen attribute array is empty.  MeshPhotoError (vcy_mesh_photo_error) renders the coloured mesh
+  // into every camera and compares it with the photographs on the device, under the silhouettes when there are any (an
+  // empty vector: none): per view {n, sad r, g, b, ssd r, g, b} over the n pixels the mesh covers.  false + LOGE on an
+  // error.  last_shade_ms(): device milliseconds of the raster and the shade launches.
+  bool ShadeMesh(const Mesh& mesh, const Camera& camera, Image3b* image, bool from_normals = false);
+  bool MeshPhotoError(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
+                      const std::vector<Image1b>& silhouettes, std::vector<std::array<std::int64_t, 7>>* sums);
+  std::array<float, 2> last_shade_ms() const;
+
   // The robust visual hull (vcy_carve_robust_silhouettes; the definition is in vacancy_hip.h): REPLACES the state by, per
   // voxel, the (tolerate + 1)-th largest sample over all cameras instead of the largest, so that a voxel is carved only
   // when more than `tolerate` (0 .. 3) views say outside -- up to `tolerate` wrong masks no longer remove a part of the

@@ -930,6 +930,67 @@ int vcy_mesh_agreement(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const 
  * fill of the key images with the raster launch, and the resolve launch.  Copies are not included.  Either may be NULL. */
 int vcy_last_raster_ms(const vcy_ctx* ctx, float* raster_ms, float* resolve_ms);
 
+/* ---- shading a rasterised mesh: attribute images, photometric error ----- */
+/* No reference counterpart: this section is the definition, a continuation of "rasterising an indexed mesh".
+ * vcy_shade_mesh_host is it in serial host code, tests/shade_ref.py restates it in numpy, vcy_shade_mesh runs it on the
+ * device; the three agree bit for bit.
+ *
+ * Inputs: the rasteriser's, per vertex `channels` floats (attributes[channels * vertex + c]: colours, normals, anything),
+ * channels in 1 .. 4, and a vcy_shade_option.  Steps 1 to 8 of the rasteriser decide the winner of every pixel; the steps
+ * below stand in the place of its step 9.  For a pixel (x, y) of view i with the winning face F = (f0, f1, f2):
+ *   9. weights    : in double.  e_0, e_1, e_2 and A are exactly those of steps 4 and 6 for F at p = ((double)x, (double)y);
+ *                   l_k = e_k / A.  Ortho b_k = l_k.  Pinhole t_k = l_k * (1.0 / z_k), T = (t_0 + t_1) + t_2,
+ *                   b_k = t_k / T -- the t_k and the sum of step 7, so that the depth image is (float)(1.0 / T) of the T
+ *                   used here.
+ *  10. value      : per channel c, with a_k the attribute of f_k,
+ *                   v_c = (float)((b_0 * (double)a_0c + b_1 * (double)a_1c) + b_2 * (double)a_2c), every product and sum
+ *                   rounded on its own.  On a miss -- every pixel outside the ROI is one -- v_c = background[c].
+ *                   Attributes that are not finite go through the same arithmetic; which NaN comes out is not part of
+ *                   the contract.
+ *  11. outputs    : value  (float [height][width][channels])  v;
+ *                   value8 (uint8 [height][width][channels])  q(v) = !(v > 0) ? 0 : v >= 255 ? 255 : (uint8)floorf(v + 0.5f),
+ *                                   the v + 0.5f one float addition: NaN gives 0, and the background goes through q too;
+ *                   bary   (float [height][width][3])         (float)b_k; 0, 0, 0 on a miss.
+ *  12. photometric error (channels == 3): with a photograph uint8 [height][width][3] per view and optionally a silhouette
+ *                   per view (vcy_mesh_agreement's: non-zero = object), per view over the pixels that have a winner and,
+ *                   where silhouettes are given, a non-zero silhouette: n = their number, sad[c] = sum |q(v_c) - photo_c|,
+ *                   ssd[c] = sum (q(v_c) - photo_c)^2, as int64 {n, sad0, sad1, sad2, ssd0, ssd1, ssd2}.  Integer sums
+ *                   have no order: any traversal gives the same seven numbers.  Background pixels never count.
+ * Errors: the rasteriser's; VCY_ERR_INVALID_ARG, nothing written, also for a NULL option, NULL attributes with
+ * n_vertices > 0, channels outside 1 .. 4, and in the error calls NULL photos or sums, a NULL photograph, or a NULL entry
+ * of a non-NULL silhouette array. */
+typedef struct vcy_shade_option {
+  int32_t channels;       /* floats per vertex, 1 .. 4 */
+  float   background[4];  /* the value of a pixel without a winner; the first `channels` are read */
+} vcy_shade_option;
+
+/* The definition above, serial, on the host (no GPU, no context): vcy_raster_mesh_host, then steps 9 to 11.  value /
+ * value8 / bary: arrays of n_views pointers; any of the three arrays, or single entries, may be NULL. */
+int vcy_shade_mesh_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                        const float* attributes, int n_views, const vcy_view* views, const vcy_shade_option* option,
+                        float* const* value, uint8_t* const* value8, float* const* bary);
+/* The same on the device of `ctx`, on its stream, from and into HOST arrays, bit for bit: vcy_raster_mesh's key images
+ * and raster launch, then one lane per pixel that re-projects the winner's corners and evaluates steps 9 to 11 (views in
+ * chunks of 64).  Any context will do, a z-slab included; the voxel state, queued views and every cache stay untouched.
+ * The arguments are checked before the context is looked at; VCY_ERR_NOT_INITIALIZED for a NULL context.  Device memory:
+ * the rasteriser's pool, with the attributes and the images asked for. */
+int vcy_shade_mesh(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                   const float* attributes, int n_views, const vcy_view* views, const vcy_shade_option* option,
+                   float* const* value_host, uint8_t* const* value8_host, float* const* bary_host);
+/* Step 12 on the host.  colors: 3 floats per vertex; the background is never counted, so there is no option.  photos:
+ * n_views pointers; masks: NULL, or n_views pointers; sums: 7 * n_views int64. */
+int vcy_mesh_photo_error_host(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                              const float* colors, int n_views, const vcy_view* views, const uint8_t* const* photos,
+                              const uint8_t* const* masks, int64_t* sums);
+/* ... and on the device: photographs and silhouettes are uploaded as given, the seven sums are reduced per wave, then per
+ * workgroup, then by one 64-bit integer atomic add per counter; no image is downloaded. */
+int vcy_mesh_photo_error(vcy_ctx* ctx, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                         const float* colors, int n_views, const vcy_view* views, const uint8_t* const* photos_host,
+                         const uint8_t* const* masks_host, int64_t* sums);
+/* Milliseconds between HIP events of the last vcy_shade_mesh / vcy_mesh_photo_error, summed over its chunks of views: the
+ * fill of the key images with the raster launch, and the shade launch.  Copies are not included.  Either may be NULL. */
+int vcy_last_shade_ms(const vcy_ctx* ctx, float* raster_ms, float* shade_ms);
+
 /* ---- mesh smoothing: Taubin passes over an indexed mesh, fresh normals ----- */
 /* No reference counterpart: this section is the definition.  vcy_smooth_mesh_host is it in serial host code,
  * tests/smooth_ref.py restates it in numpy, vcy_smooth_mesh runs it on the device; the three agree bit for bit.

@@ -107,6 +107,18 @@ class ColorOption(C.Structure):
         super().__init__(mode, interp, depth_tolerance, min_cos, (C.c_float * 3)(*fallback))
 
 
+class ShadeOption(C.Structure):
+    """vcy_shade_option: floats per vertex and the value of a pixel without a winner (vcy_shade_mesh)."""
+    _fields_ = [
+        ("channels", C.c_int32),
+        ("background", C.c_float * 4),
+    ]
+
+    def __init__(self, channels=3, background=(0.0, 0.0, 0.0, 0.0)):
+        bg = [float(x) for x in background] + [0.0] * 4
+        super().__init__(channels, (C.c_float * 4)(*bg[:4]))
+
+
 class SmoothOption(C.Structure):
     """vcy_smooth_option: the passes of vcy_smooth_mesh (one iteration = a lambda pass, then a mu pass)."""
     _fields_ = [
@@ -277,6 +289,11 @@ def load():
         "vcy_raster_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, C.c_int, P(View), P(vp), P(vp), P(vp), vp]),
         "vcy_mesh_agreement": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, C.c_int, P(View), P(vp), vp]),
         "vcy_last_raster_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float)]),
+        "vcy_shade_mesh_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, C.c_int, P(View), P(ShadeOption), P(vp), P(vp), P(vp)]),
+        "vcy_shade_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, P(View), P(ShadeOption), P(vp), P(vp), P(vp)]),
+        "vcy_mesh_photo_error_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, C.c_int, P(View), P(vp), P(vp), vp]),
+        "vcy_mesh_photo_error": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, P(View), P(vp), P(vp), vp]),
+        "vcy_last_shade_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float)]),
         "vcy_smooth_mesh_host": (C.c_int, [C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
         "vcy_smooth_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, P(SmoothOption), vp, vp, vp]),
         "vcy_last_smooth_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float), P(C.c_float)]),

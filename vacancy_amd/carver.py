@@ -201,6 +201,110 @@ def raster_mesh_host(vertices, faces, views, depth=True, face=True, hits=True):
     return _raster_result(capi.load().vcy_raster_mesh_host(*args), single, out, dropped)
 
 
+def _shade_args(vertices, faces, attributes, views, background, value, value8, bary):
+    """The arrays and ctypes arguments vcy_shade_mesh and vcy_shade_mesh_host share (everything behind the context); the
+    first element keeps every array alive for the call.  The result: one dict per view."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    a = np.ascontiguousarray(attributes, np.float32)
+    if a.ndim == 1:
+        a = a[:, None]
+    if a.ndim != 2 or len(a) != len(v):
+        raise ValueError("one row of attributes per vertex")
+    ch = a.shape[1]
+    vs = list(views)
+    n = len(vs)
+    opt = capi.ShadeOption(ch, background if background is not None else (0.0,) * 4)
+    out = [{} for _ in vs]
+    for o, w in zip(out, vs):
+        if value:
+            o["value"] = np.empty((w.height, w.width, ch), np.float32)
+        if value8:
+            o["value8"] = np.empty((w.height, w.width, ch), np.uint8)
+        if bary:
+            o["bary"] = np.empty((w.height, w.width, 3), np.float32)
+    arr = (View * max(n, 1))(*vs)
+    ptrs = [(C.c_void_p * max(n, 1))(*[o[k].ctypes.data for o in out]) if on else None
+            for k, on in (("value", value), ("value8", value8), ("bary", bary))]
+    args = (len(v), len(f), _p(v), _p(f), _p(a), n, arr, C.byref(opt), ptrs[0], ptrs[1], ptrs[2])
+    return (v, f, a, opt, arr, ptrs), args, out
+
+
+def _shade_result(rc, single, out):
+    if rc != 0:
+        e = RuntimeError(last_error())
+        e.rc = rc
+        raise e
+    return out[0] if single else out
+
+
+def shade_mesh_host(vertices, faces, attributes, views, background=None, value=True, value8=False, bary=False):
+    """vcy_shade_mesh_host: per-vertex `attributes` (float32 [n_vertices, channels], channels 1 .. 4) interpolated,
+    perspective-correct, at the winning face of every pixel of `views` (one vcy_view or a list), serial, no GPU needed
+    (definition: include/vacancy_hip.h, "shading a rasterised mesh").  Per view a dict: "value" (float32 [height, width,
+    channels]), "value8" (uint8, rounded half up and clamped to 0 .. 255), "bary" (float32 [height, width, 3], zeros on a
+    miss), each when asked for.  Pixels without a winner hold `background` (default zeros).  A single view returns its
+    dict, a list a list.  RuntimeError (with .rc) on a refusal."""
+    single = isinstance(views, View)
+    keep, args, out = _shade_args(vertices, faces, attributes, [views] if single else views, background, value, value8, bary)
+    return _shade_result(capi.load().vcy_shade_mesh_host(*args), single, out)
+
+
+def _photo_error_args(vertices, faces, colors, views, photos, masks):
+    """The arrays and ctypes arguments vcy_mesh_photo_error and vcy_mesh_photo_error_host share; the first element keeps
+    every array alive for the call.  The result: int64 [n_views, 7]."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    if col.shape != v.shape:
+        raise ValueError("one colour per vertex")
+    vs = list(views)
+    n = len(vs)
+    ph = [np.ascontiguousarray(p, np.uint8) for p in photos]
+    if len(ph) != n or any(p.shape != (w.height, w.width, 3) for p, w in zip(ph, vs)):
+        raise ValueError("one height x width x 3 uint8 photograph per view")
+    ms = None
+    if masks is not None:
+        ms = [np.ascontiguousarray(m, np.uint8) for m in masks]
+        if len(ms) != n or any(m.shape != (w.height, w.width) for m, w in zip(ms, vs)):
+            raise ValueError("one height x width silhouette per view")
+    arr = (View * max(n, 1))(*vs)
+    pp = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in ph])
+    mp = (C.c_void_p * max(n, 1))(*[m.ctypes.data for m in ms]) if ms is not None else None
+    sums = np.zeros((n, 7), np.int64)
+    args = (len(v), len(f), _p(v), _p(f), _p(col), n, arr, pp, mp, _p(sums))
+    return (v, f, col, ph, ms, arr, pp, mp), args, sums
+
+
+def mesh_photo_error_host(vertices, faces, colors, views, photos, masks=None):
+    """vcy_mesh_photo_error_host: the mesh with per-vertex `colors` (float32 [n_vertices, 3], 0 .. 255) rendered into `views`
+    and compared, as uint8, with the photographs (uint8 [height, width, 3] per view), serial, no GPU needed.  int64
+    [n_views, 7]: per view {n, sad r g b, ssd r g b} over the pixels the mesh covers -- and, with `masks`, whose silhouette
+    is non-zero.  photo_error_stats turns them into MAE and PSNR."""
+    keep, args, sums = _photo_error_args(vertices, faces, colors, views, photos, masks)
+    if capi.load().vcy_mesh_photo_error_host(*args) != 0:
+        raise RuntimeError(last_error())
+    return sums
+
+
+def photo_error_stats(sums):
+    """MAE and PSNR from the seven sums of mesh_photo_error_host / MeshPhotoError (int64 [..., 7]), in float64:
+    {"n": int64 [...], "mae": [..., 3] = sad / n, "mse": [..., 3] = ssd / n, "psnr": [..., 3] = 10 log10(255^2 / mse) in
+    dB -- +inf for mse == 0 --, "mae_all", "psnr_all": over the three channels together}.  A view with n == 0 has no
+    error to speak of: NaN everywhere."""
+    s = np.asarray(sums, np.int64)
+    n = s[..., 0]
+    nf = n.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mae = s[..., 1:4] / nf[..., None]
+        mse = s[..., 4:7] / nf[..., None]
+        mse_all = s[..., 4:7].sum(axis=-1) / (3.0 * nf)
+        psnr = 10.0 * np.log10(65025.0 / mse)
+        psnr_all = 10.0 * np.log10(65025.0 / mse_all)
+        mae_all = s[..., 1:4].sum(axis=-1) / (3.0 * nf)
+    return {"n": n, "mae": mae, "mse": mse, "psnr": psnr, "mae_all": mae_all, "psnr_all": psnr_all}
+
+
 def _smooth_args(vertices, faces, iterations, lam, mu, pin_boundary, normals):
     """The arrays and ctypes arguments vcy_smooth_mesh and vcy_smooth_mesh_host share; the first element keeps every array
     alive for the call."""
@@ -1029,6 +1133,32 @@ class VoxelCarver:
     def last_raster_ms(self):
         ms = [C.c_float(), C.c_float()]
         self._lib.vcy_last_raster_ms(self._ctx, *[C.byref(m) for m in ms])
+        return ms[0].value, ms[1].value
+
+    # -- the shading pass behind the rasteriser (no reference counterpart; definition: include/vacancy_hip.h)
+    def ShadeMesh(self, vertices, faces, attributes, views, background=None, value=True, value8=False, bary=False):
+        """vcy_shade_mesh: shade_mesh_host on this context's device and stream, the same bits.  The context only names the
+        device: its voxel state is not touched, and a z-slab will do.  Dicts as shade_mesh_host's (a single view returns its
+        dict), each with the call's device times "raster_ms" and "shade_ms".  RuntimeError (with .rc) on a refusal."""
+        single = isinstance(views, View)
+        keep, args, out = _shade_args(vertices, faces, attributes, [views] if single else views, background, value, value8, bary)
+        rc = self._lib.vcy_shade_mesh(self._ctx, *args)
+        ms = self.last_shade_ms()
+        for o in out:
+            o["raster_ms"], o["shade_ms"] = ms
+        return _shade_result(rc, single, out)
+
+    def MeshPhotoError(self, vertices, faces, colors, views, photos, masks=None):
+        """vcy_mesh_photo_error: mesh_photo_error_host on the device, the same sums; no image is downloaded.  int64
+        [n_views, 7]."""
+        keep, args, sums = _photo_error_args(vertices, faces, colors, views, photos, masks)
+        if self._lib.vcy_mesh_photo_error(self._ctx, *args) != 0:
+            raise RuntimeError(last_error())
+        return sums
+
+    def last_shade_ms(self):
+        ms = [C.c_float(), C.c_float()]
+        self._lib.vcy_last_shade_ms(self._ctx, *[C.byref(m) for m in ms])
         return ms[0].value, ms[1].value
 
     # -- colour of vertices from the photographs (no reference counterpart; definition: include/vacancy_hip.h)

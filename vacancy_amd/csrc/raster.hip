@@ -22,32 +22,11 @@
 #include <vector>
 
 #include "raster_fragment.h"
+#include "raster_launch.h"
 #include "vcy_internal.h"
 
 namespace vcy {
 namespace rs {
-
-typedef unsigned long long u64;
-
-struct Target {  // one per view of a launch, in device memory, beside its View
-  u64* keys;
-  float* depth;         // any of the three outputs may be null
-  int32_t* face;
-  u64* hits;
-  const uint8_t* mask;  // null unless the agreement is counted
-};
-
-struct Launch {
-  int64_t n_faces;
-  const float* vtx;
-  const int32_t* faces;
-  const View* views;
-  const Target* targets;
-  int n_views;
-  long long wide;   // "rasterwide"
-  u64* dropped;     // 2 per view
-  u64* counts;      // 3 per view (agreement)
-};
 
 __device__ __forceinline__ void propose(u64* keys, int64_t at, u64 key) {
   if (key < keys[at]) atomicMin(keys + at, key);
@@ -153,6 +132,12 @@ __global__ __launch_bounds__(256) void rs_resolve_kernel(const View* __restrict_
   }
 }
 
+hipError_t launch_raster(const Launch& L, hipStream_t stream) {
+  if (L.n_faces <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rs_raster_kernel, dim3((unsigned)((L.n_faces + 255) / 256)), dim3(256), 0, stream, L);
+  return hipGetLastError();
+}
+
 }  // namespace rs
 
 namespace {
@@ -255,10 +240,7 @@ int raster_device(vcy_ctx* c, int64_t n_vertices, int64_t n_faces, const float* 
     VCY_HIP_CHECK(hipEventRecord(c->ev_rs[0], c->stream));
     VCY_HIP_CHECK(hipMemsetAsync(image_base, 0xff, key_bytes, c->stream));
     L.n_views = m;
-    if (n_faces > 0) {
-      hipLaunchKernelGGL(rs::rs_raster_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, c->stream, L);
-      VCY_HIP_CHECK(hipGetLastError());
-    }
+    VCY_HIP_CHECK(rs::launch_raster(L, c->stream));
     VCY_HIP_CHECK(hipEventRecord(c->ev_rs[1], c->stream));
     const dim3 grid((unsigned)((words_max + 3) / 4), (unsigned)m);
     if (masks) hipLaunchKernelGGL((rs::rs_resolve_kernel<true>), grid, dim3(256), 0, c->stream, L.views, L.targets, L.counts);

@@ -191,6 +191,9 @@ struct vcy_ctx {
   vcy::Event ev_rs[3];                // before the key fill and the raster launch, between raster and resolve, after the resolve
   float last_raster_ms[2] = {0.0f, 0.0f};  // vcy_last_raster_ms: raster (with the key fill), resolve
   int raster_wide = 64;               // "rasterwide": a face whose candidate box holds more pixels than this is drawn by its whole wave
+  // ... and the shading pass behind it (raster_shade.hip), in the same pool
+  vcy::Event ev_sh[3];                // before the key fill and the raster launch, between raster and shade, after the shade
+  float last_shade_ms[2] = {0.0f, 0.0f};   // vcy_last_shade_ms: raster (with the key fill), shade
 
   // robust carve (carve_robust.hip)
   vcy::Event ev_rb_begin, ev_rb_end;  // around its launch (vcy_last_robust_ms)
@@ -276,6 +279,14 @@ int render_depth_device(vcy_ctx* ctx, double iso, int n_views, const vcy_view* v
 // vcy_raster_mesh_host and the argument checks of the three; what device and host share: raster_fragment.h
 int raster_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
                       int n_views, const vcy_view* views);
+// raster_shade.hip: vcy_shade_mesh, vcy_mesh_photo_error, vcy_last_shade_ms (the raster launch they share with raster.hip:
+// raster_launch.h); shade_host.hip (host code only): vcy_shade_mesh_host, vcy_mesh_photo_error_host and the argument checks
+// of the four; what device and host share: raster_shade.h
+int shade_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                     const float* attributes, int n_views, const vcy_view* views, const vcy_shade_option* option);
+int photo_error_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                           const float* colors, int n_views, const vcy_view* views, const uint8_t* const* photos,
+                           const uint8_t* const* masks, const int64_t* sums);
 // mesh_smooth.hip: vcy_smooth_mesh, vcy_last_smooth_ms; mesh_smooth_host.hip (host code only): vcy_smooth_mesh_host and
 // the argument checks of the two
 int smooth_check_args(const char* who, int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,

@@ -434,6 +434,29 @@ bool ShardedVoxelCarver::MeshAgreement(const Mesh& mesh, const std::vector<const
   return detail::MeshAgreementWith(impl_->slabs[0], "ShardedVoxelCarver::MeshAgreement", mesh, cameras, silhouettes, counts);
 }
 
+bool ShardedVoxelCarver::ShadeMesh(const Mesh& mesh, const Camera& camera, Image3b* image, bool from_normals) {
+  if (impl_->slabs.empty()) {
+    LOGE("ShardedVoxelCarver::ShadeMesh needs an initialized carver\n");
+    return false;
+  }
+  return detail::ShadeMeshWith(impl_->slabs[0], "ShardedVoxelCarver::ShadeMesh", mesh, camera, image, from_normals);
+}
+
+bool ShardedVoxelCarver::MeshPhotoError(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
+                                        const std::vector<Image1b>& silhouettes, std::vector<std::array<std::int64_t, 7>>* sums) {
+  if (impl_->slabs.empty()) {
+    LOGE("ShardedVoxelCarver::MeshPhotoError needs an initialized carver\n");
+    return false;
+  }
+  return detail::MeshPhotoErrorWith(impl_->slabs[0], "ShardedVoxelCarver::MeshPhotoError", mesh, cameras, photos, silhouettes, sums);
+}
+
+std::array<float, 2> ShardedVoxelCarver::last_shade_ms() const {
+  std::array<float, 2> ms = {{0.0f, 0.0f}};
+  if (!impl_->slabs.empty()) vcy_last_shade_ms(impl_->slabs[0], &ms[0], &ms[1]);
+  return ms;
+}
+
 bool ShardedVoxelCarver::DecimateMesh(Mesh* mesh, float cell, int mode, bool with_normals) {
   if (impl_->slabs.empty() || !mesh) {
     LOGE("ShardedVoxelCarver::DecimateMesh needs a mesh and an initialized carver\n");

@@ -393,6 +393,29 @@ bool VoxelCarver::MeshAgreement(const Mesh& mesh, const std::vector<const Camera
   return detail::MeshAgreementWith(impl_->ctx, "VoxelCarver::MeshAgreement", mesh, cameras, silhouettes, counts);
 }
 
+bool VoxelCarver::ShadeMesh(const Mesh& mesh, const Camera& camera, Image3b* image, bool from_normals) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  return detail::ShadeMeshWith(impl_->ctx, "VoxelCarver::ShadeMesh", mesh, camera, image, from_normals);
+}
+
+bool VoxelCarver::MeshPhotoError(const Mesh& mesh, const std::vector<const Camera*>& cameras, const std::vector<Image3b>& photos,
+                                 const std::vector<Image1b>& silhouettes, std::vector<std::array<std::int64_t, 7>>* sums) {
+  if (!impl_->ctx) {
+    LOGE("voxel grid has not been initialized\n");
+    return false;
+  }
+  return detail::MeshPhotoErrorWith(impl_->ctx, "VoxelCarver::MeshPhotoError", mesh, cameras, photos, silhouettes, sums);
+}
+
+std::array<float, 2> VoxelCarver::last_shade_ms() const {
+  std::array<float, 2> ms = {{0.0f, 0.0f}};
+  if (impl_->ctx) vcy_last_shade_ms(impl_->ctx, &ms[0], &ms[1]);
+  return ms;
+}
+
 std::array<float, 2> VoxelCarver::last_raster_ms() const {
   std::array<float, 2> ms = {{0.0f, 0.0f}};
   if (impl_->ctx) vcy_last_raster_ms(impl_->ctx, &ms[0], &ms[1]);

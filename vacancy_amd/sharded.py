@@ -230,6 +230,15 @@ class ShardedVoxelCarver:
         """VoxelCarver.MeshAgreement on the first slab's context: the same counts."""
         return self.slabs[0].MeshAgreement(vertices, faces, views, masks)
 
+    # -- ... and the shading pass behind it (include/vacancy_hip.h, "shading a rasterised mesh"), on the same context
+    def ShadeMesh(self, vertices, faces, attributes, views, background=None, value=True, value8=False, bary=False):
+        """VoxelCarver.ShadeMesh on the first slab's context: the same dicts."""
+        return self.slabs[0].ShadeMesh(vertices, faces, attributes, views, background, value, value8, bary)
+
+    def MeshPhotoError(self, vertices, faces, colors, views, photos, masks=None):
+        """VoxelCarver.MeshPhotoError on the first slab's context: the same sums."""
+        return self.slabs[0].MeshPhotoError(vertices, faces, colors, views, photos, masks)
+
     # -- vertex-clustering decimation of the MERGED mesh (include/vacancy_hip.h, "mesh decimation"): as SmoothMesh, on the
     # first slab's context
     def DecimateMesh(self, vertices, faces, cell, origin=None, mode=0, normals=False):
